@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: decoded MIDI tokens / second on synthetic 10 s clips.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision bf16|fp32] [--batch 32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision bf16|fp32] [--batch 32] [--dump-outputs DIR]
 
 A "step" is one pass of the whole hot path over one batch of synthetic clips:
 fused STFT/log-mel frontend -> conditioning rows -> T5 encoder -> cross-K/V
@@ -25,7 +25,9 @@ Prints ONE JSON line (rank 0).  `roofline` is measured live with hipEvents on
 the stream the kernels run on (m2m_bench_kernel); `cpu_baseline` times the
 oracle (a PyTorch-CPU restatement of the reference path — the reference's own
 Python cannot run here: torchaudio/lightning/omegaconf are absent) on a bounded
-sample on the host cores.  ``--dry-run`` exercises the launcher and both
+sample on the host cores.  ``--dump-outputs DIR`` writes what the timed path returned in its last step
+(rank 0: the generate mode's token ids; the train mode's loss and a fixed sample of the updated weights and
+gradients) as ``DIR/<name>.npy``, so two builds can be compared output for output.  ``--dry-run`` exercises the launcher and both
 collectives on CPU tensors (gloo) without any GPU work — tests/test_bench_launcher.py.
 """
 from __future__ import annotations
@@ -82,6 +84,30 @@ def _tail(path: Path, n: int = 25) -> str:
         return "\n".join(path.read_text(errors="replace").splitlines()[-n:])
     except OSError:
         return ""
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: everything written together stays under 64 MB
+DUMP_SAMPLE = 1 << 20          # elements of a fixed, seeded sample taken from a flat output larger than this
+
+
+def dump_sample(flat: torch.Tensor) -> np.ndarray:
+    """A fixed sample of a large flat tensor: the same sorted indices (seed 0) on every run of the same shape."""
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        return flat.detach().float().cpu().numpy()
+    idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+    return flat.detach().float()[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+
+
+def dump_outputs(outdir: str, arrays: dict) -> None:
+    """Write each array as <outdir>/<name>.npy in float32 / float64 (token ids go as float64: exact)."""
+    arrs = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    Path(outdir).mkdir(parents=True, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(Path(outdir) / f"{k}.npy", a)
 
 
 def spawn_ranks(n: int) -> int:
@@ -654,8 +680,9 @@ def cpu_train_baseline(cfg, state, B: int, threads: int = 16):
 
 
 def train_step_record(model_module, cfg, geom, dev, B: int, precision: str, steps: int, warmup: int, world: int = 1, dropout: float = 0.0,
-                      profile_launches: bool = False):
-    """forward + backward + (gradient all-reduce) + Adafactor on B clips per GPU; returns a dict for the JSON line."""
+                      profile_launches: bool = False, dump: dict = None):
+    """forward + backward + (gradient all-reduce) + Adafactor on B clips per GPU; returns a dict for the JSON line.
+    With ``dump`` (a dict), the last timed step's results go into it: the loss and fixed samples of the weights and gradients."""
     from music2midi_amd import distributed as D
     from music2midi_amd import synth
     from music2midi_amd.input import ModelInputs
@@ -691,6 +718,10 @@ def train_step_record(model_module, cfg, geom, dev, B: int, precision: str, step
     torch.cuda.synchronize(dev)
     D.barrier()
     dt_local = time.perf_counter() - t0
+    if dump is not None:
+        dump["loss"] = np.array([float(loss)], dtype=np.float64)
+        dump["params_sample"] = dump_sample(tr.params)
+        dump["grads_sample"] = dump_sample(tr.grads)
     per_rank_ms = [e / steps * 1e3 for e in D.all_gather_floats(dt_local, dev)]
     dt = D.all_reduce_max(dt_local, dev) / steps
     # every rank trained on ITS clips: after these steps the replicas are identical only if the gradient average reached every rank
@@ -788,7 +819,11 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="launcher + collectives on CPU tensors (gloo), no GPU work")
     ap.add_argument("--max-length", type=int, default=MAX_LENGTH,
                     help="decoder max_length (profiling runs only; the headline number uses 1024)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (rank 0; at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher (no HIP call has happened in this process)
@@ -847,7 +882,10 @@ def main():
         sys.exit(2)
     if args.mode == "train":
         Bt = 16 if args.batch == 32 else args.batch
-        rec = train_step_record(model, cfg, geom, dev, Bt, args.precision, args.steps, args.warmup, world, dropout=args.dropout)
+        dumped = {} if args.dump_outputs else None
+        rec = train_step_record(model, cfg, geom, dev, Bt, args.precision, args.steps, args.warmup, world, dropout=args.dropout, dump=dumped)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, dumped)
         if rank == 0:
             line = {"metric": "training clips/sec/node (forward+backward+Adafactor step)", "value": rec["clips_per_s"], "unit": "clips/s",
                     "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": rec["ms_per_step"],
@@ -891,6 +929,8 @@ def main():
     per_rank_ms = [e / args.steps * 1e3 for e in D.all_gather_floats(elapsed, dev)]
     elapsed = D.all_reduce_max(elapsed, dev)
     assert toks.shape[0] == B * world, toks.shape
+    if rank == 0 and args.dump_outputs:      # the all-gathered greedy ids of the last timed step, every rank's clips
+        dump_outputs(args.dump_outputs, {"tokens": toks.cpu().numpy()})
     # tokens that count: per clip, up to and including its EOS, or the whole budget when it has none.  (Random-init weights emit EOS
     # now and then; the headline clips' trajectories have had none so far — `rows_with_eos` says so in the line — but a row that ends
     # early costs less from there on (finished-row early-out), so padding must never be counted as decoded tokens.)

@@ -1,5 +1,16 @@
 """CPU: the oracle reproduces the golden vectors (which HuggingFace T5 / torch.stft produced
-in the build container, tests/golden/make_golden.py).  This is what pins the oracle."""
+in the build container, tests/golden/make_golden.py).  This is what pins the oracle.
+
+Three of the bars below (1e-5 on the fp32 log-mel, 1e-3 on the bf16 emulation's logits and margins) hold only where the host
+CPU's fp32 arithmetic is the fixture machine's bit for bit: the BLAS / FFT libraries pick their kernels, and so their summation
+orders, by CPU model, and the fixtures' own fp32 log-mel misses the float64 value of the same formula by 1.6e-5.  Whether a host
+has that arithmetic is decided once, independently of the code under test: the fp32 oracle must reproduce the fixture's fp32
+step-0 logits (t5_forced.npz ``full_s864_fp32``, which the fp32 oracle wrote) bit for bit.  Where it does, the bars are the
+ones above; where it does not, each test holds the oracle to what a different summation order of the same formula leaves: the
+fp32 log-mel to 1e-5 beyond this host's own fp32 rounding error (its distance to the float64 evaluation), the bf16 emulation to
+its own noise floor stored in the fixture (tests/forced_check.py: the bars the device is held to)."""
+from functools import lru_cache
+
 import numpy as np
 import pytest
 import torch
@@ -9,7 +20,20 @@ from music2midi_amd.config import DEFAULT_CONFIG, T5Geometry
 from oracle.logmel import LogMelOracle, melscale_fbanks
 from oracle.t5 import T5Oracle
 
+from forced_check import BF16_FLOOR_FACTORS, bf16_margin_threshold
 from test_t5_gpu import embeds, tiny_config
+
+
+@lru_cache(maxsize=None)
+def fixture_arithmetic(golden_dir) -> bool:
+    """True when this host's fp32 oracle reproduces the fixture machine's fp32 step-0 logits of full_s864 bit for bit."""
+    z = np.load(golden_dir / "t5_forced.npz")
+    geom = T5Geometry(DEFAULT_CONFIG["model"]["t5"])
+    sd = synth.t5_state_dict(geom, seed=0)
+    synth.perturb_layer_norms(sd, 0)
+    got = []
+    T5Oracle(geom, sd).generate(embeds(2, 864, geom.d_model), 2, logits_hook=lambda t, lg: got.append(lg.clone()))
+    return bool(np.array_equal(got[0].numpy(), z["full_s864_fp32/full_logits"][:, 0]))
 
 
 def _case(golden_dir, name):
@@ -70,6 +94,9 @@ def test_frontend_oracle_matches_goldens(golden_dir):
         out = orc(torch.from_numpy(synth.waveform_batch(0, 2, 4096, kind))).numpy()
         assert out.shape == (2, 17, 384)
         tol = 1e-5 if kind != "tones" else 5e-2   # "tones": fp32 STFT noise floor, see test_frontend_gpu.py
+        if kind != "tones" and not fixture_arithmetic(golden_dir):     # other fp32 summation orders: this host's own fp32 error on top
+            wav = torch.from_numpy(synth.waveform_batch(0, 2, 4096, kind))
+            tol += float(np.abs(out - orc(wav, dtype=torch.float64).numpy()).max())
         assert np.abs(out - z[f"logmel_{kind}"]).max() <= tol
     assert np.all(z["logmel_zeros"] == np.float32(np.log(np.float32(1e-6))))
 
@@ -130,8 +157,18 @@ def test_bf16_emulating_oracle_reproduces_its_headline_fixture_prefix(golden_dir
     ids, margins = T5Oracle(geom, sd, emulate="bf16").generate(x, 24, return_margins=True)
     want = z["full_s864_bf16/ids"].astype(np.int64)
     assert want.shape == (2, 1024) and z["full_s864_bf16/margins"].shape == (2, 1023)
-    assert np.array_equal(ids.numpy(), want[:, :24])
-    assert np.abs(margins.numpy() - z["full_s864_bf16/margins"][:, :23]).max() < 1e-3
+    if fixture_arithmetic(golden_dir):
+        assert np.array_equal(ids.numpy(), want[:, :24])
+        assert np.abs(margins.numpy() - z["full_s864_bf16/margins"][:, :23]).max() < 1e-3
+    else:       # the emulation's own noise floor: same ids up to the first position whose margin is under the arg-max threshold
+        zf = np.load(golden_dir / "t5_forced.npz")
+        fm = z["full_s864_bf16/margins"][:, :23]
+        for b in range(2):
+            close = np.flatnonzero(fm[b] <= bf16_margin_threshold(zf, "full_s864_bf16"))
+            n = 1 + (int(close[0]) if len(close) else 23)
+            assert np.array_equal(ids.numpy()[b, :n], want[b, :n]), b
+            m = min(n, 23)        # margins of the steps whose inputs are the same ids
+            assert np.abs(margins.numpy()[b, :m] - fm[b, :m]).max() <= BF16_FLOOR_FACTORS[0] * float(zf["full_s864_bf16/self_noise_margin"][0])
     assert z["bench_clips_bf16/ids"].shape == z["bench_clips_fp32/ids"].shape == (2, 1024)
     assert (z["bench_clips_bf16/ids"][:, 0] == 1).all() and z["bench_clips_bf16/margins"].min() > 0
 
@@ -159,5 +196,7 @@ def test_forced_fixture_is_what_the_oracle_computes(golden_dir):
     got = []
     T5Oracle(geom, sd, emulate="bf16").generate(embeds(2, 864, geom.d_model), 9, logits_hook=lambda t, lg: got.append(lg.clone()))
     got = torch.stack(got, 1).numpy()
-    assert np.abs(np.take_along_axis(got, z["full_s864_bf16/top_idx"][:, :8].astype(np.int64), 2) - z["full_s864_bf16/top_vals"][:, :8]).max() < 1e-3
-    assert np.abs(got[:, 0] - z["full_s864_bf16/full_logits"][:, 0]).max() < 1e-3
+    # other fp32 summation orders: the emulation's own noise floor (max |d logit|, median over the perturbation seeds) x 1.5
+    tol = 1e-3 if fixture_arithmetic(golden_dir) else BF16_FLOOR_FACTORS[0] * float(z["full_s864_bf16/self_noise_logit"][0])
+    assert np.abs(np.take_along_axis(got, z["full_s864_bf16/top_idx"][:, :8].astype(np.int64), 2) - z["full_s864_bf16/top_vals"][:, :8]).max() < tol
+    assert np.abs(got[:, 0] - z["full_s864_bf16/full_logits"][:, 0]).max() < tol
