@@ -197,9 +197,30 @@ int m2m_encode(m2m_session* s, const float* inputs_embeds_dev, int B, int S, flo
 int m2m_generate_greedy(m2m_session* s, int max_length, int64_t* tokens_out_dev, int* out_len_host, void* stream);
 
 /*
+ * KV-cached sampled decode (hf: generation/utils.py sample(), do_sample=True): the greedy loop above with the arg-max replaced by
+ * transformers 4.34's logits warpers in their order - temperature (logits / T, skipped for T == 1), top-k (every logit strictly
+ * below the k-th largest is removed, k = min(top_k, V); top_k = 0 disables it), top-p (sorted ascending, the entries whose
+ * cumulative softmax is <= 1 - top_p are removed, the largest always stays; top_p = 1 disables it) - and a draw from the softmax
+ * of what is left.  The uniform of clip row r at position t hashes (seed, r, t), so the same seed gives the same ids whatever the
+ * chain split, the live-row re-packing or the kernel forms; the ids are not HF's samples (another random generator).
+ * Invalid parameters return M2M_ERR_INVALID: temperature <= 0 or not finite, top_k < 0, top_p outside [0, 1]; so does a vocabulary
+ * larger than 4096.  Everything else - arguments, out_len, M2M_ERR_RANGE, the re-packing and the session state afterwards - is as
+ * for m2m_generate_greedy.
+ */
+typedef struct {
+  float temperature;
+  int top_k;
+  float top_p;
+  uint64_t seed;
+} m2m_sample_params;
+
+int m2m_generate_sample(m2m_session* s, int max_length, const m2m_sample_params* p, int64_t* tokens_out_dev, int* out_len_host,
+                        void* stream);
+
+/*
  * Rows end at different steps (ref: music2midi/model.py:115-135 decodes chunks of inference.batch_size = 128 three-second
  * segments to max_length 1024; a trained checkpoint ends a segment after tens to hundreds of tokens).  Once a quarter of the
- * rows still being decoded have emitted EOS, m2m_generate_greedy re-packs the live rows into the first slots of the batch at its
+ * rows still being decoded have emitted EOS, m2m_generate_greedy (and m2m_generate_sample) re-packs the live rows into the first slots of the batch at its
  * next host poll and goes on with smaller launches; ids do not depend on it.  The host polls after 16, 32, 64, 96 and 128 steps and
  * then every 64 (without the re-packing: every 64); each poll drains every chain, and a poll at which a re-packing is possible (a
  * chain still running, >= 64 steps left, >= 2 rows) also reads the finished flags back synchronously - so M2M_COMPACT=1 adds four

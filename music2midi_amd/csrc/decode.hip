@@ -1903,6 +1903,178 @@ bool decode_headless() {
   return on;
 }
 
+// ========================================================== sampling head ====
+// do_sample=True replaces dec_head_kernel by this kernel (the step is otherwise the non-headless one, as with M2M_HEADLESS=0).  It
+// follows transformers 4.34's logits warpers in their order (hf: generation/utils.py _get_logits_warper, generation/logits_process.py):
+//   TemperatureLogitsWarper  x / T (skipped for T == 1)
+//   TopKLogitsWarper         remove every logit strictly below the k-th largest, k = min(top_k, V) (ties at the boundary stay)
+//   TopPLogitsWarper         sorted ascending, remove the entries whose cumulative softmax is <= 1 - top_p, the largest always stays
+// then draws from the softmax of what is left by inverse CDF over the vocabulary order with a uniform from a counter-based hash of
+// (call seed, clip row tok_row[b], position t): a clip's ids do not depend on its slot, its chain or the kernel forms of the step.
+// One wavefront per row (4 rows per workgroup, every row of the chain at once), the row in registers (lane l holds the NPL logits
+// l*NPL ..), and no sort: the k-th largest logit is a radix select over the order-preserving 32-bit image of the logits (32
+// ballot counts), the nucleus cutoff the largest key c whose strictly-smaller mass is <= (1 - top_p) * Z (32 wave-wide sums) - an
+// entry is removed iff its cumulative mass, itself included, is <= (1 - top_p) * Z, i.e. iff its key is below c.  (Exact ties at
+// the nucleus boundary are kept or removed together; HF removes them in torch.sort's order.)  Non-finite logits raise the chain's
+// overflow flag (M2M_ERR_RANGE) as the greedy head does; the EOS / pad / finished bookkeeping, the token store and the embedding
+// write are the greedy branch of dec_head_kernel.  The last workgroup of a step (a ticket in DecState) closes it.
+__device__ inline unsigned ord_key(float v) {
+  unsigned u = __float_as_uint(v + 0.0f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ inline float wave_sum_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wave_sum(v)))); }
+
+constexpr int SAMPLE_ROWS = 4;   // rows (waves) per dec_sample_kernel workgroup: a chain's rows are spread over ceil(B / 4) workgroups
+
+template <int NPL>
+__global__ __launch_bounds__(64 * SAMPLE_ROWS) void dec_sample_kernel(DecHeadArgs a, const SampleParams* sp) {
+  __shared__ int s_unfinished;
+  DecState* stp = a.state;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int b = blockIdx.x * SAMPLE_ROWS + (tid >> 6);
+  const int V = a.V, v0 = lane * NPL;
+  const bool row = b < a.B;
+  // the row's logits are requested before the loop state is consumed (as in dec_head_kernel)
+  float x[NPL];
+  const float* lg = a.logits + (int64_t)(row ? b : 0) * a.ldl;
+#pragma unroll
+  for (int j = 0; j < NPL; ++j) x[j] = (v0 + j < V) ? lg[v0 + j] : 0.f;
+  const float temp = sp->temperature, top_p = sp->top_p;
+  const int top_k = sp->top_k;
+  const unsigned long long seed_h = splitmix64(sp->seed);
+  const int t = stp->t;
+  const bool live = !(stp->done | (t >= stp->max_steps));
+  if (tid == 0) s_unfinished = 0;
+  __syncthreads();
+  const int k = top_k > 0 ? min(top_k, V) : V;
+  if (row) {
+    const int fin = a.finished[b];
+    bool bad = false;
+    float m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+      if (v0 + j < V) {
+        bad |= !(fabsf(x[j]) <= 3.0e38f);
+        if (temp != 1.0f) x[j] = x[j] / temp;
+        m = fmaxf(m, x[j]);
+      }
+    }
+    m = wave_max(m);          // exact: every lane holds the same maximum
+    unsigned kk[NPL];         // order-preserving keys; 0 (below every finite logit's) past the vocabulary
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) kk[j] = (v0 + j < V) ? ord_key(x[j]) : 0u;
+    // TopK: the k-th largest key, bit by bit from the top (the largest thr with count(key >= thr) >= k); counts are ballots
+    unsigned thr = 0;
+    if (k < V) {
+      for (int bit = 31; bit >= 0; --bit) {
+        const unsigned cand = thr | (1u << bit);
+        int cnt = 0;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) cnt += __popcll(__ballot(kk[j] >= cand));
+        if (cnt >= k) thr = cand;
+      }
+    }
+    float w[NPL];
+    float z = 0.f;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+      w[j] = (v0 + j < V && kk[j] >= thr) ? expf(x[j] - m) : 0.f;
+      z += w[j];
+    }
+    z = wave_sum_uniform(z);
+    // TopP: the largest key c with mass(key < c) <= (1 - top_p) * Z, capped at the maximum's key (which always stays)
+    if (top_p < 1.0f) {
+      const float R = (1.0f - top_p) * z;
+      unsigned c = 0;
+      for (int bit = 31; bit >= 0; --bit) {
+        const unsigned cand = c | (1u << bit);
+        float lm = 0.f;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) lm += kk[j] < cand ? w[j] : 0.f;
+        if (wave_sum_uniform(lm) <= R) c = cand;
+      }
+      c = min(c, ord_key(m));
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) if (kk[j] < c) w[j] = 0.f;
+    }
+    // draw: the first kept entry (vocabulary order) whose inclusive cumulative weight exceeds u * Z
+    float ls = 0.f;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) ls += w[j];
+    float incl = ls;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const float up = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += up;
+    }
+    const float total = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, incl), 63));
+    const unsigned long long h = splitmix64(seed_h ^ (((unsigned long long)(unsigned)a.tok_row[b] << 32) | (unsigned)t));
+    const float target = (float)(h >> 40) * 0x1p-24f * total;
+    const unsigned long long over = __ballot(incl > target && ls > 0.f);
+    const unsigned long long any = __ballot(ls > 0.f);
+    const int sel = over ? __ffsll((long long)over) - 1 : (any ? 63 - __clzll((long long)any) : 0);
+    float acc = __shfl_up(incl, 1, 64);
+    if (lane == 0) acc = 0.f;
+    int tok = -1, last = -1;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+      if (w[j] > 0.f) {
+        acc += w[j];
+        last = v0 + j;
+        if (tok < 0 && acc > target) tok = v0 + j;
+      }
+    }
+    if (tok < 0) tok = last;           // rounding put the target past this lane's last kept entry
+    tok = __shfl(tok, sel, 64);
+    if (tok < 0) tok = a.pad_id;       // no finite weight at all (the overflow flag is raised)
+    if (__ballot(bad) && live && lane == 0) stp->overflow = 1;
+    // hf generation/utils.py (sample): finished rows emit pad; EOS finishes a row
+    int next = fin ? a.pad_id : tok;
+    if (lane == 0 && live) {
+      if (t + 1 < a.max_len) a.tokens[(int64_t)a.tok_row[b] * a.max_len + t + 1] = next;
+      const int nf = fin | (next == a.eos_id);
+      a.finished[b] = nf;
+      if (!nf) atomicAdd(&s_unfinished, 1);
+    }
+    if (next < 0 || next >= V) next = a.pad_id;
+    const float* emb = a.shared + (int64_t)next * a.d;
+    for (int c = lane * 4; c < a.d; c += 256) {
+      const float4 e4 = *reinterpret_cast<const float4*>(emb + c);
+      xq_t* xp = a.x + (int64_t)b * a.d + c;
+      if (live) {
+        *reinterpret_cast<longlong2*>(xp) = make_longlong2(xq_fix_guarded(e4.x, stp), xq_fix_guarded(e4.y, stp));
+        *reinterpret_cast<longlong2*>(xp + 2) = make_longlong2(xq_fix_guarded(e4.z, stp), xq_fix_guarded(e4.w, stp));
+      }
+    }
+  }
+  // the step closes when the last workgroup is through: every workgroup has read t / done above before it takes its ticket
+  __syncthreads();
+  if (tid == 0 && live) {
+    if (s_unfinished) atomicAdd(&stp->smp_unfinished, s_unfinished);
+    __threadfence();
+    if (atomicAdd(&stp->smp_ticket, 1) == (int)gridDim.x - 1) {
+      __threadfence();
+      const int nu = atomicExch(&stp->smp_unfinished, 0);
+      stp->smp_ticket = 0;
+      const int nt = t + 1;
+      stp->t = nt;
+      stp->n_unfinished = nu;
+      if (nu == 0 || nt >= stp->max_steps) { stp->done = 1; stp->out_len = nt + 1; }
+    }
+  }
+}
+
+static int launch_dec_sample(const DecHeadArgs& h, const SampleParams* sp, hipStream_t st) {
+  M2M_REQUIRE(h.V >= 1 && h.V <= SAMPLE_MAX_VOCAB, "dec_sample_kernel: vocab_size %d outside [1, %d]", h.V, SAMPLE_MAX_VOCAB);
+  const dim3 grid((unsigned)ceil_div(h.B, SAMPLE_ROWS)), block(64 * SAMPLE_ROWS);
+  if (h.V <= 64 * 8) hipLaunchKernelGGL(dec_sample_kernel<8>, grid, block, 0, st, h, sp);
+  else if (h.V <= 64 * 16) hipLaunchKernelGGL(dec_sample_kernel<16>, grid, block, 0, st, h, sp);
+  else if (h.V <= 64 * 32) hipLaunchKernelGGL(dec_sample_kernel<32>, grid, block, 0, st, h, sp);
+  else hipLaunchKernelGGL(dec_sample_kernel<64>, grid, block, 0, st, h, sp);
+  M2M_CHECK_HIP(hipGetLastError());
+  return M2M_OK;
+}
+
 // ============================================================ live-row re-packing ====
 // Clips end at different steps (a real checkpoint ends a 3 s segment after tens to hundreds of its 1 024 tokens).  The finished-row
 // early-out above stops a finished row's K/V stream, but its workgroups still launch and the chain still pays its latency floor for
@@ -1974,6 +2146,8 @@ int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int 
 
 // ============================================================ step driver ====
 static xq_t* xbuf(m2m_session* s, const DecView& v, int which);
+// the headless fold is a greedy-only form: the sampling head keeps its own kernel (the step of M2M_HEADLESS=0)
+static bool headless_for(const m2m_session* s, bool forced) { return !forced && s->head_mode == HEAD_GREEDY && decode_headless(); }
 // All per-clip buffers are [B][...] with the clip index outermost, so a view is a pointer offset.
 static DecHeadArgs head_args(m2m_session* s, const DecView& v, bool forced, float* logits_out, int Ld) {
   const m2m_model* m = s->m;
@@ -1982,14 +2156,14 @@ static DecHeadArgs head_args(m2m_session* s, const DecView& v, bool forced, floa
   h.d = m->g.d_model; h.shared = m->shared; h.x = xbuf(s, v, 0); h.x_zero = xbuf(s, v, 1);
   h.tokens = s->tokens; h.tok_row = s->tok_row + v.b0; h.row0 = v.b0; h.max_len = s->max_dec;
   h.finished = s->finished + v.b0; h.state = v.state; h.pad_id = m->g.pad_token_id; h.eos_id = m->g.eos_token_id;
-  h.keys = (!forced && decode_headless()) ? s->keys + v.b0 : nullptr;
+  h.keys = headless_for(s, forced) ? s->keys + v.b0 : nullptr;
   h.forced = forced ? s->forced_ids + (int64_t)v.b0 * Ld : nullptr; h.Ld = Ld;
   h.logits_out = logits_out ? logits_out + (int64_t)v.b0 * Ld * m->g.vocab_size : nullptr;
   return h;
 }
 
 int decode_finalize(m2m_session* s, const DecView& v, hipStream_t st) {
-  if (!decode_headless()) return M2M_OK;
+  if (!headless_for(s, false)) return M2M_OK;
   DecHeadArgs h = head_args(s, v, false, nullptr, 0);
   hipLaunchKernelGGL(dec_final_kernel, dim3(1), dim3(256), 0, st, h);
   M2M_CHECK_HIP(hipGetLastError());
@@ -2105,7 +2279,7 @@ int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* log
   xq_t* xB = xbuf(s, v, 1);
   xq_t* xC = xbuf(s, v, 2);
   int rc;
-  const bool headless = !forced && decode_headless();
+  const bool headless = headless_for(s, forced);
   for (int l = 0; l < g.num_decoder_layers; ++l) {
     const DecLayerPacked& L = m->dec[l];
     // 1. RMSNorm + per-head QKV projection + KV-cache append + causal self-attention + per-head
@@ -2131,6 +2305,7 @@ int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* log
   if ((rc = launch_dec_gemm(P, a, st))) return rc;
   if (headless) return M2M_OK;             // the arg-max key is consumed by the next step's layer 0 (or by decode_finalize)
   DecHeadArgs h = head_args(s, v, forced, logits_out, Ld);
+  if (!forced && s->head_mode == HEAD_SAMPLE) return launch_dec_sample(h, s->sample_dev, st);
   hipLaunchKernelGGL(dec_head_kernel, dim3(1), dim3(1024), 0, st, h);
   M2M_CHECK_HIP(hipGetLastError());
   return M2M_OK;

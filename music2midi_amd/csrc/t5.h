@@ -65,6 +65,18 @@ struct DecState {
   int t_copy;        // headless greedy loop: t of the current step, rewritten every step by the layer-0 cross kernel (the lm_head
                      // kernel, which ADVANCES t at its end, reads this stable copy instead of t itself)
   int zero;          // always 0 (cleared with the rest of the state, never written): what a "never skip" row flag points at
+  int smp_unfinished;  // sampling head (several workgroups per step): unfinished rows summed over the workgroups of the step ...
+  int smp_ticket;      // ... and workgroups done; the last one closes the step and clears both
+};
+
+// Parameters of the sampling head (dec_sample_kernel), a device block of the session workspace: written with an async copy before
+// every m2m_generate_sample, so one captured graph serves every call and every seed.
+struct SampleParams {
+  float temperature;        // > 0; 1 = no scaling
+  int top_k;                // 0 = no top-k filter
+  float top_p;              // [0, 1]; 1 = no nucleus filter
+  int pad_;
+  unsigned long long seed;  // the call's seed: the draw of clip row r at position t hashes (seed, r, t)
 };
 
 }  // namespace m2m
@@ -107,10 +119,10 @@ struct DecGroup {
   hipStream_t stream = nullptr;
   hipEvent_t ev_done = nullptr;
   hipGraphExec_t graph_exec = nullptr;           // the graph of the current view (an entry of `graphs`)
-  // captured graphs by (B, S, b0, nb, steps per graph, finished-row skip on / off) — all baked into the launches.  Re-packing the live
+  // captured graphs by (B, S, b0, nb, steps per graph, finished-row skip on / off, head form) — all baked into the launches.  Re-packing the live
   // rows changes (b0, nb) several times per batch, and the next batch starts from the full views again: a small cache instead of
   // a re-capture (~1 ms per 8-step graph) at every change
-  struct GraphEntry { int key[6]; hipGraph_t graph; hipGraphExec_t exec; unsigned long long used; };
+  struct GraphEntry { int key[7]; hipGraph_t graph; hipGraphExec_t exec; unsigned long long used; };
   std::vector<GraphEntry> graphs;
   unsigned long long graph_clock = 0;
 };
@@ -151,7 +163,10 @@ struct m2m_session {
   int attn_clips_self = 0; // M2M_DA_CLIPS_SELF (diagnostic): clips per self-attention workgroup when it should differ from the cross kernels
   int ff_rows = 0;         // decode feed-forward: residual rows per workgroup forced by M2M_DEC_FF_ROWS (0: by chain size)
   int ff_slices = 0;       // decode feed-forward: hidden slices per workgroup forced by M2M_DEC_FF_SLICES (0: by chain size)
-  int repacks = 0, rows_moved = 0;   // live-row re-packings / rows moved by them in the last m2m_generate_greedy
+  int repacks = 0, rows_moved = 0;   // live-row re-packings / rows moved by them in the last m2m_generate_greedy / _sample
+  int head_mode = 0;       // head form of the free-running decode step: 0 greedy (arg-max), 1 sampling (set for the length of a call)
+  m2m::SampleParams* sample_dev = nullptr;    // [1] in the workspace
+  m2m::SampleParams* sample_host = nullptr;   // pinned staging copy
   bool encoded = false;
   // decode chains
   hipEvent_t ev_in = nullptr;
@@ -246,6 +261,8 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
 int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int t, hipStream_t st);   // live-row re-packing (decode.hip)
 int decode_finalize(m2m_session* s, const DecView& v, hipStream_t st);   // headless greedy loop: write the last token, close the chain
 bool decode_headless();
+constexpr int HEAD_GREEDY = 0, HEAD_SAMPLE = 1;
+constexpr int SAMPLE_MAX_VOCAB = 4096;   // dec_sample_kernel keeps a row in the registers of one wavefront (64 lanes x 64 logits)
 int decode_attn_clips(const m2m_session* s, int nb);
 int decode_ff_rows(const m2m_session* s, int nb);
 int decode_ff_slices(const m2m_session* s, int nb);

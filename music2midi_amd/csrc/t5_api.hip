@@ -182,7 +182,7 @@ extern "C" int m2m_model_checksum(const m2m_model* m, uint64_t* out_host, void* 
 namespace {
 struct WsLayout {
   int64_t x_enc, h_enc, qkv_enc, vt_enc, attn_enc, mid_enc, enc_bias, dec_bias, dec_bias_full, cross_vt, cross_kv, self_k, self_v;
-  int64_t x_dec, logits, tokens, finished, tok_row, keys, state, forced, total;
+  int64_t x_dec, logits, tokens, finished, tok_row, keys, state, forced, sample, total;
 };
 
 WsLayout ws_layout(const m2m_model* m, int B, int S, int L) {
@@ -214,6 +214,7 @@ WsLayout ws_layout(const m2m_model* m, int B, int S, int L) {
   w.keys = take((int64_t)B * 8);
   w.state = take(sizeof(DecState) * MAX_GROUPS);
   w.forced = take((int64_t)B * L * 8);
+  w.sample = take(sizeof(SampleParams));
   w.total = off;
   return w;
 }
@@ -267,6 +268,7 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   s->x_dec = (b + w.x_dec);
   s->logits = (float*)(b + w.logits); s->tokens = (int64_t*)(b + w.tokens);
   s->finished = (int*)(b + w.finished); s->tok_row = (int*)(b + w.tok_row); s->keys = (unsigned long long*)(b + w.keys); s->states = (DecState*)(b + w.state); s->forced_ids = (int64_t*)(b + w.forced);
+  s->sample_dev = (SampleParams*)(b + w.sample);
 
   // relative-position bias tables (fp32), built on the host from the bucket function
   const m2m_t5_geometry& g = m->g;
@@ -300,6 +302,7 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   if (e == hipSuccess) e = hipMemcpy(s->dec_bias_full_tab, df.data(), df.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemset(s->states, 0, sizeof(DecState) * MAX_GROUPS);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s->sample_host, sizeof(SampleParams), hipHostMallocDefault);
   for (int i = 0; i < MAX_GROUPS && e == hipSuccess; ++i) {
     DecGroup& gr = s->groups[i];
     gr.view.state = s->states + i;
@@ -350,6 +353,7 @@ extern "C" void m2m_session_destroy(m2m_session* s) {
     if (gr.state_host) (void)hipHostFree(gr.state_host);
   }
   if (s->ev_in) (void)hipEventDestroy(s->ev_in);
+  if (s->sample_host) (void)hipHostFree(s->sample_host);
   delete s;
 }
 
@@ -444,7 +448,7 @@ static int plan_groups(m2m_session* s, int rows = -1) {       // rows: the packe
 // One graph = `steps` consecutive decode steps of one chain (kernels read the step index from
 // device memory, so the same graph replays for every position; steps past the end are no-ops).
 static int ensure_graph(m2m_session* s, DecGroup& gr, int steps) {
-  const int key[6] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, decode_finished_skip_on() ? 1 : 0};
+  const int key[7] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, decode_finished_skip_on() ? 1 : 0, s->head_mode};
   ++gr.graph_clock;
   for (auto& ge : gr.graphs)
     if (memcmp(key, ge.key, sizeof(key)) == 0) { ge.used = gr.graph_clock; gr.graph_exec = ge.exec; return M2M_OK; }
@@ -484,7 +488,7 @@ static void quiesce(m2m_session* s, hipStream_t caller) {
   (void)hipGetLastError();
 }
 
-static int generate_greedy_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev, int* out_len_host, hipStream_t caller);
+static int generate_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev, int* out_len_host, hipStream_t caller, const char* fn);
 
 // why a call that needs the encoded state finds none: never encoded, or the last greedy decode re-packed its live rows over it
 static const char* encode_missing(const m2m_session* s) {
@@ -497,12 +501,42 @@ extern "C" int m2m_generate_greedy(m2m_session* s, int max_length, int64_t* toke
   M2M_REQUIRE(s && tokens_out_dev && out_len_host, "m2m_generate_greedy: null argument");
   if (!s->encoded) { set_error("m2m_generate_greedy: %s", encode_missing(s)); return M2M_ERR_STATE; }
   M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_greedy: max_length %d outside [1, %d]", max_length, s->max_dec);
-  const int rc = generate_greedy_impl(s, max_length, tokens_out_dev, out_len_host, (hipStream_t)stream);
+  const int rc = generate_impl(s, max_length, tokens_out_dev, out_len_host, (hipStream_t)stream, "m2m_generate_greedy");
   if (rc != M2M_OK) quiesce(s, (hipStream_t)stream);
   return rc;
 }
 
-static int generate_greedy_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev, int* out_len_host, hipStream_t caller) {
+extern "C" int m2m_generate_sample(m2m_session* s, int max_length, const m2m_sample_params* p, int64_t* tokens_out_dev,
+                                   int* out_len_host, void* stream) {
+  M2M_REQUIRE(s && p && tokens_out_dev && out_len_host, "m2m_generate_sample: null argument");
+  M2M_REQUIRE(isfinite(p->temperature) && p->temperature > 0.f,
+              "m2m_generate_sample: temperature must be a strictly positive finite float, got %g", (double)p->temperature);
+  M2M_REQUIRE(p->top_k >= 0, "m2m_generate_sample: top_k must be >= 0 (0 disables the filter), got %d", p->top_k);
+  M2M_REQUIRE(p->top_p >= 0.f && p->top_p <= 1.f, "m2m_generate_sample: top_p must be a float in [0, 1], got %g", (double)p->top_p);
+  M2M_REQUIRE(s->m->g.vocab_size <= SAMPLE_MAX_VOCAB, "m2m_generate_sample: vocab_size %d > %d (the sampling head keeps a row in one "
+              "wavefront's registers)", s->m->g.vocab_size, SAMPLE_MAX_VOCAB);
+  if (!s->encoded) { set_error("m2m_generate_sample: %s", encode_missing(s)); return M2M_ERR_STATE; }
+  M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_sample: max_length %d outside [1, %d]", max_length, s->max_dec);
+  hipStream_t caller = (hipStream_t)stream;
+  // the parameters reach the captured graphs through their device block, ordered before the chains by generate_impl's event
+  s->sample_host->temperature = p->temperature; s->sample_host->top_k = p->top_k; s->sample_host->top_p = p->top_p;
+  s->sample_host->pad_ = 0; s->sample_host->seed = (unsigned long long)p->seed;
+  int rc = M2M_OK;
+  if (hipMemcpyAsync(s->sample_dev, s->sample_host, sizeof(SampleParams), hipMemcpyHostToDevice, caller) != hipSuccess) {
+    set_error("m2m_generate_sample: hipMemcpyAsync: %s", hipGetErrorString(hipGetLastError()));
+    rc = M2M_ERR_HIP;
+  }
+  if (rc == M2M_OK) {
+    s->head_mode = HEAD_SAMPLE;
+    rc = generate_impl(s, max_length, tokens_out_dev, out_len_host, caller, "m2m_generate_sample");
+    s->head_mode = HEAD_GREEDY;
+  }
+  if (rc != M2M_OK) quiesce(s, caller);
+  return rc;
+}
+
+// the free-running decode loop of both head forms (s->head_mode); fn names the entry point in error messages
+static int generate_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev, int* out_len_host, hipStream_t caller, const char* fn) {
   const int steps = max_length - 1;
   int G = plan_groups(s);
   const bool graph = use_graph();
@@ -570,7 +604,7 @@ static int generate_greedy_impl(m2m_session* s, int max_length, int64_t* tokens_
           if (hs.done) { if (hs.out_len > out_len) out_len = hs.out_len; }
           else t_cur = hs.t;
         }
-        M2M_REQUIRE(t_cur >= 0, "m2m_generate_greedy: no running chain at a re-packing point");
+        M2M_REQUIRE(t_cur >= 0, "%s: no running chain at a re-packing point", fn);
         mv_src.clear(); mv_dst.clear();
         for (int hole = 0, tail = live; hole < live; ++hole) {    // finished slots in front take the live rows from behind the packed range
           if (!fin_host[(size_t)hole]) continue;
@@ -618,8 +652,8 @@ static int generate_greedy_impl(m2m_session* s, int max_length, int64_t* tokens_
   M2M_CHECK_HIP(hipStreamSynchronize(caller));
   *out_len_host = out_len;
   if (range_error) {
-    set_error("m2m_generate_greedy: a decoder activation left the fixed-point residual range (|x| >= 2^21) or was not finite; "
-              "the fp32 reference would produce Inf/NaN logits here - token ids are not valid (check the checkpoint)");
+    set_error("%s: a decoder activation left the fixed-point residual range (|x| >= 2^21) or was not finite; "
+              "the fp32 reference would produce Inf/NaN logits here - token ids are not valid (check the checkpoint)", fn);
     return M2M_ERR_RANGE;
   }
   return M2M_OK;

@@ -54,6 +54,10 @@ class T5Weights(C.Structure):
                 ("enc", C.POINTER(EncLayerWeights)), ("dec", C.POINTER(DecLayerWeights))]
 
 
+class SampleParams(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64)]
+
+
 class TensorInfo(C.Structure):
     _fields_ = [("name", C.c_char * 160), ("offset", C.c_int64), ("rows", C.c_int), ("cols", C.c_int)]
 
@@ -84,6 +88,8 @@ _SIGNATURES = {
     "m2m_session_destroy": (None, [C.c_void_p]),
     "m2m_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "m2m_generate_greedy": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
+    "m2m_generate_sample": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SampleParams), C.c_void_p, C.POINTER(C.c_int),
+                                      C.c_void_p]),
     "m2m_session_repack_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "m2m_decode_forced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "m2m_trainer_create": (C.c_int, [C.POINTER(T5GeometryC), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,

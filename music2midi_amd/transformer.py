@@ -6,8 +6,8 @@ entry points: ``forward(ModelInputs) -> output with .loss/.logits`` and
 ``generate(ModelInputs, **kwargs) -> LongTensor [B, L]``.  The parameters live in
 a module tree whose ``state_dict()`` keys equal HuggingFace T5's, so a reference
 checkpoint loads unchanged; the arithmetic runs in the HIP library (encoder,
-cross-K/V projection, graph-replayed greedy decode) — there is no torch compute
-path and no CPU fallback.
+cross-K/V projection, graph-replayed greedy or sampled decode) — there is no torch
+compute path and no CPU fallback.
 """
 from __future__ import annotations
 
@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import native
 from .config import T5Geometry, load_config
+from .generation import GenerateConfig, resolve_generate_kwargs
 from .input import Conditioning, LogMelSpectrogram, ModelInputs
 from .tokenizer import MidiTokenizer
 
@@ -317,7 +318,14 @@ class T5Transformer(nn.Module):
             return out
 
     @torch.no_grad()
-    def generate_from_embeds(self, inputs_embeds: torch.Tensor, max_length: int = 20) -> torch.Tensor:
+    def generate_from_embeds(self, inputs_embeds: torch.Tensor, max_length: int = 20, **kwargs) -> torch.Tensor:
+        """Decode from encoder inputs [B, S, d].  Keywords as :meth:`generate` (``do_sample``, ``temperature``, ``top_k``,
+        ``top_p``, ``num_return_sequences``); without ``do_sample=True`` this is the greedy decode."""
+        if kwargs:
+            cfg = resolve_generate_kwargs(kwargs, default_max_length=max_length)
+            if cfg.do_sample:
+                return self._generate_sample(inputs_embeds, cfg)
+            max_length = cfg.max_length
         with self._lock:
             x = inputs_embeds.to(self.transformer.device, torch.float32).contiguous()
             sess, _ = self._encode(x, max_length)
@@ -326,6 +334,24 @@ class T5Transformer(nn.Module):
             with torch.cuda.device(x.device):
                 native.check(native.load().m2m_generate_greedy(sess, max_length, tokens.data_ptr(), C.byref(out_len),
                                                                native.stream_handle(x.device)), "m2m_generate_greedy")
+            return tokens[:, : out_len.value]
+
+    def _generate_sample(self, inputs_embeds: torch.Tensor, cfg: GenerateConfig) -> torch.Tensor:
+        # the call's seed: one draw from torch's default CPU generator, so torch.manual_seed(n) makes the call reproducible
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        with self._lock:
+            x = inputs_embeds.to(self.transformer.device, torch.float32)
+            if cfg.num_return_sequences > 1:      # HF's expansion: the n sequences of a clip are consecutive rows
+                x = x.repeat_interleave(cfg.num_return_sequences, dim=0)
+            x = x.contiguous()
+            max_length = cfg.max_length
+            sess, _ = self._encode(x, max_length)
+            tokens = torch.empty((x.shape[0], max_length), dtype=torch.long, device=x.device)
+            out_len = C.c_int(0)
+            p = native.SampleParams(cfg.temperature, cfg.top_k, cfg.top_p, seed)
+            with torch.cuda.device(x.device):
+                native.check(native.load().m2m_generate_sample(sess, max_length, C.byref(p), tokens.data_ptr(), C.byref(out_len),
+                                                               native.stream_handle(x.device)), "m2m_generate_sample")
             return tokens[:, : out_len.value]
 
     @torch.no_grad()
@@ -342,7 +368,7 @@ class T5Transformer(nn.Module):
             return logits
 
     def repack_stats(self):
-        """(re-packings, rows moved) of the last greedy decode on the current session: how often the live rows were moved into
+        """(re-packings, rows moved) of the last greedy or sampled decode on the current session: how often the live rows were moved into
         the first slots after a quarter of them had emitted EOS (``m2m_session_repack_stats``)."""
         with self._lock:
             if self._session is None:
@@ -388,12 +414,19 @@ class T5Transformer(nn.Module):
     _GENERATE_DEFAULT_MAX_LENGTH = 20   # HF GenerationConfig default when max_length is not given
 
     def generate(self, inputs: ModelInputs, **kwargs) -> torch.Tensor:
-        """Greedy decode (ref transformer.py:41-45).  The reference only ever passes
-        ``max_length`` (ref model.py:58,134); sampling/beam arguments are rejected loudly."""
-        max_length = int(kwargs.pop("max_length", self._GENERATE_DEFAULT_MAX_LENGTH))
-        if kwargs.pop("do_sample", False) or int(kwargs.pop("num_beams", 1)) != 1:
-            raise NotImplementedError("only greedy decoding is implemented on the MI355X path")
-        if kwargs:
-            raise NotImplementedError(f"unsupported generate kwargs on the MI355X path: {sorted(kwargs)}")
+        """Decode (ref transformer.py:41-45, which forwards every keyword to HF ``generate``).
+
+        Greedy by default (``do_sample=False``; the reference itself only ever passes ``max_length``, ref
+        model.py:58,134).  ``do_sample=True`` samples with transformers 4.34's logits warpers and defaults:
+        ``temperature=1.0``, ``top_k=50``, ``top_p=1.0`` (``top_k=0`` / ``top_p=1.0`` disable a filter), and
+        ``num_return_sequences=n`` returns n sequences per clip as consecutive rows ([B * n, L], HF's order) - the clips
+        are repeated before the encoder, so that costs n encoder passes per clip.  The call's seed is one
+        ``torch.randint`` from torch's default CPU generator, so ``torch.manual_seed`` makes a call reproducible; the ids
+        are NOT HF's samples for the same seed (the draws come from a counter-based hash on the GPU, not torch's
+        generator).  Invalid sampling values raise ``ValueError``; beam search (``num_beams != 1``) and any other
+        keyword raise ``NotImplementedError``."""
+        cfg = resolve_generate_kwargs(kwargs, default_max_length=self._GENERATE_DEFAULT_MAX_LENGTH)
         encoder_inputs = self.encoder_inputs(inputs)
-        return self.generate_from_embeds(encoder_inputs, max_length=max_length)
+        if cfg.do_sample:
+            return self._generate_sample(encoder_inputs, cfg)
+        return self.generate_from_embeds(encoder_inputs, max_length=cfg.max_length)
