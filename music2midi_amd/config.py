@@ -174,6 +174,11 @@ class T5Geometry:
         dst = g.get("decoder_start_token_id")
         self.decoder_start_token_id = int(dst) if dst is not None else self.pad_token_id
         self.bos_token_id = g.get("bos_token_id")
+        for name in ("pad_token_id", "eos_token_id", "decoder_start_token_id"):
+            v = getattr(self, name)
+            if not 0 <= v < self.vocab_size:
+                # the device path reads the embedding row of these ids (an out-of-range token decodes as pad)
+                raise ValueError(f"{name}={v} must lie in [0, vocab_size={self.vocab_size})")
         ffp = str(g["feed_forward_proj"])
         if ffp not in ("gated-gelu",):
             # The reference only ever configures gated-gelu (ref: config.yaml:22);

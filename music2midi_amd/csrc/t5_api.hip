@@ -47,6 +47,11 @@ extern "C" int m2m_model_create(const m2m_t5_geometry* geom, const m2m_t5_weight
   M2M_REQUIRE((g.num_heads * g.d_kv) % 128 == 0 && g.num_heads * g.d_kv <= 1152, "m2m_model_create: num_heads*d_kv=%d must be a multiple of 128, <= 1152", g.num_heads * g.d_kv);
   M2M_REQUIRE(g.num_heads >= 1 && g.num_layers >= 1 && g.num_decoder_layers >= 1 && g.vocab_size >= 2,
               "m2m_model_create: bad geometry");
+  // the decode kernels map an out-of-range token to pad_token_id and read its embedding row: every special id must be a row
+  M2M_REQUIRE(g.pad_token_id >= 0 && g.pad_token_id < g.vocab_size && g.eos_token_id >= 0 && g.eos_token_id < g.vocab_size &&
+                  g.decoder_start_token_id >= 0 && g.decoder_start_token_id < g.vocab_size,
+              "m2m_model_create: pad_token_id=%d, eos_token_id=%d and decoder_start_token_id=%d must lie in [0, vocab_size=%d)",
+              g.pad_token_id, g.eos_token_id, g.decoder_start_token_id, g.vocab_size);
   M2M_REQUIRE(g.num_buckets >= 4 && g.num_buckets % 2 == 0 && g.max_distance > g.num_buckets / 2,
               "m2m_model_create: bad relative-attention geometry");
   M2M_REQUIRE(w->shared && w->lm_head && w->enc_rel_bias && w->dec_rel_bias && w->enc_final_ln && w->dec_final_ln &&

@@ -3201,7 +3201,10 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
   RC(o.begin_sub(0));
   RC(o.dW(t->dlog, ldv, V, t->hD, d, d, G + t->o_lm, Md));                                        // dW_lm = dlogits^T . hD
   RC(o.end_sub());
-  RC(o.dX(TG_STORE_F32, t->dlog, ldv, t->o_lm, V, d, t->dh, d, Md));                              // dhD = dlogits . W_lm
+  // dhD = dlogits . W_lm: an NT product against the transposed copy, whose rows are V long; when V is no multiple of the product's
+  // 16-byte row unit that copy cannot be an operand, and the product reads W_lm itself k-major ([V][d] rows, d % 64 == 0)
+  if (V % (t->precision == M2M_PREC_BF16 ? 8 : 4) == 0) RC(o.dX(TG_STORE_F32, t->dlog, ldv, t->o_lm, V, d, t->dh, d, Md));
+  else RC(o.mm(TG_STORE_F32, t->dlog, ldv, 0, o.W(t->o_lm), d, 1, t->dh, d, Md, d, V));
   float* dcur = t->dxa;
   float* dnext = t->dxb;
   o.after_site = SITE_DEC + 16 * (Ld - 1) + PL_FF_OUT;
@@ -3348,6 +3351,11 @@ extern "C" int m2m_trainer_create(const m2m_t5_geometry* geom, int n_cond, const
   }
   M2M_REQUIRE(geom->d_kv == DK, "m2m_trainer_create: d_kv=%d unsupported (64 only)", geom->d_kv);
   M2M_REQUIRE(geom->d_model % 64 == 0 && geom->d_model <= 512 && geom->d_ff % 8 == 0, "m2m_trainer_create: d_model must be a multiple of 64 (<= 512), d_ff of 8");
+  // the embedding kernels map an ignored label (-100) to pad_token_id and read its row: every special id must be a row
+  M2M_REQUIRE(geom->vocab_size >= 2 && geom->pad_token_id >= 0 && geom->pad_token_id < geom->vocab_size && geom->eos_token_id >= 0 &&
+                  geom->eos_token_id < geom->vocab_size && geom->decoder_start_token_id >= 0 && geom->decoder_start_token_id < geom->vocab_size,
+              "m2m_trainer_create: pad_token_id=%d, eos_token_id=%d and decoder_start_token_id=%d must lie in [0, vocab_size=%d)",
+              geom->pad_token_id, geom->eos_token_id, geom->decoder_start_token_id, geom->vocab_size);
   M2M_REQUIRE(n_cond >= 0 && n_cond <= 8 && max_batch >= 1 && max_enc_len > n_cond && max_dec_len >= 1, "m2m_trainer_create: bad sizes");
   // embed_bwd_kernel keeps the pass's whole id list in LDS (embed_bwd_smem: 4 bytes per label position + 16 KiB against the 158 KiB opt-in)
   M2M_REQUIRE(embed_bwd_smem(max_batch * max_dec_len) <= (size_t)158 * 1024,

@@ -62,6 +62,64 @@ def test_relative_position_buckets_match_pinned_tables_and_hf_formula():
             assert lib.m2m_rel_bucket(-n, 0, 32, 128) == b, (n, b)
 
 
+@pytest.mark.parametrize("num_buckets,max_distance", [(4, 3), (6, 4), (8, 16), (8, 64), (16, 20), (32, 33), (32, 128), (64, 256),
+                                                       (128, 1024)])
+def test_relative_position_buckets_match_the_oracle_at_other_bucket_geometries(num_buckets, max_distance):
+    """m2m_rel_bucket (which the session's bias tables and their constant far range are built from) against the oracle's HF
+    formula over rel in [-3000, 3000], both directions: small tables where nearly every distance is in the log range, float32 logs
+    landing on integers (e.g. 16 / 20: log(n / 4) / log(5) * 4 is integral at n = 20, 100, 500, 2500)"""
+    lib = native.load()
+    from oracle.t5 import relative_position_bucket as rpb
+    rel = torch.arange(-3000, 3001)
+    for bidir in (1, 0):
+        got = torch.tensor([lib.m2m_rel_bucket(int(r), bidir, num_buckets, max_distance) for r in rel])
+        want = rpb(rel, bool(bidir), num_buckets, max_distance)
+        bad = (got != want).nonzero().flatten()
+        assert bad.numel() == 0, [(int(rel[i]), int(got[i]), int(want[i])) for i in bad[:8]]
+        assert int(got.max()) == num_buckets - 1 and int(got.min()) == 0
+
+
+def _geometry_c(**kw):
+    g = dict(d_model=128, d_ff=256, num_layers=2, num_decoder_layers=2, num_heads=2, d_kv=64, vocab_size=513, num_buckets=32,
+             max_distance=128, pad_token_id=0, eos_token_id=2, decoder_start_token_id=1)
+    g.update(kw)
+    return native.T5GeometryC(*g.values(), 1e-6)
+
+
+@pytest.mark.parametrize("ids", [dict(pad_token_id=513), dict(pad_token_id=-1), dict(eos_token_id=513), dict(eos_token_id=-2),
+                                 dict(decoder_start_token_id=513), dict(decoder_start_token_id=-1), dict(vocab_size=2)])
+def test_special_token_ids_outside_the_vocabulary_are_refused_at_create_time(ids):
+    """The decode kernels map an out-of-range token to pad_token_id and read its embedding row; the trainer reads the pad row for
+    ignored labels.  Every special id outside [0, vocab_size) is refused by both create functions (before anything is allocated or
+    launched) and by T5Geometry."""
+    lib = native.load()
+    weights = native.T5Weights()
+    model = C.c_void_p()
+    geom = _geometry_c(**ids)
+    assert lib.m2m_model_create(C.byref(geom), C.byref(weights), 0, None, C.byref(model)) == -1
+    assert b"must lie in [0, vocab_size" in lib.m2m_last_error(), lib.m2m_last_error()
+    trainer = C.c_void_p()
+    rows = (C.c_int * 2)(6, 3)
+    assert lib.m2m_trainer_create(C.byref(geom), 2, rows, 0, 2, 40, 16, C.byref(trainer)) == -1
+    assert b"must lie in [0, vocab_size" in lib.m2m_last_error(), lib.m2m_last_error()
+    assert not model.value and not trainer.value
+    t5 = {**DEFAULT_CONFIG["model"]["t5"], "vocab_size": 513, **ids}
+    with pytest.raises(ValueError, match=r"must lie in \[0, vocab_size"):
+        T5Geometry(t5)
+
+
+def test_special_token_ids_inside_the_vocabulary_pass_the_check():
+    """the same check at its edges (every id at 0 or V - 1) lets the create function go on to its next check (null weights)"""
+    lib = native.load()
+    weights = native.T5Weights()
+    model = C.c_void_p()
+    for ids in (dict(pad_token_id=512, eos_token_id=0, decoder_start_token_id=512), dict(vocab_size=3, eos_token_id=2, decoder_start_token_id=1)):
+        geom = _geometry_c(**ids)
+        assert lib.m2m_model_create(C.byref(geom), C.byref(weights), 0, None, C.byref(model)) == -1
+        assert b"null weight pointer" in lib.m2m_last_error(), lib.m2m_last_error()
+        T5Geometry({**DEFAULT_CONFIG["model"]["t5"], "vocab_size": 513, **ids})
+
+
 # ------------------------------------------------------------------ config
 def test_config_access_styles_match_omegaconf_usage(tmp_path):
     import yaml

@@ -235,18 +235,26 @@ def test_sampled_distribution_matches_the_warped_softmax(setting):
     n_rows, seeds = 256, 8
     draws = torch.cat([_sample(model, x1.repeat(n_rows, 1, 1), 2, 1000 + s, temperature=T, top_k=k, top_p=p)[:, 1]
                        for s in range(seeds)])
+    assert draws.numel() == 2048
+    l1 = assert_draws_follow(probs, draws)
+    print(f"{setting}: T={T:.2f} H={H:.2f} bits, support {int((probs > 0).sum())}, L1 {l1:.4f} (bound 0.16)")
+
+
+def assert_draws_follow(probs, draws):
+    """2048 draws against the warped softmax `probs` [V]: every draw in its support, and the histogram over 16 bins (the 15 most likely
+    tokens + the rest) within the L1 bound of Weissman et al. (2003) that a correct sampler exceeds with probability < 1e-6; -> L1"""
     n = draws.numel()
     assert n == 2048
     assert bool((probs[draws] > 0).all()), "a draw outside the warped support"
     top = torch.argsort(probs, descending=True)[:15]
-    emp = torch.bincount(draws, minlength=g.vocab_size).double() / n
+    emp = torch.bincount(draws, minlength=probs.numel()).double() / n
     bins_p = torch.cat([probs[top], (1 - probs[top].sum()).clamp_min(0)[None]])
     bins_e = torch.cat([emp[top], (1 - emp[top].sum()).clamp_min(0)[None]])
     m, eps = 16, 0.16
     assert (2 ** m - 2) * math.exp(-n * eps * eps / 2) < 1e-6
     l1 = float((bins_p - bins_e).abs().sum())
-    print(f"{setting}: T={T:.2f} H={H:.2f} bits, support {int((probs > 0).sum())}, L1 {l1:.4f} (bound {eps})")
     assert l1 < eps, l1
+    return l1
 
 
 # ----------------------------------------------------------------------------------------------------------------------------
