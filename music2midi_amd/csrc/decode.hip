@@ -1382,7 +1382,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
 #pragma unroll
   for (int st = 0; st < CIF; ++st) {
     const unsigned mine = walk & (SETBITS << st);
-    const int c_first = mine ? __builtin_ctz(mine) : st;
+    // a set without a walking clip re-reads a clip of the workgroup (dropped), never one past the chain's end: that lies outside the
+    // descriptors' span, and their range check sees the lane offset only, not the clip's scalar offset (clip 0 always exists)
+    const int c_first = mine ? __builtin_ctz(mine) : (st == 0 ? 0 : min(st, min(C, nb - b0) - 1));
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
       const unsigned off = (unsigned)((min(kslot + u * KPB, last) * DK + sub * E) * (int)sizeof(T));
@@ -1695,14 +1697,14 @@ static void launch_dec_attn_t(bool self, bool nt, const DecAttnArgs& a, dim3 gri
 
 // several clips per workgroup (dec_attn_mc_kernel): C = 2 or 4
 template <typename T, int C>
-static void launch_dec_attn_mc_t(bool self, bool nt, const DecAttnArgs& a, int nb, size_t smem, hipStream_t st) {
+static void launch_dec_attn_mc_t(bool self, bool nt, const DecAttnArgs& a, int nb, int cif, size_t smem, hipStream_t st) {
   const dim3 grid((unsigned)a.H, (unsigned)ceil_div(nb, C));
-  // M2M_MC_CIF=2 (diagnostic): two clips in flight in the cross-attention.  At S = 190 a clip's whole stream is one round trip, so the
-  // kernel is C dependent round trips long and two register-slot sets overlap them - on paper 14 -> ~10.5 us per launch; measured on
-  // one box (tools/native_mc_sweep.py, us per step, one / two in flight): 2 x 64 clips bf16 340.6 / 338.9 against 351.4 / 350.9,
-  // fp32 577.2 against 591.9, 2 x 32 clips 220.4 against 226.6, 2 x 64 at S = 864 480.9 against 485.0.  One in flight.
-  static const int cif_env = [] { const char* v = getenv("M2M_MC_CIF"); return v ? atoi(v) : -1; }();
-  const bool two_in_flight = !self && cif_env == 2;
+  // M2M_MC_CIF=2 (diagnostic, latched per session): two clips in flight in the cross-attention.  At S = 190 a clip's whole stream is
+  // one round trip, so the kernel is C dependent round trips long and two register-slot sets overlap them - on paper 14 -> ~10.5 us
+  // per launch; measured on one box (tools/native_mc_sweep.py, us per step, one / two in flight): 2 x 64 clips bf16 340.6 / 338.9
+  // against 351.4 / 350.9, fp32 577.2 against 591.9, 2 x 32 clips 220.4 against 226.6, 2 x 64 at S = 864 480.9 against 485.0.  One
+  // in flight.
+  const bool two_in_flight = !self && cif == 2;
   if (self && a.emb) {
     if (nt) hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, true, true, C>), grid, dim3(1024), smem, st, a, nb);
     else hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, false, true, C>), grid, dim3(1024), smem, st, a, nb);
@@ -1718,7 +1720,7 @@ static void launch_dec_attn_mc_t(bool self, bool nt, const DecAttnArgs& a, int n
   }
 }
 
-static int launch_dec_attn(int precision, bool self, bool nt, DecAttnArgs a, int B, int clips, hipStream_t st) {
+static int launch_dec_attn(int precision, bool self, bool nt, DecAttnArgs a, int B, int clips, int cif, hipStream_t st) {
   const size_t smem = ((size_t)a.d * (size_t)clips + (self ? (size_t)a.bias_stride : 0)) * sizeof(float);   // hn rows + (self) the bias row
   M2M_REQUIRE(smem <= 24 * 1024, "decode attention: max_dec_len=%d too long for the LDS bias row (<= %d)", a.bias_stride,
               (24 * 1024 - a.d * 4 * clips) / 4);
@@ -1728,11 +1730,11 @@ static int launch_dec_attn(int precision, bool self, bool nt, DecAttnArgs a, int
     if (bf) launch_dec_attn_t<bf16_t>(self, nt, a, grid, smem, st);
     else launch_dec_attn_t<float>(self, nt, a, grid, smem, st);
   } else if (clips == 2) {
-    if (bf) launch_dec_attn_mc_t<bf16_t, 2>(self, nt, a, B, smem, st);
-    else launch_dec_attn_mc_t<float, 2>(self, nt, a, B, smem, st);
+    if (bf) launch_dec_attn_mc_t<bf16_t, 2>(self, nt, a, B, cif, smem, st);
+    else launch_dec_attn_mc_t<float, 2>(self, nt, a, B, cif, smem, st);
   } else if (clips == 4) {
-    if (bf) launch_dec_attn_mc_t<bf16_t, 4>(self, nt, a, B, smem, st);
-    else launch_dec_attn_mc_t<float, 4>(self, nt, a, B, smem, st);
+    if (bf) launch_dec_attn_mc_t<bf16_t, 4>(self, nt, a, B, cif, smem, st);
+    else launch_dec_attn_mc_t<float, 4>(self, nt, a, B, cif, smem, st);
   } else {
     set_error("decode attention: %d clips per workgroup not instantiated (1, 2, 4)", clips);
     return M2M_ERR_INVALID;
@@ -2259,7 +2261,7 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
     a.Vc = (unsigned char*)s->self_v + off;
     a.kv_stride = s->max_dec; a.n_keys = 0; a.self_len_override = self_len;
     a.bias = s->dec_bias_tab; a.bias_stride = s->max_dec;
-    return launch_dec_attn(m->precision, true, nt, a, v.nb, clips, st);
+    return launch_dec_attn(m->precision, true, nt, a, v.nb, clips, s->mc_cif, st);
   }
   // cross K/V: [L][2][B][H][S][64] with B, S = the encoded problem
   const size_t per = (size_t)s->B * H * s->S * DK;
@@ -2268,7 +2270,7 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
   a.Kc = (unsigned char*)s->cross_kv + (((size_t)layer * 2 + 0) * per + voff) * es;
   a.Vc = (unsigned char*)s->cross_kv + (((size_t)layer * 2 + 1) * per + voff) * es;
   a.kv_stride = s->S; a.n_keys = s->S; a.self_len_override = 0; a.bias = nullptr; a.bias_stride = 0;
-  return launch_dec_attn(m->precision, false, nt, a, v.nb, clips, st);
+  return launch_dec_attn(m->precision, false, nt, a, v.nb, clips, s->mc_cif, st);
 }
 
 int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* logits_out, int Ld, hipStream_t st) {

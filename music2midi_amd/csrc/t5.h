@@ -163,6 +163,7 @@ struct m2m_session {
   int attn_clips_self = 0; // M2M_DA_CLIPS_SELF (diagnostic): clips per self-attention workgroup when it should differ from the cross kernels
   int ff_rows = 0;         // decode feed-forward: residual rows per workgroup forced by M2M_DEC_FF_ROWS (0: by chain size)
   int ff_slices = 0;       // decode feed-forward: hidden slices per workgroup forced by M2M_DEC_FF_SLICES (0: by chain size)
+  int mc_cif = 1;          // multi-clip cross-attention: clips in flight, M2M_MC_CIF (diagnostic: 2; 0 or unset: 1, the product)
   int repacks = 0, rows_moved = 0;   // live-row re-packings / rows moved by them in the last m2m_generate_greedy / _sample
   int head_mode = 0;       // head form of the free-running decode step: 0 greedy (arg-max), 1 sampling (set for the length of a call)
   m2m::SampleParams* sample_dev = nullptr;    // [1] in the workspace

@@ -259,10 +259,14 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   const int ff_slices = (fs_env && fs_env[0]) ? atoi(fs_env) : 0;
   M2M_REQUIRE(ff_slices == 0 || ff_slices == 1 || ff_slices == 2 || ff_slices == 4,
               "M2M_DEC_FF_SLICES=%d: hidden slices per decode feed-forward workgroup must be 0 (by chain size), 1, 2 or 4", ff_slices);
+  const char* cif_env = getenv("M2M_MC_CIF");
+  const int mc_cif = (cif_env && cif_env[0]) ? atoi(cif_env) : 0;
+  M2M_REQUIRE(mc_cif == 0 || mc_cif == 1 || mc_cif == 2,
+              "M2M_MC_CIF=%d: clips in flight in the multi-clip cross-attention must be 0 (default: 1), 1 or 2", mc_cif);
   m2m_session* s = new m2m_session();
   s->m = m; s->max_batch = max_batch; s->max_enc = max_enc_len; s->max_dec = max_dec_len;
   s->ws = (unsigned char*)workspace_dev; s->ws_bytes = workspace_bytes;
-  s->attn_clips = da_clips; s->ff_rows = ff_rows; s->ff_slices = ff_slices;
+  s->attn_clips = da_clips; s->ff_rows = ff_rows; s->ff_slices = ff_slices; s->mc_cif = mc_cif == 2 ? 2 : 1;
   s->enc_sw = read_enc_switches();
   { const char* v = getenv("M2M_DA_CLIPS_SELF"); const int c = (v && v[0]) ? atoi(v) : 0; s->attn_clips_self = (c == 1 || c == 2 || c == 4) ? c : 0; }
   unsigned char* b = s->ws;

@@ -236,7 +236,7 @@ def test_large_activation_fp32_still_matches_oracle():
     assert torch.equal(model.generate_from_embeds(x.cuda(), max_length=24).cpu(), T5Oracle(geom, sd).generate(x, 24))
 
 
-@pytest.mark.parametrize("precision,B,S", [("bf16", 32, 190), ("fp32", 9, 61), ("bf16", 5, 864)])
+@pytest.mark.parametrize("precision,B,S", [("bf16", 32, 190), ("fp32", 9, 61), ("bf16", 5, 864), ("bf16", 98, 864)])
 def test_finished_row_early_out_does_not_change_ids(monkeypatch, precision, B, S):
     """Round 4: a (clip, head) workgroup of the decode attention kernels whose row has emitted EOS stops re-requesting K/V
     (csrc/decode.hip `row_fin`).  HF keeps computing such rows and forces their tokens to pad (hf generation/utils.py:2929), so
@@ -329,7 +329,8 @@ def test_attention_wide_form_against_the_first_form(monkeypatch, cfg_name, B, S,
     assert torch.equal(o32["1"], o32["0"])
 
 
-@pytest.mark.parametrize("precision,B,S", [("bf16", 32, 190), ("fp32", 9, 61), ("bf16", 5, 864), ("bf16", 128, 40), ("fp32", 33, 30)])
+@pytest.mark.parametrize("precision,B,S", [("bf16", 32, 190), ("fp32", 9, 61), ("bf16", 5, 864), ("bf16", 128, 40), ("fp32", 33, 30),
+                                        ("bf16", 96, 864)])
 def test_live_row_repacking_does_not_change_ids(monkeypatch, precision, B, S):
     """Round 5: at a host poll of the greedy loop, once a quarter of the rows still being decoded have emitted EOS,
     the live rows are MOVED into the first slots (self K/V up to the current position, cross K/V, pending arg-max key, residual row;
