@@ -92,6 +92,24 @@ int  m2m_frontend_fb_nnz(const m2m_frontend* fe);
 int m2m_logmel_f32(const m2m_frontend* fe, const float* wav_dev, int B, int T,
                    float* out_dev, int64_t out_batch_stride, int row_offset, void* stream);
 
+/* The kernel form and launch geometry m2m_logmel_f32(fe, B, T, ...) uses (read-only; launches nothing). */
+enum {
+  M2M_FE_FORM_V2_NJ6 = 0,         /* logmel_v2_kernel<16, 6>: hop <= 272, n_mels <= 384 */
+  M2M_FE_FORM_V2_NJ8 = 1,         /* logmel_v2_kernel<16, 8>: hop <= 272, 385 <= n_mels <= 512 */
+  M2M_FE_FORM_V1_TAPS_LDS = 2,    /* logmel_kernel<true>: first form, padded tap table in LDS */
+  M2M_FE_FORM_V1_TAPS_GLOBAL = 3  /* logmel_kernel<false>: first form, padded tap table read from memory */
+};
+typedef struct {
+  int form;              /* M2M_FE_FORM_* */
+  int grid_x, grid_y;    /* workgroups: chunk groups per clip, clips */
+  int chunks;            /* chunks each workgroup walks */
+  int frames_per_chunk;  /* FR (16 in the second form) */
+  int frames;            /* 1 + T / hop */
+  int n_wpad;            /* floats in the padded tap table */
+  int lds_bytes;         /* dynamic LDS per workgroup */
+} m2m_frontend_plan_t;
+int m2m_frontend_plan(const m2m_frontend* fe, int B, int T, m2m_frontend_plan_t* out);
+
 /*
  * Conditioning rows, replaces ref: music2midi/input.py:57-59.
  * tables_dev_host: host array of n_tables device pointers, table i is [n_i, n_dim] fp32.

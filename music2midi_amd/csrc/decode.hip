@@ -1194,7 +1194,9 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
         s += redo[wv][tid];
         L += redlf[wv];
       }
-      put_in<T>(oh, tid, L > 0.f ? s / L : 0.f);     // the projection input is rounded to T, as every GEMM input (L = 0: a finished row's empty cross softmax)
+      // the projection input is rounded to T, as every GEMM input (L = 0: a finished row's empty cross softmax).  !(L <= 0) keeps a NaN
+      // softmax (NaN encoder states, e.g. from a NaN sample) NaN, so the residual's range guard sees it instead of a zero head output.
+      put_in<T>(oh, tid, !(L <= 0.f) ? s / L : 0.f);
     }
     __syncthreads();
     M2M_STAMP(6 + (SELF ? 1 : 0), 7);
@@ -1634,7 +1636,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
           s += redo[wv][tid];
           L += redlf[wv];
         }
-        put_in<T>(oh[c], tid, L > 0.f ? s / L : 0.f);
+        put_in<T>(oh[c], tid, !(L <= 0.f) ? s / L : 0.f);   // NaN stays NaN for the range guard (see dec_attn_kernel)
       }
       __syncthreads();
     }

@@ -313,7 +313,8 @@ __global__ __launch_bounds__(FE_THREADS, M2M_FE_WGS_PER_CU) void logmel_kernel(
         res[j] = acc;
       }
       // clamp(min=1e-6).log(): the floor is the correctly rounded fp32 ln(1e-6f), so silent (zero-padded) regions are
-      // bit-identical to the reference's constant.  All groups' logarithms and stores together, after the last LDS read.
+      // bit-identical to the reference's constant; !(acc <= 1e-6f) is also true for NaN, which stays NaN as in torch.clamp.
+      // All groups' logarithms and stores together, after the last LDS read.
 #pragma unroll
       for (int j = 0; j < FE_MAXJ; ++j) {
         if (64 * j >= n_mels) break;                               // uniform
@@ -324,7 +325,7 @@ __global__ __launch_bounds__(FE_THREADS, M2M_FE_WGS_PER_CU) void logmel_kernel(
 #elif defined(M2M_FE_SKIP_STORE)
         if (m < n_mels && acc == 12345.678f) orow[m] = acc;
 #else
-        if (m < n_mels) orow[m] = (acc > 1e-6f) ? logf(acc) : -13.815510749816895f;
+        if (m < n_mels) orow[m] = !(acc <= 1e-6f) ? logf(acc) : -13.815510749816895f;
 #endif
       }
     }
@@ -617,10 +618,11 @@ __global__ __launch_bounds__(64 * WAVES) void logmel_v2_kernel(const float* __re
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         if (64 * j >= n_mels) break;                               // uniform
-        // clamp(min=1e-6).log(): the floor is the correctly rounded fp32 ln(1e-6f), so silence is bit-identical to the reference's constant
+        // clamp(min=1e-6).log(): the floor is the correctly rounded fp32 ln(1e-6f), so silence is bit-identical to the reference's constant.
+        // The unordered compare lets a NaN mel power through to the log (NaN, as torch.clamp keeps it) at no extra instruction.
         if (M2M_FE2_SKIP & 64) { if (ln + 64 * j < n_mels && res[j] == 12345.678f) orow[64 * j] = res[j]; }
         else if (M2M_FE2_SKIP & 32) { if (ln + 64 * j < n_mels) orow[64 * j] = res[j]; }
-        else if (ln + 64 * j < n_mels) orow[64 * j] = (res[j] > 1e-6f) ? fe_log(res[j]) : -13.815510749816895f;
+        else if (ln + 64 * j < n_mels) orow[64 * j] = !(res[j] <= 1e-6f) ? fe_log(res[j]) : -13.815510749816895f;
       }
     }
     if (more) {
@@ -759,15 +761,16 @@ static size_t frontend_smem_bytes(int FR, int hop, int nnz) {
          (nnz <= FE_FBW_LDS ? (size_t)nnz * sizeof(float) : 0);
 }
 
-extern "C" int m2m_logmel_f32(const m2m_frontend* fe, const float* wav_dev, int B, int T, float* out_dev,
-                              int64_t out_batch_stride, int row_offset, void* stream) {
-  M2M_REQUIRE(fe && wav_dev && out_dev, "m2m_logmel_f32: null argument");
-  M2M_REQUIRE(B >= 1 && B <= 65535, "m2m_logmel_f32: batch %d out of range", B);
-  M2M_REQUIRE(T >= fe->n_fft / 2 + 1, "m2m_logmel_f32: T=%d too short for reflect padding (need > %d)", T, fe->n_fft / 2);
-  M2M_REQUIRE(row_offset >= 0, "m2m_logmel_f32: negative row_offset");
+// Which kernel form a call (fe, B, T) launches and with what geometry: m2m_logmel_f32 launches exactly what this returns, and
+// m2m_frontend_plan reports it.  Reads M2M_FE_CHUNKS / M2M_FE_FR on every call (M2M_FE_V2 once per process).
+static int frontend_plan(const m2m_frontend* fe, int B, int T, m2m_frontend_plan_t* p, const char* fn) {
+  M2M_REQUIRE(B >= 1 && B <= 65535, "%s: batch %d out of range", fn, B);
+  M2M_REQUIRE(T >= fe->n_fft / 2 + 1, "%s: T=%d too short for reflect padding (need > %d)", fn, T, fe->n_fft / 2);
   const int F = 1 + T / fe->hop;
-  M2M_REQUIRE(out_batch_stride >= (int64_t)(row_offset + F) * fe->n_mels,
-              "m2m_logmel_f32: out_batch_stride %lld smaller than (row_offset+frames)*n_mels", (long long)out_batch_stride);
+  memset(p, 0, sizeof(*p));
+  p->frames = F;
+  p->n_wpad = fe->n_wpad;
+  p->grid_y = B;
   // Second form (one 16-wave workgroup per CU, tables and half-plane exchanges in LDS, four waves per SIMD) whenever its LDS image
   // fits: hop <= 272 (15 hop + 2048 samples in 6 prefetch registers per thread) and the tap table inside 160 KB, i.e. every configuration
   // the reference uses (hop 256, 384 mels) and e.g. hop 128.  Longer hops, and M2M_FE_V2=0, run the first form.
@@ -782,43 +785,75 @@ extern "C" int m2m_logmel_f32(const m2m_frontend* fe, const float* wav_dev, int 
       per_clip = per_clip < 1 ? 1 : (per_clip > cpc ? cpc : per_clip);
       int NCH = ceil_div(cpc, per_clip);
       if (const char* v = getenv("M2M_FE_CHUNKS")) NCH = atoi(v) > 0 ? atoi(v) : NCH;
-      dim3 grid((unsigned)ceil_div(cpc, NCH), (unsigned)B);
-      if (fe->n_mels <= 384) {
-        M2M_OPT_IN_LDS((logmel_v2_kernel<WAVES, 6>), 160 * 1024);
-        hipLaunchKernelGGL((logmel_v2_kernel<WAVES, 6>), grid, dim3(64 * WAVES), (size_t)L.total * sizeof(float), (hipStream_t)stream, wav_dev, T, F,
-                           fe->dev, out_dev, out_batch_stride, row_offset, NCH);
-      } else {
-        M2M_OPT_IN_LDS((logmel_v2_kernel<WAVES, 8>), 160 * 1024);
-        hipLaunchKernelGGL((logmel_v2_kernel<WAVES, 8>), grid, dim3(64 * WAVES), (size_t)L.total * sizeof(float), (hipStream_t)stream, wav_dev, T, F,
-                           fe->dev, out_dev, out_batch_stride, row_offset, NCH);
-      }
-      M2M_CHECK_HIP(hipGetLastError());
+      p->form = fe->n_mels <= 384 ? M2M_FE_FORM_V2_NJ6 : M2M_FE_FORM_V2_NJ8;
+      p->grid_x = ceil_div(cpc, NCH);
+      p->chunks = NCH;
+      p->frames_per_chunk = WAVES;
+      p->lds_bytes = L.total * (int)sizeof(float);
       return M2M_OK;
     }
   }
   // 16 frames per workgroup: waveform re-read factor 1.44 at hop 256, two workgroups per CU.
   int FR = getenv("M2M_FE_FR") ? atoi(getenv("M2M_FE_FR")) : 16;
+  M2M_REQUIRE(FR >= 1 && FR <= 64, "%s: M2M_FE_FR=%d out of range", fn, FR);
   while (FR > 4 && frontend_smem_bytes(FR, fe->hop, fe->n_wpad) > 80 * 1024) FR -= 4;      // two workgroups per CU (160 KB)
   const size_t smem = frontend_smem_bytes(FR, fe->hop, fe->n_wpad);
+  M2M_REQUIRE(smem <= 160 * 1024, "%s: %zu bytes of LDS at FR=%d", fn, smem, FR);
   // chunks of FR frames per workgroup.  Measured on MI355X (B = 64 / 32, us per launch): 1 chunk 199.9 / 108.3,
   // 2 chunks 196.0 / 112.5, 3 chunks 208.1 / 136.9: the table loads are not what bounds the kernel, so one chunk
   // (most workgroups, best balance) unless a launch has thousands of workgroups to spare.
   int NCH = ((int64_t)ceil_div(F, FR * 2) * B >= 1536) ? 2 : 1;
   if (const char* v = getenv("M2M_FE_CHUNKS")) NCH = atoi(v) > 0 ? atoi(v) : NCH;
-  dim3 grid((unsigned)ceil_div(F, FR * NCH), (unsigned)B);
 #ifdef M2M_FE_TAPS_GLOBAL       // diagnostic builds only
   const bool taps_lds = false;
 #else
   const bool taps_lds = fe->n_wpad <= FE_FBW_LDS;
 #endif
-  if (taps_lds) {
-    M2M_OPT_IN_LDS(logmel_kernel<true>, 160 * 1024);
-    hipLaunchKernelGGL(logmel_kernel<true>, grid, dim3(FE_THREADS), smem, (hipStream_t)stream, wav_dev, T, F, fe->dev,
-                       out_dev, out_batch_stride, row_offset, FR, NCH);
-  } else {
-    M2M_OPT_IN_LDS(logmel_kernel<false>, 160 * 1024);
-    hipLaunchKernelGGL(logmel_kernel<false>, grid, dim3(FE_THREADS), smem, (hipStream_t)stream, wav_dev, T, F, fe->dev,
-                       out_dev, out_batch_stride, row_offset, FR, NCH);
+  p->form = taps_lds ? M2M_FE_FORM_V1_TAPS_LDS : M2M_FE_FORM_V1_TAPS_GLOBAL;
+  p->grid_x = ceil_div(F, FR * NCH);
+  p->chunks = NCH;
+  p->frames_per_chunk = FR;
+  p->lds_bytes = (int)smem;
+  return M2M_OK;
+}
+
+extern "C" int m2m_frontend_plan(const m2m_frontend* fe, int B, int T, m2m_frontend_plan_t* out) {
+  M2M_REQUIRE(fe && out, "m2m_frontend_plan: null argument");
+  return frontend_plan(fe, B, T, out, "m2m_frontend_plan");
+}
+
+extern "C" int m2m_logmel_f32(const m2m_frontend* fe, const float* wav_dev, int B, int T, float* out_dev,
+                              int64_t out_batch_stride, int row_offset, void* stream) {
+  M2M_REQUIRE(fe && wav_dev && out_dev, "m2m_logmel_f32: null argument");
+  m2m_frontend_plan_t p;
+  if (int st = frontend_plan(fe, B, T, &p, "m2m_logmel_f32")) return st;
+  M2M_REQUIRE(row_offset >= 0, "m2m_logmel_f32: negative row_offset");
+  const int F = p.frames;
+  M2M_REQUIRE(out_batch_stride >= (int64_t)(row_offset + F) * fe->n_mels,
+              "m2m_logmel_f32: out_batch_stride %lld smaller than (row_offset+frames)*n_mels", (long long)out_batch_stride);
+  const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
+  const hipStream_t s = (hipStream_t)stream;
+  switch (p.form) {
+    case M2M_FE_FORM_V2_NJ6:
+      M2M_OPT_IN_LDS((logmel_v2_kernel<16, 6>), 160 * 1024);
+      hipLaunchKernelGGL((logmel_v2_kernel<16, 6>), grid, dim3(64 * 16), (size_t)p.lds_bytes, s, wav_dev, T, F, fe->dev, out_dev,
+                         out_batch_stride, row_offset, p.chunks);
+      break;
+    case M2M_FE_FORM_V2_NJ8:
+      M2M_OPT_IN_LDS((logmel_v2_kernel<16, 8>), 160 * 1024);
+      hipLaunchKernelGGL((logmel_v2_kernel<16, 8>), grid, dim3(64 * 16), (size_t)p.lds_bytes, s, wav_dev, T, F, fe->dev, out_dev,
+                         out_batch_stride, row_offset, p.chunks);
+      break;
+    case M2M_FE_FORM_V1_TAPS_LDS:
+      M2M_OPT_IN_LDS(logmel_kernel<true>, 160 * 1024);
+      hipLaunchKernelGGL(logmel_kernel<true>, grid, dim3(FE_THREADS), (size_t)p.lds_bytes, s, wav_dev, T, F, fe->dev, out_dev,
+                         out_batch_stride, row_offset, p.frames_per_chunk, p.chunks);
+      break;
+    default:
+      M2M_OPT_IN_LDS(logmel_kernel<false>, 160 * 1024);
+      hipLaunchKernelGGL(logmel_kernel<false>, grid, dim3(FE_THREADS), (size_t)p.lds_bytes, s, wav_dev, T, F, fe->dev, out_dev,
+                         out_batch_stride, row_offset, p.frames_per_chunk, p.chunks);
+      break;
   }
   M2M_CHECK_HIP(hipGetLastError());
   return M2M_OK;

@@ -72,6 +72,14 @@ class LogMelSpectrogram(nn.Module):
     def num_frames(self, n_samples: int) -> int:
         return 1 + n_samples // self.hop_length
 
+    def plan(self, batch: int, n_samples: int) -> dict:
+        """The kernel form and launch geometry a forward of (batch, n_samples) uses (m2m_frontend_plan; launches nothing)."""
+        p = native.FrontendPlan()
+        native.check(native.load().m2m_frontend_plan(self._get_plan(), batch, n_samples, C.byref(p)), "m2m_frontend_plan")
+        d = {name: getattr(p, name) for name, _ in native.FrontendPlan._fields_}
+        d["form"] = native.FE_FORMS[p.form]
+        return d
+
     # -- forward -------------------------------------------------------------
     def forward_into(self, x: torch.Tensor, out: torch.Tensor, row_offset: int = 0) -> torch.Tensor:
         """Write log-mel rows into ``out[:, row_offset:row_offset+frames, :]`` (no concat copy)."""

@@ -10,8 +10,8 @@ filter weight (``linspace`` and ``10 ** x`` in float32) are done with the same
 torch CPU ops torchaudio itself uses, so the table equals torchaudio's for the
 installed torch; a 1-ulp change of a band edge near 8 kHz moves a weight by
 ~2e-5, which would eat into the 1e-4 log-mel tolerance.  A real checkpoint carries both buffers in its
-state dict and ``LogMelSpectrogram.load_buffers`` takes them
-verbatim instead.
+state dict, and ``LogMelSpectrogram.load_state_dict`` copies them
+verbatim over these (the native plan is rebuilt from whatever ``mel_scale.fb`` then holds).
 """
 from __future__ import annotations
 

@@ -32,6 +32,14 @@ class FrontendDesc(C.Structure):
                 ("window_host", C.c_void_p), ("fb_host", C.c_void_p)]
 
 
+class FrontendPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in
+                ("form", "grid_x", "grid_y", "chunks", "frames_per_chunk", "frames", "n_wpad", "lds_bytes")]
+
+
+FE_FORMS = ("v2_nj6", "v2_nj8", "v1_taps_lds", "v1_taps_global")   # FrontendPlan.form -> name (M2M_FE_FORM_*)
+
+
 class T5GeometryC(C.Structure):
     _fields_ = [(n, C.c_int) for n in
                 ("d_model", "d_ff", "num_layers", "num_decoder_layers", "num_heads", "d_kv", "vocab_size",
@@ -73,6 +81,7 @@ _SIGNATURES = {
     "m2m_frontend_fb_nnz": (C.c_int, [C.c_void_p]),
     "m2m_logmel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int,
                                  C.c_void_p]),
+    "m2m_frontend_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(FrontendPlan)]),
     "m2m_cond_rows_f32": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p,
                                     C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "m2m_model_create": (C.c_int, [C.POINTER(T5GeometryC), C.POINTER(T5Weights), C.c_int, C.c_void_p,

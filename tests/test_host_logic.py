@@ -338,3 +338,48 @@ def test_conditioning_index_out_of_range_raises_index_error_on_the_host():
     assert m._cond_rows(2, None).tolist() == [[0, 0]] * 2
     with pytest.raises(IndexError):
         m._cond_rows(3, [6, 0])
+
+
+# ------------------------------------------------------------------ log-mel frontend case table (tests/frontend_cases.py)
+def test_frontend_case_table_reaches_the_paths_it_claims():
+    """The geometry table the GPU frontend tests run is recomputed here from melbank: it must contain partial filter groups for
+    both second-form instantiations, 48-bin filters, empty filters, both sides of the v2 LDS gate at hop 272 and FR 16/12/8/4 in
+    the first form, and every case's declared form must be the one the host model of frontend_plan predicts."""
+    import frontend_cases as fc
+    forms, frs, partial, empties, widest = set(), set(), set(), 0, 0
+    gate = {}
+    for c, _ in fc.FP32_NOISE_MISSES:      # the recorded misses declare their form too
+        p = fc.case_plan(c)
+        assert (p["form"], p["frames_per_chunk"]) == (c.form, c.fr), c.id
+    # a partitioned device (fewer CUs) changes only how many workgroups share a clip
+    assert fc.plan(384, 256, 3072, 4, 220500, n_cu=64)["grid_x"] == 14 and fc.plan(384, 256, 3072, 4, 220500)["grid_x"] == 54
+    for c in fc.CASES:
+        p = fc.case_plan(c)
+        assert (p["form"], p["frames_per_chunk"]) == (c.form, c.fr), c.id
+        _, width = fc.taps(fc.filterbank(c.sr, c.f_min, c.n_mels))
+        assert width.max() <= fc.MAX_WIDTH, c.id
+        forms.add(c.form)
+        if c.form.startswith("v1"):
+            frs.add(c.fr)
+        if c.n_mels % 64:
+            partial.add(c.form)
+        empties = max(empties, int((width == 0).sum()))
+        widest = max(widest, int(width.max()))
+        if c.hop == 272:
+            gate[c.form.startswith("v2")] = p["n_wpad"]
+    assert {"v2_nj6", "v2_nj8", "v1_taps_lds"} <= forms and {"v2_nj6", "v2_nj8"} <= partial
+    assert frs == {16, 12, 8, 4}
+    assert empties >= 40 and widest == 48
+    assert set(c.hop for c in fc.CASES) >= {2, 160, 200, 270, 272, 274, 320, 512, 640, 1000, 1024}
+    assert set(c.sr for c in fc.CASES) == {8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000}
+    assert set(c.f_min for c in fc.CASES) == {0.0, 20.0, 1000.0}
+    # hop 272: one tap table under the 160 KB gate (second form), one above it (first form)
+    assert gate[True] <= 5536 < gate[False]
+    assert fc.v2_lds_floats(272, 5536)[0] * 4 == 160 * 1024
+    for sr, f_min, n_mels in fc.WIDTH_48:
+        assert int(fc.taps(fc.filterbank(sr, f_min, n_mels))[1].max()) == 48
+    for sr, f_min, n_mels in fc.REFUSED_WIDTH:
+        assert int(fc.taps(fc.filterbank(sr, f_min, n_mels))[1].max()) >= 49
+    # empty filters at 512 mels: 16 kHz has 2, 48 kHz (f_min 0) has 43
+    assert int((fc.taps(fc.filterbank(16000, 20.0, 512))[1] == 0).sum()) == 2
+    assert int((fc.taps(fc.filterbank(48000, 0.0, 512))[1] == 0).sum()) == 43
