@@ -310,6 +310,20 @@ int m2m_train_forward_backward(m2m_trainer* t, const float* params_dev, const fl
                                const int64_t* cond_idx_dev, const int64_t* labels_dev, int B, int S, int Ld,
                                float* loss_out_dev, float* grads_dev, float* logits_out_dev, void* stream);
 
+/* Gradient accumulation (pytorch-lightning's Trainer(accumulate_grad_batches=N): each micro-batch's backward sees loss / N and the
+ * gradients add up until the optimizer steps).  The same pass as m2m_train_forward_backward, except:
+ * grads_dev      required; d (loss * grad_scale) / d params is ADDED to it when accumulate = 1, and OVERWRITES it when
+ *                accumulate = 0 (the first micro-batch of a window).  Every writer of the buffer adds in its own epilogue:
+ *                no separate pass over the buffer.  The alignment padding between tensors is zeroed as before.
+ * grad_scale     finite, > 0 (1 / N); it multiplies the gradient of the logits only.  loss_out_dev stays the UNSCALED mean.
+ * The mode (scaled, accumulate) is part of the per-shape graph key; the factor is not: it is read from a device word written
+ * before every replay, so one graph per shape and mode serves any N.  With a sync stream set, the early ranges are released
+ * once their accumulated values are final.  m2m_train_forward_backward keeps its contract (grads OVERWRITTEN, factor 1). */
+int m2m_train_forward_backward_acc(m2m_trainer* t, const float* params_dev, const float* enc_inputs_dev,
+                                   const int64_t* cond_idx_dev, const int64_t* labels_dev, int B, int S, int Ld,
+                                   float* loss_out_dev, float* grads_dev, float* logits_out_dev, float grad_scale, int accumulate,
+                                   void* stream);
+
 /* Dropout of the teacher-forced pass (hf T5Config.dropout_rate, 0.1 in the reference's config; active because
  * ref: train.py:33 puts the module in train() mode): on the embeddings, the attention probabilities, every
  * residual branch, the gated activation and the final norms, as hf: modeling_t5.py places them.  Masks come from a

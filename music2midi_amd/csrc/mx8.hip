@@ -431,14 +431,16 @@ int launch_mxgemm_q(int fmt_a, int epi, const MxGemmArgs& g, hipStream_t st) {
   return fmt_a == 0 ? launch_mxgemm_q_f<0>(epi, g, st) : launch_mxgemm_q_f<1>(epi, g, st);
 }
 
-__global__ void mx_splitk_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, int M, int N, int64_t ldc, int ksplit) {
+// (accumulate != 0: C += the sum — a weight gradient in accumulate mode)
+__global__ void mx_splitk_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, int M, int N, int64_t ldc, int ksplit, int accumulate) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t n = (int64_t)M * N, stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
     float acc = 0.f;
     for (int z = 0; z < ksplit; ++z) acc += part[(int64_t)z * n + i];
     const int64_t row = i / N;
-    C[row * ldc + (i - row * N)] = acc;
+    float* c = C + row * ldc + (i - row * N);
+    *c = accumulate ? *c + acc : acc;
   }
 }
 
@@ -463,7 +465,7 @@ int launch_mxgemm(int fmt_a, int fmt_b, int epi, const MxGemmArgs& g, hipStream_
   M2M_REQUIRE(fmt_b == 0 && (fmt_a == 0 || fmt_a == 1), "mxgemm: formats (A e4m3|e5m2, B e4m3) only");
   int rc;
   if (g.ksplit > 1) {
-    M2M_REQUIRE(epi == TG_STORE_F32 && g.Cpart && g.kchunk % 128 == 0, "mxgemm: split-K is for plain fp32-store products");
+    M2M_REQUIRE((epi == TG_STORE_F32 || epi == TG_ACC_F32) && g.Cpart && g.kchunk % 128 == 0, "mxgemm: split-K is for plain fp32-store / fp32-accumulate products");
   }
   static const bool plain = getenv("M2M_MXGEMM_PLAIN") != nullptr;      // diagnostic: the unprefetched 64x64 kernel
   static const int wide_from = [] { const char* v = getenv("M2M_MXP_WIDE_FROM"); return v ? atoi(v) : 512; }();
@@ -476,7 +478,7 @@ int launch_mxgemm(int fmt_a, int fmt_b, int epi, const MxGemmArgs& g, hipStream_
   if (g.ksplit > 1) {
     const int64_t n = (int64_t)g.M * g.N;
     hipLaunchKernelGGL(mx_splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), dim3(256), 0, st, g.Cpart,
-                       reinterpret_cast<float*>(g.C), g.M, g.N, g.ldc, g.ksplit);
+                       reinterpret_cast<float*>(g.C), g.M, g.N, g.ldc, g.ksplit, epi == TG_ACC_F32 ? 1 : 0);
     M2M_CHECK_HIP(hipGetLastError());
   }
   return M2M_OK;

@@ -195,14 +195,17 @@ static int launch_bgemm_t(int epi, const BGemmArgs& g_in, hipStream_t st) {
 }
 
 // C[row][col] = alpha * sum_z part[z][row][col]   (z ascending: fixed order)
-__global__ void splitk_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, int M, int N, int64_t ldc, int ksplit, float alpha) {
+// (accumulate != 0: C[row][col] += alpha * sum — the accumulate mode of a weight gradient, m2m_train_forward_backward_acc)
+__global__ void splitk_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, int M, int N, int64_t ldc, int ksplit, float alpha,
+                                     int accumulate) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t n = (int64_t)M * N, stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
     float acc = 0.f;
     for (int z = 0; z < ksplit; ++z) acc += part[(int64_t)z * n + i];
     const int64_t row = i / N;
-    C[row * ldc + (i - row * N)] = alpha * acc;
+    float* c = C + row * ldc + (i - row * N);
+    *c = accumulate ? *c + alpha * acc : alpha * acc;
   }
 }
 
@@ -222,15 +225,20 @@ struct DwGemmArgs {
   int N1, N2, K;
   int64_t lda, ldb, ldc;
   int ksplit, kchunk;
+  int accum;             // 1: C += A^T . B (gradient accumulation; never set on a k-slice's partial tile)
 };
 
 template <typename T> struct DwCfg;
 template <> struct DwCfg<bf16_t> { static constexpr int BK = 64, E = 8; };
 template <> struct DwCfg<float> { static constexpr int BK = 32, E = 4; };
 
-// one output tile [n1_0, +BT) x [n2_0, +BT) over k in [kbeg, kend), written to out (row stride ldo)
+// the epilogue's store: overwrite, or (accum, workgroup-uniform) add to what the buffer holds — one extra read per element
+__device__ inline void dw_put(float* p, float v, int accum) { *p = accum ? *p + v : v; }
+
+// one output tile [n1_0, +BT) x [n2_0, +BT) over k in [kbeg, kend), written to (accum: added to) out (row stride ldo)
 template <typename T, int TF>
-__device__ inline void dw_tile(const DwGemmArgs& g, T* __restrict__ AB, int n1_0, int n2_0, int kbeg, int kend, float* __restrict__ out, int64_t ldo) {
+__device__ inline void dw_tile(const DwGemmArgs& g, T* __restrict__ AB, int n1_0, int n2_0, int kbeg, int kend, float* __restrict__ out, int64_t ldo,
+                               int accum) {
   using Cfg = DwCfg<T>;
   constexpr int BK = Cfg::BK, E = Cfg::E, PITCH = BK + E;
   constexpr int BT = 64 * TF, WT = 32 * TF;
@@ -313,7 +321,7 @@ __device__ inline void dw_tile(const DwGemmArgs& g, T* __restrict__ AB, int n1_0
 #pragma unroll
       for (int ni = 0; ni < TF; ++ni) {
         const int col = n2_0 + wn * WT + ni * 32 + r;
-        if (col < g.N2) out[(int64_t)row * ldo + col] = acc[mi][ni][e];
+        if (col < g.N2) dw_put(out + (int64_t)row * ldo + col, acc[mi][ni][e], accum);
       }
     }
 }
@@ -340,7 +348,7 @@ __device__ inline Frag<bf16_t> dw_tr_frag(const bf16_t* p) {            // p: th
 // select, no 64-bit multiply per load — and one guarded step takes the ragged end (M = 4 176 rows = 65 steps + 16 rows).
 template <bool FULL>
 __device__ inline void dw_tile_tr(const DwGemmArgs& g, bf16_t* __restrict__ AB, int n1_0, int n2_0, int kbeg, int kend, float* __restrict__ out,
-                                  int64_t ldo) {
+                                  int64_t ldo, int accum) {
   constexpr int BK = 64, P = DWT_PITCH;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -413,7 +421,7 @@ __device__ inline void dw_tile_tr(const DwGemmArgs& g, bf16_t* __restrict__ AB, 
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
         const int col = n2_0 + wn * 64 + ni * 32 + r;
-        if (FULL || col < g.N2) out[(int64_t)row * ldo + col] = acc[mi][ni][e];
+        if (FULL || col < g.N2) dw_put(out + (int64_t)row * ldo + col, acc[mi][ni][e], accum);
       }
     }
 }
@@ -425,7 +433,7 @@ __global__ __launch_bounds__(256) void dw_gemm_kernel(DwGemmArgs g) {
   const bool split = g.ksplit > 1;
   const int kbeg = split ? blockIdx.z * g.kchunk : 0, kend = split ? min(g.K, kbeg + g.kchunk) : g.K;
   dw_tile<T, TF>(g, AB, blockIdx.y * BT, blockIdx.x * BT, kbeg, kend, split ? g.Cpart + (int64_t)blockIdx.z * g.N1 * g.N2 : g.C,
-                 split ? (int64_t)g.N2 : g.ldc);
+                 split ? (int64_t)g.N2 : g.ldc, split ? 0 : g.accum);
 }
 
 // Every weight gradient of a step in ONE launch: the backward pass only records (dY, X, dW) triples — each sub-layer
@@ -454,15 +462,15 @@ __global__ __launch_bounds__(256) void dw_group_kernel(const DwProb* __restrict_
   const int tl = tile - pr.tile0;
   if constexpr (TR) {
     const int n1_0 = (tl / pr.tn2) * 128, n2_0 = (tl % pr.tn2) * 128;
-    if (n1_0 + 128 <= pr.g.N1 && n2_0 + 128 <= pr.g.N2) dw_tile_tr<true>(pr.g, AB, n1_0, n2_0, 0, pr.g.K, pr.g.C, pr.g.ldc);      // (workgroup-uniform)
-    else dw_tile_tr<false>(pr.g, AB, n1_0, n2_0, 0, pr.g.K, pr.g.C, pr.g.ldc);
-  } else dw_tile<T, 2>(pr.g, AB, (tl / pr.tn2) * 128, (tl % pr.tn2) * 128, 0, pr.g.K, pr.g.C, pr.g.ldc);
+    if (n1_0 + 128 <= pr.g.N1 && n2_0 + 128 <= pr.g.N2) dw_tile_tr<true>(pr.g, AB, n1_0, n2_0, 0, pr.g.K, pr.g.C, pr.g.ldc, pr.g.accum);      // (workgroup-uniform)
+    else dw_tile_tr<false>(pr.g, AB, n1_0, n2_0, 0, pr.g.K, pr.g.C, pr.g.ldc, pr.g.accum);
+  } else dw_tile<T, 2>(pr.g, AB, (tl / pr.tn2) * 128, (tl % pr.tn2) * 128, 0, pr.g.K, pr.g.C, pr.g.ldc, pr.g.accum);
 }
 
 // C = A^T . B with the split chosen here: enough workgroups to fill the chip, as few k-slices as that allows (every slice
 // writes and re-reads an fp32 image of C).
 int launch_dw_gemm(int precision, const void* A, int64_t lda, int N1, const void* B, int64_t ldb, int N2, int K, float* C, int64_t ldc,
-                   float* kpart, int64_t kpart_floats, hipStream_t st) {
+                   float* kpart, int64_t kpart_floats, hipStream_t st, int accumulate) {
   const int E = precision == M2M_PREC_BF16 ? 8 : 4, BK = precision == M2M_PREC_BF16 ? 64 : 32;
   M2M_REQUIRE(N1 % E == 0 && N2 % E == 0 && lda % E == 0 && ldb % E == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(B) & 15) == 0,
@@ -481,6 +489,7 @@ int launch_dw_gemm(int precision, const void* A, int64_t lda, int N1, const void
   g.A = A; g.B = B; g.C = C; g.Cpart = kpart; g.N1 = N1; g.N2 = N2; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.ksplit = 1; g.kchunk = K;
   if (ks > 1) { g.kchunk = (int)align_up(ceil_div(K, ks), BK); g.ksplit = ceil_div(K, g.kchunk); }
+  g.accum = accumulate;                   // (a split product adds in splitk_reduce_kernel; its partial tiles are stored)
   dim3 grid((unsigned)ceil_div(N2, bt), (unsigned)ceil_div(N1, bt), (unsigned)g.ksplit);
   if (precision == M2M_PREC_BF16) {
     if (tf == 2) hipLaunchKernelGGL((dw_gemm_kernel<bf16_t, 2>), grid, dim3(256), 0, st, g);
@@ -493,7 +502,7 @@ int launch_dw_gemm(int precision, const void* A, int64_t lda, int N1, const void
   if (g.ksplit > 1) {
     const int64_t n = (int64_t)N1 * N2;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), dim3(256), 0, st, kpart, C, N1, N2,
-                       ldc, g.ksplit, 1.0f);
+                       ldc, g.ksplit, 1.0f, accumulate);
     M2M_CHECK_HIP(hipGetLastError());
   }
   return M2M_OK;
@@ -648,12 +657,13 @@ int launch_bgemm(int precision, int epi, const BGemmArgs& g, hipStream_t st) {
   M2M_REQUIRE((!g.a_kmajor || g.lda >= align_up(g.M, E)) && (!g.b_kmajor || g.ldb >= align_up(g.N, E)),
               "bgemm: a k-major operand's row stride must cover its rows padded to %d", E);
   if (g.ksplit > 1) {
-    M2M_REQUIRE(g.nb1 == 1 && g.nb2 == 1 && epi == TG_STORE_F32 && g.Cpart && g.kchunk % TG_BK_MAX == 0, "bgemm: split-K is for plain fp32-store products");
+    M2M_REQUIRE(g.nb1 == 1 && g.nb2 == 1 && (epi == TG_STORE_F32 || epi == TG_ACC_F32) && g.Cpart && g.kchunk % TG_BK_MAX == 0,
+                "bgemm: split-K is for plain fp32-store / fp32-accumulate products");
     int rc = precision == M2M_PREC_BF16 ? launch_bgemm_t<bf16_t>(epi, g, st) : launch_bgemm_t<float>(epi, g, st);
     if (rc != M2M_OK) return rc;
     const int64_t n = (int64_t)g.M * g.N;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), dim3(256), 0, st, g.Cpart,
-                       reinterpret_cast<float*>(g.C), g.M, g.N, g.ldc, g.ksplit, g.alpha);
+                       reinterpret_cast<float*>(g.C), g.M, g.N, g.ldc, g.ksplit, g.alpha, epi == TG_ACC_F32 ? 1 : 0);
     M2M_CHECK_HIP(hipGetLastError());
     return M2M_OK;
   }
@@ -1531,9 +1541,9 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ p
   }
 }
 
-// every RMSNorm weight gradient of a step in one launch: partial image j ([parts][d]) -> out_base + off[j]
+// every RMSNorm weight gradient of a step in one launch: partial image j ([parts][d]) -> (accumulate: added to) out_base + off[j]
 __global__ __launch_bounds__(256) void colsum_group_kernel(const float* __restrict__ part_all, const int64_t* __restrict__ offs, float* __restrict__ out_base,
-                                                           int parts, int d) {
+                                                           int parts, int d, int accumulate) {
   // block = 64 columns (16 lanes x 16 bytes: 256-byte row pieces) x 16 row groups, eight rows in flight per thread; the first form read
   // 128-byte pieces one 4-byte element per lane (54 us for the step's 17 MB of partial rows)
   __shared__ float4 sred[16][16];
@@ -1559,6 +1569,7 @@ __global__ __launch_bounds__(256) void colsum_group_kernel(const float* __restri
 #pragma unroll
     for (int u = 1; u < 16; ++u) { const float4 o = sred[u][cx]; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
     float* out = out_base + offs[j] + col;
+    if (accumulate) { v.x += out[0]; v.y += out[1]; v.z += out[2]; v.w += out[3]; }
     out[0] = v.x; out[1] = v.y; out[2] = v.z; out[3] = v.w;
   }
 }
@@ -1630,7 +1641,7 @@ template <int NW>
 __global__ __launch_bounds__(64 * NW) void embed_bwd_kernel(const int64_t* __restrict__ ids, int n_ids, int id_stride, int id_off,
                                                         const float* __restrict__ dx, int64_t x_row_stride, int64_t x_row_off,
                                                         float* __restrict__ gtab, int d, int pad_to_zero_id, int V, DropKey dk, uint32_t thresh,
-                                                        float scale) {
+                                                        float scale, int accumulate) {
   extern __shared__ __align__(16) int emb_smem[];
   int* list = emb_smem;                                          // [round_up_4(n_ids)]
   float* part = reinterpret_cast<float*>(list + ((n_ids + 3) & ~3));      // [NW][256]: one column block of the waves' sums
@@ -1691,7 +1702,8 @@ __global__ __launch_bounds__(64 * NW) void embed_bwd_kernel(const int64_t* __res
       float sum = part[threadIdx.x];
 #pragma unroll
       for (int w = 1; w < NW; ++w) sum += part[256 * w + threadIdx.x];
-      gtab[(int64_t)v * d + cc] = sum;
+      float* gp = gtab + (int64_t)v * d + cc;
+      *gp = accumulate ? *gp + sum : sum;
     }
     __syncthreads();
   }
@@ -1772,8 +1784,10 @@ __global__ __launch_bounds__(256) void embed_rows_drop_kernel(const int64_t* __r
 
 // the three inputs of a pass into the trainer's own buffers (what a captured graph reads): x as 16-byte pieces, labels, conditioning indices
 __global__ void stage_inputs_kernel(const float4* __restrict__ x, float4* __restrict__ x_dst, int64_t n4, const int64_t* __restrict__ lab,
-                                    int64_t* __restrict__ lab_dst, int64_t nl, const int64_t* __restrict__ cond, int64_t* __restrict__ cond_dst, int64_t nc) {
+                                    int64_t* __restrict__ lab_dst, int64_t nl, const int64_t* __restrict__ cond, int64_t* __restrict__ cond_dst, int64_t nc,
+                                    float* __restrict__ gscale_dst, float gscale) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x, n = n4 + nl + nc;
+  if (gscale_dst && blockIdx.x == 0 && threadIdx.x == 0) *gscale_dst = gscale;      // the gradient factor of a scaled pass
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     if (i < n4) x_dst[i] = x[i];
     else if (i < n4 + nl) lab_dst[i - n4] = lab[i - n4];
@@ -2098,6 +2112,13 @@ struct m2m_trainer {
   uint64_t drop_seed = 0;
   uint64_t *step_key_dev = nullptr, *step_ctr_dev = nullptr;   // key of the current pass / passes since set_dropout (device words:
                                                                // a captured graph advances them itself, see train_prologue_kernel)
+  // gradient accumulation (m2m_train_forward_backward_acc, for the duration of one call): GM_SCALED = dlogits carry the factor
+  // `gscale` (d (loss * gscale)); GM_ACC = the gradient writers add to the flat buffer.  The factor itself is not baked into a
+  // graph: a staged pass reads it from the device word inv_n[3] (gscale_src), written by stage_inputs_kernel before every replay.
+  enum { GM_SCALED = 1, GM_ACC = 2 };
+  int gmode = 0;
+  float gscale = 1.f;
+  const float* gscale_src = nullptr;
   // The operands the weight-gradient products read (dxT, dab, dqkv, dcq, dckv) live in per-sub-layer buffers (rings, one
   // entry per use in a pass): the products of a whole step are issued as ONE grouped launch after the backward pass
   // (or, in fp8 mode, on the side stream while the main stream moves on), so nothing may be overwritten before.
@@ -2122,9 +2143,9 @@ struct m2m_trainer {
   int64_t* cond_buf = nullptr;
   float* loss_dev = nullptr;
   struct GraphKey {
-    const float* P = nullptr; float* G = nullptr; int B = 0, S = 0, L = 0; uint32_t thresh = 0; uint64_t seed = 0; bool split = false;
+    const float* P = nullptr; float* G = nullptr; int B = 0, S = 0, L = 0; uint32_t thresh = 0; uint64_t seed = 0; bool split = false; int gmode = 0;
     bool operator==(const GraphKey& o) const {
-      return P == o.P && G == o.G && B == o.B && S == o.S && L == o.L && thresh == o.thresh && seed == o.seed && split == o.split;
+      return P == o.P && G == o.G && B == o.B && S == o.S && L == o.L && thresh == o.thresh && seed == o.seed && split == o.split && gmode == o.gmode;
     }
   };
   // One captured graph PER SHAPE.  The grouped weight-gradient launch and the norm column sums read device-resident tables
@@ -2428,6 +2449,10 @@ struct Ops {
     return nullptr;
   }
   float* Gbase = nullptr;     // flat gradient buffer of this call (dW recognises its weight by the output offset)
+  // accumulate mode (m2m_train_forward_backward_acc): every writer of the flat gradient buffer adds its result to what the
+  // buffer holds instead of overwriting it.  (Not the bias reductions' `accumulate` argument: that one sums the layers of a
+  // stack into their shared table within ONE pass.)
+  int gacc = 0;
 
   // dropout sites: one key per (layer, place); site < 0 or p == 0: no dropout
   bool dropping(int site) const { return site >= 0 && t->drop_thresh != 0; }
@@ -2506,7 +2531,7 @@ struct Ops {
     }
     const int d = t->g.d_model;
     hipLaunchKernelGGL(colsum_group_kernel, dim3(ceil_div(d, 64), (unsigned)norm_offs.size()), dim3(256), 0, st,
-                       t->dw_part + (int64_t)norm_slot_base * RN_BLOCKS * d, offs_dev, Gbase, RN_BLOCKS, d);
+                       t->dw_part + (int64_t)norm_slot_base * RN_BLOCKS * d, offs_dev, Gbase, RN_BLOCKS, d, gacc);
     M2M_CHECK_HIP(hipGetLastError());
     norm_slot_base += (int)norm_offs.size();
     norm_offs.clear();
@@ -2629,6 +2654,7 @@ struct Ops {
         DwProb p;
         memset(&p, 0, sizeof(p));                     // the table is compared bytewise: no uninitialised padding
         p.g.A = dY; p.g.B = X; p.g.C = Gout; p.g.N1 = Ny; p.g.N2 = Kx; p.g.K = M; p.g.lda = ldy; p.g.ldb = ldx; p.g.ldc = Kx; p.g.ksplit = 1; p.g.kchunk = M;
+        p.g.accum = gacc;
         probs.push_back(p);
         return M2M_OK;
       }
@@ -2651,14 +2677,14 @@ struct Ops {
       if (ks > 32) ks = 32;
       while (ks > 1 && ((int64_t)ks * Ny * Kx > t->kpart_floats || Mp8 / ks < 128)) --ks;
       if (ks > 1) { m.kchunk = (int)align_up(ceil_div(Mp8, ks), 128); m.ksplit = ceil_div(Mp8, m.kchunk); m.Cpart = t->kpart; }
-      return launch_mxgemm(t->grad_fmt, 0, TG_STORE_F32, m, st);
+      return launch_mxgemm(t->grad_fmt, 0, gacc ? TG_ACC_F32 : TG_STORE_F32, m, st);
     }
     // (the generic kernel's k-major staging — 2-byte LDS scatters — and the transpose-then-NT route it replaced cost
     //  ~30 us per weight gradient at 16 clips; M2M_TRAIN_DW_OLD=1 keeps them for comparison)
     static const bool old_path = getenv("M2M_TRAIN_DW_OLD") != nullptr;
     const int Ealign = t->precision == M2M_PREC_BF16 ? 8 : 4;
     if (!old_path && Ny % Ealign == 0 && Kx % Ealign == 0 && ldy % Ealign == 0 && ldx % Ealign == 0)
-      return launch_dw_gemm(t->precision, dY, ldy, Ny, X, ldx, Kx, M, Gout, Kx, t->kpart, t->kpart_floats, st);
+      return launch_dw_gemm(t->precision, dY, ldy, Ny, X, ldx, Kx, M, Gout, Kx, t->kpart, t->kpart_floats, st, gacc);
     const int Mp = (int)align_up(M, 8);
     BGemmArgs g{};
     g.C = Gout; g.M = Ny; g.N = Kx; g.K = M; g.ldc = Kx; g.nb1 = 1; g.nb2 = 1; g.alpha = 1.0f;
@@ -2675,7 +2701,7 @@ struct Ops {
     if (ks > 32) ks = 32;
     while (ks > 1 && ((int64_t)ks * Ny * Kx > t->kpart_floats || ceil_div(M, ks) < 64)) --ks;
     if (ks > 1) { g.ksplit = ks; g.kchunk = (int)align_up(ceil_div(M, ks), TG_BK_MAX); g.ksplit = ceil_div(M, g.kchunk); g.Cpart = t->kpart; }
-    return launch_bgemm(t->precision, TG_STORE_F32, g, st);
+    return launch_bgemm(t->precision, gacc ? TG_ACC_F32 : TG_STORE_F32, g, st);
   }
   int cvt(const float* src, void* dst, int64_t n) const { return launch_cvt(t->precision, src, dst, n, st); }
   // (A row-complete residual product that carries the next sub-layer's RMSNorm in its epilogue — 32 whole rows per workgroup, the
@@ -2714,7 +2740,7 @@ struct Ops {
     hipLaunchKernelGGL(rmsnorm_bwd_kernel<T>, dim3(RN_BLOCKS), dim3(256), (size_t)4 * d * sizeof(float), st, x, P + w_off, dy, dx_res, dx_out,
                        part, M, d, t->g.layer_norm_eps, out_t, dk, thr, t->drop_scale, din ? key(dy_site) : DropKey{nullptr, 0}, din ? t->drop_thresh : 0u);
     if (group) norm_offs.push_back(w_off);
-    else hipLaunchKernelGGL(colsum_kernel, dim3(ceil_div(d, 32)), dim3(256), 0, st, part, G + w_off, RN_BLOCKS, d, 0);
+    else hipLaunchKernelGGL(colsum_kernel, dim3(ceil_div(d, 32)), dim3(256), 0, st, part, G + w_off, RN_BLOCKS, d, gacc);
     M2M_CHECK_HIP(hipGetLastError());
     return M2M_OK;
   }
@@ -2833,7 +2859,7 @@ struct Ops {
     float* tmp = t->drel + (int64_t)(t->g.num_layers + t->g.num_decoder_layers) * t->drel_slot_floats;
     hipLaunchKernelGGL(bias_stripes_sum_kernel, dim3(H, ceil_div(nrel, 64), j.layers), dim3(1024), 0, st, t->drel + (int64_t)j.first_slot * t->drel_slot_floats,
                        tmp, j.nB, H, stripes, j.Sq, j.Sk, t->drel_slot_floats);
-    hipLaunchKernelGGL(bias_bucket_kernel, dim3(t->g.num_buckets * H), dim3(256), 0, st, tmp, j.buckets, j.Gtab, j.layers, H, nrel, accumulate);
+    hipLaunchKernelGGL(bias_bucket_kernel, dim3(t->g.num_buckets * H), dim3(256), 0, st, tmp, j.buckets, j.Gtab, j.layers, H, nrel, accumulate | gacc);
     M2M_CHECK_HIP(hipGetLastError());
     return M2M_OK;
   }
@@ -2858,7 +2884,7 @@ struct Ops {
     float* part = t->drel + (int64_t)(t->g.num_layers + t->g.num_decoder_layers) * t->drel_slot_floats +
                   (int64_t)std::max(t->g.num_layers, t->g.num_decoder_layers) * H * 2 * std::max(t->max_enc, t->max_dec);
     hipLaunchKernelGGL(bias_diag_kernel<T>, dim3(nB * H, ceil_div(nrel, 64)), dim3(256), 0, st, (const T*)dS, part, H, Sq, Sk, ldp);
-    hipLaunchKernelGGL(bias_bucket_kernel, dim3(t->g.num_buckets * H), dim3(256), 0, st, part, buckets, Gtab, nB, H, nrel, accumulate);
+    hipLaunchKernelGGL(bias_bucket_kernel, dim3(t->g.num_buckets * H), dim3(256), 0, st, part, buckets, Gtab, nB, H, nrel, accumulate | gacc);
     M2M_CHECK_HIP(hipGetLastError());
     return M2M_OK;
   }
@@ -3025,7 +3051,8 @@ int ff_bwd(const Ops<T>& o, const float* x_in, const float* dx_out, float* dx_in
 // Everything a pass needs before its first product and that depends on nothing but the inputs, in ONE launch.  (The pad ranges: the
 // flat gradient buffer is OVERWRITTEN by every pass — each tensor in full, by its own product / reduction — so all that needs zeroing
 // is the alignment padding between tensors, <= 63 floats each, instead of a 121 MB memset; tests fill the buffer with NaN before a
-// pass, so a tensor nobody wrote would show.)  In ONE launch (they were six:
+// pass, so a tensor nobody wrote would show.  An accumulating pass — m2m_train_forward_backward_acc — ADDS every tensor instead; the
+// pads, which belong to no tensor, are zeroed all the same.)  In ONE launch (they were six:
 // two bias-table gathers, the dropout key, the pad zeroing, the valid-label count, the decoder inputs — ~5 us of launch each for
 // microseconds of work).  Block roles by index: [0, nb_e) encoder bias table, [nb_e, nb_e + nb_d) decoder bias table, then the pad
 // ranges (one wave each), then shift_right; block 0 also advances the dropout key (thread 0) and, the LAST block counts
@@ -3044,6 +3071,9 @@ struct PrologueArgs {
   int64_t* dec_in;
   int B, L, start_id, pad_id, nb_s;
   float* inv_n;
+  int scaled;                          // accumulate-mode passes: inv_n[2] = inv_n[0] * (gscale_dev ? *gscale_dev : gscale), the dlogits factor
+  const float* gscale_dev;
+  float gscale;
 };
 __global__ __launch_bounds__(256) void train_prologue_kernel(PrologueArgs a) {
   int blk = blockIdx.x;
@@ -3093,7 +3123,10 @@ __global__ __launch_bounds__(256) void train_prologue_kernel(PrologueArgs a) {
     __syncthreads();
   }
   // no label to score: the mean over zero rows is NaN, as torch's CrossEntropyLoss gives (its gradient is zero there too)
-  if (threadIdx.x == 0) { a.inv_n[0] = cnt[0] > 0 ? 1.0f / (float)cnt[0] : __builtin_nanf(""); a.inv_n[1] = (float)cnt[0]; }
+  if (threadIdx.x == 0) {
+    a.inv_n[0] = cnt[0] > 0 ? 1.0f / (float)cnt[0] : __builtin_nanf(""); a.inv_n[1] = (float)cnt[0];
+    if (a.scaled) a.inv_n[2] = a.inv_n[0] * (a.gscale_dev ? *a.gscale_dev : a.gscale);
+  }
 }
 
 template <typename T>
@@ -3105,6 +3138,8 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
   const int Me = B * S, Md = B * L, lps = (int)align_up(S, 8), ldv = (int)align_up(V, 8);
   Ops<T> o{t, st, P};
   o.Gbase = G;
+  o.gacc = G && (t->gmode & m2m_trainer::GM_ACC) ? 1 : 0;
+  const bool scaled = G && (t->gmode & m2m_trainer::GM_SCALED);
   o.group = G && t->use_group && !(t->fp8 && t->fp8_dw);
   o.st2 = (G && !o.group) ? st_side : nullptr;
   int rc;
@@ -3117,6 +3152,7 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
     a.pads = t->pads_dev; a.n_pads = G ? t->n_pads : 0; a.nb_p = ceil_div(a.n_pads, 4); a.G = G;
     a.labels = labels; a.dec_in = t->dec_in; a.B = B; a.L = L; a.start_id = g.decoder_start_token_id; a.pad_id = g.pad_token_id;
     a.nb_s = ceil_div(Md, 256); a.inv_n = t->inv_n;
+    a.scaled = scaled ? 1 : 0; a.gscale_dev = t->gscale_src; a.gscale = t->gscale;
     hipLaunchKernelGGL(train_prologue_kernel, dim3(a.nb_e + a.nb_d + a.nb_p + a.nb_s + 1), dim3(256), 0, st, a);
     M2M_CHECK_HIP(hipGetLastError());
   }
@@ -3191,8 +3227,10 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
   RC(o.norm_drop(t->xd[3 * Ld], t->o_dln, t->hD, Md, SITE_DEC + SITE_FIN));
   RC(o.mm(TG_STORE_F32, t->hD, d, 0, o.W(t->o_lm), d, 0, t->logits, V, Md, V, d));
   if (logits_out) M2M_CHECK_HIP(hipMemcpyAsync(logits_out, t->logits, (size_t)Md * V * 4, hipMemcpyDeviceToDevice, st));
-  // loss + gradient of the logits
-  hipLaunchKernelGGL(ce_kernel<T>, dim3(ceil_div(Md, 4)), dim3(256), 0, st, t->logits, labels, t->inv_n, t->row_loss, (T*)t->dlog, Md, V, ldv);
+  // loss + gradient of the logits (a scaled pass: d (loss * gscale) — where autograd meets the 1/N of gradient accumulation; the loss
+  // itself stays unscaled)
+  hipLaunchKernelGGL(ce_kernel<T>, dim3(ceil_div(Md, 4)), dim3(256), 0, st, t->logits, labels, scaled ? t->inv_n + 2 : t->inv_n, t->row_loss, (T*)t->dlog,
+                     Md, V, ldv);
   hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, st, t->row_loss, Md, t->inv_n, loss_out);
   M2M_CHECK_HIP(hipGetLastError());
   if (!G) return M2M_OK;
@@ -3274,7 +3312,7 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
     const bool dr = o.dropping(SITE_DEC + SITE_EMB);
     M2M_OPT_IN_LDS(embed_bwd_kernel<EMB_NW_SHARED>, 158 * 1024);
     hipLaunchKernelGGL(embed_bwd_kernel<EMB_NW_SHARED>, dim3(V), dim3(64 * EMB_NW_SHARED), embed_bwd_smem(Md), st, t->dec_in, Md, 1, 0, dcur, (int64_t)1, (int64_t)0, G + t->o_shared, d,
-                       g.pad_token_id, V, dr ? o.key(SITE_DEC + SITE_EMB) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u, t->drop_scale);
+                       g.pad_token_id, V, dr ? o.key(SITE_DEC + SITE_EMB) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u, t->drop_scale, o.gacc);
   }
   // Split pass (data-parallel overlap): everything the decoder side deferred is issued now, so the gradients of the shared embedding,
   // lm_head and every decoder block are FINAL here — the caller's hook releases whoever waits for them — and the encoder side
@@ -3319,7 +3357,7 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
     const bool dr = o.dropping(SITE_ENC + SITE_EMB);
     hipLaunchKernelGGL(embed_bwd_kernel<4>, dim3(t->cond_rows[i]), dim3(256), embed_bwd_smem(B, 4), small, cond_idx, B, t->n_cond, i, dcur, (int64_t)S, (int64_t)i,
                        G + t->o_cond[i], d, 0, t->cond_rows[i], dr ? o.key(SITE_ENC + SITE_EMB) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u,
-                       t->drop_scale);
+                       t->drop_scale, o.gacc);
   }
   M2M_CHECK_HIP(hipGetLastError());
   RC(o.join_side());
@@ -3504,6 +3542,7 @@ extern "C" int m2m_train_forward_backward(m2m_trainer* t, const float* params_de
   // the END of the pass instead of half-way (no overlap, no race)
   const bool release_at_end = grads_dev && t->sync_stream && t->ev_mid && !split;
   if (!two) {
+    t->gscale_src = nullptr;                      // (a scaled pass issued directly carries its factor as a kernel argument)
     t->cur_slot = m2m_trainer::N_SLOTS;
     rc = run_pass(t, params_dev, enc_inputs_dev, cond_idx_dev, labels_dev, B, S, Ld, loss_out_dev, grads_dev, logits_out_dev, caller, nullptr,
                   split ? &release : nullptr);
@@ -3518,13 +3557,14 @@ extern "C" int m2m_train_forward_backward(m2m_trainer* t, const float* params_de
     const int64_t n4 = (int64_t)B * S * g.d_model / 4, nl = (int64_t)B * Ld, nc = (int64_t)B * t->n_cond;
     hipLaunchKernelGGL(stage_inputs_kernel, dim3(grid_1d(n4 + nl + nc)), dim3(256), 0, caller, reinterpret_cast<const float4*>(enc_inputs_dev),
                        reinterpret_cast<float4*>(t->xe[0]), n4, labels_dev, reinterpret_cast<int64_t*>(t->labels_buf), nl, cond_idx_dev,
-                       reinterpret_cast<int64_t*>(t->cond_buf), nc);
+                       reinterpret_cast<int64_t*>(t->cond_buf), nc, (t->gmode & m2m_trainer::GM_SCALED) ? t->inv_n + 3 : nullptr, t->gscale);
     M2M_CHECK_HIP(hipGetLastError());
   }
   M2M_CHECK_HIP(hipEventRecord(t->ev_in, caller));
   M2M_CHECK_HIP(hipStreamWaitEvent(t->s_main, t->ev_in, 0));
+  t->gscale_src = (t->gmode & m2m_trainer::GM_SCALED) ? t->inv_n + 3 : nullptr;     // staged above: one graph serves every factor
 
-  const m2m_trainer::GraphKey key{params_dev, grads_dev, B, S, Ld, t->drop_thresh, t->drop_seed, split};
+  const m2m_trainer::GraphKey key{params_dev, grads_dev, B, S, Ld, t->drop_thresh, t->drop_seed, split, t->gmode};
   const int si = slot_for(t, key);
   m2m_trainer::GraphSlot& slot = t->slots[si];
   slot.calls += 1;
@@ -3604,6 +3644,26 @@ extern "C" int m2m_train_forward_backward(m2m_trainer* t, const float* params_de
   if (logits_out_dev)
     M2M_CHECK_HIP(hipMemcpyAsync(logits_out_dev, t->logits, (size_t)B * Ld * g.vocab_size * 4, hipMemcpyDeviceToDevice, caller));
   return M2M_OK;
+}
+
+// Gradient accumulation: the same pass with d (loss * grad_scale) as its gradient, ADDED to grads_dev when `accumulate` is set (every
+// writer of the flat buffer — the grouped weight-gradient launch, the norm column sums, the bias-table and embedding reductions —
+// adds in its own epilogue; there is no extra pass over the buffer).  The pad ranges between tensors are zeroed as in the
+// overwriting pass.  The mode is part of the per-shape graph key; the factor is not (one graph per shape and mode serves any N).
+extern "C" int m2m_train_forward_backward_acc(m2m_trainer* t, const float* params_dev, const float* enc_inputs_dev, const int64_t* cond_idx_dev,
+                                              const int64_t* labels_dev, int B, int S, int Ld, float* loss_out_dev, float* grads_dev,
+                                              float* logits_out_dev, float grad_scale, int accumulate, void* stream) {
+  M2M_REQUIRE(t && grads_dev, "m2m_train_forward_backward_acc: null trainer or gradient buffer");
+  M2M_REQUIRE(isfinite(grad_scale) && grad_scale > 0.f && (accumulate == 0 || accumulate == 1),
+              "m2m_train_forward_backward_acc: grad_scale must be finite and > 0 (got %g), accumulate 0 or 1 (got %d)", (double)grad_scale, accumulate);
+  t->gmode = m2m_trainer::GM_SCALED | (accumulate ? m2m_trainer::GM_ACC : 0);
+  t->gscale = grad_scale;
+  const int rc = m2m_train_forward_backward(t, params_dev, enc_inputs_dev, cond_idx_dev, labels_dev, B, S, Ld, loss_out_dev, grads_dev,
+                                            logits_out_dev, stream);
+  t->gmode = 0;
+  t->gscale = 1.f;
+  t->gscale_src = nullptr;
+  return rc;
 }
 
 extern "C" int m2m_trainer_set_dropout(m2m_trainer* t, float p, uint64_t seed) {

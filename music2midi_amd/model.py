@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import distributed as D
+from .accumulation import check_accumulate_grad_batches, micro_step, windows
 from .audio import load_audio as _load_audio
 from .checkpoint import load_t5_state, read_checkpoint
 from .config import load_config
@@ -57,13 +58,15 @@ class Music2MIDI(nn.Module):
     _trainer = None
     global_step = 0
 
-    def _native_trainer(self, B: int = 0, S: int = 0, L: int = 0):
-        """The native trainer, (re)built when a batch exceeds the sizes it was created for."""
+    def _native_trainer(self, B: int = 0, S: int = 0, L: int = 0, keep_grads: bool = False):
+        """The native trainer, (re)built when a batch exceeds the sizes it was created for.  ``keep_grads``: the next pass adds to
+        the gradients (a micro-batch inside an accumulation window), so a rebuild carries the flat gradient buffer over."""
         from .training import NativeTrainer
         tr = self._trainer
         if tr is None or not tr.fits(B, S, L):
             old = tr.limits if tr is not None else (0, 0, 0)
             state = tr.optimizer_state() if tr is not None and tr.step_count > 0 else None
+            grads = tr.grads if tr is not None and keep_grads else None      # (a torch allocation: it outlives close())
             if tr is not None:
                 tr.close()
             limits = (max(B, old[0], int(self.config.dataloader.batch_size)), max(S, old[1]), max(L, old[2], 64))
@@ -72,14 +75,23 @@ class Music2MIDI(nn.Module):
                 state, self._resume_optimizer_state = self._resume_optimizer_state, None
             if state is not None:
                 self._trainer.load_optimizer_state(state)
+            if grads is not None:
+                if grads.numel() != self._trainer.grads.numel():
+                    raise RuntimeError(f"trainer rebuild inside an accumulation window: gradient layout changed ({grads.numel()} -> "
+                                       f"{self._trainer.grads.numel()} floats)")
+                self._trainer.grads.copy_(grads)
             if D.dist.is_available() and D.dist.is_initialized() and D.dist.get_world_size() > 1 and self._trainer.device.type == "cuda":
                 # every pass of this trainer releases the decoder-side gradients half-way (distributed.all_reduce_gradients_overlapped)
                 self._trainer.set_sync_stream(torch.cuda.Stream(device=self._trainer.device))
         # dropout as the reference trains: model.train() (ref train.py:33) activates T5Config.dropout_rate (0.1 unless the
         # config says otherwise); .eval() switches it off
+        # The mask sequence is indexed by passes: a trainer (re)built or resumed after P passes restarts it at seed + P, where the
+        # uninterrupted trainer is.  With N = 1 the passes are the optimizer steps (global_step); with gradient accumulation they are
+        # counted (_train_passes, kept in the checkpoint), so a rebuild inside a window continues the masks too.
         want = float(self.config.model.t5.get("dropout_rate", 0.1)) if self.training else 0.0
         if self._trainer.dropout != want:
-            self._trainer.set_dropout(want, seed=int(getattr(self, "seed", 0)) + self.global_step)
+            done = self.global_step if self._accumulation() == 1 else self._train_passes
+            self._trainer.set_dropout(want, seed=int(getattr(self, "seed", 0)) + done)
         return self._trainer
 
     _resume_optimizer_state = None
@@ -105,17 +117,37 @@ class Music2MIDI(nn.Module):
             labels = torch.nn.functional.pad(labels, (0, pad), value=-100)
         return labels
 
+    _accumulate_override = None
+    _train_passes = 0                  # forward + backward passes of training_step (the dropout mask index; see _native_trainer)
+    _micro = None                      # the MicroStep fit_batches hands the next training_step
+
+    def _accumulation(self) -> int:
+        """N of gradient accumulation: ``fit_batches(accumulate_grad_batches=)`` if given, else ``config.trainer.accumulate_grad_batches``
+        (ref config.yaml; 1 when the key is absent)."""
+        if self._accumulate_override is not None:
+            return check_accumulate_grad_batches(self._accumulate_override)
+        return check_accumulate_grad_batches(self.config.trainer.get("accumulate_grad_batches", 1))
+
     def training_step(self, inputs: ModelInputs, batch_idx):
         """ref model.py:32-43.  Lightning calls backward() on the returned loss; here forward AND backward have
         already been ENQUEUED when this returns: every parameter's ``.grad`` will hold d loss / d parameter (views of one flat
         buffer), ready for ``distributed.all_reduce_gradients`` and ``optimizer.step()``.  Nothing here waits for the device: the
         returned loss and ``self.logged["train/loss"]`` are 0-dim tensors on the GPU (``logged_metrics()`` reads them), so the
-        gradient all-reduce the caller enqueues next overlaps the backward pass that is still running."""
+        gradient all-reduce the caller enqueues next overlaps the backward pass that is still running.
+        With ``accumulate_grad_batches = N`` > 1 this is one micro-batch of a window (position ``batch_idx % N`` unless ``fit_batches``
+        says otherwise): the gradient of loss / N is written (first of the window) or added (the others); the returned and logged
+        loss is the unscaled one."""
         t5 = self.model
         labels = self._labels(inputs.notes_batch)
         x = t5.encoder_inputs(inputs)
-        tr = self._native_trainer(x.shape[0], x.shape[1], labels.shape[1])
-        loss, _ = tr.forward_backward(x, inputs.cond_index, labels)
+        n = self._accumulation()
+        ms = self._micro if self._micro is not None else micro_step(n, int(batch_idx) % n)
+        tr = self._native_trainer(x.shape[0], x.shape[1], labels.shape[1], keep_grads=n > 1 and ms.accumulate)
+        if n == 1:
+            loss, _ = tr.forward_backward(x, inputs.cond_index, labels)
+        else:
+            loss, _ = tr.forward_backward(x, inputs.cond_index, labels, grad_scale=ms.grad_scale, accumulate=ms.accumulate)
+        self._train_passes += 1
         loss = loss[0].clone()                                # the trainer's loss word is rewritten by the next pass
         self.logged = {"train/loss": loss, "batch_size": int(x.shape[0])}
         if (self.global_step + 1) % int(self.config.trainer.log_every_n_steps) == 0:
@@ -148,7 +180,9 @@ class Music2MIDI(nn.Module):
                 path = Path(path)
                 tmp = path.with_name(f".{path.name}.tmp{os.getpid()}")
                 try:
+                    extra = {"train_passes": int(self._train_passes)} if self._accumulation() > 1 else {}     # (see _native_trainer)
                     torch.save({
+                        **extra,
                         "epoch": int(getattr(self, "current_epoch", 0)), "global_step": int(self.global_step), "pytorch-lightning_version": "2.1.0",
                         "state_dict": {k: v.detach().cpu().clone() for k, v in self.state_dict().items()},
                         "callbacks": {}, "optimizer_states": [opt],
@@ -184,6 +218,8 @@ class Music2MIDI(nn.Module):
         else:
             load_t5_state(self.model, inner if inner else state, strict=False)
         self.global_step = int(ckpt.get("global_step", 0))
+        # passes so far (written by save_checkpoint under gradient accumulation; without it, every earlier window was complete)
+        self._train_passes = int(ckpt.get("train_passes", self.global_step * self._accumulation()))
         opts = ckpt.get("optimizer_states") or []
         opt = opts[0] if opts else None
         if opt is not None and opt.get("state"):
@@ -194,12 +230,28 @@ class Music2MIDI(nn.Module):
         if tr is not None:
             tr.dropout = -1.0                                # the mask sequence restarts from the restored step (see _native_trainer)
 
-    def fit_batches(self, batches, optimizer=None, world_size: int = 1, ckpt_path=None, save_path=None, save_every_n_steps: int = 0):
+    def fit_batches(self, batches, optimizer=None, world_size: int = 1, ckpt_path=None, save_path=None, save_every_n_steps: int = 0,
+                    accumulate_grad_batches=None):
         """Minimal stand-in for ``pl.Trainer.fit`` (ref train.py:40-41): step over an iterable of ModelInputs.  ``ckpt_path``
         resumes a run (weights + Adafactor state + step counter) as ``trainer.fit(..., ckpt_path=)`` does; ``save_path`` is
         (re)written every ``save_every_n_steps`` steps and at the end.  The host never waits for a step: losses stay on the device
         until the loop is over, metrics are reduced over the ranks and read every ``trainer.log_every_n_steps`` steps
-        (``self.log_history``)."""
+        (``self.log_history``).
+        Gradient accumulation (``accumulate_grad_batches``, default ``config.trainer.accumulate_grad_batches``; see
+        ``music2midi_amd.accumulation``): the optimizer steps — and the gradients are all-reduced — once per window of N batches
+        and after the last batch; ``global_step``, ``save_every_n_steps`` and ``log_every_n_steps`` count optimizer steps, so
+        checkpoints fall on window boundaries.  The returned losses are per batch, unscaled.  The override holds for this call only."""
+        if accumulate_grad_batches is not None:
+            check_accumulate_grad_batches(accumulate_grad_batches)
+        previous = self._accumulate_override
+        self._accumulate_override = accumulate_grad_batches
+        try:
+            n = self._accumulation()                     # ValueError before the first step
+            return self._fit_windows(batches, n, optimizer, ckpt_path, save_path, save_every_n_steps)
+        finally:
+            self._accumulate_override = previous
+
+    def _fit_windows(self, batches, n, optimizer, ckpt_path, save_path, save_every_n_steps):
         if ckpt_path is not None:
             self.resume_from_checkpoint(ckpt_path)
         if optimizer is None:
@@ -207,8 +259,15 @@ class Music2MIDI(nn.Module):
         log_every = max(1, int(self.config.trainer.log_every_n_steps))
         self.log_history = getattr(self, "log_history", [])
         losses, pending = [], []          # host floats so far / device scalars of the steps since the last read
-        for i, batch in enumerate(batches):
-            loss = self.training_step(batch, i)
+        for i, (batch, ms) in enumerate(windows(batches, n)):
+            self._micro = ms
+            try:
+                loss = self.training_step(batch, i)
+            finally:
+                self._micro = None
+            pending.append(loss)
+            if not ms.step:                      # inside a window: no all-reduce, no optimizer step (Lightning's no_sync)
+                continue
             tr = self._trainer
             if tr.sync_stream is not None:       # data-parallel (set when the trainer was built): decoder-side pieces overlap the encoder backward
                 D.all_reduce_gradients_overlapped(tr.grads, tr.early_ranges, tr.sync_stream)
@@ -216,7 +275,6 @@ class Music2MIDI(nn.Module):
                 D.all_reduce_gradients(tr.grads)
             optimizer.step()
             self.global_step += 1
-            pending.append(loss)
             if self.global_step % log_every == 0:
                 self.log_history.append(dict(self.logged_metrics(), step=self.global_step))
                 # logged_metrics() has just waited for this step: move the window's losses to the host here, so that a long run

@@ -110,6 +110,8 @@ _SIGNATURES = {
     "m2m_trainer_workspace_bytes": (C.c_int64, [C.c_void_p]),
     "m2m_train_forward_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m2m_train_forward_backward_acc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                 C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
     "m2m_trainer_set_dropout": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64]),
     "m2m_trainer_set_sync_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "m2m_trainer_early_grad_ranges": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

@@ -124,10 +124,12 @@ class NativeTrainer:
 
     # -- one step ------------------------------------------------------------------
     def forward_backward(self, encoder_inputs: torch.Tensor, cond_index: torch.Tensor, labels: torch.Tensor,
-                         want_logits: bool = False, backward: bool = True):
+                         want_logits: bool = False, backward: bool = True, grad_scale: float = 1.0, accumulate: bool = False):
         """encoder_inputs [B, S, d] fp32 (log-mel rows in place, cond rows are filled by the trainer),
         cond_index [B, n_cond] int64, labels [B, Ld] int64 with -100 = ignore.  Returns (loss[1] on the device, logits or None);
-        the flat gradient buffer (= every parameter's .grad) is overwritten."""
+        the flat gradient buffer (= every parameter's .grad) is overwritten with d loss / d params.
+        Gradient accumulation (``music2midi_amd.accumulation``): the gradient is d (loss * grad_scale) / d params, ADDED to the
+        buffer when ``accumulate``; the returned loss stays unscaled.  (grad_scale = 1 without accumulate is the plain pass.)"""
         B, S, _ = encoder_inputs.shape
         Ld = labels.shape[1]
         assert self.fits(B, S, Ld), (B, S, Ld, self.limits)
@@ -135,6 +137,15 @@ class NativeTrainer:
         idx = cond_index.to(self.device, torch.long).contiguous()
         lab = labels.to(self.device, torch.long).contiguous()
         logits = torch.empty((B, Ld, self.module.geometry.vocab_size), dtype=torch.float32, device=self.device) if want_logits else None
+        if grad_scale != 1.0 or accumulate:
+            if not backward:
+                raise ValueError("grad_scale / accumulate need the backward pass")
+            with torch.cuda.device(self.device):
+                native.check(native.load().m2m_train_forward_backward_acc(
+                    self.handle, self.params.data_ptr(), x.data_ptr(), idx.data_ptr(), lab.data_ptr(), B, S, Ld, self.loss.data_ptr(),
+                    self.grads.data_ptr(), logits.data_ptr() if want_logits else None, float(grad_scale), 1 if accumulate else 0,
+                    native.stream_handle(self.device)), "m2m_train_forward_backward_acc")
+            return self.loss, logits
         with torch.cuda.device(self.device):
             native.check(native.load().m2m_train_forward_backward(
                 self.handle, self.params.data_ptr(), x.data_ptr(), idx.data_ptr(), lab.data_ptr(), B, S, Ld, self.loss.data_ptr(),
