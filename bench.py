@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: decoded MIDI tokens / second on synthetic 10 s clips.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision bf16|fp32] [--batch 32] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision bf16|fp32] [--batch 32] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the whole hot path over one batch of synthetic clips:
 fused STFT/log-mel frontend -> conditioning rows -> T5 encoder -> cross-K/V
@@ -21,7 +21,13 @@ that case THIS process starts N fresh rank processes itself (before it has made
 any HIP call; nothing that touched the GPU is ever exec'ed or forked), forwards
 rank 0's JSON line and exits non-zero if any rank failed.
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with hipEvents on
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps,
+writes its outputs if asked and prints the headline line, nothing more.
+``--full`` adds (N = 1, rank 0, after the timed steps) the records beside the
+headline: phase timings and `roofline`, the configs[1] frontend, the reference's
+own geometry and the ragged-EOS batches, the fp32 parity mode, the configs[4]
+training step and the CPU baselines; the ``--no-*`` options leave single ones
+out.  `roofline` is measured live with hipEvents on
 the stream the kernels run on (m2m_bench_kernel); `cpu_baseline` times the
 oracle (a PyTorch-CPU restatement of the reference path — the reference's own
 Python cannot run here: torchaudio/lightning/omegaconf are absent) on a bounded
@@ -814,13 +820,16 @@ def main():
     ap.add_argument("--no-native", action="store_true", help="skip the reference-native-geometry and ragged-EOS records")
     ap.add_argument("--mode", default="generate", choices=["generate", "train"],
                     help="train: BASELINE configs[4] (forward+backward+Adafactor, 16 clips/GPU, gradient all-reduce over RCCL)")
-    ap.add_argument("--no-train", action="store_true", help="skip the configs[4] training-step record of the default line")
+    ap.add_argument("--no-train", action="store_true", help="skip the configs[4] training-step record of the --full line")
     ap.add_argument("--dropout", type=float, default=0.1, help="--mode train: T5Config.dropout_rate of the step (0.1: what the reference's train() mode runs; 0 = off)")
     ap.add_argument("--dry-run", action="store_true", help="launcher + collectives on CPU tensors (gloo), no GPU work")
     ap.add_argument("--max-length", type=int, default=MAX_LENGTH,
                     help="decoder max_length (profiling runs only; the headline number uses 1024)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last step's outputs as DIR/<name>.npy (rank 0; at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the records beside it (N = 1): roofline and phase timings, configs[1] frontend, "
+                         "reference-native geometry and ragged EOS, fp32 parity mode, configs[4] training step, CPU baselines")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -970,8 +979,11 @@ def main():
             out["replica_checksums"] = replicas["checksums"]
             out["per_rank_ms_per_step"] = per_rank_ms
 
-    # ---- phase timings + roofline of the dominant kernel (rank 0 only, N = 1) ----
-    if rank == 0 and world == 1 and not args.no_roofline:
+    # ---- --full: the records beside the headline (rank 0 only, N = 1), each after the timed steps ----
+    full = rank == 0 and world == 1 and args.full
+
+    # ---- phase timings + roofline of the dominant kernel ----
+    if full and not args.no_roofline:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         ev[0].record()
         x = model.encoder_inputs(inputs)
@@ -1003,7 +1015,7 @@ def main():
         }
 
     # ---- BASELINE configs[1]: the log-mel kernel alone, 64 clips, beside torch.stft on the host ----
-    if rank == 0 and world == 1 and not args.no_frontend:
+    if full and not args.no_frontend:
         Bf = 64
         wav64 = torch.from_numpy(synth.waveform_batch(0, Bf, N_SAMPLES)).to(dev)
         buf = torch.empty((Bf, N_FRAMES, geom.d_model), device=dev, dtype=torch.float32)
@@ -1029,14 +1041,14 @@ def main():
         del wav64, buf
 
     # ---- the reference's own geometry (128 x 3 s segments) and a batch whose rows END (finished-row early-out) ----
-    if rank == 0 and world == 1 and not args.no_native and args.precision == "bf16":
+    if full and not args.no_native and args.precision == "bf16":
         out["reference_native"] = reference_native_record(model, cfg, geom, dev)
         out["ragged_eos"] = ragged_eos_record(cfg, geom, dev, B, S)
         out["ragged_eos_native"] = ragged_eos_record(cfg, geom, dev, int(cfg.inference.batch_size),
                                                      1 + int(cfg.model.sample_rate * cfg.dataset.segment_duration) // 256 + 2)
 
     # ---- parity mode: fp32 (bit-exact against the fp32 reference) on the same workload ----
-    if rank == 0 and world == 1 and not args.no_parity and args.precision == "bf16":
+    if full and not args.no_parity and args.precision == "bf16":
         ids_bf16 = model.generate(inputs, max_length=MAX_LENGTH)
         m32 = T5Transformer(cfg.to_dict(), precision="fp32")
         load_t5_state(m32, state, strict=False)
@@ -1094,7 +1106,7 @@ def main():
         del m32
 
     # ---- BASELINE configs[4] (per-GPU share: 128 clips / 8 GPUs): one training step, timed on this GPU ----
-    if rank == 0 and world == 1 and not args.no_train:
+    if full and not args.no_train:
         mt = T5Transformer(cfg.to_dict(), precision="fp32")
         load_t5_state(mt, state, strict=False)
         mt = mt.to(dev)
@@ -1115,7 +1127,7 @@ def main():
         del mt
         out["train_configs4"]["class_surface"] = train_surface_record(cfg, state, dev, 16, 20, 3)
 
-    if rank == 0 and world == 1 and args.cpu_tokens > 0:
+    if full and args.cpu_tokens > 0:
         out["cpu_baseline"] = cpu_baseline(cfg, state, args.cpu_tokens)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -6,7 +6,7 @@ TAG=${1:-r2}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 D=gpurun_out/prof_$TAG
 mkdir -p $D
-python3 bench.py > $D/bench.json 2> $D/bench.err
+python3 bench.py --full > $D/bench.json 2> $D/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/ks -o ks -- python3 bench.py --steps 3 --warmup 1 --no-roofline --no-parity --no-frontend --no-train --cpu-tokens 0 > $D/ks.log 2>&1
 cp $D/ks/ks_kernel_stats.csv $D/kernel_stats.csv 2>/dev/null
 export PMC_OUT=$D/pmc_traffic; bash tools/pmc_traffic.sh > $D/pmc_traffic.log 2>&1; cp $PMC_OUT/summary.txt $D/pmc_traffic_summary.txt 2>/dev/null

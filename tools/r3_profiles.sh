@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-3 profile set, run on the GPU box from the repo root:  bash tools/r3_profiles.sh <tag>   (writes gpurun_out/prof_<tag>/)
-#   bench.json                       the default bench line of this build
+#   bench.json                       the full bench line of this build (--full)
 #   kernel_stats.csv                 rocprofv3 --kernel-trace --stats of the headline bench command (decode kernels)
 #   pmc_traffic_summary.txt          FETCH_SIZE / WRITE_SIZE per decode-kernel launch, separate passes, WITH the clips/launch header
 #   pmc_mfma_summary.txt             matrix-core counters of the inference kernels
@@ -11,7 +11,7 @@ TAG=${1:-r3}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 D=gpurun_out/prof_$TAG
 mkdir -p $D
-python3 bench.py > $D/bench.json 2> $D/bench.err
+python3 bench.py --full > $D/bench.json 2> $D/bench.err
 echo "bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/ks -o ks -- python3 bench.py --steps 3 --warmup 1 --no-roofline --no-parity --no-frontend --no-train --cpu-tokens 0 > $D/ks.log 2>&1
 cp $D/ks/ks_kernel_stats.csv $D/kernel_stats.csv 2>/dev/null

@@ -5,7 +5,7 @@ TAG=${1:-r6_fp32}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 D=gpurun_out/prof_$TAG
 mkdir -p $D
-python3 bench.py --precision fp32 --no-parity --no-native --no-frontend --no-train --cpu-tokens 0 > $D/fp32_bench.json 2> $D/fp32_bench.err
+python3 bench.py --full --precision fp32 --no-parity --no-native --no-frontend --no-train --cpu-tokens 0 > $D/fp32_bench.json 2> $D/fp32_bench.err
 echo "bench done"; cut -c1-600 $D/fp32_bench.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $D/ks -o ks -- python3 bench.py --precision fp32 --steps 3 --warmup 1 --no-roofline --no-parity --no-native --no-frontend --no-train --cpu-tokens 0 > $D/ks.log 2>&1
 cp $D/ks/ks_kernel_stats.csv $D/fp32_kernel_stats.csv 2>/dev/null
