@@ -236,6 +236,38 @@ int m2m_generate_sample(m2m_session* s, int max_length, const m2m_sample_params*
                         void* stream);
 
 /*
+ * KV-cached beam search (hf: generation/utils.py _beam_search, generation/beam_search.py BeamSearchScorer / BeamHypotheses,
+ * transformers 4.34 read for an encoder-decoder; no logits processors apply to T5): each of the B encoded clips is decoded as
+ * num_beams rows.  Every step scores log_softmax(logits) + the running beam score (fp32), takes the clip's top 2 num_beams over
+ * num_beams x V (ties to the lower beam-major index) and walks them in rank order: an EOS of rank < num_beams becomes a hypothesis
+ * (score sum_logprobs / len ** length_penalty, len = the start token plus the generated tokens, EOS not counted; at most
+ * num_beams kept per clip), an EOS of rank >= num_beams is dropped, any other candidate is the next running beam until there are
+ * num_beams.  A clip is done once it holds num_beams hypotheses and early_stopping is 1 (True), or the worst of them reaches the best
+ * running score of the step divided by cur_len ** length_penalty (0, False) - by max_length ** length_penalty instead when
+ * length_penalty > 0 (2, "never").  The loop ends when every clip is done or at max_length; a clip that is not done then adds its
+ * running beams at length max_length.
+ * Output (finalize): the best num_return_sequences = n hypotheses of clip c, best first (the later-added first among equal
+ * scores), in rows c * n .. c * n + n - 1 of tokens_out_dev [B * n, max_length] (row pitch max_length): the hypothesis, EOS at
+ * column len when len < max_length, pad_token_id after.  *out_len_host = min(longest returned hypothesis + 1, max_length): the
+ * columns HF returns.  scores_out_dev (optional, may be NULL) [B * n] receives the hypotheses' scores (HF sequences_scores).
+ * The session needs max_batch >= B * num_beams.  The self-attention reads a beam's K/V through its ancestry (the slot of every
+ * cached position) instead of copying caches; the beams of a clip share its cross K/V; live rows are NOT re-packed, so the encode
+ * stays valid for a later m2m_generate_greedy / m2m_decode_forced.  Invalid parameters return M2M_ERR_INVALID without launching
+ * anything: num_beams outside [2, 32], num_return_sequences outside [1, num_beams], early_stopping outside {0, 1, 2}, a
+ * non-finite length_penalty, a vocabulary larger than 4096 or smaller than 2 num_beams, B * num_beams > max_batch.  Non-finite
+ * logits return M2M_ERR_RANGE as m2m_generate_greedy does.
+ */
+typedef struct {
+  int num_beams;
+  float length_penalty;
+  int early_stopping;       /* 0 False, 1 True, 2 "never" */
+  int num_return_sequences;
+} m2m_beam_params;
+
+int m2m_generate_beam(m2m_session* s, int max_length, const m2m_beam_params* p, int64_t* tokens_out_dev, float* scores_out_dev,
+                      int* out_len_host, void* stream);
+
+/*
  * Rows end at different steps (ref: music2midi/model.py:115-135 decodes chunks of inference.batch_size = 128 three-second
  * segments to max_length 1024; a trained checkpoint ends a segment after tens to hundreds of tokens).  Once a quarter of the
  * rows still being decoded have emitted EOS, m2m_generate_greedy (and m2m_generate_sample) re-packs the live rows into the first slots of the batch at its

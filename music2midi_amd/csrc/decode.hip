@@ -761,6 +761,14 @@ struct DecAttnArgs {
   // the prologue's block of loads, see the kernel).
   const int* fin_skip;
   int fin_stride;
+  // Beam search (the BEAM instantiations only; beam_nb = 0 elsewhere).  The rows of a chain are clips x beam_nb beams, beam-major.
+  // Cross: row b reads the cross K/V of clip b / beam_nb (Kc / Vc hold the view's clips, not its rows).  Self: entry (slot s,
+  // position j) of the cache is written once, at step j, by row s; row b reads key / value j from slot
+  // (b / beam_nb) * beam_nb + anc[b][j] - its beam's path - instead of its own slot, so beams reorder without copying caches.
+  const unsigned char* anc;    // self: [rows][anc_ld] ancestry of the view's first row, parity 0; parity (t & 1) at + anc_par
+  int64_t anc_par;
+  int anc_ld;
+  int beam_nb;
 };
 
 // K/V rows are read once per step.  When the per-step K/V working set is larger than the 256 MB
@@ -811,9 +819,10 @@ template <typename T> __device__ inline void put_in(float* in_lds, int i, float 
   else in_lds[i] = v;
 }
 
-template <typename T, bool SELF, bool NT, bool FETCH = false>
+template <typename T, bool SELF, bool NT, bool FETCH = false, bool BEAM = false>
 __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   static_assert(!FETCH || SELF, "only the layer-0 self-attention fetches its input row from the embedding table");
+  static_assert(!(FETCH && BEAM), "the beam step is not headless");
   constexpr int E = 16 / sizeof(T);      // elements per 16-byte chunk: 8 (bf16) / 4 (fp32)
   constexpr int LPR = DK / E;            // lanes per key row (a "group"): 8 / 16
   constexpr int KPW = 64 / LPR;          // keys per wave-load: 8 / 4
@@ -874,8 +883,25 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   const int row_fin = a.fin_skip[(int64_t)b * a.fin_stride];
   const int sub = lane % LPR;
   const int kslot = wave * KPW + lane / LPR;
-  T* Kb = reinterpret_cast<T*>(a.Kc) + ((int64_t)b * a.H + hh) * a.kv_stride * DK;
-  T* Vb = reinterpret_cast<T*>(a.Vc) + ((int64_t)b * a.H + hh) * a.kv_stride * DK;
+  const int bkv = (BEAM && !SELF) ? b / a.beam_nb : b;      // beam cross-attention: the clip's K/V, shared by its beams
+  T* Kb = reinterpret_cast<T*>(a.Kc) + ((int64_t)bkv * a.H + hh) * a.kv_stride * DK;
+  T* Vb = reinterpret_cast<T*>(a.Vc) + ((int64_t)bkv * a.H + hh) * a.kv_stride * DK;
+  // beam self-attention: this row's ancestry (slot of every cached position) goes to LDS before any K/V request, which it addresses
+  // (one more round trip at entry; a byte per position).  Values are clamped into the clip, so no request leaves its beams' slots.
+  unsigned char* const ancl = reinterpret_cast<unsigned char*>(hn + a.d + (SELF ? a.bias_stride : 0));   // [kv_stride] (BEAM && SELF)
+  const int beam = (BEAM && SELF) ? b % a.beam_nb : 0;
+  if constexpr (BEAM && SELF) {
+    const unsigned char* ar = a.anc + (int64_t)(st_t & 1) * a.anc_par + (int64_t)b * a.anc_ld;
+    const int na = min(max(st_t, 1), a.kv_stride);
+    for (int j = tid; j < na; j += 1024) ancl[j] = j < st_t ? (unsigned char)min((int)ar[j], a.beam_nb - 1) : (unsigned char)beam;
+    __syncthreads();
+  }
+  // element offset of key row `key` (clamped) from Kb / Vb, for this lane's part of it
+  auto kvoff = [&](int key) -> int64_t {
+    int64_t o = (int64_t)key * DK + sub * E;
+    if constexpr (BEAM && SELF) o += ((int64_t)ancl[key] - beam) * ((int64_t)a.H * a.kv_stride * DK);
+    return o;
+  };
 
   // ---- 0. requests for the prologue: x row, norm weights, this lane's projection weights.
   //         Every kernel starts with a cold L2 for data other XCDs produced, so these come from
@@ -930,7 +956,7 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   Vec16<T> kv[PF], vv[PF];
 #pragma unroll
   for (int u = 0; u < PF; ++u) {   // clamped addresses, never predicated
-    const int64_t off = (int64_t)min(kslot + u * KPB, last) * DK + sub * E;
+    const int64_t off = kvoff(min(kslot + u * KPB, last));
     kv[u].v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Kb + off));
     vv[u].v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Vb + off));
   }
@@ -1072,7 +1098,7 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
 #pragma unroll
     for (int e = 0; e < E; ++e) vrow[e] = vs.get(e);
     if (reissue == 1 || (reissue == 2 && k0 + (u + PF) * KPB < n_live)) {   // workgroup-uniform, no lane is predicated
-      const int64_t off = (int64_t)min(key + PF * KPB, last) * DK + sub * E;
+      const int64_t off = kvoff(min(key + PF * KPB, last));
       ks.v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Kb + off));
       vs.v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Vb + off));
     }
@@ -1093,7 +1119,7 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
       visit(s, vrow);
     }
     if (reissue == 1 || (reissue == 2 && k0 + (u + PF) * KPB < n_live)) {   // workgroup-uniform, no lane is predicated
-      const int64_t off = (int64_t)min(key + PF * KPB, last) * DK + sub * E;
+      const int64_t off = kvoff(min(key + PF * KPB, last));
       ks.v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Kb + off));
       vs.v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Vb + off));
     }
@@ -1273,8 +1299,9 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
 #endif
 // CIF = clips in flight: register-slot sets, clip c in set c % CIF, a clip's last rounds handed to the next walking clip OF ITS SET.
 // 1: one stream, clip after clip (the product).  2 (cross-attention, M2M_MC_CIF=2): measured slower, see launch_dec_attn_mc_t.
-template <typename T, bool SELF, bool NT, bool FETCH, int C, int CIF = 1>
+template <typename T, bool SELF, bool NT, bool FETCH, int C, int CIF = 1, bool BEAM = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAVES, M2M_MC_WAVES))) void dec_attn_mc_kernel(DecAttnArgs a, int nb) {
+  static_assert(!BEAM || (CIF == 1 && !FETCH), "beam search: one clip in flight, not headless");
   static_assert(CIF == 1 || (CIF == 2 && !SELF && C % 2 == 0), "two clips in flight: cross-attention, an even clip count");
   static_assert(!FETCH || SELF, "only the layer-0 self-attention fetches its input row from the embedding table");
   static_assert(C >= 2 && C <= 8, "a wave pair normalises one clip's row: at most 8 clips per 16-wave workgroup");
@@ -1312,8 +1339,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
   const int sub = lane % LPR;
   const int kslot = wave * KPW + lane / LPR;
   const int64_t kv_clip = (int64_t)a.H * a.kv_stride * DK;                       // elements between two clips' blocks
-  T* const Kb0 = reinterpret_cast<T*>(a.Kc) + ((int64_t)b0 * a.H + hh) * a.kv_stride * DK;
-  T* const Vb0 = reinterpret_cast<T*>(a.Vc) + ((int64_t)b0 * a.H + hh) * a.kv_stride * DK;
+  // beam cross-attention: row b0 + c reads the K/V block of clip (b0 + c) / beam_nb (kb0 = the first one's)
+  const int kb0 = (BEAM && !SELF) ? b0 / a.beam_nb : b0;
+  T* const Kb0 = reinterpret_cast<T*>(a.Kc) + ((int64_t)kb0 * a.H + hh) * a.kv_stride * DK;
+  T* const Vb0 = reinterpret_cast<T*>(a.Vc) + ((int64_t)kb0 * a.H + hh) * a.kv_stride * DK;
 
   // ---- 0. requests for the prologue.  Wave pair cl = wave / 2 owns clip cl's row: wave 2 cl holds its elements 0..255, wave
   //         2 cl + 1 the rest - the lane -> element map and the reduction tree of the first kernel's waves 0 and 1 ----
@@ -1371,9 +1400,39 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
   // slot serves K and V (with flat 64-bit addresses the compiler kept a register PAIR per load and slot alive across the loop:
   // 2 x 2 x PF registers, which is what limited the depth of the window).
   const unsigned clip_bytes = (unsigned)(kv_clip * (int64_t)sizeof(T));
-  const unsigned span_bytes = (unsigned)(min(C, nb - b0) - 1) * clip_bytes + (unsigned)(a.kv_stride * DK * (int)sizeof(T));
-  const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc(Kb0, 0, (int)span_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc(Vb0, 0, (int)span_bytes, 0x00020000);
+  // BEAM: the descriptors start at the first block any of the C rows reads - its clip (cross) or its clip's beam 0 (self: every
+  // ancestor row) - and end with the last one; a row's block inside them is cb(c) (cross) / its ancestry (self)
+  const int last_row = min(b0 + C, nb) - 1;
+  const int lo_blk = !BEAM ? b0 : (SELF ? b0 / a.beam_nb * a.beam_nb : kb0);
+  const int hi_blk = !BEAM ? last_row : (SELF ? (last_row / a.beam_nb + 1) * a.beam_nb - 1 : last_row / a.beam_nb);
+  auto cb = [&](int c) -> unsigned {       // byte offset of row b0 + c's own block (cross: its clip's) from the descriptors' base
+    if constexpr (BEAM && !SELF) return (unsigned)(min(b0 + c, nb - 1) / a.beam_nb - kb0) * clip_bytes;
+    else return (unsigned)c * clip_bytes;
+  };
+  T* const Kd0 = (BEAM && SELF) ? reinterpret_cast<T*>(a.Kc) + ((int64_t)lo_blk * a.H + hh) * a.kv_stride * DK : Kb0;
+  T* const Vd0 = (BEAM && SELF) ? reinterpret_cast<T*>(a.Vc) + ((int64_t)lo_blk * a.H + hh) * a.kv_stride * DK : Vb0;
+  const unsigned span_bytes = (BEAM ? (unsigned)(hi_blk - lo_blk) : (unsigned)(min(C, nb - b0) - 1)) * clip_bytes +
+                              (unsigned)(a.kv_stride * DK * (int)sizeof(T));
+  const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc(Kd0, 0, (int)span_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc(Vd0, 0, (int)span_bytes, 0x00020000);
+  // BEAM self: the C rows' ancestries to LDS before the first request (they address it); entries clamped into the clip
+  unsigned char* const ancl = reinterpret_cast<unsigned char*>(hn + C * a.d + (SELF ? a.bias_stride : 0));   // [C][kv_stride]
+  if constexpr (BEAM && SELF) {
+    const int na = min(max(st_t, 1), a.kv_stride);
+    for (int i = tid; i < C * na; i += 1024) {
+      const int c = i / na, j = i - c * na;
+      const int r = min(b0 + c, nb - 1);
+      const int v = j < st_t ? min((int)a.anc[(int64_t)(st_t & 1) * a.anc_par + (int64_t)r * a.anc_ld + j], a.beam_nb - 1) : r % a.beam_nb;
+      ancl[c * a.kv_stride + j] = (unsigned char)(r / a.beam_nb * a.beam_nb - lo_blk + v);    // the block, relative to the base
+    }
+    __syncthreads();
+  }
+  // (lane offset, scalar offset) of this lane's part of key row `key` (clamped) of row b0 + c
+  auto kvo = [&](int c, int key, int subc, unsigned& voff, unsigned& soff) {
+    voff = (unsigned)((key * DK + subc * E) * (int)sizeof(T));
+    if constexpr (BEAM && SELF) { voff += (unsigned)ancl[c * a.kv_stride + key] * clip_bytes; soff = 0u; }
+    else soff = cb(c);
+  };
   auto kvload = [](__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(V16, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, NT ? 2 : 0));   // aux 2 = nt
   };
@@ -1389,9 +1448,16 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
     const int c_first = mine ? __builtin_ctz(mine) : (st == 0 ? 0 : min(st, min(C, nb - b0) - 1));
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
-      const unsigned off = (unsigned)((min(kslot + u * KPB, last) * DK + sub * E) * (int)sizeof(T));
-      kv[st][u].v = kvload(rK, off, (unsigned)c_first * clip_bytes);
-      vv[st][u].v = kvload(rV, off, (unsigned)c_first * clip_bytes);
+      if constexpr (BEAM) {
+        unsigned off, so;
+        kvo(c_first, min(kslot + u * KPB, last), sub, off, so);
+        kv[st][u].v = kvload(rK, off, so);
+        vv[st][u].v = kvload(rV, off, so);
+      } else {
+        const unsigned off = (unsigned)((min(kslot + u * KPB, last) * DK + sub * E) * (int)sizeof(T));
+        kv[st][u].v = kvload(rK, off, (unsigned)c_first * clip_bytes);
+        vv[st][u].v = kvload(rV, off, (unsigned)c_first * clip_bytes);
+      }
     }
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -1521,7 +1587,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
   for (int st = 0; st < CIF; ++st) {
     const int c = c0 + st;
     const bool walks = (walk >> c) & 1u;                                          // uniform
-    const unsigned cbase = (unsigned)c * clip_bytes;      // this clip inside the descriptors (an invalid tail clip walks nothing)
+    const unsigned cbase = BEAM ? cb(c) : (unsigned)c * clip_bytes;   // this clip inside the descriptors (an invalid tail clip walks nothing)
     // per-clip OPAQUE copies of the lane's place in a round: derived from threadIdx the hand-over offsets below are loop invariants
     // that the compiler keeps from the prologue, spills (64 registers), and reloads in the middle of the stream - and a scratch
     // reload waits vmcnt(0), i.e. for every round in flight
@@ -1566,7 +1632,18 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
       // compiler sinks V's unpacking into the predicated block, keeps the packed V alive past the request, loads into a SECOND
       // register set and copies it back behind a vmcnt(0) at the end of every iteration (seen in the ISA at PF = 4: the window
       // became batches)
-      if (mode == 1) {
+      if (BEAM && SELF && mode == 1) {
+        unsigned off, so;
+        kvo(c, min(key + PF * KPB, last), sub_c, off, so);
+        ks.v = kvload(rK, off, so);
+        vs.v = kvload(rV, off, so);
+      } else if (BEAM && SELF && mode == 2) {    // nxt: the next walking clip's index, or the out-of-range marker
+        const bool oob = nxt >= 0x7F000000u;
+        unsigned off = nxt, so = 0u;
+        if (!oob) kvo((int)nxt, min(kslot_c + u * KPB, last), sub_c, off, so);
+        ks.v = kvload(rK, off, so);
+        vs.v = kvload(rV, off, so);
+      } else if (mode == 1) {
         const unsigned off = (unsigned)((min(key + PF * KPB, last) * DK + sub_c * E) * (int)sizeof(T));
         ks.v = kvload(rK, off, cbase);
         vs.v = kvload(rV, off, cbase);
@@ -1591,7 +1668,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
       // drops them (zeros, no memory access) - one code path, so the slots stay in ONE register set (with a second, load-free path
       // for the last clip the register allocator kept a second set of 8 PF registers for the handed-over rounds and copied it back)
       const unsigned rest = (walk >> (c + CIF)) & SETBITS;                     // later walking clips of this set
-      const unsigned nxt = rest ? cbase + (unsigned)(__builtin_ctz(rest) + CIF) * clip_bytes : 0x7F000000u;
+      unsigned nxt;
+      if constexpr (BEAM && SELF) nxt = rest ? (unsigned)(c + __builtin_ctz(rest) + CIF) : 0x7F000000u;
+      else if constexpr (BEAM) nxt = rest ? cb(c + __builtin_ctz(rest) + CIF) : 0x7F000000u;
+      else nxt = rest ? cbase + (unsigned)(__builtin_ctz(rest) + CIF) * clip_bytes : 0x7F000000u;
 #pragma unroll
       for (int u = 0; u < PF; ++u) round(k0, u, kv[st][u], vv[st][u], 2, nxt);
     }
@@ -1685,7 +1765,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
 
 template <typename T>
 static void launch_dec_attn_t(bool self, bool nt, const DecAttnArgs& a, dim3 grid, size_t smem, hipStream_t st) {
-  if (self && a.emb) {
+  if (a.beam_nb > 0) {          // beam search: ancestry reads (self) / a clip's K/V shared by its beams (cross)
+    if (self && nt) hipLaunchKernelGGL((dec_attn_kernel<T, true, true, false, true>), grid, dim3(1024), smem, st, a);
+    else if (self) hipLaunchKernelGGL((dec_attn_kernel<T, true, false, false, true>), grid, dim3(1024), smem, st, a);
+    else if (nt) hipLaunchKernelGGL((dec_attn_kernel<T, false, true, false, true>), grid, dim3(1024), smem, st, a);
+    else hipLaunchKernelGGL((dec_attn_kernel<T, false, false, false, true>), grid, dim3(1024), smem, st, a);
+  } else if (self && a.emb) {
     if (nt) hipLaunchKernelGGL((dec_attn_kernel<T, true, true, true>), grid, dim3(1024), smem, st, a);
     else hipLaunchKernelGGL((dec_attn_kernel<T, true, false, true>), grid, dim3(1024), smem, st, a);
   } else if (self) {
@@ -1707,7 +1792,12 @@ static void launch_dec_attn_mc_t(bool self, bool nt, const DecAttnArgs& a, int n
   // against 351.4 / 350.9, fp32 577.2 against 591.9, 2 x 32 clips 220.4 against 226.6, 2 x 64 at S = 864 480.9 against 485.0.  One
   // in flight.
   const bool two_in_flight = !self && cif == 2;
-  if (self && a.emb) {
+  if (a.beam_nb > 0) {          // beam search (one clip in flight whatever M2M_MC_CIF says)
+    if (self && nt) hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, true, false, C, 1, true>), grid, dim3(1024), smem, st, a, nb);
+    else if (self) hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, false, false, C, 1, true>), grid, dim3(1024), smem, st, a, nb);
+    else if (nt) hipLaunchKernelGGL((dec_attn_mc_kernel<T, false, true, false, C, 1, true>), grid, dim3(1024), smem, st, a, nb);
+    else hipLaunchKernelGGL((dec_attn_mc_kernel<T, false, false, false, C, 1, true>), grid, dim3(1024), smem, st, a, nb);
+  } else if (self && a.emb) {
     if (nt) hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, true, true, C>), grid, dim3(1024), smem, st, a, nb);
     else hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, false, true, C>), grid, dim3(1024), smem, st, a, nb);
   } else if (self) {
@@ -1723,9 +1813,11 @@ static void launch_dec_attn_mc_t(bool self, bool nt, const DecAttnArgs& a, int n
 }
 
 static int launch_dec_attn(int precision, bool self, bool nt, DecAttnArgs a, int B, int clips, int cif, hipStream_t st) {
-  const size_t smem = ((size_t)a.d * (size_t)clips + (self ? (size_t)a.bias_stride : 0)) * sizeof(float);   // hn rows + (self) the bias row
-  M2M_REQUIRE(smem <= 24 * 1024, "decode attention: max_dec_len=%d too long for the LDS bias row (<= %d)", a.bias_stride,
-              (24 * 1024 - a.d * 4 * clips) / 4);
+  size_t smem = ((size_t)a.d * (size_t)clips + (self ? (size_t)a.bias_stride : 0)) * sizeof(float);   // hn rows + (self) the bias row
+  if (self && a.beam_nb > 0) smem += (size_t)clips * a.kv_stride;         // + the rows' ancestries (a byte per position)
+  M2M_REQUIRE(smem <= 24 * 1024, "decode attention: max_dec_len=%d too long for the LDS bias row%s (<= %d)", a.bias_stride,
+              self && a.beam_nb > 0 ? " and ancestries" : "",
+              (24 * 1024 - a.d * 4 * clips) / (self && a.beam_nb > 0 ? 4 + clips : 4));
   const bool bf = precision == M2M_PREC_BF16;
   if (clips == 1) {
     dim3 grid((unsigned)a.H, (unsigned)B);
@@ -2079,6 +2171,296 @@ static int launch_dec_sample(const DecHeadArgs& h, const SampleParams* sp, hipSt
   return M2M_OK;
 }
 
+// ============================================================== beam head ====
+// Beam search (m2m_generate_beam) replaces dec_head_kernel by this kernel, one workgroup per clip (its beam_nb rows), and follows
+// transformers 4.34 (hf: generation/utils.py _beam_search, generation/beam_search.py BeamSearchScorer.process / BeamHypotheses):
+//   scores = log_softmax(logits) + running beam score (fp32); the clip's top 2 nb over nb x V, ties to the lower flat (beam-major)
+//   index; walked in rank order, an EOS candidate of rank < nb becomes a hypothesis (score sum / len^lp in double, len = t + 1:
+//   the start token and the generated ones, not EOS; at most nb kept, BeamHypotheses.add's worst-score bookkeeping), an EOS of
+//   rank >= nb is dropped, every other candidate is the next running beam until there are nb; then is_done.
+// A beam is a path through the self K/V caches (DecAttnArgs::anc): new beam i of parent p gets p's ancestry plus p at position t,
+// double-buffered by the parity of t; the token fed at position j of slot s stays in the token matrix at [s][j] (written once).
+// A hypothesis keeps a snapshot of its tokens.  The rows of a done clip are marked finished (their K/V streams stop); the step
+// closes when the last workgroup is through (the sampling head's ticket), the chain is done when every clip is.
+struct DecBeamArgs {
+  BeamParams* p;           // the call's parameters (device block; max_hyp_len is written by the finalize kernel)
+  BeamClip* clip;          // [clips of the view]
+  BeamRow* row;            // [rows of the view]: running beams, and hypothesis slot h of clip c in row c * nb + h
+  unsigned char* anc;      // [rows][anc_ld] ancestries of the view, parity 0; parity 1 at + anc_par
+  int64_t anc_par;
+  int anc_ld;
+  int64_t* hyp_tok;        // [rows][max_len] hypothesis snapshots (slot as in `row`)
+};
+
+__device__ inline float ord_key_inv(unsigned k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+__device__ inline unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o, 64);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+// one hypothesis into the clip's store (BeamHypotheses.add); slots [r0, r0 + nb) of the row block; returns the slot or -1
+__device__ inline int beam_hyp_add(BeamClip* bc, BeamRow* row, int r0, int nb, double score) {
+  if (!(bc->n_hyp < nb || score > bc->worst)) return -1;
+  int slot;
+  if (bc->n_hyp < nb) {
+    slot = bc->n_hyp++;
+    bc->worst = fmin(score, bc->worst);
+  } else {                 // full: the new one replaces the worst (the earliest added among equal scores), worst = the new minimum
+    slot = 0;
+    for (int h = 1; h < nb; ++h) {
+      const BeamRow& a = row[r0 + h];
+      const BeamRow& b = row[r0 + slot];
+      if (a.hyp_score < b.hyp_score || (a.hyp_score == b.hyp_score && a.hyp_stamp < b.hyp_stamp)) slot = h;
+    }
+  }
+  row[r0 + slot].hyp_score = score;
+  row[r0 + slot].hyp_stamp = bc->stamp++;
+  if (bc->n_hyp == nb) {
+    double w = row[r0].hyp_score;
+    for (int h = 1; h < nb; ++h) w = fmin(w, row[r0 + h].hyp_score);
+    bc->worst = w;
+  }
+  return slot;
+}
+
+template <int NPL>
+__global__ __launch_bounds__(1024) void dec_beam_kernel(DecHeadArgs a, DecBeamArgs bm) {
+  __shared__ unsigned long long cand[BEAM_MAX][2 * BEAM_MAX];   // per beam: its top 2 nb keys, descending
+  __shared__ unsigned long long top[2 * BEAM_MAX];              // the clip's top 2 nb
+  __shared__ int s_par[BEAM_MAX], s_tok[BEAM_MAX], s_src[BEAM_MAX];
+  __shared__ float s_score[BEAM_MAX];
+  __shared__ int s_bad, s_done;
+  DecState* stp = a.state;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nb = bm.p->nb, K = 2 * nb, V = a.V, r0 = blockIdx.x * nb;
+  const int t = stp->t;
+  const bool live = !(stp->done | (t >= stp->max_steps));
+  BeamClip* bc = bm.clip + blockIdx.x;
+  const int was_done = bc->done;
+  const bool work = live && !was_done;
+  if (tid == 0) { s_bad = 0; s_done = was_done; }
+  if (tid < BEAM_MAX) s_src[tid] = -1;
+  __syncthreads();
+  if (work) {
+    // A. per beam (one wave): fp32 log-softmax plus the running score, then the beam's own top 2 nb by repeated arg-max
+    for (int r = wave; r < nb; r += 16) {
+      const float* lg = a.logits + (int64_t)(r0 + r) * a.ldl;
+      const int v0 = lane * NPL;
+      float x[NPL];
+      bool bad = false;
+      float m = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) {
+        x[j] = (v0 + j < V) ? lg[v0 + j] : 0.f;
+        if (v0 + j < V) { bad |= !(fabsf(x[j]) <= 3.0e38f); m = fmaxf(m, x[j]); }
+      }
+      m = wave_max(m);
+      float z = 0.f;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) if (v0 + j < V) z += expf(x[j] - m);
+      z = wave_sum(z);                    // butterfly: the same bits in every lane
+      const float lz = logf(z), bs = bm.row[r0 + r].score;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) x[j] = ((x[j] - m) - lz) + bs;
+      if (__ballot(bad) && lane == 0) s_bad = 1;
+      unsigned long long taken = 0ull;
+      for (int k = 0; k < K; ++k) {
+        float bv = 0.f;
+        int bj = -1;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j)
+          if (v0 + j < V && !((taken >> j) & 1ull) && (bj < 0 || x[j] > bv)) { bv = x[j]; bj = j; }
+        const unsigned long long key = bj < 0 ? 0ull
+            : ((unsigned long long)ord_key(bv) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)(r * V + v0 + bj));
+        const unsigned long long w = wave_max_u64(key);
+        if (bj >= 0 && key == w) taken |= 1ull << bj;      // keys are unique (the flat index is part of them)
+        if (lane == 0) cand[r][k] = w;
+      }
+    }
+  }
+  __syncthreads();
+  if (work && wave == 0) {          // B. merge the nb sorted lists (lane i walks beam i's) into the clip's top 2 nb
+    int ptr = 0;
+    for (int k = 0; k < K; ++k) {
+      const unsigned long long h = (lane < nb && ptr < K) ? cand[lane][ptr] : 0ull;
+      const unsigned long long w = wave_max_u64(h);
+      if (lane < nb && h == w) ++ptr;
+      if (lane == 0) top[k] = w;
+    }
+  }
+  __syncthreads();
+  if (work && tid == 0) {           // C. BeamSearchScorer.process for this clip (serial: 2 nb candidates)
+    const BeamParams P = *bm.p;
+    const int cur_len = t + 1;
+    int bi = 0;
+    for (int k = 0; k < K && bi < nb; ++k) {
+      const unsigned long long key = top[k];
+      const float sc = ord_key_inv((unsigned)(key >> 32));
+      const int flat = (int)(0xFFFFFFFFu - (unsigned)key);
+      const int beam = flat / V, tok = flat - beam * V;
+      if (tok == a.eos_id) {
+        if (k >= nb) continue;
+        const int slot = beam_hyp_add(bc, bm.row, r0, nb, (double)sc / pow((double)cur_len, (double)P.lp));
+        if (slot >= 0) { bm.row[r0 + slot].hyp_len = cur_len; s_src[slot] = beam; }
+      } else {
+        s_par[bi] = beam; s_tok[bi] = tok; s_score[bi] = sc; ++bi;
+      }
+    }
+    bool done = false;              // BeamHypotheses.is_done(best running score of the step, cur_len)
+    if (bc->n_hyp >= nb) {
+      if (P.early == 1) done = true;
+      else {
+        const double best = (double)ord_key_inv((unsigned)(top[0] >> 32));
+        const double len = (P.early == 2 && P.lp > 0.f) ? (double)P.max_length : (double)cur_len;
+        done = bc->worst >= best / pow(len, (double)P.lp);
+      }
+    }
+    if (done) bc->done = 1;
+    s_done = done ? 1 : 0;
+  }
+  __syncthreads();
+  if (work) {                        // D. hypothesis snapshots, the new beams' ancestries and tokens, the next input rows
+    const unsigned char* ac = bm.anc + (int64_t)(t & 1) * bm.anc_par;
+    unsigned char* an = bm.anc + (int64_t)((t + 1) & 1) * bm.anc_par;
+    int64_t* tk = a.tokens + (int64_t)a.row0 * a.max_len;          // the view's rows of the token matrix (no re-packing: identity)
+    for (int h = 0; h < nb; ++h) {
+      const int p = s_src[h];
+      if (p < 0) continue;
+      for (int j = tid; j <= t; j += 1024) {
+        const int sl = j < t ? min((int)ac[(int64_t)(r0 + p) * bm.anc_ld + j], nb - 1) : p;
+        bm.hyp_tok[(int64_t)(r0 + h) * a.max_len + j] = tk[(int64_t)(r0 + sl) * a.max_len + j];
+      }
+    }
+    const bool dn = s_done != 0;
+    for (int i = wave; i < nb; i += 16) {
+      const int p = dn ? i : s_par[i];
+      if (!dn) {
+        for (int j = lane; j < t; j += 64) an[(int64_t)(r0 + i) * bm.anc_ld + j] = ac[(int64_t)(r0 + p) * bm.anc_ld + j];
+        if (lane == 0) {
+          an[(int64_t)(r0 + i) * bm.anc_ld + t] = (unsigned char)p;
+          if (t + 1 < a.max_len) tk[(int64_t)(r0 + i) * a.max_len + t + 1] = s_tok[i];
+          bm.row[r0 + i].score = s_score[i];
+        }
+      } else if (lane == 0) {
+        a.finished[r0 + i] = 1;     // a done clip: its rows stop streaming K/V
+      }
+      int next = dn ? a.pad_id : s_tok[i];
+      if (next < 0 || next >= V) next = a.pad_id;
+      const float* emb = a.shared + (int64_t)next * a.d;
+      for (int c = lane * 4; c < a.d; c += 256) {
+        const float4 e4 = *reinterpret_cast<const float4*>(emb + c);
+        xq_t* xp = a.x + (int64_t)(r0 + i) * a.d + c;
+        *reinterpret_cast<longlong2*>(xp) = make_longlong2(xq_fix_guarded(e4.x, stp), xq_fix_guarded(e4.y, stp));
+        *reinterpret_cast<longlong2*>(xp + 2) = make_longlong2(xq_fix_guarded(e4.z, stp), xq_fix_guarded(e4.w, stp));
+      }
+    }
+  }
+  // E. the step closes when the last workgroup is through (every workgroup has read t / done above before it takes its ticket)
+  __syncthreads();
+  if (tid == 0 && live) {
+    if (s_bad) stp->overflow = 1;
+    if (!s_done) atomicAdd(&stp->smp_unfinished, 1);
+    __threadfence();
+    if (atomicAdd(&stp->smp_ticket, 1) == (int)gridDim.x - 1) {
+      __threadfence();
+      const int nu = atomicExch(&stp->smp_unfinished, 0);
+      stp->smp_ticket = 0;
+      const int nt = t + 1;
+      stp->t = nt;
+      stp->n_unfinished = nu;
+      if (nu == 0 || nt >= stp->max_steps) { stp->done = 1; stp->out_len = nt + 1; }
+    }
+  }
+}
+
+static int launch_dec_beam(const DecHeadArgs& h, const DecBeamArgs& bm, int nbeams, hipStream_t st) {
+  M2M_REQUIRE(h.V >= 1 && h.V <= SAMPLE_MAX_VOCAB, "dec_beam_kernel: vocab_size %d outside [1, %d]", h.V, SAMPLE_MAX_VOCAB);
+  M2M_REQUIRE(nbeams >= 2 && nbeams <= BEAM_MAX && h.B % nbeams == 0, "dec_beam_kernel: %d rows are not clips of %d beams", h.B, nbeams);
+  const dim3 grid((unsigned)(h.B / nbeams)), block(1024);
+  if (h.V <= 64 * 8) hipLaunchKernelGGL(dec_beam_kernel<8>, grid, block, 0, st, h, bm);
+  else if (h.V <= 64 * 16) hipLaunchKernelGGL(dec_beam_kernel<16>, grid, block, 0, st, h, bm);
+  else if (h.V <= 64 * 32) hipLaunchKernelGGL(dec_beam_kernel<32>, grid, block, 0, st, h, bm);
+  else hipLaunchKernelGGL(dec_beam_kernel<64>, grid, block, 0, st, h, bm);
+  M2M_CHECK_HIP(hipGetLastError());
+  return M2M_OK;
+}
+
+// before the first step of a chain: beam 0 of every clip starts at score 0, the others at -1e9 (hf _beam_search), empty stores
+__global__ void dec_beam_init_kernel(DecBeamArgs bm, int rows) {
+  const int nb = bm.p->nb;
+  for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += gridDim.x * blockDim.x) {
+    BeamRow br{};
+    br.score = (r % nb == 0) ? 0.f : -1e9f;
+    bm.row[r] = br;
+    if (r % nb == 0) {
+      BeamClip c{};
+      c.worst = 1e9;
+      bm.clip[r / nb] = c;
+    }
+  }
+}
+
+// after every chain: BeamSearchScorer.finalize, one workgroup per clip.  A clip that is not done adds its running beams at length
+// T + 1 (= max_length); the best n hypotheses, highest score first and the later-added first among equal scores (sorted(...).pop()),
+// go to the output rows clip * n + j: their tokens, EOS at column len when len < max_length, pad after.  The longest picked
+// hypothesis goes to BeamParams::max_hyp_len (the host trims the width to min(it + 1, max_length)).
+__global__ __launch_bounds__(256) void dec_beam_final_kernel(DecBeamArgs bm, const int64_t* tokens, int max_len, int T, int64_t* out,
+                                                             float* scores, int max_length, int pad_id, int eos_id) {
+  __shared__ int s_src[BEAM_MAX], s_pick[BEAM_MAX];
+  const int tid = threadIdx.x, nb = bm.p->nb, n = bm.p->n, clip = blockIdx.x, r0 = clip * nb;
+  BeamClip* bc = bm.clip + clip;
+  if (tid < BEAM_MAX) s_src[tid] = -1;
+  __syncthreads();
+  if (tid == 0) {
+    if (!bc->done) {
+      for (int i = 0; i < nb; ++i) {
+        const int slot = beam_hyp_add(bc, bm.row, r0, nb, (double)bm.row[r0 + i].score / pow((double)(T + 1), (double)bm.p->lp));
+        if (slot >= 0) { bm.row[r0 + slot].hyp_len = T + 1; s_src[slot] = i; }
+      }
+    }
+    unsigned taken = 0;
+    int longest = 0;
+    for (int j = 0; j < n; ++j) {
+      int b = -1;
+      for (int h = 0; h < bc->n_hyp; ++h) {
+        if ((taken >> h) & 1u) continue;
+        const BeamRow& x = bm.row[r0 + h];
+        if (b < 0 || x.hyp_score > bm.row[r0 + b].hyp_score ||
+            (x.hyp_score == bm.row[r0 + b].hyp_score && x.hyp_stamp > bm.row[r0 + b].hyp_stamp)) b = h;
+      }
+      if (b < 0) b = 0;              // (never: a finalized clip holds nb >= n hypotheses)
+      taken |= 1u << b;
+      s_pick[j] = b;
+      longest = max(longest, bm.row[r0 + b].hyp_len);
+    }
+    atomicMax(&bm.p->max_hyp_len, longest);
+  }
+  __syncthreads();
+  const unsigned char* ac = bm.anc + (int64_t)(T & 1) * bm.anc_par;
+  for (int h = 0; h < nb; ++h) {     // snapshots of the running beams that became hypotheses here
+    const int p = s_src[h];
+    if (p < 0) continue;
+    for (int j = tid; j <= T; j += blockDim.x) {
+      const int sl = j < T ? min((int)ac[(int64_t)(r0 + p) * bm.anc_ld + j], nb - 1) : p;
+      bm.hyp_tok[(int64_t)(r0 + h) * max_len + j] = tokens[(int64_t)(r0 + sl) * max_len + j];
+    }
+  }
+  __syncthreads();
+  for (int j = 0; j < n; ++j) {
+    const int h = s_pick[j];
+    const int len = bm.row[r0 + h].hyp_len;
+    const int64_t* src = bm.hyp_tok + (int64_t)(r0 + h) * max_len;
+    int64_t* dst = out + (int64_t)(clip * n + j) * max_length;
+    for (int c = tid; c < max_length; c += blockDim.x) dst[c] = c < len ? src[c] : (c == len ? eos_id : pad_id);
+    if (tid == 0 && scores) scores[clip * n + j] = (float)bm.row[r0 + h].hyp_score;
+  }
+}
+
 // ============================================================ live-row re-packing ====
 // Clips end at different steps (a real checkpoint ends a 3 s segment after tens to hundreds of its 1 024 tokens).  The finished-row
 // early-out above stops a finished row's K/V stream, but its workgroups still launch and the chain still pays its latency floor for
@@ -2166,6 +2548,30 @@ static DecHeadArgs head_args(m2m_session* s, const DecView& v, bool forced, floa
   return h;
 }
 
+static DecBeamArgs beam_args(m2m_session* s, const DecView& v) {
+  DecBeamArgs b{};
+  const int nb = s->beam_nb > 0 ? s->beam_nb : 1;
+  b.p = s->beam_dev; b.clip = s->beam_clip + v.b0 / nb; b.row = s->beam_row + v.b0;
+  b.anc = s->anc + (int64_t)v.b0 * s->max_dec; b.anc_par = (int64_t)s->max_batch * s->max_dec; b.anc_ld = s->max_dec;
+  b.hyp_tok = s->hyp_tok + (int64_t)v.b0 * s->max_dec;
+  return b;
+}
+
+int decode_beam_init(m2m_session* s, const DecView& v, hipStream_t st) {
+  hipLaunchKernelGGL(dec_beam_init_kernel, dim3((unsigned)ceil_div(v.nb, 256)), dim3(256), 0, st, beam_args(s, v), v.nb);
+  M2M_CHECK_HIP(hipGetLastError());
+  return M2M_OK;
+}
+
+int decode_beam_finalize(m2m_session* s, int rows, int steps, int64_t* out, float* scores, int max_length, hipStream_t st) {
+  const DecView all{0, rows, nullptr};
+  const m2m_t5_geometry& g = s->m->g;
+  hipLaunchKernelGGL(dec_beam_final_kernel, dim3((unsigned)(rows / s->beam_nb)), dim3(256), 0, st, beam_args(s, all), s->tokens,
+                     s->max_dec, steps, out, scores, max_length, g.pad_token_id, g.eos_token_id);
+  M2M_CHECK_HIP(hipGetLastError());
+  return M2M_OK;
+}
+
 int decode_finalize(m2m_session* s, const DecView& v, hipStream_t st) {
   if (!headless_for(s, false)) return M2M_OK;
   DecHeadArgs h = head_args(s, v, false, nullptr, 0);
@@ -2251,6 +2657,12 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
   a.H = H; a.inner = m->inner; a.state = v.state;
   if (skip_finished && decode_finished_skip_on()) { a.fin_skip = s->finished + v.b0; a.fin_stride = 1; }
   else { a.fin_skip = &v.state->zero; a.fin_stride = 0; }
+  // beam search: the view's rows are clips x beam_nb beams (the view starts at a clip boundary)
+  const bool beam = s->head_mode == HEAD_BEAM && s->beam_nb > 0;
+  if (beam) {
+    a.beam_nb = s->beam_nb;
+    a.anc = s->anc + (int64_t)v.b0 * s->max_dec; a.anc_par = (int64_t)s->max_batch * s->max_dec; a.anc_ld = s->max_dec;
+  }
   if (headless && layer == 0) {            // the greedy loop without the head kernel: layer 0 takes over its work
     a.keys = s->keys + v.b0; a.finished = s->finished + v.b0; a.tokens = s->tokens; a.tok_row = s->tok_row + v.b0;
     a.max_len = s->max_dec; a.V = g.vocab_size; a.pad_id = g.pad_token_id; a.eos_id = g.eos_token_id;
@@ -2267,7 +2679,7 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
   }
   // cross K/V: [L][2][B][H][S][64] with B, S = the encoded problem
   const size_t per = (size_t)s->B * H * s->S * DK;
-  const size_t voff = (size_t)v.b0 * H * s->S * DK;
+  const size_t voff = (size_t)(beam ? v.b0 / s->beam_nb : v.b0) * H * s->S * DK;
   a.ln_w = L.ln1; a.Wp = L.wcq; a.Wo = L.wco;
   a.Kc = (unsigned char*)s->cross_kv + (((size_t)layer * 2 + 0) * per + voff) * es;
   a.Vc = (unsigned char*)s->cross_kv + (((size_t)layer * 2 + 1) * per + voff) * es;
@@ -2310,6 +2722,7 @@ int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* log
   if (headless) return M2M_OK;             // the arg-max key is consumed by the next step's layer 0 (or by decode_finalize)
   DecHeadArgs h = head_args(s, v, forced, logits_out, Ld);
   if (!forced && s->head_mode == HEAD_SAMPLE) return launch_dec_sample(h, s->sample_dev, st);
+  if (!forced && s->head_mode == HEAD_BEAM) return launch_dec_beam(h, beam_args(s, v), s->beam_nb, st);
   hipLaunchKernelGGL(dec_head_kernel, dim3(1), dim3(1024), 0, st, h);
   M2M_CHECK_HIP(hipGetLastError());
   return M2M_OK;

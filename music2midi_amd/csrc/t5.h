@@ -79,6 +79,32 @@ struct SampleParams {
   unsigned long long seed;  // the call's seed: the draw of clip row r at position t hashes (seed, r, t)
 };
 
+// Beam search (m2m_generate_beam): the call's parameters, a device block of the workspace written before the chains start (as
+// SampleParams), and the per-clip / per-row state of the beam head (decode.hip dec_beam_kernel).
+struct BeamParams {
+  int nb;                   // beams per clip, 2..BEAM_MAX
+  float lp;                 // length_penalty
+  int early;                // early_stopping: 0 False, 1 True, 2 "never"
+  int n;                    // num_return_sequences, 1..nb
+  int max_length;
+  int max_hyp_len;          // written by the finalize kernel: the longest returned hypothesis (0 before)
+  int pad_[2];
+};
+struct BeamClip {           // BeamHypotheses of one clip
+  double worst;             // worst kept score (1e9 while empty)
+  int n_hyp;                // hypotheses kept (<= nb)
+  int done;
+  int stamp;                // hypotheses added so far (the order of BeamHypotheses.beams)
+  int pad_;
+};
+struct BeamRow {            // row c * nb + h: running beam h of clip c, and hypothesis slot h of that clip
+  double hyp_score;         // sum_logprobs / len ** length_penalty (double: HF computes it in Python floats)
+  float score;              // running beam score (fp32, as HF's beam_scores)
+  int hyp_len;              // tokens of the hypothesis (start token included, EOS not)
+  int hyp_stamp;            // when it was added
+  int pad_;
+};
+
 }  // namespace m2m
 
 namespace m2m {
@@ -119,10 +145,10 @@ struct DecGroup {
   hipStream_t stream = nullptr;
   hipEvent_t ev_done = nullptr;
   hipGraphExec_t graph_exec = nullptr;           // the graph of the current view (an entry of `graphs`)
-  // captured graphs by (B, S, b0, nb, steps per graph, finished-row skip on / off, head form) — all baked into the launches.  Re-packing the live
+  // captured graphs by (B, S, b0, nb, steps per graph, finished-row skip on / off, head form, beams) — all baked into the launches.  Re-packing the live
   // rows changes (b0, nb) several times per batch, and the next batch starts from the full views again: a small cache instead of
   // a re-capture (~1 ms per 8-step graph) at every change
-  struct GraphEntry { int key[7]; hipGraph_t graph; hipGraphExec_t exec; unsigned long long used; };
+  struct GraphEntry { int key[8]; hipGraph_t graph; hipGraphExec_t exec; unsigned long long used; };
   std::vector<GraphEntry> graphs;
   unsigned long long graph_clock = 0;
 };
@@ -165,9 +191,17 @@ struct m2m_session {
   int ff_slices = 0;       // decode feed-forward: hidden slices per workgroup forced by M2M_DEC_FF_SLICES (0: by chain size)
   int mc_cif = 1;          // multi-clip cross-attention: clips in flight, M2M_MC_CIF (diagnostic: 2; 0 or unset: 1, the product)
   int repacks = 0, rows_moved = 0;   // live-row re-packings / rows moved by them in the last m2m_generate_greedy / _sample
-  int head_mode = 0;       // head form of the free-running decode step: 0 greedy (arg-max), 1 sampling (set for the length of a call)
+  int head_mode = 0;       // head form of the free-running decode step: 0 greedy (arg-max), 1 sampling, 2 beam (set for the length of a call)
   m2m::SampleParams* sample_dev = nullptr;    // [1] in the workspace
   m2m::SampleParams* sample_host = nullptr;   // pinned staging copy
+  // beam search (m2m_generate_beam): rows = encoded clips x beam_nb; every buffer below is in the workspace
+  int beam_nb = 0;                            // beams per clip during a beam call, 0 otherwise
+  m2m::BeamParams* beam_dev = nullptr;        // [1]
+  m2m::BeamParams* beam_host = nullptr;       // pinned staging copy
+  m2m::BeamClip* beam_clip = nullptr;         // [max_batch]
+  m2m::BeamRow* beam_row = nullptr;           // [max_batch]
+  unsigned char* anc = nullptr;               // [2][max_batch][max_dec] ancestries (slot within the clip of every cached position)
+  int64_t* hyp_tok = nullptr;                 // [max_batch][max_dec] hypothesis snapshots
   bool encoded = false;
   // decode chains
   hipEvent_t ev_in = nullptr;
@@ -262,7 +296,10 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
 int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int t, hipStream_t st);   // live-row re-packing (decode.hip)
 int decode_finalize(m2m_session* s, const DecView& v, hipStream_t st);   // headless greedy loop: write the last token, close the chain
 bool decode_headless();
-constexpr int HEAD_GREEDY = 0, HEAD_SAMPLE = 1;
+constexpr int HEAD_GREEDY = 0, HEAD_SAMPLE = 1, HEAD_BEAM = 2;
+constexpr int BEAM_MAX = 32;             // beams per clip: one LDS list of 2 x 32 candidates per beam, ancestries in bytes
+int decode_beam_init(m2m_session* s, const DecView& v, hipStream_t st);
+int decode_beam_finalize(m2m_session* s, int rows, int steps, int64_t* out, float* scores, int max_length, hipStream_t st);
 constexpr int SAMPLE_MAX_VOCAB = 4096;   // dec_sample_kernel keeps a row in the registers of one wavefront (64 lanes x 64 logits)
 int decode_attn_clips(const m2m_session* s, int nb);
 int decode_ff_rows(const m2m_session* s, int nb);

@@ -187,7 +187,7 @@ extern "C" int m2m_model_checksum(const m2m_model* m, uint64_t* out_host, void* 
 namespace {
 struct WsLayout {
   int64_t x_enc, h_enc, qkv_enc, vt_enc, attn_enc, mid_enc, enc_bias, dec_bias, dec_bias_full, cross_vt, cross_kv, self_k, self_v;
-  int64_t x_dec, logits, tokens, finished, tok_row, keys, state, forced, sample, total;
+  int64_t x_dec, logits, tokens, finished, tok_row, keys, state, forced, sample, beam, beam_clip, beam_row, anc, hyp_tok, total;
 };
 
 WsLayout ws_layout(const m2m_model* m, int B, int S, int L) {
@@ -220,6 +220,11 @@ WsLayout ws_layout(const m2m_model* m, int B, int S, int L) {
   w.state = take(sizeof(DecState) * MAX_GROUPS);
   w.forced = take((int64_t)B * L * 8);
   w.sample = take(sizeof(SampleParams));
+  w.beam = take(sizeof(BeamParams));
+  w.beam_clip = take((int64_t)B * sizeof(BeamClip));
+  w.beam_row = take((int64_t)B * sizeof(BeamRow));
+  w.anc = take(2 * (int64_t)B * L);
+  w.hyp_tok = take((int64_t)B * L * 8);
   w.total = off;
   return w;
 }
@@ -278,6 +283,8 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   s->logits = (float*)(b + w.logits); s->tokens = (int64_t*)(b + w.tokens);
   s->finished = (int*)(b + w.finished); s->tok_row = (int*)(b + w.tok_row); s->keys = (unsigned long long*)(b + w.keys); s->states = (DecState*)(b + w.state); s->forced_ids = (int64_t*)(b + w.forced);
   s->sample_dev = (SampleParams*)(b + w.sample);
+  s->beam_dev = (BeamParams*)(b + w.beam); s->beam_clip = (BeamClip*)(b + w.beam_clip); s->beam_row = (BeamRow*)(b + w.beam_row);
+  s->anc = b + w.anc; s->hyp_tok = (int64_t*)(b + w.hyp_tok);
 
   // relative-position bias tables (fp32), built on the host from the bucket function
   const m2m_t5_geometry& g = m->g;
@@ -312,6 +319,7 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   if (e == hipSuccess) e = hipMemset(s->states, 0, sizeof(DecState) * MAX_GROUPS);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming);
   if (e == hipSuccess) e = hipHostMalloc((void**)&s->sample_host, sizeof(SampleParams), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s->beam_host, sizeof(BeamParams), hipHostMallocDefault);
   for (int i = 0; i < MAX_GROUPS && e == hipSuccess; ++i) {
     DecGroup& gr = s->groups[i];
     gr.view.state = s->states + i;
@@ -363,6 +371,7 @@ extern "C" void m2m_session_destroy(m2m_session* s) {
   }
   if (s->ev_in) (void)hipEventDestroy(s->ev_in);
   if (s->sample_host) (void)hipHostFree(s->sample_host);
+  if (s->beam_host) (void)hipHostFree(s->beam_host);
   delete s;
 }
 
@@ -444,11 +453,14 @@ static int plan_groups(m2m_session* s, int rows = -1) {       // rows: the packe
   int G = rows_env > 0 ? ceil_div(nrows, rows_env) : (nrows >= 24 ? 2 : 1);
   if (G < 1) G = 1;
   if (G > MAX_GROUPS) G = MAX_GROUPS;
-  const int base = nrows / G, extra = nrows % G;
+  // beam search: a clip's beams share a chain (the beam head ranks them together), so chains split at multiples of beam_nb
+  const int unit = s->beam_nb > 0 ? s->beam_nb : 1, units = nrows / unit;
+  if (G > units) G = units;
+  const int base = units / G, extra = units % G;
   int b0 = 0;
   for (int i = 0; i < G; ++i) {
     s->groups[i].view.b0 = b0;
-    s->groups[i].view.nb = base + (i < extra ? 1 : 0);
+    s->groups[i].view.nb = (base + (i < extra ? 1 : 0)) * unit;
     b0 += s->groups[i].view.nb;
   }
   return G;
@@ -457,7 +469,7 @@ static int plan_groups(m2m_session* s, int rows = -1) {       // rows: the packe
 // One graph = `steps` consecutive decode steps of one chain (kernels read the step index from
 // device memory, so the same graph replays for every position; steps past the end are no-ops).
 static int ensure_graph(m2m_session* s, DecGroup& gr, int steps) {
-  const int key[7] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, decode_finished_skip_on() ? 1 : 0, s->head_mode};
+  const int key[8] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, decode_finished_skip_on() ? 1 : 0, s->head_mode, s->beam_nb};
   ++gr.graph_clock;
   for (auto& ge : gr.graphs)
     if (memcmp(key, ge.key, sizeof(key)) == 0) { ge.used = gr.graph_clock; gr.graph_exec = ge.exec; return M2M_OK; }
@@ -666,6 +678,108 @@ static int generate_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev
     return M2M_ERR_RANGE;
   }
   return M2M_OK;
+}
+
+// Beam search (hf 4.34 _beam_search / BeamSearchScorer, see include/music2midi_amd.h): the B encoded clips are decoded as B x nb
+// rows (clip-major), in chains that split at clip boundaries; no live-row re-packing (a clip's beams move through each other's
+// cache slots), so the encode is not consumed.  The step's head is dec_beam_kernel; dec_beam_final_kernel writes the output.
+static int beam_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev, float* scores_out_dev, int* out_len_host, hipStream_t caller) {
+  const char* fn = "m2m_generate_beam";
+  const int steps = max_length - 1, rows = s->B * s->beam_nb;
+  const int G = plan_groups(s, rows);
+  const bool graph = use_graph();
+  const int U = env_int("M2M_GRAPH_STEPS", 8) < 1 ? 1 : env_int("M2M_GRAPH_STEPS", 8);
+  int rc;
+  M2M_CHECK_HIP(hipEventRecord(s->ev_in, caller));
+  for (int i = 0; i < G; ++i) {
+    DecGroup& gr = s->groups[i];
+    M2M_CHECK_HIP(hipStreamWaitEvent(gr.stream, s->ev_in, 0));
+    if ((rc = decode_init(s, gr.view, steps, false, gr.stream))) return rc;
+    if ((rc = decode_beam_init(s, gr.view, gr.stream))) return rc;
+    if (graph && (rc = ensure_graph(s, gr, U))) return rc;
+    gr.state_host->done = (steps == 0);
+  }
+  s->repacks = 0; s->rows_moved = 0;
+  const int CHUNK = 64;
+  int launched = 0;
+  bool all_done = steps == 0;
+  while (!all_done && launched < steps) {
+    const int n = steps - launched < CHUNK ? steps - launched : CHUNK;
+    for (int k = 0; k < n; k += (graph ? U : 1)) {
+      for (int i = 0; i < G; ++i) {
+        DecGroup& gr = s->groups[i];
+        if (gr.state_host->done) continue;
+        if (graph) M2M_CHECK_HIP(hipGraphLaunch(gr.graph_exec, gr.stream));
+        else if ((rc = decode_launch_step(s, gr.view, false, nullptr, 0, gr.stream))) return rc;
+      }
+    }
+    launched += ceil_div(n, graph ? U : 1) * (graph ? U : 1);
+    for (int i = 0; i < G; ++i) {
+      DecGroup& gr = s->groups[i];
+      if (gr.state_host->done) continue;
+      M2M_CHECK_HIP(hipMemcpyAsync(gr.state_host, gr.view.state, sizeof(DecState), hipMemcpyDeviceToHost, gr.stream));
+    }
+    all_done = true;
+    for (int i = 0; i < G; ++i) {
+      M2M_CHECK_HIP(hipStreamSynchronize(s->groups[i].stream));
+      if (!s->groups[i].state_host->done) all_done = false;
+    }
+  }
+  bool range_error = false;
+  for (int i = 0; i < G; ++i) {
+    DecGroup& gr = s->groups[i];
+    M2M_CHECK_HIP(hipMemcpyAsync(gr.state_host, gr.view.state, sizeof(DecState), hipMemcpyDeviceToHost, gr.stream));
+    M2M_CHECK_HIP(hipStreamSynchronize(gr.stream));
+    range_error |= gr.state_host->overflow != 0;
+  }
+  // every chain is idle: finalize on the caller's stream (a clip that is not done stopped at max_length, t = steps)
+  if ((rc = decode_beam_finalize(s, rows, steps, tokens_out_dev, scores_out_dev, max_length, caller))) return rc;
+  M2M_CHECK_HIP(hipMemcpyAsync(s->beam_host, s->beam_dev, sizeof(BeamParams), hipMemcpyDeviceToHost, caller));
+  M2M_CHECK_HIP(hipStreamSynchronize(caller));
+  const int w = s->beam_host->max_hyp_len + 1;
+  *out_len_host = w < max_length ? w : max_length;
+  if (range_error) {
+    set_error("%s: a decoder activation left the fixed-point residual range (|x| >= 2^21) or was not finite; "
+              "the fp32 reference would produce Inf/NaN logits here - token ids are not valid (check the checkpoint)", fn);
+    return M2M_ERR_RANGE;
+  }
+  return M2M_OK;
+}
+
+extern "C" int m2m_generate_beam(m2m_session* s, int max_length, const m2m_beam_params* p, int64_t* tokens_out_dev,
+                                 float* scores_out_dev, int* out_len_host, void* stream) {
+  M2M_REQUIRE(s && p && tokens_out_dev && out_len_host, "m2m_generate_beam: null argument");
+  M2M_REQUIRE(p->num_beams >= 2 && p->num_beams <= BEAM_MAX, "m2m_generate_beam: num_beams %d outside [2, %d] (one beam is "
+              "m2m_generate_greedy)", p->num_beams, BEAM_MAX);
+  M2M_REQUIRE(p->num_return_sequences >= 1 && p->num_return_sequences <= p->num_beams,
+              "m2m_generate_beam: num_return_sequences %d has to be in [1, num_beams = %d]", p->num_return_sequences, p->num_beams);
+  M2M_REQUIRE(p->early_stopping >= 0 && p->early_stopping <= 2,
+              "m2m_generate_beam: early_stopping %d must be 0 (False), 1 (True) or 2 (\"never\")", p->early_stopping);
+  M2M_REQUIRE(isfinite(p->length_penalty), "m2m_generate_beam: length_penalty must be finite, got %g", (double)p->length_penalty);
+  const int V = s->m->g.vocab_size;
+  M2M_REQUIRE(V <= SAMPLE_MAX_VOCAB && V >= 2 * p->num_beams, "m2m_generate_beam: vocab_size %d outside [2 num_beams, %d] (the beam "
+              "head keeps a row in one wavefront's registers)", V, SAMPLE_MAX_VOCAB);
+  if (!s->encoded) { set_error("m2m_generate_beam: %s", encode_missing(s)); return M2M_ERR_STATE; }
+  M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_beam: max_length %d outside [1, %d]", max_length, s->max_dec);
+  M2M_REQUIRE((int64_t)s->B * p->num_beams <= s->max_batch, "m2m_generate_beam: %d clips x %d beams > the session's max_batch %d",
+              s->B, p->num_beams, s->max_batch);
+  hipStream_t caller = (hipStream_t)stream;
+  BeamParams& h = *s->beam_host;
+  h = BeamParams{};
+  h.nb = p->num_beams; h.lp = p->length_penalty; h.early = p->early_stopping; h.n = p->num_return_sequences;
+  h.max_length = max_length; h.max_hyp_len = 0;
+  int rc = M2M_OK;
+  if (hipMemcpyAsync(s->beam_dev, s->beam_host, sizeof(BeamParams), hipMemcpyHostToDevice, caller) != hipSuccess) {
+    set_error("m2m_generate_beam: hipMemcpyAsync: %s", hipGetErrorString(hipGetLastError()));
+    rc = M2M_ERR_HIP;
+  }
+  if (rc == M2M_OK) {
+    s->head_mode = HEAD_BEAM; s->beam_nb = p->num_beams;
+    rc = beam_impl(s, max_length, tokens_out_dev, scores_out_dev, out_len_host, caller);
+    s->head_mode = HEAD_GREEDY; s->beam_nb = 0;
+  }
+  if (rc != M2M_OK) quiesce(s, caller);
+  return rc;
 }
 
 // Teacher-forced decoder pass over all Ld positions at once (hf: modeling_t5.py:448-509 per block, :898-1066 wrapper):

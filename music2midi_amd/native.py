@@ -66,6 +66,11 @@ class SampleParams(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64)]
 
 
+class BeamParams(C.Structure):
+    _fields_ = [("num_beams", C.c_int), ("length_penalty", C.c_float), ("early_stopping", C.c_int),
+                ("num_return_sequences", C.c_int)]
+
+
 class TensorInfo(C.Structure):
     _fields_ = [("name", C.c_char * 160), ("offset", C.c_int64), ("rows", C.c_int), ("cols", C.c_int)]
 
@@ -99,6 +104,8 @@ _SIGNATURES = {
     "m2m_generate_greedy": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "m2m_generate_sample": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SampleParams), C.c_void_p, C.POINTER(C.c_int),
                                       C.c_void_p]),
+    "m2m_generate_beam": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BeamParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                    C.c_void_p]),
     "m2m_session_repack_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "m2m_decode_forced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "m2m_trainer_create": (C.c_int, [C.POINTER(T5GeometryC), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,

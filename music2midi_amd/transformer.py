@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import native
 from .config import T5Geometry, load_config
-from .generation import GenerateConfig, resolve_generate_kwargs
+from .generation import GenerateConfig, resolve_beam_kwargs, resolve_generate_kwargs
 from .input import Conditioning, LogMelSpectrogram, ModelInputs
 from .tokenizer import MidiTokenizer
 
@@ -299,9 +299,9 @@ class T5Transformer(nn.Module):
         self.conditioning.write_rows(inputs.cond_index, buf)
         return buf
 
-    def _encode(self, x: torch.Tensor, max_dec: int, want_states: bool = False):
+    def _encode(self, x: torch.Tensor, max_dec: int, want_states: bool = False, rows: Optional[int] = None):
         B, S, _ = x.shape
-        sess = self._get_session(B, S, max_dec)
+        sess = self._get_session(max(B, rows or 0), S, max_dec)
         enc_out = torch.empty_like(x) if want_states else None
         with torch.cuda.device(x.device):
             native.check(native.load().m2m_encode(sess, x.data_ptr(), B, S,
@@ -353,6 +353,43 @@ class T5Transformer(nn.Module):
                 native.check(native.load().m2m_generate_sample(sess, max_length, C.byref(p), tokens.data_ptr(), C.byref(out_len),
                                                                native.stream_handle(x.device)), "m2m_generate_sample")
             return tokens[:, : out_len.value]
+
+    @torch.no_grad()
+    def beam_search_from_embeds(self, inputs_embeds: torch.Tensor, num_beams: int, max_length: int = 20,
+                                length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1,
+                                return_scores: bool = False):
+        """Beam search from encoder inputs [B, S, d]; keywords and result as :meth:`beam_search`."""
+        cfg = resolve_beam_kwargs(num_beams, max_length, length_penalty, early_stopping, num_return_sequences)
+        with self._lock:
+            x = inputs_embeds.to(self.transformer.device, torch.float32).contiguous()
+            B, n = x.shape[0], cfg.num_return_sequences
+            sess, _ = self._encode(x, cfg.max_length, rows=B * cfg.num_beams)   # encoded once per clip, decoded as B x nb rows
+            tokens = torch.empty((B * n, cfg.max_length), dtype=torch.long, device=x.device)
+            scores = torch.empty((B * n,), dtype=torch.float32, device=x.device) if return_scores else None
+            out_len = C.c_int(0)
+            p = native.BeamParams(cfg.num_beams, cfg.length_penalty, cfg.early_stopping_code, n)
+            with torch.cuda.device(x.device):
+                native.check(native.load().m2m_generate_beam(sess, cfg.max_length, C.byref(p), tokens.data_ptr(),
+                                                             scores.data_ptr() if return_scores else None, C.byref(out_len),
+                                                             native.stream_handle(x.device)), "m2m_generate_beam")
+            ids = tokens[:, : out_len.value]
+            return (ids, scores) if return_scores else ids
+
+    def beam_search(self, inputs: ModelInputs, num_beams: int, max_length: int = 20, length_penalty: float = 1.0,
+                    early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False):
+        """Beam search decoding with transformers 4.34 semantics (``generate(num_beams=..., do_sample=False)``).
+
+        Returns ``LongTensor [B * num_return_sequences, L]`` in HF's order: the n sequences of a clip are consecutive rows,
+        best first, EOS-terminated and right-padded with pad_token_id.  With ``return_scores=True`` also HF's
+        ``sequences_scores`` (float32 [B * n], length-normalised: sum of log-probs / len ** length_penalty).
+        ``early_stopping`` is True, False or "never"; ``num_beams`` is 2..32.  Each clip is encoded once; its beams share
+        its cross-attention K/V and read their self-attention K/V through an ancestry table on the GPU.
+        ``generate(num_beams > 1)`` still raises ``NotImplementedError``; beam sampling, group / diverse and constrained beams
+        are not implemented."""
+        encoder_inputs = self.encoder_inputs(inputs)
+        return self.beam_search_from_embeds(encoder_inputs, num_beams, max_length=max_length, length_penalty=length_penalty,
+                                            early_stopping=early_stopping, num_return_sequences=num_return_sequences,
+                                            return_scores=return_scores)
 
     @torch.no_grad()
     def logits_from_embeds(self, inputs_embeds: torch.Tensor, decoder_input_ids: torch.Tensor) -> torch.Tensor:
