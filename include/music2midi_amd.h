@@ -268,9 +268,53 @@ int m2m_generate_beam(m2m_session* s, int max_length, const m2m_beam_params* p, 
                       int* out_len_host, void* stream);
 
 /*
+ * KV-cached greedy or sampled decode with transformers 4.34's logits processors (hf: generation/utils.py _get_logits_processor for
+ * an encoder-decoder, generation/logits_process.py).  input_ids are the decoder ids so far: the start token and the t generated
+ * ids at step t, cur_len = t + 1.  The processors change the raw logits of every row at every step, in this order:
+ *   repetition_penalty != 1   every id present in input_ids (the start token included): logit < 0 -> logit * p, else logit / p
+ *   no_repeat_ngram_size n>0  -inf for every id that would complete an n-gram already in input_ids
+ *   bad_words                 a sequence equal to [eos_token_id] is dropped; a one-id sequence -> -inf at every step; a longer one
+ *                             -> -inf on its last id when input_ids end with the others (skipped while it is longer than input_ids)
+ *   min_length                EOS -> -inf while cur_len < min_length
+ *   min_new_tokens            EOS -> -inf while cur_len - 1 < min_new_tokens
+ *   forced_bos_token_id       at cur_len == 1 every id but it -> -inf, it -> 0
+ *   forced_eos_token_id       at cur_len == max_length - 1 every id but it -> -inf, it -> 0
+ *   suppress_tokens           -> -inf at every step
+ *   begin_suppress_tokens     -> -inf at cur_len == 2 with forced_bos_token_id set, at cur_len == 1 without
+ * then select: sample == NULL takes the arg-max (ties to the lower id), otherwise m2m_generate_sample's warpers and draw follow
+ * (same seed semantics).  1.0 / 0 / -1 / an empty list leave a processor out; the history of a row is the clip's own token row, so
+ * ids do not depend on the live-row re-packing or the chain split.  Non-finite RAW logits return M2M_ERR_RANGE (the -inf of the
+ * processors is legal).
+ * Invalid parameters return M2M_ERR_INVALID without launching anything: repetition_penalty <= 0 or not finite, a negative
+ * no_repeat_ngram_size / min_length / min_new_tokens / count, a forced id outside [-1, V), a listed id outside [0, V), a null list
+ * with a non-zero count, a bad-words sequence of length < 1, invalid sample parameters (as m2m_generate_sample), and the device
+ * limits: a vocabulary larger than 4096, max_length > 2048, more than 64 bad-words sequences of two or more ids or more than 512
+ * ids in them.  bad_words_ids holds the n_bad_words sequences concatenated, bad_words_lengths their lengths.  Everything else -
+ * arguments, out_len, M2M_ERR_RANGE, the re-packing and the session state afterwards - is as for m2m_generate_greedy.
+ */
+typedef struct {
+  float repetition_penalty;               /* > 0; 1 = off */
+  int no_repeat_ngram_size;               /* >= 0; 0 = off */
+  int min_length;                         /* >= 0; 0 = off */
+  int min_new_tokens;                     /* >= 0; 0 = off */
+  int forced_bos_token_id;                /* -1 = off */
+  int forced_eos_token_id;                /* -1 = off */
+  const int32_t* suppress_tokens;
+  int n_suppress_tokens;
+  const int32_t* begin_suppress_tokens;
+  int n_begin_suppress_tokens;
+  const int32_t* bad_words_ids;           /* the sequences concatenated */
+  const int32_t* bad_words_lengths;       /* [n_bad_words] */
+  int n_bad_words;
+} m2m_process_params;
+
+int m2m_generate_processed(m2m_session* s, int max_length, const m2m_process_params* proc, const m2m_sample_params* sample,
+                           int64_t* tokens_out_dev, int* out_len_host, void* stream);
+
+/*
  * Rows end at different steps (ref: music2midi/model.py:115-135 decodes chunks of inference.batch_size = 128 three-second
  * segments to max_length 1024; a trained checkpoint ends a segment after tens to hundreds of tokens).  Once a quarter of the
- * rows still being decoded have emitted EOS, m2m_generate_greedy (and m2m_generate_sample) re-packs the live rows into the first slots of the batch at its
+ * rows still being decoded have emitted EOS, m2m_generate_greedy (and m2m_generate_sample, m2m_generate_processed) re-packs the live rows into the first slots of the batch at its
  * next host poll and goes on with smaller launches; ids do not depend on it.  The host polls after 16, 32, 64, 96 and 128 steps and
  * then every 64 (without the re-packing: every 64); each poll drains every chain, and a poll at which a re-packing is possible (a
  * chain still running, >= 64 steps left, >= 2 rows) also reads the finished flags back synchronously - so M2M_COMPACT=1 adds four

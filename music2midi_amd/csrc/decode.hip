@@ -2171,6 +2171,261 @@ static int launch_dec_sample(const DecHeadArgs& h, const SampleParams* sp, hipSt
   return M2M_OK;
 }
 
+// ======================================================== processed head ====
+// Logits processors (m2m_generate_processed; transformers 4.34 _get_logits_processor, see include/music2midi_amd.h): the sampling
+// head's form with the processors applied to the row in registers before the select - the arg-max (GREEDY) or the warpers and the
+// draw.  Per workgroup (4 rows) 16 KB of LDS hold the rows' histories as 16-bit ids and 4 KB their "seen" / ban bitmaps; the ids
+// that do not depend on the history (suppress, begin-suppress, one-id bad words) come as bitmaps of the parameter block.  The
+// overflow check looks at the raw logits.  The warper and draw code below repeats dec_sample_kernel's: a body shared by inlining
+// changed that kernel's instructions, and the sampling path must stay what it was.
+template <int NPL>
+__device__ inline unsigned long long lane_bits(const unsigned* w, int v0) {   // bits v0 .. v0 + NPL - 1 of a vocabulary bitmap
+  if constexpr (NPL == 64) return (unsigned long long)w[v0 >> 5] | ((unsigned long long)w[(v0 >> 5) + 1] << 32);
+  else return (w[v0 >> 5] >> (v0 & 31)) & ((1ull << NPL) - 1);
+}
+
+template <int NPL, bool GREEDY>
+__device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleParams* sp, const ProcessParams* pp,
+                                             unsigned short* s_hist, unsigned* s_bits) {
+  __shared__ int s_unfinished;
+  DecState* stp = a.state;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int b = blockIdx.x * SAMPLE_ROWS + (tid >> 6);
+  const int V = a.V, v0 = lane * NPL;
+  const bool row = b < a.B;
+  // the row's logits are requested before the loop state is consumed (as in dec_head_kernel)
+  float x[NPL];
+  const float* lg = a.logits + (int64_t)(row ? b : 0) * a.ldl;
+#pragma unroll
+  for (int j = 0; j < NPL; ++j) x[j] = (v0 + j < V) ? lg[v0 + j] : 0.f;
+  const float temp = GREEDY ? 1.0f : sp->temperature, top_p = GREEDY ? 1.0f : sp->top_p;
+  const int top_k = GREEDY ? 0 : sp->top_k;
+  const unsigned long long seed_h = GREEDY ? 0ull : splitmix64(sp->seed);
+  const int t = stp->t;
+  const bool live = !(stp->done | (t >= stp->max_steps));
+  if (tid == 0) s_unfinished = 0;
+  __syncthreads();
+  // Processors that read the history (input_ids = the start token and t generated ids, cur_len = t + 1): the row's ids are staged
+  // in LDS from the token matrix (row tok_row[b]: the clip's own row whatever its slot), then one lane-strided pass each sets the
+  // "seen" bits (repetition penalty) and the ban bits (n-gram, bad words of two or more ids) of the row's bitmaps.
+  const int cur = t + 1;
+  unsigned long long m_seen = 0, m_ban = 0, m_post = 0;
+  {
+    unsigned short* hist = s_hist + (tid >> 6) * PROC_MAX_LEN;
+    unsigned* seen = s_bits + (tid >> 6) * 2 * PROC_BITS;
+    unsigned* ban = seen + PROC_BITS;
+    const bool scan = row && live && cur <= PROC_MAX_LEN && !a.finished[b];   // a finished row emits pad whatever its scores
+    for (int i = lane; i < PROC_BITS; i += 64) { seen[i] = 0u; ban[i] = 0u; }
+    if (scan) {
+      const int64_t* hr = a.tokens + (int64_t)a.tok_row[b] * a.max_len;
+      for (int p = lane; p < cur; p += 64) hist[p] = (unsigned short)min((unsigned long long)hr[p], (unsigned long long)(PROC_MAX_VOCAB - 1));
+    }
+    __syncthreads();
+    if (scan) {
+      if (pp->penalty != 1.0f)
+        for (int p = lane; p < cur; p += 64) atomicOr(&seen[hist[p] >> 5], 1u << (hist[p] & 31));
+      // NoRepeatNGram: every complete window i .. i + n - 1 whose first n - 1 ids equal the last n - 1 ids bans its last id
+      const int n = pp->ngram;
+      if (n > 0) {
+        const int pre = cur - n + 1;
+        for (int i = lane; i + n <= cur; i += 64) {
+          int k = 0;
+          while (k < n - 1 && hist[i + k] == hist[pre + k]) ++k;
+          if (k == n - 1) atomicOr(&ban[hist[i + n - 1] >> 5], 1u << (hist[i + n - 1] & 31));
+        }
+      }
+      // NoBadWords (sequences of L >= 2 ids): the last id is banned when the history ends with the other L - 1; a sequence longer
+      // than the history is skipped (4.34's SequenceBiasLogitsProcessor)
+      for (int q = lane; q < pp->n_bad; q += 64) {
+        const int o = pp->bad_off[q], L = pp->bad_off[q + 1] - o;
+        if (L > cur) continue;
+        int k = 0;
+        while (k < L - 1 && (int)hist[cur - L + 1 + k] == pp->bad_ids[o + k]) ++k;
+        const int last = pp->bad_ids[o + L - 1];
+        if (k == L - 1) atomicOr(&ban[last >> 5], 1u << (last & 31));
+      }
+    }
+    __syncthreads();
+    if (scan) {
+      m_seen = pp->penalty != 1.0f ? lane_bits<NPL>(seen, v0) : 0ull;
+      m_ban = lane_bits<NPL>(ban, v0) | (pp->has_bad1 ? lane_bits<NPL>(pp->bad1, v0) : 0ull);
+      m_post = (pp->has_supp ? lane_bits<NPL>(pp->supp, v0) : 0ull) |
+               (pp->has_begin && cur == pp->begin_index ? lane_bits<NPL>(pp->begin, v0) : 0ull);
+    }
+  }
+  const int k = top_k > 0 ? min(top_k, V) : V;
+  if (row) {
+    const int fin = a.finished[b];
+    bool bad = false;
+    float m = -INFINITY;
+    const float pen = pp->penalty;
+    const bool eos_ban = cur < pp->min_length || cur - 1 < pp->min_new;
+    const int fbos = cur == 1 ? pp->forced_bos : -1;
+    const int feos = cur == pp->max_length - 1 ? pp->forced_eos : -1;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+      if (v0 + j < V) {
+        bad |= !(fabsf(x[j]) <= 3.0e38f);   // the RAW logits: the -inf the processors write is legal
+        // 4.34's _get_logits_processor order: repetition, n-gram, bad words, min length, min new tokens, forced BOS, forced EOS,
+        // suppress, begin-suppress
+        const int v = v0 + j;
+        if ((m_seen >> j) & 1) x[j] = x[j] < 0.f ? x[j] * pen : x[j] / pen;
+        if (((m_ban >> j) & 1) || (eos_ban && v == a.eos_id)) x[j] = -INFINITY;
+        if (fbos >= 0) x[j] = v == fbos ? 0.f : -INFINITY;
+        if (feos >= 0) x[j] = v == feos ? 0.f : -INFINITY;
+        if ((m_post >> j) & 1) x[j] = -INFINITY;
+        if (temp != 1.0f) x[j] = x[j] / temp;
+        m = fmaxf(m, x[j]);
+      }
+    }
+    int tok;
+    if constexpr (GREEDY) {
+      // arg-max, ties to the lower id (dec_head_kernel; an all -inf row gives id 0, as torch.argmax)
+      float best = -INFINITY;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j)
+        if (v0 + j < V && (x[j] > best || (x[j] == best && v0 + j < bi))) { best = x[j]; bi = v0 + j; }
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+      }
+      tok = bi == 0x7fffffff ? 0 : bi;
+    } else {
+      m = wave_max(m);          // exact: every lane holds the same maximum
+      unsigned kk[NPL];         // order-preserving keys; 0 (below every finite logit's) past the vocabulary
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) kk[j] = (v0 + j < V) ? ord_key(x[j]) : 0u;
+      // TopK: the k-th largest key, bit by bit from the top (the largest thr with count(key >= thr) >= k); counts are ballots
+      unsigned thr = 0;
+      if (k < V) {
+        for (int bit = 31; bit >= 0; --bit) {
+          const unsigned cand = thr | (1u << bit);
+          int cnt = 0;
+#pragma unroll
+          for (int j = 0; j < NPL; ++j) cnt += __popcll(__ballot(kk[j] >= cand));
+          if (cnt >= k) thr = cand;
+        }
+      }
+      float w[NPL];
+      float z = 0.f;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) {
+        w[j] = (v0 + j < V && kk[j] >= thr) ? expf(x[j] - m) : 0.f;
+        z += w[j];
+      }
+      z = wave_sum_uniform(z);
+      // TopP: the largest key c with mass(key < c) <= (1 - top_p) * Z, capped at the maximum's key (which always stays)
+      if (top_p < 1.0f) {
+        const float R = (1.0f - top_p) * z;
+        unsigned c = 0;
+        for (int bit = 31; bit >= 0; --bit) {
+          const unsigned cand = c | (1u << bit);
+          float lm = 0.f;
+#pragma unroll
+          for (int j = 0; j < NPL; ++j) lm += kk[j] < cand ? w[j] : 0.f;
+          if (wave_sum_uniform(lm) <= R) c = cand;
+        }
+        c = min(c, ord_key(m));
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) if (kk[j] < c) w[j] = 0.f;
+      }
+      // draw: the first kept entry (vocabulary order) whose inclusive cumulative weight exceeds u * Z
+      float ls = 0.f;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) ls += w[j];
+      float incl = ls;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const float up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+      }
+      const float total = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, incl), 63));
+      const unsigned long long h = splitmix64(seed_h ^ (((unsigned long long)(unsigned)a.tok_row[b] << 32) | (unsigned)t));
+      const float target = (float)(h >> 40) * 0x1p-24f * total;
+      const unsigned long long over = __ballot(incl > target && ls > 0.f);
+      const unsigned long long any = __ballot(ls > 0.f);
+      const int sel = over ? __ffsll((long long)over) - 1 : (any ? 63 - __clzll((long long)any) : 0);
+      float acc = __shfl_up(incl, 1, 64);
+      if (lane == 0) acc = 0.f;
+      int tk = -1, last = -1;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) {
+        if (w[j] > 0.f) {
+          acc += w[j];
+          last = v0 + j;
+          if (tk < 0 && acc > target) tk = v0 + j;
+        }
+      }
+      if (tk < 0) tk = last;             // rounding put the target past this lane's last kept entry
+      tk = __shfl(tk, sel, 64);
+      if (tk < 0) tk = a.pad_id;         // no finite weight at all (the overflow flag is raised)
+      tok = tk;
+    }
+    if (__ballot(bad) && live && lane == 0) stp->overflow = 1;
+    // hf generation/utils.py (sample): finished rows emit pad; EOS finishes a row
+    int next = fin ? a.pad_id : tok;
+    if (lane == 0 && live) {
+      if (t + 1 < a.max_len) a.tokens[(int64_t)a.tok_row[b] * a.max_len + t + 1] = next;
+      const int nf = fin | (next == a.eos_id);
+      a.finished[b] = nf;
+      if (!nf) atomicAdd(&s_unfinished, 1);
+    }
+    if (next < 0 || next >= V) next = a.pad_id;
+    const float* emb = a.shared + (int64_t)next * a.d;
+    for (int c = lane * 4; c < a.d; c += 256) {
+      const float4 e4 = *reinterpret_cast<const float4*>(emb + c);
+      xq_t* xp = a.x + (int64_t)b * a.d + c;
+      if (live) {
+        *reinterpret_cast<longlong2*>(xp) = make_longlong2(xq_fix_guarded(e4.x, stp), xq_fix_guarded(e4.y, stp));
+        *reinterpret_cast<longlong2*>(xp + 2) = make_longlong2(xq_fix_guarded(e4.z, stp), xq_fix_guarded(e4.w, stp));
+      }
+    }
+  }
+  // the step closes when the last workgroup is through: every workgroup has read t / done above before it takes its ticket
+  __syncthreads();
+  if (tid == 0 && live) {
+    if (s_unfinished) atomicAdd(&stp->smp_unfinished, s_unfinished);
+    __threadfence();
+    if (atomicAdd(&stp->smp_ticket, 1) == (int)gridDim.x - 1) {
+      __threadfence();
+      const int nu = atomicExch(&stp->smp_unfinished, 0);
+      stp->smp_ticket = 0;
+      const int nt = t + 1;
+      stp->t = nt;
+      stp->n_unfinished = nu;
+      if (nu == 0 || nt >= stp->max_steps) { stp->done = 1; stp->out_len = nt + 1; }
+    }
+  }
+}
+
+template <int NPL, bool GREEDY>
+__global__ __launch_bounds__(64 * SAMPLE_ROWS) void dec_process_kernel(DecHeadArgs a, const SampleParams* sp, const ProcessParams* pp) {
+  __shared__ unsigned short s_hist[SAMPLE_ROWS * PROC_MAX_LEN];
+  __shared__ unsigned s_bits[SAMPLE_ROWS * 2 * PROC_BITS];
+  process_head<NPL, GREEDY>(a, sp, pp, s_hist, s_bits);
+}
+
+template <bool GREEDY>
+static void launch_dec_process_v(const DecHeadArgs& h, const SampleParams* sp, const ProcessParams* pp, dim3 grid, dim3 block,
+                                 hipStream_t st) {
+  if (h.V <= 64 * 8) hipLaunchKernelGGL((dec_process_kernel<8, GREEDY>), grid, block, 0, st, h, sp, pp);
+  else if (h.V <= 64 * 16) hipLaunchKernelGGL((dec_process_kernel<16, GREEDY>), grid, block, 0, st, h, sp, pp);
+  else if (h.V <= 64 * 32) hipLaunchKernelGGL((dec_process_kernel<32, GREEDY>), grid, block, 0, st, h, sp, pp);
+  else hipLaunchKernelGGL((dec_process_kernel<64, GREEDY>), grid, block, 0, st, h, sp, pp);
+}
+
+static int launch_dec_process(const DecHeadArgs& h, const SampleParams* sp, const ProcessParams* pp, bool greedy, hipStream_t st) {
+  M2M_REQUIRE(h.V >= 1 && h.V <= PROC_MAX_VOCAB, "dec_process_kernel: vocab_size %d outside [1, %d]", h.V, PROC_MAX_VOCAB);
+  const dim3 grid((unsigned)ceil_div(h.B, SAMPLE_ROWS)), block(64 * SAMPLE_ROWS);
+  if (greedy) launch_dec_process_v<true>(h, sp, pp, grid, block, st);
+  else launch_dec_process_v<false>(h, sp, pp, grid, block, st);
+  M2M_CHECK_HIP(hipGetLastError());
+  return M2M_OK;
+}
+
 // ============================================================== beam head ====
 // Beam search (m2m_generate_beam) replaces dec_head_kernel by this kernel, one workgroup per clip (its beam_nb rows), and follows
 // transformers 4.34 (hf: generation/utils.py _beam_search, generation/beam_search.py BeamSearchScorer.process / BeamHypotheses):
@@ -2532,7 +2787,7 @@ int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int 
 
 // ============================================================ step driver ====
 static xq_t* xbuf(m2m_session* s, const DecView& v, int which);
-// the headless fold is a greedy-only form: the sampling head keeps its own kernel (the step of M2M_HEADLESS=0)
+// the headless fold is a greedy-only form: the sampling and processed heads keep their own kernel (the step of M2M_HEADLESS=0)
 static bool headless_for(const m2m_session* s, bool forced) { return !forced && s->head_mode == HEAD_GREEDY && decode_headless(); }
 // All per-clip buffers are [B][...] with the clip index outermost, so a view is a pointer offset.
 static DecHeadArgs head_args(m2m_session* s, const DecView& v, bool forced, float* logits_out, int Ld) {
@@ -2721,6 +2976,8 @@ int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* log
   if ((rc = launch_dec_gemm(P, a, st))) return rc;
   if (headless) return M2M_OK;             // the arg-max key is consumed by the next step's layer 0 (or by decode_finalize)
   DecHeadArgs h = head_args(s, v, forced, logits_out, Ld);
+  if (!forced && (s->head_mode & HEAD_PROCESSED))
+    return launch_dec_process(h, s->sample_dev, s->proc_dev, !(s->head_mode & HEAD_SAMPLE), st);
   if (!forced && s->head_mode == HEAD_SAMPLE) return launch_dec_sample(h, s->sample_dev, st);
   if (!forced && s->head_mode == HEAD_BEAM) return launch_dec_beam(h, beam_args(s, v), s->beam_nb, st);
   hipLaunchKernelGGL(dec_head_kernel, dim3(1), dim3(1024), 0, st, h);

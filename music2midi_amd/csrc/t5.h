@@ -79,6 +79,31 @@ struct SampleParams {
   unsigned long long seed;  // the call's seed: the draw of clip row r at position t hashes (seed, r, t)
 };
 
+// Logits processors (m2m_generate_processed, decode.hip dec_process_kernel): the call's parameters, a device block of the workspace
+// written before the chains start (as SampleParams).  Vocabulary bitmaps hold the id lists that do not depend on the history.
+constexpr int PROC_MAX_VOCAB = 4096;      // = SAMPLE_MAX_VOCAB: the row lives in one wavefront's registers
+constexpr int PROC_BITS = PROC_MAX_VOCAB / 32;   // words of a vocabulary bitmap
+constexpr int PROC_MAX_LEN = 2048;        // max_length: a row's history is staged in LDS as 16-bit ids
+constexpr int PROC_MAX_BAD = 64;          // bad-word sequences of two or more ids (one lane each)
+constexpr int PROC_MAX_BAD_IDS = 512;     // ids in those sequences together
+struct ProcessParams {
+  float penalty;            // repetition_penalty; 1 = off
+  int ngram;                // no_repeat_ngram_size; 0 = off
+  int min_length;           // EOS is banned while cur_len < min_length (0 = off)
+  int min_new;              // ... and while cur_len - 1 < min_new_tokens (0 = off)
+  int forced_bos;           // -1 = off
+  int forced_eos;           // -1 = off
+  int begin_index;          // cur_len at which begin_suppress applies (1, or 2 with forced_bos)
+  int max_length;           // the call's max_length (forced EOS at cur_len == max_length - 1)
+  int has_bad1, has_supp, has_begin;   // the bitmaps below are not empty
+  int n_bad;                // bad-word sequences of two or more ids
+  int bad_off[PROC_MAX_BAD + 1];       // sequence q is bad_ids[bad_off[q] .. bad_off[q + 1])
+  int bad_ids[PROC_MAX_BAD_IDS];
+  unsigned bad1[PROC_BITS];            // one-id bad words (the [eos] entry filtered out)
+  unsigned supp[PROC_BITS];            // suppress_tokens
+  unsigned begin[PROC_BITS];           // begin_suppress_tokens
+};
+
 // Beam search (m2m_generate_beam): the call's parameters, a device block of the workspace written before the chains start (as
 // SampleParams), and the per-clip / per-row state of the beam head (decode.hip dec_beam_kernel).
 struct BeamParams {
@@ -191,9 +216,12 @@ struct m2m_session {
   int ff_slices = 0;       // decode feed-forward: hidden slices per workgroup forced by M2M_DEC_FF_SLICES (0: by chain size)
   int mc_cif = 1;          // multi-clip cross-attention: clips in flight, M2M_MC_CIF (diagnostic: 2; 0 or unset: 1, the product)
   int repacks = 0, rows_moved = 0;   // live-row re-packings / rows moved by them in the last m2m_generate_greedy / _sample
-  int head_mode = 0;       // head form of the free-running decode step: 0 greedy (arg-max), 1 sampling, 2 beam (set for the length of a call)
+  int head_mode = 0;       // head form of the free-running decode step: 0 greedy (arg-max), 1 sampling, 2 beam, | 4 processed
+                           // (set for the length of a call)
   m2m::SampleParams* sample_dev = nullptr;    // [1] in the workspace
   m2m::SampleParams* sample_host = nullptr;   // pinned staging copy
+  m2m::ProcessParams* proc_dev = nullptr;     // [1] in the workspace
+  m2m::ProcessParams* proc_host = nullptr;    // pinned staging copy
   // beam search (m2m_generate_beam): rows = encoded clips x beam_nb; every buffer below is in the workspace
   int beam_nb = 0;                            // beams per clip during a beam call, 0 otherwise
   m2m::BeamParams* beam_dev = nullptr;        // [1]
@@ -297,6 +325,7 @@ int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int 
 int decode_finalize(m2m_session* s, const DecView& v, hipStream_t st);   // headless greedy loop: write the last token, close the chain
 bool decode_headless();
 constexpr int HEAD_GREEDY = 0, HEAD_SAMPLE = 1, HEAD_BEAM = 2;
+constexpr int HEAD_PROCESSED = 4;        // bit: logits processors before the greedy (| 0) or sampling (| HEAD_SAMPLE) select
 constexpr int BEAM_MAX = 32;             // beams per clip: one LDS list of 2 x 32 candidates per beam, ancestries in bytes
 int decode_beam_init(m2m_session* s, const DecView& v, hipStream_t st);
 int decode_beam_finalize(m2m_session* s, int rows, int steps, int64_t* out, float* scores, int max_length, hipStream_t st);

@@ -187,7 +187,7 @@ extern "C" int m2m_model_checksum(const m2m_model* m, uint64_t* out_host, void* 
 namespace {
 struct WsLayout {
   int64_t x_enc, h_enc, qkv_enc, vt_enc, attn_enc, mid_enc, enc_bias, dec_bias, dec_bias_full, cross_vt, cross_kv, self_k, self_v;
-  int64_t x_dec, logits, tokens, finished, tok_row, keys, state, forced, sample, beam, beam_clip, beam_row, anc, hyp_tok, total;
+  int64_t x_dec, logits, tokens, finished, tok_row, keys, state, forced, sample, proc, beam, beam_clip, beam_row, anc, hyp_tok, total;
 };
 
 WsLayout ws_layout(const m2m_model* m, int B, int S, int L) {
@@ -220,6 +220,7 @@ WsLayout ws_layout(const m2m_model* m, int B, int S, int L) {
   w.state = take(sizeof(DecState) * MAX_GROUPS);
   w.forced = take((int64_t)B * L * 8);
   w.sample = take(sizeof(SampleParams));
+  w.proc = take(sizeof(ProcessParams));
   w.beam = take(sizeof(BeamParams));
   w.beam_clip = take((int64_t)B * sizeof(BeamClip));
   w.beam_row = take((int64_t)B * sizeof(BeamRow));
@@ -283,6 +284,7 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   s->logits = (float*)(b + w.logits); s->tokens = (int64_t*)(b + w.tokens);
   s->finished = (int*)(b + w.finished); s->tok_row = (int*)(b + w.tok_row); s->keys = (unsigned long long*)(b + w.keys); s->states = (DecState*)(b + w.state); s->forced_ids = (int64_t*)(b + w.forced);
   s->sample_dev = (SampleParams*)(b + w.sample);
+  s->proc_dev = (ProcessParams*)(b + w.proc);
   s->beam_dev = (BeamParams*)(b + w.beam); s->beam_clip = (BeamClip*)(b + w.beam_clip); s->beam_row = (BeamRow*)(b + w.beam_row);
   s->anc = b + w.anc; s->hyp_tok = (int64_t*)(b + w.hyp_tok);
 
@@ -319,6 +321,7 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   if (e == hipSuccess) e = hipMemset(s->states, 0, sizeof(DecState) * MAX_GROUPS);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming);
   if (e == hipSuccess) e = hipHostMalloc((void**)&s->sample_host, sizeof(SampleParams), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s->proc_host, sizeof(ProcessParams), hipHostMallocDefault);
   if (e == hipSuccess) e = hipHostMalloc((void**)&s->beam_host, sizeof(BeamParams), hipHostMallocDefault);
   for (int i = 0; i < MAX_GROUPS && e == hipSuccess; ++i) {
     DecGroup& gr = s->groups[i];
@@ -371,6 +374,7 @@ extern "C" void m2m_session_destroy(m2m_session* s) {
   }
   if (s->ev_in) (void)hipEventDestroy(s->ev_in);
   if (s->sample_host) (void)hipHostFree(s->sample_host);
+  if (s->proc_host) (void)hipHostFree(s->proc_host);
   if (s->beam_host) (void)hipHostFree(s->beam_host);
   delete s;
 }
@@ -556,7 +560,98 @@ extern "C" int m2m_generate_sample(m2m_session* s, int max_length, const m2m_sam
   return rc;
 }
 
-// the free-running decode loop of both head forms (s->head_mode); fn names the entry point in error messages
+// Logits processors (include/music2midi_amd.h): the id lists are checked and laid out into the ProcessParams block on the host; the
+// decode loop is generate_impl's with the processed head (HEAD_PROCESSED, greedy or sampling select).
+static int fill_process_params(const m2m_session* s, int max_length, const m2m_process_params* p, ProcessParams& h) {
+  const char* fn = "m2m_generate_processed";
+  const m2m_t5_geometry& g = s->m->g;
+  const int V = g.vocab_size;
+  M2M_REQUIRE(V <= PROC_MAX_VOCAB, "%s: vocab_size %d > %d (the processed head keeps a row in one wavefront's registers)", fn, V,
+              PROC_MAX_VOCAB);
+  M2M_REQUIRE(max_length <= PROC_MAX_LEN, "%s: max_length %d > %d (a row's history is staged in LDS)", fn, max_length, PROC_MAX_LEN);
+  M2M_REQUIRE(isfinite(p->repetition_penalty) && p->repetition_penalty > 0.f,
+              "%s: repetition_penalty must be a strictly positive finite float, got %g", fn, (double)p->repetition_penalty);
+  M2M_REQUIRE(p->no_repeat_ngram_size >= 0, "%s: no_repeat_ngram_size must be >= 0, got %d", fn, p->no_repeat_ngram_size);
+  M2M_REQUIRE(p->min_length >= 0, "%s: min_length must be >= 0, got %d", fn, p->min_length);
+  M2M_REQUIRE(p->min_new_tokens >= 0, "%s: min_new_tokens must be >= 0, got %d", fn, p->min_new_tokens);
+  M2M_REQUIRE(p->forced_bos_token_id >= -1 && p->forced_bos_token_id < V, "%s: forced_bos_token_id %d outside [-1, %d)", fn,
+              p->forced_bos_token_id, V);
+  M2M_REQUIRE(p->forced_eos_token_id >= -1 && p->forced_eos_token_id < V, "%s: forced_eos_token_id %d outside [-1, %d)", fn,
+              p->forced_eos_token_id, V);
+  M2M_REQUIRE(p->n_suppress_tokens >= 0 && (p->n_suppress_tokens == 0 || p->suppress_tokens), "%s: bad suppress_tokens list", fn);
+  M2M_REQUIRE(p->n_begin_suppress_tokens >= 0 && (p->n_begin_suppress_tokens == 0 || p->begin_suppress_tokens),
+              "%s: bad begin_suppress_tokens list", fn);
+  M2M_REQUIRE(p->n_bad_words >= 0 && (p->n_bad_words == 0 || (p->bad_words_ids && p->bad_words_lengths)), "%s: bad bad_words list", fn);
+  h = ProcessParams{};
+  h.penalty = p->repetition_penalty; h.ngram = p->no_repeat_ngram_size; h.min_length = p->min_length; h.min_new = p->min_new_tokens;
+  h.forced_bos = p->forced_bos_token_id; h.forced_eos = p->forced_eos_token_id;
+  h.begin_index = p->forced_bos_token_id >= 0 ? 2 : 1;   // 4.34: input_ids_seq_length (1), + 1 with forced_bos_token_id
+  h.max_length = max_length;
+  for (int i = 0; i < p->n_suppress_tokens; ++i) {
+    const int v = p->suppress_tokens[i];
+    M2M_REQUIRE(v >= 0 && v < V, "%s: suppress_tokens id %d outside [0, %d)", fn, v, V);
+    h.supp[v >> 5] |= 1u << (v & 31); h.has_supp = 1;
+  }
+  for (int i = 0; i < p->n_begin_suppress_tokens; ++i) {
+    const int v = p->begin_suppress_tokens[i];
+    M2M_REQUIRE(v >= 0 && v < V, "%s: begin_suppress_tokens id %d outside [0, %d)", fn, v, V);
+    h.begin[v >> 5] |= 1u << (v & 31); h.has_begin = 1;
+  }
+  int64_t off = 0;
+  for (int q = 0; q < p->n_bad_words; ++q) {
+    const int L = p->bad_words_lengths[q];
+    M2M_REQUIRE(L >= 1 && L <= PROC_MAX_BAD_IDS, "%s: bad_words sequence %d has length %d (1 .. %d)", fn, q, L, PROC_MAX_BAD_IDS);
+    const int32_t* ids = p->bad_words_ids + off;
+    off += L;
+    for (int k = 0; k < L; ++k) M2M_REQUIRE(ids[k] >= 0 && ids[k] < V, "%s: bad_words id %d outside [0, %d)", fn, ids[k], V);
+    if (L == 1) {
+      if (ids[0] == g.eos_token_id) continue;               // 4.34 filters the sequence [eos] out
+      h.bad1[ids[0] >> 5] |= 1u << (ids[0] & 31); h.has_bad1 = 1;
+      continue;
+    }
+    M2M_REQUIRE(h.n_bad < PROC_MAX_BAD, "%s: more than %d bad_words sequences of two or more ids", fn, PROC_MAX_BAD);
+    const int o = h.bad_off[h.n_bad];
+    M2M_REQUIRE(o + L <= PROC_MAX_BAD_IDS, "%s: bad_words sequences of two or more ids hold more than %d ids", fn, PROC_MAX_BAD_IDS);
+    for (int k = 0; k < L; ++k) h.bad_ids[o + k] = ids[k];
+    h.bad_off[++h.n_bad] = o + L;
+  }
+  return M2M_OK;
+}
+
+extern "C" int m2m_generate_processed(m2m_session* s, int max_length, const m2m_process_params* proc, const m2m_sample_params* sample,
+                                      int64_t* tokens_out_dev, int* out_len_host, void* stream) {
+  M2M_REQUIRE(s && proc && tokens_out_dev && out_len_host, "m2m_generate_processed: null argument");
+  if (sample) {
+    M2M_REQUIRE(isfinite(sample->temperature) && sample->temperature > 0.f,
+                "m2m_generate_processed: temperature must be a strictly positive finite float, got %g", (double)sample->temperature);
+    M2M_REQUIRE(sample->top_k >= 0, "m2m_generate_processed: top_k must be >= 0 (0 disables the filter), got %d", sample->top_k);
+    M2M_REQUIRE(sample->top_p >= 0.f && sample->top_p <= 1.f, "m2m_generate_processed: top_p must be a float in [0, 1], got %g",
+                (double)sample->top_p);
+  }
+  M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_processed: max_length %d outside [1, %d]", max_length, s->max_dec);
+  int rc = fill_process_params(s, max_length, proc, *s->proc_host);
+  if (rc != M2M_OK) return rc;
+  if (!s->encoded) { set_error("m2m_generate_processed: %s", encode_missing(s)); return M2M_ERR_STATE; }
+  hipStream_t caller = (hipStream_t)stream;
+  // both parameter blocks reach the captured graphs through the workspace, ordered before the chains by generate_impl's event
+  if (sample) {
+    s->sample_host->temperature = sample->temperature; s->sample_host->top_k = sample->top_k; s->sample_host->top_p = sample->top_p;
+    s->sample_host->pad_ = 0; s->sample_host->seed = (unsigned long long)sample->seed;
+    if (hipMemcpyAsync(s->sample_dev, s->sample_host, sizeof(SampleParams), hipMemcpyHostToDevice, caller) != hipSuccess) rc = M2M_ERR_HIP;
+  }
+  if (rc == M2M_OK && hipMemcpyAsync(s->proc_dev, s->proc_host, sizeof(ProcessParams), hipMemcpyHostToDevice, caller) != hipSuccess)
+    rc = M2M_ERR_HIP;
+  if (rc != M2M_OK) set_error("m2m_generate_processed: hipMemcpyAsync: %s", hipGetErrorString(hipGetLastError()));
+  if (rc == M2M_OK) {
+    s->head_mode = HEAD_PROCESSED | (sample ? HEAD_SAMPLE : HEAD_GREEDY);
+    rc = generate_impl(s, max_length, tokens_out_dev, out_len_host, caller, "m2m_generate_processed");
+    s->head_mode = HEAD_GREEDY;
+  }
+  if (rc != M2M_OK) quiesce(s, caller);
+  return rc;
+}
+
+// the free-running decode loop of the greedy, sampling and processed head forms (s->head_mode); fn names the entry point in error messages
 static int generate_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev, int* out_len_host, hipStream_t caller, const char* fn) {
   const int steps = max_length - 1;
   int G = plan_groups(s);

@@ -4,7 +4,10 @@
 MI355X path runs, with transformers 4.34's ``GenerationConfig`` defaults (hf: generation/configuration_utils.py:
 ``max_length=20``, ``do_sample=False``, ``temperature=1.0``, ``top_k=50``, ``top_p=1.0``, ``num_return_sequences=1``)
 and the argument checks of its logits warpers (hf: generation/logits_process.py ``TemperatureLogitsWarper``,
-``TopKLogitsWarper``, ``TopPLogitsWarper``), which raise ``ValueError``.  Beam search and every other keyword raise
+``TopKLogitsWarper``, ``TopPLogitsWarper``), which raise ``ValueError``.  The logits-processor keywords (``repetition_penalty``,
+``no_repeat_ngram_size``, ``bad_words_ids``, ``min_length``, ``min_new_tokens``, ``forced_bos_token_id``,
+``forced_eos_token_id``, ``suppress_tokens``, ``begin_suppress_tokens``) and ``max_new_tokens`` follow 4.34's
+``_get_logits_processor`` and its processors' checks.  Beam search and every other keyword raise
 ``NotImplementedError`` there; beam search has its own entry point (``T5Transformer.beam_search``), whose keywords
 ``resolve_beam_kwargs`` checks.
 """
@@ -20,6 +23,31 @@ DEFAULT_TEMPERATURE = 1.0
 DEFAULT_TOP_K = 50
 DEFAULT_TOP_P = 1.0
 
+# device limits of the processed head (music2midi_amd/csrc/t5.h PROC_*)
+PROCESS_MAX_VOCAB = 4096
+PROCESS_MAX_LENGTH = 2048
+PROCESS_MAX_BAD_SEQUENCES = 64      # bad-words sequences of two or more ids
+PROCESS_MAX_BAD_IDS = 512           # ids in those sequences together
+
+
+@dataclass(frozen=True)
+class ProcessConfig:
+    """The active logits processors of a call (transformers 4.34 ``_get_logits_processor``); neutral values are absent ones."""
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    bad_words_ids: tuple = ()            # tuple of tuples of ids, as given (the [eos] entry is filtered where it is applied)
+    min_length: int = 0
+    min_new_tokens: int = 0
+    forced_bos_token_id: int = -1
+    forced_eos_token_id: int = -1
+    suppress_tokens: tuple = ()
+    begin_suppress_tokens: tuple = ()
+
+    @property
+    def begin_index(self) -> int:
+        """cur_len at which begin_suppress_tokens apply: the decoder prompt length (1), + 1 with forced_bos_token_id (4.34)."""
+        return 2 if self.forced_bos_token_id >= 0 else 1
+
 
 @dataclass(frozen=True)
 class GenerateConfig:
@@ -29,6 +57,7 @@ class GenerateConfig:
     top_k: int = DEFAULT_TOP_K           # 0: no top-k filter
     top_p: float = DEFAULT_TOP_P         # 1.0: no nucleus filter
     num_return_sequences: int = 1
+    process: "ProcessConfig | None" = None   # None: no logits processor (the plain greedy / sampling head)
 
 
 def _is_int(v) -> bool:
@@ -45,13 +74,106 @@ def _is_real(v) -> bool:
     return isinstance(v, numbers.Real) and not isinstance(v, bool)
 
 
-def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_LENGTH) -> GenerateConfig:
+def _id_list(name, v, vocab_size):
+    if not isinstance(v, (list, tuple)) or not all(_is_int(i) for i in v):
+        raise ValueError(f"`{name}` has to be a list of token ids, but is {v!r}")
+    ids = tuple(operator.index(i) for i in v)
+    _check_ids(name, ids, vocab_size)
+    return ids
+
+
+def _check_ids(name, ids, vocab_size):
+    if any(i < 0 for i in ids):
+        raise ValueError(f"`{name}` has to hold non-negative token ids, but is {list(ids)!r}")
+    if vocab_size is not None and any(i >= vocab_size for i in ids):
+        raise ValueError(f"The model vocabulary size is {vocab_size}, but `{name}` holds the ids "
+                         f"{sorted({i for i in ids if i >= vocab_size})}")
+
+
+def resolve_process_kwargs(kw: dict, vocab_size=None) -> "ProcessConfig | None":
+    """Pop the logits-processor keywords from ``kw`` and check them (4.34's gates and ``ValueError`` messages; ids outside
+    the vocabulary raise too).  -> ``None`` when no processor is active."""
+    p = {}
+    rp = kw.pop("repetition_penalty", None)
+    if rp is not None and rp != 1.0:
+        if not isinstance(rp, float) or not (rp > 0):            # RepetitionPenaltyLogitsProcessor
+            raise ValueError(f"`penalty` has to be a strictly positive float, but is {rp}")
+        if not math.isfinite(rp):
+            raise ValueError(f"`repetition_penalty` has to be finite on the MI355X path, but is {rp}")
+        p["repetition_penalty"] = float(rp)
+    n = kw.pop("no_repeat_ngram_size", None)
+    if n is not None and n > 0:
+        if not _is_int(n):                                       # NoRepeatNGramLogitsProcessor
+            raise ValueError(f"`ngram_size` has to be a strictly positive integer, but is {n}")
+        p["no_repeat_ngram_size"] = operator.index(n)
+    bw = kw.pop("bad_words_ids", None)
+    if bw is not None:                                           # NoBadWordsLogitsProcessor._validate_arguments
+        if not isinstance(bw, list) or len(bw) == 0:
+            raise ValueError(f"`bad_words_ids` has to be a non-empty list, but is {bw}.")
+        if any(not isinstance(s, list) for s in bw):
+            raise ValueError(f"`bad_words_ids` has to be a list of lists, but is {bw}.")
+        if any(any(not _is_int(i) or i < 0 for i in s) for s in bw):
+            raise ValueError(f"Each list in `bad_words_ids` has to be a list of positive integers, but is {bw}.")
+        if any(len(s) == 0 for s in bw):
+            raise ValueError(f"`bad_words_ids` holds an empty sequence: {bw}")
+        seqs = tuple(tuple(operator.index(i) for i in s) for s in bw)
+        _check_ids("bad_words_ids", tuple(i for s in seqs for i in s), vocab_size)
+        long_ = [s for s in seqs if len(s) >= 2]
+        if len(long_) > PROCESS_MAX_BAD_SEQUENCES or sum(map(len, long_)) > PROCESS_MAX_BAD_IDS:
+            raise ValueError(f"`bad_words_ids` holds {len(long_)} sequences of two or more ids with {sum(map(len, long_))} ids: "
+                             f"the MI355X processed head takes at most {PROCESS_MAX_BAD_SEQUENCES} such sequences and "
+                             f"{PROCESS_MAX_BAD_IDS} ids")
+        p["bad_words_ids"] = seqs
+    for name in ("min_length", "min_new_tokens"):
+        v = kw.pop(name, None)
+        if v is not None and v > 0:
+            if not _is_int(v):                                   # MinLength / MinNewTokensLength LogitsProcessor
+                raise ValueError(f"`{name}` has to be a positive integer, but is {v}" if name == "min_new_tokens" else
+                                 f"`min_length` has to be a non-negative integer, but is {v}")
+            p[name] = operator.index(v)
+    for name in ("forced_bos_token_id", "forced_eos_token_id"):
+        v = kw.pop(name, None)
+        if v is None:
+            continue
+        if name == "forced_eos_token_id" and isinstance(v, (list, tuple)):
+            if len(v) != 1:
+                raise ValueError(f"`forced_eos_token_id` = {v!r}: the MI355X processed head forces one EOS id")
+            v = v[0]
+        if not _is_int(v):
+            raise ValueError(f"`{name}` has to be a token id, but is {v!r}")
+        _check_ids(name, (operator.index(v),), vocab_size)
+        p[name] = operator.index(v)
+    for name in ("suppress_tokens", "begin_suppress_tokens"):
+        v = kw.pop(name, None)
+        if v is not None:
+            ids = _id_list(name, v, vocab_size)
+            if ids:
+                p[name] = ids
+    if not p:
+        return None
+    if vocab_size is not None and vocab_size > PROCESS_MAX_VOCAB:
+        raise ValueError(f"logits processors on the MI355X path need a vocabulary of at most {PROCESS_MAX_VOCAB} ids "
+                         f"(the model has {vocab_size})")
+    return ProcessConfig(**p)
+
+
+def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_LENGTH, vocab_size=None) -> GenerateConfig:
     """Validate ``generate`` keywords and fill in HF's defaults.  ``kwargs`` is not modified.
 
     ``None`` for temperature / top_k / top_p means "no such warper", as in HF (the warper is only built when the value is
-    not None).  With ``do_sample=False`` the sampling keywords are ignored (HF warns and decodes greedily)."""
+    not None).  With ``do_sample=False`` the sampling keywords are ignored (HF warns and decodes greedily).
+    ``max_new_tokens`` sets ``max_length = max_new_tokens + 1`` (the decoder prompt is the start token) and wins over
+    ``max_length``, as in 4.34.  ``vocab_size`` (optional) range-checks the processors' token ids."""
     kw = dict(kwargs)
     max_length = int(kw.pop("max_length", default_max_length))   # range-checked by the library, as before
+    max_new = kw.pop("max_new_tokens", None)
+    if max_new is not None:
+        if not _is_int(max_new) or max_new <= 0:                 # GenerationConfig.validate
+            raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new}.")
+        max_length = operator.index(max_new) + 1
+    process = resolve_process_kwargs(kw, vocab_size)
+    if process is not None and max_length > PROCESS_MAX_LENGTH:
+        raise ValueError(f"logits processors on the MI355X path take max_length <= {PROCESS_MAX_LENGTH}, got {max_length}")
     do_sample = bool(kw.pop("do_sample", False))
     if int(kw.pop("num_beams", 1)) != 1:
         raise NotImplementedError("generate() does not decode with num_beams > 1 on the MI355X path; "
@@ -70,7 +192,7 @@ def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_
         if n != 1:   # hf: generation/utils.py (greedy mode) raises the same
             raise ValueError("Greedy methods without beam search do not support `num_return_sequences` different than 1 "
                              f"(got {n}).")
-        return GenerateConfig(max_length=max_length)
+        return GenerateConfig(max_length=max_length, process=process)
     # TemperatureLogitsWarper: a strictly positive float
     if temperature is None:
         temperature = DEFAULT_TEMPERATURE
@@ -90,7 +212,7 @@ def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_
     if not _is_real(top_p) or not (0.0 <= float(top_p) <= 1.0):
         raise ValueError(f"`top_p` has to be a float >= 0 and <= 1, but is {top_p!r}")
     return GenerateConfig(max_length=max_length, do_sample=True, temperature=float(temperature), top_k=operator.index(top_k),
-                          top_p=float(top_p), num_return_sequences=operator.index(n))
+                          top_p=float(top_p), num_return_sequences=operator.index(n), process=process)
 
 
 BEAM_MAX = 32   # beams per clip the device beam head supports

@@ -66,6 +66,14 @@ class SampleParams(C.Structure):
     _fields_ = [("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64)]
 
 
+class ProcessParams(C.Structure):
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int), ("min_length", C.c_int),
+                ("min_new_tokens", C.c_int), ("forced_bos_token_id", C.c_int), ("forced_eos_token_id", C.c_int),
+                ("suppress_tokens", C.POINTER(C.c_int32)), ("n_suppress_tokens", C.c_int),
+                ("begin_suppress_tokens", C.POINTER(C.c_int32)), ("n_begin_suppress_tokens", C.c_int),
+                ("bad_words_ids", C.POINTER(C.c_int32)), ("bad_words_lengths", C.POINTER(C.c_int32)), ("n_bad_words", C.c_int)]
+
+
 class BeamParams(C.Structure):
     _fields_ = [("num_beams", C.c_int), ("length_penalty", C.c_float), ("early_stopping", C.c_int),
                 ("num_return_sequences", C.c_int)]
@@ -104,6 +112,8 @@ _SIGNATURES = {
     "m2m_generate_greedy": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "m2m_generate_sample": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SampleParams), C.c_void_p, C.POINTER(C.c_int),
                                       C.c_void_p]),
+    "m2m_generate_processed": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ProcessParams), C.POINTER(SampleParams), C.c_void_p,
+                                         C.POINTER(C.c_int), C.c_void_p]),
     "m2m_generate_beam": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BeamParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                     C.c_void_p]),
     "m2m_session_repack_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
