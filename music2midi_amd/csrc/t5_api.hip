@@ -513,55 +513,62 @@ static void quiesce(m2m_session* s, hipStream_t caller) {
   (void)hipGetLastError();
 }
 
-static int generate_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev, int* out_len_host, hipStream_t caller, const char* fn);
+// One call of a decode export.  Beam search (HEAD_BEAM) decodes the B encoded clips as B x beam_nb rows and never re-packs them;
+// the other heads decode B rows.
+namespace {
+struct DecodeCall {
+  const char* fn;          // the export, for messages
+  int head_mode, beam_nb;  // the session's head form for this call
+  int64_t* tokens_out;
+  float* scores_out;       // beam search: optional sequence scores
+};
+}  // namespace
 
-// why a call that needs the encoded state finds none: never encoded, or the last greedy decode re-packed its live rows over it
-static const char* encode_missing(const m2m_session* s) {
-  return s->rows_moved > 0 ? "re-encode: the last m2m_generate_greedy re-packed its live rows over the encoded state (it consumes the encode "
-                             "whenever m2m_session_repack_stats reports rows moved)"
-                           : "call m2m_encode first";
+static int decode_call(m2m_session* s, const DecodeCall& c, int max_length, int* out_len_host, hipStream_t caller);
+
+// M2M_ERR_STATE unless the session holds an encode: never encoded, or the last greedy decode re-packed its live rows over it
+static int require_encoded(const m2m_session* s, const char* fn) {
+  if (s->encoded) return M2M_OK;
+  set_error("%s: %s", fn, s->rows_moved > 0 ? "re-encode: the last m2m_generate_greedy re-packed its live rows over the encoded state (it "
+                                              "consumes the encode whenever m2m_session_repack_stats reports rows moved)"
+                                            : "call m2m_encode first");
+  return M2M_ERR_STATE;
+}
+
+// the sampling parameters (m2m_generate_sample, m2m_generate_processed), checked and laid out into the SampleParams block on the host
+static int fill_sample_params(const m2m_sample_params* p, SampleParams& h, const char* fn) {
+  M2M_REQUIRE(isfinite(p->temperature) && p->temperature > 0.f, "%s: temperature must be a strictly positive finite float, got %g", fn,
+              (double)p->temperature);
+  M2M_REQUIRE(p->top_k >= 0, "%s: top_k must be >= 0 (0 disables the filter), got %d", fn, p->top_k);
+  M2M_REQUIRE(p->top_p >= 0.f && p->top_p <= 1.f, "%s: top_p must be a float in [0, 1], got %g", fn, (double)p->top_p);
+  h.temperature = p->temperature; h.top_k = p->top_k; h.top_p = p->top_p; h.pad_ = 0; h.seed = (unsigned long long)p->seed;
+  return M2M_OK;
 }
 
 extern "C" int m2m_generate_greedy(m2m_session* s, int max_length, int64_t* tokens_out_dev, int* out_len_host, void* stream) {
+  const char* fn = "m2m_generate_greedy";
   M2M_REQUIRE(s && tokens_out_dev && out_len_host, "m2m_generate_greedy: null argument");
-  if (!s->encoded) { set_error("m2m_generate_greedy: %s", encode_missing(s)); return M2M_ERR_STATE; }
+  int rc;
+  if ((rc = require_encoded(s, fn))) return rc;
   M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_greedy: max_length %d outside [1, %d]", max_length, s->max_dec);
-  const int rc = generate_impl(s, max_length, tokens_out_dev, out_len_host, (hipStream_t)stream, "m2m_generate_greedy");
-  if (rc != M2M_OK) quiesce(s, (hipStream_t)stream);
-  return rc;
+  return decode_call(s, {fn, HEAD_GREEDY, 0, tokens_out_dev, nullptr}, max_length, out_len_host, (hipStream_t)stream);
 }
 
 extern "C" int m2m_generate_sample(m2m_session* s, int max_length, const m2m_sample_params* p, int64_t* tokens_out_dev,
                                    int* out_len_host, void* stream) {
+  const char* fn = "m2m_generate_sample";
   M2M_REQUIRE(s && p && tokens_out_dev && out_len_host, "m2m_generate_sample: null argument");
-  M2M_REQUIRE(isfinite(p->temperature) && p->temperature > 0.f,
-              "m2m_generate_sample: temperature must be a strictly positive finite float, got %g", (double)p->temperature);
-  M2M_REQUIRE(p->top_k >= 0, "m2m_generate_sample: top_k must be >= 0 (0 disables the filter), got %d", p->top_k);
-  M2M_REQUIRE(p->top_p >= 0.f && p->top_p <= 1.f, "m2m_generate_sample: top_p must be a float in [0, 1], got %g", (double)p->top_p);
+  int rc;
+  if ((rc = fill_sample_params(p, *s->sample_host, fn))) return rc;
   M2M_REQUIRE(s->m->g.vocab_size <= SAMPLE_MAX_VOCAB, "m2m_generate_sample: vocab_size %d > %d (the sampling head keeps a row in one "
               "wavefront's registers)", s->m->g.vocab_size, SAMPLE_MAX_VOCAB);
-  if (!s->encoded) { set_error("m2m_generate_sample: %s", encode_missing(s)); return M2M_ERR_STATE; }
+  if ((rc = require_encoded(s, fn))) return rc;
   M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_sample: max_length %d outside [1, %d]", max_length, s->max_dec);
-  hipStream_t caller = (hipStream_t)stream;
-  // the parameters reach the captured graphs through their device block, ordered before the chains by generate_impl's event
-  s->sample_host->temperature = p->temperature; s->sample_host->top_k = p->top_k; s->sample_host->top_p = p->top_p;
-  s->sample_host->pad_ = 0; s->sample_host->seed = (unsigned long long)p->seed;
-  int rc = M2M_OK;
-  if (hipMemcpyAsync(s->sample_dev, s->sample_host, sizeof(SampleParams), hipMemcpyHostToDevice, caller) != hipSuccess) {
-    set_error("m2m_generate_sample: hipMemcpyAsync: %s", hipGetErrorString(hipGetLastError()));
-    rc = M2M_ERR_HIP;
-  }
-  if (rc == M2M_OK) {
-    s->head_mode = HEAD_SAMPLE;
-    rc = generate_impl(s, max_length, tokens_out_dev, out_len_host, caller, "m2m_generate_sample");
-    s->head_mode = HEAD_GREEDY;
-  }
-  if (rc != M2M_OK) quiesce(s, caller);
-  return rc;
+  return decode_call(s, {fn, HEAD_SAMPLE, 0, tokens_out_dev, nullptr}, max_length, out_len_host, (hipStream_t)stream);
 }
 
 // Logits processors (include/music2midi_amd.h): the id lists are checked and laid out into the ProcessParams block on the host; the
-// decode loop is generate_impl's with the processed head (HEAD_PROCESSED, greedy or sampling select).
+// decode loop runs the processed head (HEAD_PROCESSED, greedy or sampling select).
 static int fill_process_params(const m2m_session* s, int max_length, const m2m_process_params* p, ProcessParams& h) {
   const char* fn = "m2m_generate_processed";
   const m2m_t5_geometry& g = s->m->g;
@@ -620,46 +627,29 @@ static int fill_process_params(const m2m_session* s, int max_length, const m2m_p
 
 extern "C" int m2m_generate_processed(m2m_session* s, int max_length, const m2m_process_params* proc, const m2m_sample_params* sample,
                                       int64_t* tokens_out_dev, int* out_len_host, void* stream) {
+  const char* fn = "m2m_generate_processed";
   M2M_REQUIRE(s && proc && tokens_out_dev && out_len_host, "m2m_generate_processed: null argument");
-  if (sample) {
-    M2M_REQUIRE(isfinite(sample->temperature) && sample->temperature > 0.f,
-                "m2m_generate_processed: temperature must be a strictly positive finite float, got %g", (double)sample->temperature);
-    M2M_REQUIRE(sample->top_k >= 0, "m2m_generate_processed: top_k must be >= 0 (0 disables the filter), got %d", sample->top_k);
-    M2M_REQUIRE(sample->top_p >= 0.f && sample->top_p <= 1.f, "m2m_generate_processed: top_p must be a float in [0, 1], got %g",
-                (double)sample->top_p);
-  }
+  int rc;
+  if (sample && (rc = fill_sample_params(sample, *s->sample_host, fn))) return rc;
   M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_processed: max_length %d outside [1, %d]", max_length, s->max_dec);
-  int rc = fill_process_params(s, max_length, proc, *s->proc_host);
-  if (rc != M2M_OK) return rc;
-  if (!s->encoded) { set_error("m2m_generate_processed: %s", encode_missing(s)); return M2M_ERR_STATE; }
-  hipStream_t caller = (hipStream_t)stream;
-  // both parameter blocks reach the captured graphs through the workspace, ordered before the chains by generate_impl's event
-  if (sample) {
-    s->sample_host->temperature = sample->temperature; s->sample_host->top_k = sample->top_k; s->sample_host->top_p = sample->top_p;
-    s->sample_host->pad_ = 0; s->sample_host->seed = (unsigned long long)sample->seed;
-    if (hipMemcpyAsync(s->sample_dev, s->sample_host, sizeof(SampleParams), hipMemcpyHostToDevice, caller) != hipSuccess) rc = M2M_ERR_HIP;
-  }
-  if (rc == M2M_OK && hipMemcpyAsync(s->proc_dev, s->proc_host, sizeof(ProcessParams), hipMemcpyHostToDevice, caller) != hipSuccess)
-    rc = M2M_ERR_HIP;
-  if (rc != M2M_OK) set_error("m2m_generate_processed: hipMemcpyAsync: %s", hipGetErrorString(hipGetLastError()));
-  if (rc == M2M_OK) {
-    s->head_mode = HEAD_PROCESSED | (sample ? HEAD_SAMPLE : HEAD_GREEDY);
-    rc = generate_impl(s, max_length, tokens_out_dev, out_len_host, caller, "m2m_generate_processed");
-    s->head_mode = HEAD_GREEDY;
-  }
-  if (rc != M2M_OK) quiesce(s, caller);
-  return rc;
+  if ((rc = fill_process_params(s, max_length, proc, *s->proc_host))) return rc;
+  if ((rc = require_encoded(s, fn))) return rc;
+  return decode_call(s, {fn, HEAD_PROCESSED | (sample ? HEAD_SAMPLE : HEAD_GREEDY), 0, tokens_out_dev, nullptr}, max_length, out_len_host,
+                     (hipStream_t)stream);
 }
 
-// the free-running decode loop of the greedy, sampling and processed head forms (s->head_mode); fn names the entry point in error messages
-static int generate_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev, int* out_len_host, hipStream_t caller, const char* fn) {
-  const int steps = max_length - 1;
-  int G = plan_groups(s);
+// the decode loop of every head form (s->head_mode, set by decode_call)
+static int decode_loop(m2m_session* s, const DecodeCall& c, int max_length, int* out_len_host, hipStream_t caller) {
+  const char* fn = c.fn;
+  const bool beam = c.head_mode == HEAD_BEAM;
+  const int steps = max_length - 1, rows = beam ? s->B * c.beam_nb : s->B;
+  int G = plan_groups(s, rows);        // beam search: chains split at clip boundaries
   const bool graph = use_graph();
   const int U = env_int("M2M_GRAPH_STEPS", 8) < 1 ? 1 : env_int("M2M_GRAPH_STEPS", 8);   // decode steps per graph
   // Live-row re-packing at the host polls (decode.hip "live-row re-packing"): once a quarter of the packed rows have emitted EOS the
-  // live ones are moved into the first slots and smaller chains take over.  M2M_COMPACT=0: rows keep their slots (round 4).
-  const bool compact = env_int("M2M_COMPACT", 1) != 0;
+  // live ones are moved into the first slots and smaller chains take over.  M2M_COMPACT=0: rows keep their slots (round 4).  Never in
+  // beam search: a clip's beams move through each other's cache slots, so a beam call does not consume the encode.
+  const bool compact = !beam && env_int("M2M_COMPACT", 1) != 0;
   int rc;
   // order every chain after whatever the caller enqueued (encode ran on the caller's stream)
   M2M_CHECK_HIP(hipEventRecord(s->ev_in, caller));
@@ -667,6 +657,7 @@ static int generate_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev
     DecGroup& gr = s->groups[i];
     M2M_CHECK_HIP(hipStreamWaitEvent(gr.stream, s->ev_in, 0));
     if ((rc = decode_init(s, gr.view, steps, false, gr.stream))) return rc;
+    if (beam && (rc = decode_beam_init(s, gr.view, gr.stream))) return rc;
     if (graph && (rc = ensure_graph(s, gr, U))) return rc;
     gr.state_host->done = (steps == 0);
   }
@@ -675,7 +666,7 @@ static int generate_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev
   // no-ops once their chain's state.done is set).
   const int CHUNK = 64;
   int launched = 0;
-  int cur_rows = s->B;                 // packed slots still being decoded
+  int cur_rows = rows;                 // packed slots still being decoded
   s->repacks = 0; s->rows_moved = 0;
   int out_len = 1;                     // longest finished chain so far (chains retired by a re-packing included)
   bool range_error = false;
@@ -750,7 +741,7 @@ static int generate_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev
     }
   }
   // headless loop: the last step's arg-max is still a pending key (no later step consumed it)
-  if (steps > 0)
+  if (!beam && steps > 0)
     for (int i = 0; i < G; ++i)
       if ((rc = decode_finalize(s, s->groups[i].view, s->groups[i].stream))) return rc;
   // valid length = the longest chain (one process decoding the whole batch stops when EVERY row has finished)
@@ -762,10 +753,16 @@ static int generate_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev
     if (l > out_len) out_len = l;
     range_error |= gr.state_host->overflow != 0;
   }
-  // pack [B, max_dec] -> caller's [B, max_length] on the caller's stream (all chains are idle now)
-  M2M_CHECK_HIP(hipMemcpy2DAsync(tokens_out_dev, (size_t)max_length * 8, s->tokens, (size_t)s->max_dec * 8,
-                                 (size_t)max_length * 8, (size_t)s->B, hipMemcpyDeviceToDevice, caller));
+  // the output, on the caller's stream (all chains are idle now)
+  if (beam) {   // finalize (a clip that is not done stopped at max_length, t = steps); valid length = the longest hypothesis
+    if ((rc = decode_beam_finalize(s, rows, steps, c.tokens_out, c.scores_out, max_length, caller))) return rc;
+    M2M_CHECK_HIP(hipMemcpyAsync(s->beam_host, s->beam_dev, sizeof(BeamParams), hipMemcpyDeviceToHost, caller));
+  } else {      // pack [B, max_dec] -> caller's [B, max_length]
+    M2M_CHECK_HIP(hipMemcpy2DAsync(c.tokens_out, (size_t)max_length * 8, s->tokens, (size_t)s->max_dec * 8,
+                                   (size_t)max_length * 8, (size_t)s->B, hipMemcpyDeviceToDevice, caller));
+  }
   M2M_CHECK_HIP(hipStreamSynchronize(caller));
+  if (beam) { const int w = s->beam_host->max_hyp_len + 1; out_len = w < max_length ? w : max_length; }
   *out_len_host = out_len;
   if (range_error) {
     set_error("%s: a decoder activation left the fixed-point residual range (|x| >= 2^21) or was not finite; "
@@ -775,74 +772,34 @@ static int generate_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev
   return M2M_OK;
 }
 
-// Beam search (hf 4.34 _beam_search / BeamSearchScorer, see include/music2midi_amd.h): the B encoded clips are decoded as B x nb
-// rows (clip-major), in chains that split at clip boundaries; no live-row re-packing (a clip's beams move through each other's
-// cache slots), so the encode is not consumed.  The step's head is dec_beam_kernel; dec_beam_final_kernel writes the output.
-static int beam_impl(m2m_session* s, int max_length, int64_t* tokens_out_dev, float* scores_out_dev, int* out_len_host, hipStream_t caller) {
-  const char* fn = "m2m_generate_beam";
-  const int steps = max_length - 1, rows = s->B * s->beam_nb;
-  const int G = plan_groups(s, rows);
-  const bool graph = use_graph();
-  const int U = env_int("M2M_GRAPH_STEPS", 8) < 1 ? 1 : env_int("M2M_GRAPH_STEPS", 8);
-  int rc;
-  M2M_CHECK_HIP(hipEventRecord(s->ev_in, caller));
-  for (int i = 0; i < G; ++i) {
-    DecGroup& gr = s->groups[i];
-    M2M_CHECK_HIP(hipStreamWaitEvent(gr.stream, s->ev_in, 0));
-    if ((rc = decode_init(s, gr.view, steps, false, gr.stream))) return rc;
-    if ((rc = decode_beam_init(s, gr.view, gr.stream))) return rc;
-    if (graph && (rc = ensure_graph(s, gr, U))) return rc;
-    gr.state_host->done = (steps == 0);
-  }
-  s->repacks = 0; s->rows_moved = 0;
-  const int CHUNK = 64;
-  int launched = 0;
-  bool all_done = steps == 0;
-  while (!all_done && launched < steps) {
-    const int n = steps - launched < CHUNK ? steps - launched : CHUNK;
-    for (int k = 0; k < n; k += (graph ? U : 1)) {
-      for (int i = 0; i < G; ++i) {
-        DecGroup& gr = s->groups[i];
-        if (gr.state_host->done) continue;
-        if (graph) M2M_CHECK_HIP(hipGraphLaunch(gr.graph_exec, gr.stream));
-        else if ((rc = decode_launch_step(s, gr.view, false, nullptr, 0, gr.stream))) return rc;
-      }
-    }
-    launched += ceil_div(n, graph ? U : 1) * (graph ? U : 1);
-    for (int i = 0; i < G; ++i) {
-      DecGroup& gr = s->groups[i];
-      if (gr.state_host->done) continue;
-      M2M_CHECK_HIP(hipMemcpyAsync(gr.state_host, gr.view.state, sizeof(DecState), hipMemcpyDeviceToHost, gr.stream));
-    }
-    all_done = true;
-    for (int i = 0; i < G; ++i) {
-      M2M_CHECK_HIP(hipStreamSynchronize(s->groups[i].stream));
-      if (!s->groups[i].state_host->done) all_done = false;
-    }
-  }
-  bool range_error = false;
-  for (int i = 0; i < G; ++i) {
-    DecGroup& gr = s->groups[i];
-    M2M_CHECK_HIP(hipMemcpyAsync(gr.state_host, gr.view.state, sizeof(DecState), hipMemcpyDeviceToHost, gr.stream));
-    M2M_CHECK_HIP(hipStreamSynchronize(gr.stream));
-    range_error |= gr.state_host->overflow != 0;
-  }
-  // every chain is idle: finalize on the caller's stream (a clip that is not done stopped at max_length, t = steps)
-  if ((rc = decode_beam_finalize(s, rows, steps, tokens_out_dev, scores_out_dev, max_length, caller))) return rc;
-  M2M_CHECK_HIP(hipMemcpyAsync(s->beam_host, s->beam_dev, sizeof(BeamParams), hipMemcpyDeviceToHost, caller));
-  M2M_CHECK_HIP(hipStreamSynchronize(caller));
-  const int w = s->beam_host->max_hyp_len + 1;
-  *out_len_host = w < max_length ? w : max_length;
-  if (range_error) {
-    set_error("%s: a decoder activation left the fixed-point residual range (|x| >= 2^21) or was not finite; "
-              "the fp32 reference would produce Inf/NaN logits here - token ids are not valid (check the checkpoint)", fn);
-    return M2M_ERR_RANGE;
-  }
-  return M2M_OK;
+// a parameter block filled on the host -> its device block in the workspace, on the caller's stream
+static int upload(void* dev, const void* host, size_t bytes, hipStream_t caller, const char* fn) {
+  if (hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, caller) == hipSuccess) return M2M_OK;
+  set_error("%s: hipMemcpyAsync: %s", fn, hipGetErrorString(hipGetLastError()));
+  return M2M_ERR_HIP;
 }
 
+// The parameter blocks the head reads reach the captured graphs through the workspace, ordered before the chains by the loop's event.
+// The session's head mode holds for this call only, and nothing of a failed call is left running.
+static int decode_call(m2m_session* s, const DecodeCall& c, int max_length, int* out_len_host, hipStream_t caller) {
+  int rc = M2M_OK;
+  if (c.head_mode & HEAD_SAMPLE) rc = upload(s->sample_dev, s->sample_host, sizeof(SampleParams), caller, c.fn);
+  if (rc == M2M_OK && (c.head_mode & HEAD_PROCESSED)) rc = upload(s->proc_dev, s->proc_host, sizeof(ProcessParams), caller, c.fn);
+  if (rc == M2M_OK && c.head_mode == HEAD_BEAM) rc = upload(s->beam_dev, s->beam_host, sizeof(BeamParams), caller, c.fn);
+  if (rc == M2M_OK) {
+    s->head_mode = c.head_mode; s->beam_nb = c.beam_nb;
+    rc = decode_loop(s, c, max_length, out_len_host, caller);
+    s->head_mode = HEAD_GREEDY; s->beam_nb = 0;
+  }
+  if (rc != M2M_OK) quiesce(s, caller);
+  return rc;
+}
+
+// Beam search (hf 4.34 _beam_search / BeamSearchScorer, see include/music2midi_amd.h): the B encoded clips are decoded as B x nb
+// rows (clip-major).  The step's head is dec_beam_kernel; dec_beam_final_kernel writes the output.
 extern "C" int m2m_generate_beam(m2m_session* s, int max_length, const m2m_beam_params* p, int64_t* tokens_out_dev,
                                  float* scores_out_dev, int* out_len_host, void* stream) {
+  const char* fn = "m2m_generate_beam";
   M2M_REQUIRE(s && p && tokens_out_dev && out_len_host, "m2m_generate_beam: null argument");
   M2M_REQUIRE(p->num_beams >= 2 && p->num_beams <= BEAM_MAX, "m2m_generate_beam: num_beams %d outside [2, %d] (one beam is "
               "m2m_generate_greedy)", p->num_beams, BEAM_MAX);
@@ -854,27 +811,16 @@ extern "C" int m2m_generate_beam(m2m_session* s, int max_length, const m2m_beam_
   const int V = s->m->g.vocab_size;
   M2M_REQUIRE(V <= SAMPLE_MAX_VOCAB && V >= 2 * p->num_beams, "m2m_generate_beam: vocab_size %d outside [2 num_beams, %d] (the beam "
               "head keeps a row in one wavefront's registers)", V, SAMPLE_MAX_VOCAB);
-  if (!s->encoded) { set_error("m2m_generate_beam: %s", encode_missing(s)); return M2M_ERR_STATE; }
+  int rc;
+  if ((rc = require_encoded(s, fn))) return rc;
   M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_beam: max_length %d outside [1, %d]", max_length, s->max_dec);
   M2M_REQUIRE((int64_t)s->B * p->num_beams <= s->max_batch, "m2m_generate_beam: %d clips x %d beams > the session's max_batch %d",
               s->B, p->num_beams, s->max_batch);
-  hipStream_t caller = (hipStream_t)stream;
   BeamParams& h = *s->beam_host;
   h = BeamParams{};
   h.nb = p->num_beams; h.lp = p->length_penalty; h.early = p->early_stopping; h.n = p->num_return_sequences;
   h.max_length = max_length; h.max_hyp_len = 0;
-  int rc = M2M_OK;
-  if (hipMemcpyAsync(s->beam_dev, s->beam_host, sizeof(BeamParams), hipMemcpyHostToDevice, caller) != hipSuccess) {
-    set_error("m2m_generate_beam: hipMemcpyAsync: %s", hipGetErrorString(hipGetLastError()));
-    rc = M2M_ERR_HIP;
-  }
-  if (rc == M2M_OK) {
-    s->head_mode = HEAD_BEAM; s->beam_nb = p->num_beams;
-    rc = beam_impl(s, max_length, tokens_out_dev, scores_out_dev, out_len_host, caller);
-    s->head_mode = HEAD_GREEDY; s->beam_nb = 0;
-  }
-  if (rc != M2M_OK) quiesce(s, caller);
-  return rc;
+  return decode_call(s, {fn, HEAD_BEAM, p->num_beams, tokens_out_dev, scores_out_dev}, max_length, out_len_host, (hipStream_t)stream);
 }
 
 // Teacher-forced decoder pass over all Ld positions at once (hf: modeling_t5.py:448-509 per block, :898-1066 wrapper):
@@ -947,7 +893,7 @@ extern "C" int m2m_session_repack_stats(const m2m_session* s, int* repacks_out, 
 
 extern "C" int m2m_decode_forced(m2m_session* s, const int64_t* dec_input_ids_dev, int Ld, float* logits_out_dev, void* stream) {
   M2M_REQUIRE(s && dec_input_ids_dev && logits_out_dev, "m2m_decode_forced: null argument");
-  if (!s->encoded) { set_error("m2m_decode_forced: %s", encode_missing(s)); return M2M_ERR_STATE; }
+  if (const int rc = require_encoded(s, "m2m_decode_forced")) return rc;
   M2M_REQUIRE(Ld >= 1 && Ld <= s->max_dec, "m2m_decode_forced: Ld %d outside [1, %d]", Ld, s->max_dec);
   hipStream_t st = (hipStream_t)stream;
   const EncSwitchScope sw_scope(&s->enc_sw);
@@ -974,7 +920,7 @@ extern "C" int m2m_decode_forced(m2m_session* s, const int64_t* dec_input_ids_de
 extern "C" int m2m_bench_kernel(m2m_session* s, int which, int self_len, int iters, float* avg_us_host,
                                 int64_t* bytes_host, void* stream) {
   M2M_REQUIRE(s && avg_us_host && bytes_host && iters >= 1, "m2m_bench_kernel: bad argument");
-  if (!s->encoded) { set_error("m2m_bench_kernel: %s", encode_missing(s)); return M2M_ERR_STATE; }
+  if (const int rc = require_encoded(s, "m2m_bench_kernel")) return rc;
   M2M_REQUIRE(self_len >= 1 && self_len <= s->max_dec, "m2m_bench_kernel: self_len out of range");
   M2M_REQUIRE(which == M2M_KERNEL_DEC_CROSS_ATTN || which == M2M_KERNEL_DEC_SELF_ATTN || which == M2M_KERNEL_DEC_STEP,
               "m2m_bench_kernel: unknown kernel id %d", which);

@@ -322,70 +322,46 @@ class T5Transformer(nn.Module):
         """Decode from encoder inputs [B, S, d].  Keywords as :meth:`generate` (``do_sample``, ``temperature``, ``top_k``,
         ``top_p``, ``num_return_sequences``, the logits processors, ``max_new_tokens``); without ``do_sample=True`` this is the
         greedy decode."""
-        if kwargs:
-            cfg = resolve_generate_kwargs(kwargs, default_max_length=max_length, vocab_size=self.geometry.vocab_size)
-            if cfg.process is not None:
-                return self._generate_processed(inputs_embeds, cfg)
-            if cfg.do_sample:
-                return self._generate_sample(inputs_embeds, cfg)
-            max_length = cfg.max_length
-        with self._lock:
-            x = inputs_embeds.to(self.transformer.device, torch.float32).contiguous()
-            sess, _ = self._encode(x, max_length)
-            tokens = torch.empty((x.shape[0], max_length), dtype=torch.long, device=x.device)
-            out_len = C.c_int(0)
-            with torch.cuda.device(x.device):
-                native.check(native.load().m2m_generate_greedy(sess, max_length, tokens.data_ptr(), C.byref(out_len),
-                                                               native.stream_handle(x.device)), "m2m_generate_greedy")
-            return tokens[:, : out_len.value]
+        cfg = (resolve_generate_kwargs(kwargs, default_max_length=max_length, vocab_size=self.geometry.vocab_size) if kwargs
+               else GenerateConfig(max_length=max_length))
+        return self._decode(inputs_embeds, cfg)
 
-    def _generate_sample(self, inputs_embeds: torch.Tensor, cfg: GenerateConfig) -> torch.Tensor:
-        # the call's seed: one draw from torch's default CPU generator, so torch.manual_seed(n) makes the call reproducible
-        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-        with self._lock:
-            x = inputs_embeds.to(self.transformer.device, torch.float32)
-            if cfg.num_return_sequences > 1:      # HF's expansion: the n sequences of a clip are consecutive rows
-                x = x.repeat_interleave(cfg.num_return_sequences, dim=0)
-            x = x.contiguous()
-            max_length = cfg.max_length
-            sess, _ = self._encode(x, max_length)
-            tokens = torch.empty((x.shape[0], max_length), dtype=torch.long, device=x.device)
-            out_len = C.c_int(0)
-            p = native.SampleParams(cfg.temperature, cfg.top_k, cfg.top_p, seed)
-            with torch.cuda.device(x.device):
-                native.check(native.load().m2m_generate_sample(sess, max_length, C.byref(p), tokens.data_ptr(), C.byref(out_len),
-                                                               native.stream_handle(x.device)), "m2m_generate_sample")
-            return tokens[:, : out_len.value]
-
-    def _generate_processed(self, inputs_embeds: torch.Tensor, cfg: GenerateConfig) -> torch.Tensor:
-        pc = cfg.process
+    @torch.no_grad()
+    def _decode(self, inputs_embeds: torch.Tensor, cfg: GenerateConfig) -> torch.Tensor:
+        """Greedy, sampled or processed decode of encoder inputs [B, S, d] as the resolved ``cfg`` asks."""
         sp = None
-        if cfg.do_sample:   # the seed as in _generate_sample
+        if cfg.do_sample:
+            # the call's seed: one draw from torch's default CPU generator, so torch.manual_seed(n) makes the call reproducible
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
             sp = native.SampleParams(cfg.temperature, cfg.top_k, cfg.top_p, seed)
+        if cfg.process is not None:
+            pc = cfg.process
 
-        def ids(v):
-            return (C.c_int32 * max(len(v), 1))(*v), len(v)
+            def ids(v):
+                return (C.c_int32 * max(len(v), 1))(*v), len(v)
 
-        supp, n_supp = ids(pc.suppress_tokens)
-        begin, n_begin = ids(pc.begin_suppress_tokens)
-        bad, _ = ids([i for w in pc.bad_words_ids for i in w])
-        bad_len, n_bad = ids([len(w) for w in pc.bad_words_ids])
-        p = native.ProcessParams(pc.repetition_penalty, pc.no_repeat_ngram_size, pc.min_length, pc.min_new_tokens,
-                                 pc.forced_bos_token_id, pc.forced_eos_token_id, supp, n_supp, begin, n_begin, bad, bad_len, n_bad)
+            supp, n_supp = ids(pc.suppress_tokens)
+            begin, n_begin = ids(pc.begin_suppress_tokens)
+            bad, _ = ids([i for w in pc.bad_words_ids for i in w])
+            bad_len, n_bad = ids([len(w) for w in pc.bad_words_ids])
+            pp = native.ProcessParams(pc.repetition_penalty, pc.no_repeat_ngram_size, pc.min_length, pc.min_new_tokens,
+                                      pc.forced_bos_token_id, pc.forced_eos_token_id, supp, n_supp, begin, n_begin, bad, bad_len, n_bad)
+            export, params = "m2m_generate_processed", (C.byref(pp), C.byref(sp) if sp is not None else None)
+        elif sp is not None:
+            export, params = "m2m_generate_sample", (C.byref(sp),)
+        else:
+            export, params = "m2m_generate_greedy", ()
         with self._lock:
             x = inputs_embeds.to(self.transformer.device, torch.float32)
             if cfg.num_return_sequences > 1:      # HF's expansion: the n sequences of a clip are consecutive rows
                 x = x.repeat_interleave(cfg.num_return_sequences, dim=0)
             x = x.contiguous()
-            max_length = cfg.max_length
-            sess, _ = self._encode(x, max_length)
-            tokens = torch.empty((x.shape[0], max_length), dtype=torch.long, device=x.device)
+            sess, _ = self._encode(x, cfg.max_length)
+            tokens = torch.empty((x.shape[0], cfg.max_length), dtype=torch.long, device=x.device)
             out_len = C.c_int(0)
             with torch.cuda.device(x.device):
-                native.check(native.load().m2m_generate_processed(sess, max_length, C.byref(p), C.byref(sp) if sp is not None else None,
-                                                                  tokens.data_ptr(), C.byref(out_len), native.stream_handle(x.device)),
-                             "m2m_generate_processed")
+                native.check(getattr(native.load(), export)(sess, cfg.max_length, *params, tokens.data_ptr(), C.byref(out_len),
+                                                            native.stream_handle(x.device)), export)
             return tokens[:, : out_len.value]
 
     @torch.no_grad()
@@ -501,9 +477,4 @@ class T5Transformer(nn.Module):
         any other keyword raise ``NotImplementedError``."""
         cfg = resolve_generate_kwargs(kwargs, default_max_length=self._GENERATE_DEFAULT_MAX_LENGTH,
                                       vocab_size=self.geometry.vocab_size)
-        encoder_inputs = self.encoder_inputs(inputs)
-        if cfg.process is not None:
-            return self._generate_processed(encoder_inputs, cfg)
-        if cfg.do_sample:
-            return self._generate_sample(encoder_inputs, cfg)
-        return self.generate_from_embeds(encoder_inputs, max_length=cfg.max_length)
+        return self._decode(self.encoder_inputs(inputs), cfg)
