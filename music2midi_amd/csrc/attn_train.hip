@@ -267,8 +267,7 @@ __global__ __launch_bounds__(512, 2) void attn_head_fwd_kernel(HeadAttnArgs a) {
 
 // waves per workgroup for `blocks` 32-row blocks: every workgroup stages the whole head, so idle waves in the last one are pure cost
 // (9 blocks: 3 x 3 waves instead of 4 + 4 + 1)
-static int ah_waves(int blocks) {
-  static const int forced = [] { const char* v = getenv("M2M_AH_WAVES"); return v ? atoi(v) : 0; }();
+static int ah_waves(int blocks, int forced) {      // forced: TrainSwitches::ah_waves
   if (forced >= 1 && forced <= 4) return forced;
   if (blocks <= 4) return blocks;
   return (ceil_div(blocks, 3) * 3 - blocks) < (ceil_div(blocks, 4) * 4 - blocks) ? 3 : 4;
@@ -281,7 +280,7 @@ size_t attn_head_fwd_smem(int Sk, bool bias, int tab_stride) {
   return kv + bias_b > out_stage ? kv + bias_b : out_stage;
 }
 
-int launch_attn_head_fwd(const HeadAttnArgs& a, int nB, hipStream_t st) {
+int launch_attn_head_fwd(const HeadAttnArgs& a, int nB, hipStream_t st, const TrainSwitches& sw) {
   M2M_REQUIRE(a.Sq >= 1 && a.Sk >= 1 && a.Sq <= AH_MAX_S && a.Sk <= AH_MAX_S, "attn_head: sequence lengths (%d, %d) beyond %d", a.Sq, a.Sk, AH_MAX_S);
   M2M_REQUIRE(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0 && a.sQb % 8 == 0 && a.sKb % 8 == 0 && a.sVb % 8 == 0 && a.sOb % 8 == 0,
               "attn_head: operand strides must keep 16-byte alignment");
@@ -290,10 +289,9 @@ int launch_attn_head_fwd(const HeadAttnArgs& a, int nB, hipStream_t st) {
   const size_t smem = attn_head_fwd_smem(a.Sk, bias, a.tab_stride);
   M2M_REQUIRE(smem <= 78 * 1024, "attn_head: %zu bytes of LDS", smem);
   // two waves per query block (halves of the key tiles) when the head has at least two key tiles; M2M_AH_SPLIT=1 / 2 / 3 forces the count
-  static const int forced_split = [] { const char* v = getenv("M2M_AH_SPLIT"); return v ? atoi(v) : 0; }();
   const int nkt = ceil_div(a.Sk, 32);
-  const int split = std::max(1, std::min(forced_split >= 1 && forced_split <= 3 ? forced_split : 2, nkt));
-  int nw = ah_waves(ceil_div(a.Sq, 32));
+  const int split = std::max(1, std::min(sw.ah_split >= 1 && sw.ah_split <= 3 ? sw.ah_split : 2, nkt));
+  int nw = ah_waves(ceil_div(a.Sq, 32), sw.ah_waves);
   if (nw * split > 8) nw = 8 / split;
   if (split > 1 && nw > 3 && ceil_div(a.Sq, 32) % 4 != 0) nw = 3;      // (six waves, two workgroups per CU; eight when the blocks come in fours)
   HeadAttnArgs a2 = a;
@@ -637,7 +635,7 @@ size_t attn_head_bwd_smem(int Sq, int Sk, bool bias, int tab_stride) {
   return 2 * (size_t)AH_IMG * sizeof(bf16_t) + 2 * sqp * 4 + (bias ? ((size_t)2 * (tab_stride + 32) * 4 + 15) / 16 * 16 : 0);
 }
 
-int launch_attn_head_bwd(const HeadAttnArgs& a, int nB, hipStream_t st) {
+int launch_attn_head_bwd(const HeadAttnArgs& a, int nB, hipStream_t st, const TrainSwitches& sw) {
   M2M_REQUIRE(a.Sq >= 1 && a.Sk >= 1 && a.Sq <= AH_MAX_S && a.Sk <= AH_MAX_S, "attn_head: sequence lengths (%d, %d) beyond %d", a.Sq, a.Sk, AH_MAX_S);
   M2M_REQUIRE(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0 && a.lddq % 8 == 0 && a.lddk % 8 == 0 && a.lddv % 8 == 0 &&
                   a.sQb % 8 == 0 && a.sKb % 8 == 0 && a.sVb % 8 == 0 && a.sOb % 8 == 0 && a.sdQb % 8 == 0 && a.sdKb % 8 == 0 && a.sdVb % 8 == 0,
@@ -647,7 +645,7 @@ int launch_attn_head_bwd(const HeadAttnArgs& a, int nB, hipStream_t st) {
   const size_t smem = attn_head_bwd_smem(a.Sq, a.Sk, bias, a.tab_stride);
   M2M_REQUIRE(smem <= 80 * 1024, "attn_head: %zu bytes of LDS", smem);
   const int nq = ceil_div(a.Sq, 32), nk = ceil_div(a.Sk, 32);
-  const int nw = ah_waves(std::max(nq, nk));
+  const int nw = ah_waves(std::max(nq, nk), sw.ah_waves);
   dim3 grid((unsigned)ceil_div(std::max(nq, nk), nw), (unsigned)(nB * a.H));
 #define M2M_AH_BWD(C_, B_, D_)                                                                   \
   do {                                                                                           \
@@ -703,7 +701,7 @@ extern "C" int m2m_attn_head_fwd_bf16(const uint16_t* q, const uint16_t* k, cons
   a.bias_tab = bias_tab; a.tab_stride = Sq + Sk - 1; a.tab_center = Sq - 1;
   a.H = H; a.Sq = Sq; a.Sk = Sk; a.causal = causal; a.ldp = (Sk + 7) / 8 * 8;
   a.dk = DropKey{word.dev, site_salt}; a.thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u; a.scale = 1.0f / (1.0f - drop_p); a.keep_bits = keep_bits;
-  return launch_attn_head_fwd(a, B, st);
+  return launch_attn_head_fwd(a, B, st, process_train_switches());
 }
 
 extern "C" int m2m_attn_head_bwd_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* out, const float* lse, const uint16_t* d_out,
@@ -723,5 +721,5 @@ extern "C" int m2m_attn_head_bwd_bf16(const uint16_t* q, const uint16_t* k, cons
   a.bias_tab = bias_tab; a.tab_stride = Sq + Sk - 1; a.tab_center = Sq - 1; a.diag_part = diag_part;
   a.H = H; a.Sq = Sq; a.Sk = Sk; a.causal = causal; a.ldp = (Sk + 7) / 8 * 8;
   a.dk = DropKey{word.dev, site_salt}; a.thresh = drop_p > 0.f ? (uint32_t)((double)drop_p * 4294967296.0) : 0u; a.scale = 1.0f / (1.0f - drop_p); a.keep_bits = const_cast<uint32_t*>(keep_bits);
-  return launch_attn_head_bwd(a, B, st);
+  return launch_attn_head_bwd(a, B, st, process_train_switches());
 }

@@ -25,8 +25,6 @@
 
 namespace m2m {
 
-bool decode_headless();
-
 // ---- optional in-kernel wall-clock stamps (diagnostic builds only: -DM2M_STAMPS) ----
 // s_memrealtime runs at a constant 100 MHz and is the same clock on every CU, so stamps from
 // different kernels can be laid on one timeline.  Block 0 / thread 0 of every decode kernel logs
@@ -1536,7 +1534,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
   if (SELF) {
     // the k,v rows of this step: projected, rounded to T, appended to the cache and kept in LDS for the clips' own-key visits.
     // Their weights are requested only now, into the registers the q weights have left (one more L2 round trip in this workgroup's
-    // chain, which the co-resident workgroup fills: the kernel is held to 64 registers so that TWO workgroups share a CU)
+    // chain; only the M2M_MC_WAVES = 8 build, 64 registers, has a co-resident workgroup to fill it: the product build, 4 waves per
+    // SIMD and 128 registers, runs ONE workgroup per CU)
     Vec16<T> wkv[WMAX2];
 #pragma unroll
     for (int u = 0; u < WMAX2; ++u) wkv[u].v = *reinterpret_cast<const V16*>(wrow2 + (min(u, cnt2 - 1) * LPO2 + part2) * E);
@@ -1589,7 +1588,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
     const bool walks = (walk >> c) & 1u;                                          // uniform
     const unsigned cbase = BEAM ? cb(c) : (unsigned)c * clip_bytes;   // this clip inside the descriptors (an invalid tail clip walks nothing)
     // per-clip OPAQUE copies of the lane's place in a round: derived from threadIdx the hand-over offsets below are loop invariants
-    // that the compiler keeps from the prologue, spills (64 registers), and reloads in the middle of the stream - and a scratch
+    // that the compiler keeps from the prologue, spills (at the 64 registers of the M2M_MC_WAVES = 8 build), and reloads in the middle of the stream - and a scratch
     // reload waits vmcnt(0), i.e. for every round in flight
     int kslot_c = kslot, sub_c = sub;
     asm volatile("" : "+v"(kslot_c), "+v"(sub_c));
@@ -1991,12 +1990,6 @@ __global__ void dec_final_kernel(DecHeadArgs a) {
   }
   __syncthreads();
   if (threadIdx.x == 0) { st->done = 1; st->out_len = t + 1; }
-}
-
-// M2M_HEADLESS=0 keeps dec_head_kernel in the greedy loop (the round-1 step: 20 kernels); default: folded away (19 kernels)
-bool decode_headless() {
-  static const bool on = [] { const char* v = getenv("M2M_HEADLESS"); return !(v && v[0] == '0'); }();
-  return on;
 }
 
 // ========================================================== sampling head ====
@@ -2788,7 +2781,7 @@ int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int 
 // ============================================================ step driver ====
 static xq_t* xbuf(m2m_session* s, const DecView& v, int which);
 // the headless fold is a greedy-only form: the sampling and processed heads keep their own kernel (the step of M2M_HEADLESS=0)
-static bool headless_for(const m2m_session* s, bool forced) { return !forced && s->head_mode == HEAD_GREEDY && decode_headless(); }
+static bool headless_for(const m2m_session* s, bool forced) { return !forced && s->head_mode == HEAD_GREEDY && s->headless; }
 // All per-clip buffers are [B][...] with the clip index outermost, so a view is a pointer offset.
 static DecHeadArgs head_args(m2m_session* s, const DecView& v, bool forced, float* logits_out, int Ld) {
   const m2m_model* m = s->m;
@@ -2854,12 +2847,6 @@ static xq_t* xbuf(m2m_session* s, const DecView& v, int which) {
   return reinterpret_cast<xq_t*>(s->x_dec) + (size_t)which * stride + (size_t)v.b0 * s->m->g.d_model;
 }
 
-// M2M_FINISHED_SKIP=0: finished rows keep streaming their K/V (the behaviour before round 4; bench.py's ragged_eos "before" leg)
-bool decode_finished_skip_on() {
-  const char* v = getenv("M2M_FINISHED_SKIP");      // read per launch (graphs bake it at capture: the bench re-creates the session)
-  return !(v && v[0] == '0');
-}
-
 // Clips of one head per attention workgroup for a chain of nb clips: the multi-clip form (dec_attn_mc_kernel) from the chain sizes at
 // which the launches stop being single latency chains and become rounds of workgroups (measured: tools/native_chain_sweep.py, DESIGN
 // 4.3); s->attn_clips > 0 forces a value (M2M_DA_CLIPS, latched when the session is created; tests and A/B runs).
@@ -2899,9 +2886,8 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
     // ... but as many whole layers of cross K/V as fit a 180 MB budget keep the default policy and stay
     // cache-resident from step to step (they are re-read every step; the rest streams past them
     // non-temporally).  B = 32: 3 of 6 layers, 271.0 -> 266.6 ms per batch.
-    static const int forced = [] { const char* v = getenv("M2M_KV_RESIDENT_LAYERS"); return v ? atoi(v) : -1; }();
     const double per_layer = 2.0 * s->B * m->inner * (double)s->S * (double)es;
-    const int resident = forced >= 0 ? forced : (int)(180e6 / per_layer);
+    const int resident = s->kv_resident_layers >= 0 ? s->kv_resident_layers : (int)(180e6 / per_layer);
     if (layer < resident) nt = false;
   }
   int clips = decode_attn_clips(s, v.nb);
@@ -2910,7 +2896,7 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
   a.x = xbuf(s, v, self ? 0 : 1); a.x_out = xbuf(s, v, self ? 1 : 2); a.x_zero = xbuf(s, v, self ? 2 : 0);
   a.eps = g.layer_norm_eps; a.d = g.d_model;
   a.H = H; a.inner = m->inner; a.state = v.state;
-  if (skip_finished && decode_finished_skip_on()) { a.fin_skip = s->finished + v.b0; a.fin_stride = 1; }
+  if (skip_finished && s->finished_skip) { a.fin_skip = s->finished + v.b0; a.fin_stride = 1; }
   else { a.fin_skip = &v.state->zero; a.fin_stride = 0; }
   // beam search: the view's rows are clips x beam_nb beams (the view starts at a clip boundary)
   const bool beam = s->head_mode == HEAD_BEAM && s->beam_nb > 0;

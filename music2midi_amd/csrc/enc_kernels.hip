@@ -6,6 +6,7 @@
 //
 // All three are templated on the storage type T of the precision mode: float (f32-input MFMA,
 // exact fp32 FMA chains: parity mode) or bf16 (bf16 MFMA, fp32 accumulate: throughput mode).
+#include "env.h"
 #include "mma.h"
 #include "t5.h"
 
@@ -577,7 +578,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
 // Tile choice: the 128x128 kernel unless its grid is smaller than `M2M_GEMM_SMALL_BELOW` tiles (default 512 = two rounds
 // of the chip) and the epilogue is one of the plain ones; then 64x64 tiles (see the note above gemm_kernel).
 static int gemm_small_below() {
-  static const int v = [] { const char* e = getenv("M2M_GEMM_SMALL_BELOW"); return e ? atoi(e) : 512; }();
+  static const int v = env_int("M2M_GEMM_SMALL_BELOW", 512);
   return v;
 }
 
@@ -589,11 +590,11 @@ static int gemm_small_below() {
 // 128x128 tiles (18.1 -> 24.8: 96 KiB, one workgroup per CU).  So: the ring for small tiles with K >= M2M_GEMM_DMA_MINK (512),
 // the register-staged loop otherwise.  M2M_GEMM_DMA=0 / =all force one or the other; M2M_GEMM_DMA_NS1 / _NS2 pick the depths.
 static int gemm_dma_ns(int tf, int K, int tiles) {
-  static const int mode = [] { const char* e = getenv("M2M_GEMM_DMA"); return !e ? 1 : e[0] == '0' ? 0 : e[0] == 'a' ? 2 : 1; }();
-  static const int ns1 = [] { const char* e = getenv("M2M_GEMM_DMA_NS1"); return e ? atoi(e) : 4; }();
-  static const int ns2 = [] { const char* e = getenv("M2M_GEMM_DMA_NS2"); return e ? atoi(e) : 3; }();
-  static const int mink = [] { const char* e = getenv("M2M_GEMM_DMA_MINK"); return e ? atoi(e) : 512; }();
-  static const int maxt = [] { const char* e = getenv("M2M_GEMM_DMA_MAXT"); return e ? atoi(e) : 1024; }();      // (64 clips: 1 566 tiles per N = 384 product, the ring costs 1 %)
+  static const int mode = [] { const char* e = env_str("M2M_GEMM_DMA"); return !e ? 1 : e[0] == '0' ? 0 : e[0] == 'a' ? 2 : 1; }();
+  static const int ns1 = env_int("M2M_GEMM_DMA_NS1", 4);
+  static const int ns2 = env_int("M2M_GEMM_DMA_NS2", 3);
+  static const int mink = env_int("M2M_GEMM_DMA_MINK", 512);
+  static const int maxt = env_int("M2M_GEMM_DMA_MAXT", 1024);      // (64 clips: 1 566 tiles per N = 384 product, the ring costs 1 %)
   if (mode == 0) return 0;
   if (mode == 2) return tf == 1 ? ns1 : ns2;
   return (tf == 1 && K >= mink && tiles <= maxt) ? ns1 : 0;
@@ -795,7 +796,7 @@ __global__ __launch_bounds__(RP_THREADS) void resid_panel_kernel(GemmArgs g) {
 static bool resid_panel_takes(int precision, int epi, const GemmArgs& a) {
   if (precision != M2M_PREC_BF16 || epi != EPI_RESID || a.resid || a.drop_thresh) return false;
   if (!(a.N == 128 || a.N == 256 || a.N == 384) || a.K % 64 != 0 || a.K < 128 || a.ldo != a.N) return false;
-  const EncSwitches sw = enc_switches_now();
+  const EncSwitches& sw = enc_switches_now();
   if (sw.resid_panel == 1) return false;
   if (sw.resid_panel == 2) return true;
   return ceil_div(a.M, RP_BM) >= sw.min_blocks;
@@ -1142,7 +1143,7 @@ __global__ __launch_bounds__(NG_THREADS) void norm_gemm_kernel(GemmArgs g) {
 // gives 190; below M2M_NORM_GEMM_MIN_BLOCKS (default 160) the two-kernel path runs.  M2M_NORM_GEMM: "0" never, "force" whatever the
 // size (the parity tests), "e<digits>" not for the listed epilogue ids (diagnostic).  Latched per session (t5.h EncSwitches).
 static bool norm_gemm_on(int epi, int M) {
-  const EncSwitches sw = enc_switches_now();
+  const EncSwitches& sw = enc_switches_now();
   if (sw.norm_gemm == 1) return false;
   if (sw.norm_gemm_skip) return !((sw.norm_gemm_skip >> epi) & 1u);
   if (sw.norm_gemm == 2) return true;
@@ -1151,7 +1152,7 @@ static bool norm_gemm_on(int epi, int M) {
 // column groups per row block: one from a chip's worth of row blocks on (the round-5 form), else as many as keep the launch at about
 // one workgroup per CU - down to one column tile per workgroup (M2M_NORM_GEMM_SPLIT=0: never split, the two-kernel path below the gate)
 static int norm_gemm_groups(int M, int N) {
-  const EncSwitches sw = enc_switches_now();
+  const EncSwitches& sw = enc_switches_now();
   const int rb = ceil_div(M, NG_BM), ntn = ceil_div(N, NG_BN);
   if (rb >= sw.min_blocks || !sw.norm_gemm_split) return 1;
   int gq = 256 / rb;
@@ -1159,21 +1160,22 @@ static int norm_gemm_groups(int M, int N) {
   return gq > ntn ? ntn : gq;
 }
 
-// the switches as the environment has them now (a session latches the result when it is created: t5.h EncSwitches)
+// the switches as the environment has them now (a session or a trainer latches the result when it is created: t5.h EncSwitches)
 thread_local const EncSwitches* tl_enc_switches = nullptr;
 EncSwitches read_enc_switches() {
   EncSwitches sw;
-  auto tri = [](const char* name) { const char* v = getenv(name); return !v ? 0 : v[0] == '0' ? 1 : v[0] == 'f' ? 2 : 0; };
-  sw.norm_gemm = tri("M2M_NORM_GEMM");
-  if (const char* v = getenv("M2M_NORM_GEMM"))
-    if (v[0] == 'e') for (const char* c = v + 1; *c; ++c) if (*c >= '0' && *c <= '9') sw.norm_gemm_skip |= 1u << (*c - '0');
-  sw.resid_panel = tri("M2M_RESID_PANEL");
-  if (const char* e = getenv("M2M_ATTN_WIDE")) sw.attn_wide = e[0] == '0' ? 0 : 1;
-  if (const char* e = getenv("M2M_NORM_GEMM_MIN_BLOCKS")) sw.min_blocks = atoi(e);
-  sw.norm_gemm_hout = getenv("M2M_NORM_GEMM_HOUT") ? 1 : 0;
-  if (const char* e = getenv("M2M_NORM_GEMM_SPLIT")) sw.norm_gemm_split = e[0] == '0' ? 0 : 1;
+  const auto tri = [](const char* v) { return !v ? 0 : v[0] == '0' ? 1 : v[0] == 'f' ? 2 : 0; };
+  const char* ng = env_str("M2M_NORM_GEMM");
+  sw.norm_gemm = tri(ng);
+  if (ng && ng[0] == 'e') for (const char* c = ng + 1; *c; ++c) if (*c >= '0' && *c <= '9') sw.norm_gemm_skip |= 1u << (*c - '0');
+  sw.resid_panel = tri(env_str("M2M_RESID_PANEL"));
+  sw.attn_wide = env_on("M2M_ATTN_WIDE");
+  sw.min_blocks = env_int("M2M_NORM_GEMM_MIN_BLOCKS", sw.min_blocks);
+  sw.norm_gemm_hout = env_set("M2M_NORM_GEMM_HOUT");
+  sw.norm_gemm_split = env_on("M2M_NORM_GEMM_SPLIT");
   return sw;
 }
+const EncSwitches& process_enc_switches() { static const EncSwitches sw = read_enc_switches(); return sw; }
 
 int launch_norm_gemm(int precision, int epi, const GemmArgs& a_in, hipStream_t st) {
   {

@@ -20,6 +20,7 @@
 // Roofline: algorithmic HBM bytes/clip = 4*T + 4*frames*n_mels; arithmetic ~56.8 MFLOP/clip
 // (~26 flop/B, at the fp32-vector ridge) — see DESIGN.md.
 #include "common.h"
+#include "env.h"
 
 #include <algorithm>
 #include <math.h>
@@ -762,11 +763,12 @@ static size_t frontend_smem_bytes(int FR, int hop, int nnz) {
 }
 
 // Which kernel form a call (fe, B, T) launches and with what geometry: m2m_logmel_f32 launches exactly what this returns, and
-// m2m_frontend_plan reports it.  Reads M2M_FE_CHUNKS / M2M_FE_FR on every call (M2M_FE_V2 once per process).
+// m2m_frontend_plan reports it.  Reads M2M_FE_CHUNKS / M2M_FE_FR once per call, here (M2M_FE_V2 once per process).
 static int frontend_plan(const m2m_frontend* fe, int B, int T, m2m_frontend_plan_t* p, const char* fn) {
   M2M_REQUIRE(B >= 1 && B <= 65535, "%s: batch %d out of range", fn, B);
   M2M_REQUIRE(T >= fe->n_fft / 2 + 1, "%s: T=%d too short for reflect padding (need > %d)", fn, T, fe->n_fft / 2);
   const int F = 1 + T / fe->hop;
+  const int chunks_env = env_int("M2M_FE_CHUNKS", 0);      // > 0: chunks per workgroup, either form
   memset(p, 0, sizeof(*p));
   p->frames = F;
   p->n_wpad = fe->n_wpad;
@@ -777,14 +779,14 @@ static int frontend_plan(const m2m_frontend* fe, int B, int T, m2m_frontend_plan
   {
     constexpr int WAVES = 16;
     const V2Layout L = v2_layout(WAVES, fe->hop, fe->n_wpad);
-    static const bool v2_on = [] { const char* v = getenv("M2M_FE_V2"); return !(v && v[0] == '0'); }();
+    static const bool v2_on = env_on("M2M_FE_V2");
     if (v2_on && (size_t)L.total * sizeof(float) <= 160 * 1024 && L.span_pad <= V2_NPRE * 64 * WAVES && fe->n_mels <= 512) {
       const int cpc = ceil_div(F, WAVES);                              // chunks per clip
       static const int n_cu = [] { int dev = 0, n = 256; if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n > 0 ? n : 256; }();
       int per_clip = (n_cu + B / 2) / B;                               // workgroups per clip: about one per CU in total
       per_clip = per_clip < 1 ? 1 : (per_clip > cpc ? cpc : per_clip);
       int NCH = ceil_div(cpc, per_clip);
-      if (const char* v = getenv("M2M_FE_CHUNKS")) NCH = atoi(v) > 0 ? atoi(v) : NCH;
+      if (chunks_env > 0) NCH = chunks_env;
       p->form = fe->n_mels <= 384 ? M2M_FE_FORM_V2_NJ6 : M2M_FE_FORM_V2_NJ8;
       p->grid_x = ceil_div(cpc, NCH);
       p->chunks = NCH;
@@ -794,7 +796,7 @@ static int frontend_plan(const m2m_frontend* fe, int B, int T, m2m_frontend_plan
     }
   }
   // 16 frames per workgroup: waveform re-read factor 1.44 at hop 256, two workgroups per CU.
-  int FR = getenv("M2M_FE_FR") ? atoi(getenv("M2M_FE_FR")) : 16;
+  int FR = env_int("M2M_FE_FR", 16);
   M2M_REQUIRE(FR >= 1 && FR <= 64, "%s: M2M_FE_FR=%d out of range", fn, FR);
   while (FR > 4 && frontend_smem_bytes(FR, fe->hop, fe->n_wpad) > 80 * 1024) FR -= 4;      // two workgroups per CU (160 KB)
   const size_t smem = frontend_smem_bytes(FR, fe->hop, fe->n_wpad);
@@ -803,7 +805,7 @@ static int frontend_plan(const m2m_frontend* fe, int B, int T, m2m_frontend_plan
   // 2 chunks 196.0 / 112.5, 3 chunks 208.1 / 136.9: the table loads are not what bounds the kernel, so one chunk
   // (most workgroups, best balance) unless a launch has thousands of workgroups to spare.
   int NCH = ((int64_t)ceil_div(F, FR * 2) * B >= 1536) ? 2 : 1;
-  if (const char* v = getenv("M2M_FE_CHUNKS")) NCH = atoi(v) > 0 ? atoi(v) : NCH;
+  if (chunks_env > 0) NCH = chunks_env;
 #ifdef M2M_FE_TAPS_GLOBAL       // diagnostic builds only
   const bool taps_lds = false;
 #else

@@ -382,11 +382,11 @@ __global__ __launch_bounds__(256) void mxgemm_p_kernel(MxGemmArgs g) {
     }
   }
 }
-static dim3 mx_xcd_grid(MxGemmArgs& g, dim3 grid);
+static dim3 mx_xcd_grid(MxGemmArgs& g, dim3 grid, bool xcd_order);
 template <int FA, int TN>
-static int launch_mxgemm_p_ft(int epi, const MxGemmArgs& g_in, hipStream_t st) {
+static int launch_mxgemm_p_ft(int epi, const MxGemmArgs& g_in, hipStream_t st, bool xcd_order) {
   MxGemmArgs g = g_in;
-  const dim3 grid = mx_xcd_grid(g, dim3((unsigned)ceil_div(g.N, 64 * TN), (unsigned)ceil_div(g.M, 64)));
+  const dim3 grid = mx_xcd_grid(g, dim3((unsigned)ceil_div(g.N, 64 * TN), (unsigned)ceil_div(g.M, 64)), xcd_order);
   switch (epi) {
     case TG_STORE_T: hipLaunchKernelGGL((mxgemm_p_kernel<FA, TG_STORE_T, TN>), grid, dim3(256), 0, st, g); break;
     case TG_STORE_F32: hipLaunchKernelGGL((mxgemm_p_kernel<FA, TG_STORE_F32, TN>), grid, dim3(256), 0, st, g); break;
@@ -398,16 +398,15 @@ static int launch_mxgemm_p_ft(int epi, const MxGemmArgs& g_in, hipStream_t st) {
   return M2M_OK;
 }
 
-static bool mx_xcd_order() { static const bool on = [] { const char* v = getenv("M2M_XCD_ORDER"); return !(v && v[0] == '0'); }(); return on; }
-static dim3 mx_xcd_grid(MxGemmArgs& g, dim3 grid) {
-  if (!mx_xcd_order() || grid.x * grid.y < 64) return grid;
+static dim3 mx_xcd_grid(MxGemmArgs& g, dim3 grid, bool xcd_order) {
+  if (!xcd_order || grid.x * grid.y < 64) return grid;
   g.xcd_nx = (int)grid.x; g.xcd_total = (int)(grid.x * grid.y);
   return dim3((unsigned)(8 * ceil_div(g.xcd_total, 8)));
 }
 template <int FA, int TN>
-static int launch_mxgemm_q_ft(int epi, const MxGemmArgs& g_in, hipStream_t st) {
+static int launch_mxgemm_q_ft(int epi, const MxGemmArgs& g_in, hipStream_t st, bool xcd_order) {
   MxGemmArgs g = g_in;
-  const dim3 grid = mx_xcd_grid(g, dim3((unsigned)ceil_div(g.N, 64 * TN), (unsigned)ceil_div(g.M, 64)));
+  const dim3 grid = mx_xcd_grid(g, dim3((unsigned)ceil_div(g.N, 64 * TN), (unsigned)ceil_div(g.M, 64)), xcd_order);
   switch (epi) {
     case TG_STORE_T: hipLaunchKernelGGL((mxgemm_q_kernel<FA, TG_STORE_T, TN>), grid, dim3(256), 0, st, g); break;
     case TG_STORE_F32: hipLaunchKernelGGL((mxgemm_q_kernel<FA, TG_STORE_F32, TN>), grid, dim3(256), 0, st, g); break;
@@ -418,17 +417,15 @@ static int launch_mxgemm_q_ft(int epi, const MxGemmArgs& g_in, hipStream_t st) {
   M2M_CHECK_HIP(hipGetLastError());
   return M2M_OK;
 }
-template <int FA>
-static int launch_mxgemm_q_f(int epi, const MxGemmArgs& g, hipStream_t st) {
-  static const int wide_from = [] { const char* v = getenv("M2M_MXQ_WIDE_FROM"); return v ? atoi(v) : 512; }();      // N from which the 64 x 128 tile is used
-  return g.N >= wide_from ? launch_mxgemm_q_ft<FA, 2>(epi, g, st) : launch_mxgemm_q_ft<FA, 1>(epi, g, st);
-}
-int launch_mxgemm_q(int fmt_a, int epi, const MxGemmArgs& g, hipStream_t st) {
+int launch_mxgemm_q(int fmt_a, int epi, const MxGemmArgs& g, hipStream_t st, const TrainSwitches& sw) {
   M2M_REQUIRE(g.Asrc && g.M >= 1 && g.N >= 1 && g.K >= 128 && g.K % 128 == 0 && g.ldb % 128 == 0 && g.K <= g.ldb && g.Kvalid <= g.K && g.ld_src % 8 == 0 &&
                   g.Kvalid % 8 == 0 && (reinterpret_cast<uintptr_t>(g.Asrc) & 15) == 0,
               "mxgemm_q: K=%d (valid %d), ld_src=%lld, ldb=%lld", g.K, g.Kvalid, (long long)g.ld_src, (long long)g.ldb);
   M2M_REQUIRE(fmt_a == 0 || fmt_a == 1, "mxgemm_q: A format e4m3 | e5m2");
-  return fmt_a == 0 ? launch_mxgemm_q_f<0>(epi, g, st) : launch_mxgemm_q_f<1>(epi, g, st);
+  static const int wide_from = env_int("M2M_MXQ_WIDE_FROM", 512);      // N from which the 64 x 128 tile is used (library-wide: once per process)
+  const bool wide = g.N >= wide_from;
+  if (fmt_a == 0) return wide ? launch_mxgemm_q_ft<0, 2>(epi, g, st, sw.xcd_order) : launch_mxgemm_q_ft<0, 1>(epi, g, st, sw.xcd_order);
+  return wide ? launch_mxgemm_q_ft<1, 2>(epi, g, st, sw.xcd_order) : launch_mxgemm_q_ft<1, 1>(epi, g, st, sw.xcd_order);
 }
 
 // (accumulate != 0: C += the sum — a weight gradient in accumulate mode)
@@ -459,7 +456,7 @@ static int launch_mxgemm_f(int epi, const MxGemmArgs& g, hipStream_t st) {
   return M2M_OK;
 }
 
-int launch_mxgemm(int fmt_a, int fmt_b, int epi, const MxGemmArgs& g, hipStream_t st) {
+int launch_mxgemm(int fmt_a, int fmt_b, int epi, const MxGemmArgs& g, hipStream_t st, const TrainSwitches& sw) {
   M2M_REQUIRE(g.M >= 1 && g.N >= 1 && g.K >= 1 && g.K % 128 == 0 && g.lda % 128 == 0 && g.ldb % 128 == 0 && g.K <= g.lda && g.K <= g.ldb,
               "mxgemm: K=%d, lda=%lld, ldb=%lld must be multiples of 128 with K <= ld", g.K, (long long)g.lda, (long long)g.ldb);
   M2M_REQUIRE(fmt_b == 0 && (fmt_a == 0 || fmt_a == 1), "mxgemm: formats (A e4m3|e5m2, B e4m3) only");
@@ -467,11 +464,11 @@ int launch_mxgemm(int fmt_a, int fmt_b, int epi, const MxGemmArgs& g, hipStream_
   if (g.ksplit > 1) {
     M2M_REQUIRE((epi == TG_STORE_F32 || epi == TG_ACC_F32) && g.Cpart && g.kchunk % 128 == 0, "mxgemm: split-K is for plain fp32-store / fp32-accumulate products");
   }
-  static const bool plain = getenv("M2M_MXGEMM_PLAIN") != nullptr;      // diagnostic: the unprefetched 64x64 kernel
-  static const int wide_from = [] { const char* v = getenv("M2M_MXP_WIDE_FROM"); return v ? atoi(v) : 512; }();
+  static const bool plain = env_set("M2M_MXGEMM_PLAIN");      // diagnostic: the unprefetched 64x64 kernel
+  static const int wide_from = env_int("M2M_MXP_WIDE_FROM", 512);
   if (g.ksplit <= 1 && !plain) {
-    if (g.N >= wide_from) return fmt_a == 0 ? launch_mxgemm_p_ft<0, 2>(epi, g, st) : launch_mxgemm_p_ft<1, 2>(epi, g, st);
-    return fmt_a == 0 ? launch_mxgemm_p_ft<0, 1>(epi, g, st) : launch_mxgemm_p_ft<1, 1>(epi, g, st);
+    if (g.N >= wide_from) return fmt_a == 0 ? launch_mxgemm_p_ft<0, 2>(epi, g, st, sw.xcd_order) : launch_mxgemm_p_ft<1, 2>(epi, g, st, sw.xcd_order);
+    return fmt_a == 0 ? launch_mxgemm_p_ft<0, 1>(epi, g, st, sw.xcd_order) : launch_mxgemm_p_ft<1, 1>(epi, g, st, sw.xcd_order);
   }
   rc = fmt_a == 0 ? launch_mxgemm_f<0, 0>(epi, g, st) : launch_mxgemm_f<1, 0>(epi, g, st);
   if (rc != M2M_OK) return rc;
@@ -531,7 +528,7 @@ extern "C" int m2m_mx8_matmul_f32(const float* a_dev, const float* b_dev, int M,
   if (rc == M2M_OK) rc = launch_mxq_rows(0, b_dev, K, B8, SB, N, K, Kp, 0, st);
   MxGemmArgs g{};
   g.A = A8; g.B = B8; g.sA = SA; g.sB = SB; g.C = c_dev; g.M = M; g.N = N; g.K = Kp; g.lda = Kp; g.ldb = Kp; g.ldc = N;
-  if (rc == M2M_OK) rc = launch_mxgemm(a_is_e5m2 ? 1 : 0, 0, TG_STORE_F32, g, st);
+  if (rc == M2M_OK) rc = launch_mxgemm(a_is_e5m2 ? 1 : 0, 0, TG_STORE_F32, g, st, process_train_switches());
   hipError_t e = hipStreamSynchronize(st);
   (void)hipFree(buf);
   if (rc == M2M_OK && e != hipSuccess) { set_error("m2m_mx8_matmul_f32: %s", hipGetErrorString(e)); rc = M2M_ERR_HIP; }
@@ -555,10 +552,10 @@ extern "C" int m2m_mx8_matmul_bf16a(const uint16_t* a_bf16_dev, const float* b_d
   if (rc == M2M_OK) {
     if (fused) {
       g.Asrc = a_bf16_dev; g.ld_src = K; g.Kvalid = K;
-      rc = launch_mxgemm_q(a_is_e5m2 ? 1 : 0, TG_STORE_F32, g, st);
+      rc = launch_mxgemm_q(a_is_e5m2 ? 1 : 0, TG_STORE_F32, g, st, process_train_switches());
     } else {
       rc = launch_mxq_rows(1, a_bf16_dev, K, A8, SA, M, K, Kp, a_is_e5m2 ? 1 : 0, st);
-      if (rc == M2M_OK) rc = launch_mxgemm(a_is_e5m2 ? 1 : 0, 0, TG_STORE_F32, g, st);
+      if (rc == M2M_OK) rc = launch_mxgemm(a_is_e5m2 ? 1 : 0, 0, TG_STORE_F32, g, st, process_train_switches());
     }
   }
   hipError_t e = hipStreamSynchronize(st);

@@ -135,9 +135,9 @@ struct BeamRow {            // row c * nb + h: running beam h of clip c, and hyp
 namespace m2m {
 // Environment switches of the encoder-side kernel families (enc_kernels.hip), read ONCE when a session is created: they choose
 // between kernels that are not all bit-identical (the two attention forms differ in the last bits), so a session keeps the forms
-// it started with whatever the environment does later, and no launch calls getenv (not safe against a concurrent setenv).
-// The public entry points of a session put theirs in scope (EncSwitchScope); launches outside any scope (tools, the trainer's
-// products) read the environment themselves, as before.
+// it started with whatever the environment does later, and no launch reads the environment (not safe against a concurrent setenv;
+// ADVICE r5).  A trainer latches its own the same way.  The public entry points of a session and of a trainer put theirs in scope
+// (EncSwitchScope); launches outside any scope (tools, the single-product hooks) take the process-wide value, read once.
 struct EncSwitches {
   int norm_gemm = 0;            // M2M_NORM_GEMM: 0 by size, 1 never ("0"), 2 always ("force")
   unsigned norm_gemm_skip = 0;  // "e<digits>": not for the listed epilogue ids (diagnostic)
@@ -148,13 +148,14 @@ struct EncSwitches {
   int norm_gemm_split = 1;      // M2M_NORM_GEMM_SPLIT=0: below min_blocks the two-kernel path instead of the column-group form (round 6)
 };
 EncSwitches read_enc_switches();
+const EncSwitches& process_enc_switches();      // read at its first use, once per process
 extern thread_local const EncSwitches* tl_enc_switches;
 struct EncSwitchScope {
   const EncSwitches* prev;
   explicit EncSwitchScope(const EncSwitches* s) : prev(tl_enc_switches) { tl_enc_switches = s; }
   ~EncSwitchScope() { tl_enc_switches = prev; }
 };
-inline EncSwitches enc_switches_now() { return tl_enc_switches ? *tl_enc_switches : read_enc_switches(); }
+inline const EncSwitches& enc_switches_now() { return tl_enc_switches ? *tl_enc_switches : process_enc_switches(); }
 
 constexpr int MAX_GROUPS = 8;
 
@@ -215,6 +216,9 @@ struct m2m_session {
   int ff_rows = 0;         // decode feed-forward: residual rows per workgroup forced by M2M_DEC_FF_ROWS (0: by chain size)
   int ff_slices = 0;       // decode feed-forward: hidden slices per workgroup forced by M2M_DEC_FF_SLICES (0: by chain size)
   int mc_cif = 1;          // multi-clip cross-attention: clips in flight, M2M_MC_CIF (diagnostic: 2; 0 or unset: 1, the product)
+  bool headless = true;    // M2M_HEADLESS=0 keeps dec_head_kernel in the greedy loop (the round-1 step: 20 kernels); default: folded away (19 kernels)
+  bool finished_skip = true;   // M2M_FINISHED_SKIP=0: finished rows keep streaming their K/V (the behaviour before round 4; bench.py's ragged_eos "before" leg)
+  int kv_resident_layers = -1; // M2M_KV_RESIDENT_LAYERS: layers of cross K/V kept cache-resident when the rest streams non-temporally (-1: by a 180 MB budget)
   int repacks = 0, rows_moved = 0;   // live-row re-packings / rows moved by them in the last m2m_generate_greedy / _sample
   int head_mode = 0;       // head form of the free-running decode step: 0 greedy (arg-max), 1 sampling, 2 beam, | 4 processed
                            // (set for the length of a call)
@@ -318,12 +322,10 @@ int launch_checksum(const void* buf, int64_t bytes, unsigned long long* acc_dev,
 // decoder-side (decode.hip)
 int decode_init(m2m_session* s, const DecView& v, int max_steps, bool forced, hipStream_t st);
 int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* logits_out, int Ld, hipStream_t st);
-bool decode_finished_skip_on();
 int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, int self_len, hipStream_t st, bool headless = false,
                        bool skip_finished = false);
 int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int t, hipStream_t st);   // live-row re-packing (decode.hip)
 int decode_finalize(m2m_session* s, const DecView& v, hipStream_t st);   // headless greedy loop: write the last token, close the chain
-bool decode_headless();
 constexpr int HEAD_GREEDY = 0, HEAD_SAMPLE = 1, HEAD_BEAM = 2;
 constexpr int HEAD_PROCESSED = 4;        // bit: logits processors before the greedy (| 0) or sampling (| HEAD_SAMPLE) select
 constexpr int BEAM_MAX = 32;             // beams per clip: one LDS list of 2 x 32 candidates per beam, ancestries in bytes

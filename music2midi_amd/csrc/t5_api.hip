@@ -1,10 +1,12 @@
 // C ABI of the T5 encoder/decoder path: model (repacked weights), session (workspace +
 // captured decode-step graph), encode, greedy generate, teacher-forced decode, bench hooks.
+#include "env.h"
 #include "t5.h"
 
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <vector>
 
 using namespace m2m;
@@ -253,20 +255,16 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
               "m2m_session_create: max_enc_len=%d too long (attention bias table must fit LDS)", max_enc_len);
   M2M_REQUIRE((size_t)max_enc_len * 4 <= 60 * 1024 && (size_t)max_dec_len * 4 <= 60 * 1024,
               "m2m_session_create: sequence too long for the decode attention score buffer");
-  // switches of the decode path are read ONCE per session (graphs bake them in; getenv is not safe against a concurrent setenv)
-  const char* da_env = getenv("M2M_DA_CLIPS");
-  const int da_clips = (da_env && da_env[0]) ? atoi(da_env) : 0;
+  // switches of the decode path are read ONCE per session (graphs bake them in; the environment is not safe against a concurrent setenv)
+  const int da_clips = env_int("M2M_DA_CLIPS", 0);
   M2M_REQUIRE(da_clips == 0 || da_clips == 1 || da_clips == 2 || da_clips == 4,
               "M2M_DA_CLIPS=%d: clips per decode-attention workgroup must be 0 (by chain size), 1, 2 or 4", da_clips);
-  const char* ff_env = getenv("M2M_DEC_FF_ROWS");
-  const int ff_rows = (ff_env && ff_env[0]) ? atoi(ff_env) : 0;
+  const int ff_rows = env_int("M2M_DEC_FF_ROWS", 0);
   M2M_REQUIRE(ff_rows == 0 || ff_rows == 8 || ff_rows == 16, "M2M_DEC_FF_ROWS=%d: rows per decode feed-forward workgroup must be 0 (by chain size), 8 or 16", ff_rows);
-  const char* fs_env = getenv("M2M_DEC_FF_SLICES");
-  const int ff_slices = (fs_env && fs_env[0]) ? atoi(fs_env) : 0;
+  const int ff_slices = env_int("M2M_DEC_FF_SLICES", 0);
   M2M_REQUIRE(ff_slices == 0 || ff_slices == 1 || ff_slices == 2 || ff_slices == 4,
               "M2M_DEC_FF_SLICES=%d: hidden slices per decode feed-forward workgroup must be 0 (by chain size), 1, 2 or 4", ff_slices);
-  const char* cif_env = getenv("M2M_MC_CIF");
-  const int mc_cif = (cif_env && cif_env[0]) ? atoi(cif_env) : 0;
+  const int mc_cif = env_int("M2M_MC_CIF", 0);
   M2M_REQUIRE(mc_cif == 0 || mc_cif == 1 || mc_cif == 2,
               "M2M_MC_CIF=%d: clips in flight in the multi-clip cross-attention must be 0 (default: 1), 1 or 2", mc_cif);
   m2m_session* s = new m2m_session();
@@ -274,7 +272,10 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   s->ws = (unsigned char*)workspace_dev; s->ws_bytes = workspace_bytes;
   s->attn_clips = da_clips; s->ff_rows = ff_rows; s->ff_slices = ff_slices; s->mc_cif = mc_cif == 2 ? 2 : 1;
   s->enc_sw = read_enc_switches();
-  { const char* v = getenv("M2M_DA_CLIPS_SELF"); const int c = (v && v[0]) ? atoi(v) : 0; s->attn_clips_self = (c == 1 || c == 2 || c == 4) ? c : 0; }
+  { const int c = env_int("M2M_DA_CLIPS_SELF", 0); s->attn_clips_self = (c == 1 || c == 2 || c == 4) ? c : 0; }
+  s->headless = env_on("M2M_HEADLESS");
+  s->finished_skip = env_on("M2M_FINISHED_SKIP");
+  s->kv_resident_layers = env_int("M2M_KV_RESIDENT_LAYERS", -1);
   unsigned char* b = s->ws;
   s->x_enc = (float*)(b + w.x_enc); s->h_enc = b + w.h_enc; s->qkv_enc = b + w.qkv_enc; s->vt_enc = b + w.vt_enc; s->attn_enc = b + w.attn_enc;
   s->mid_enc = b + w.mid_enc; s->enc_bias_tab = (float*)(b + w.enc_bias); s->dec_bias_tab = (float*)(b + w.dec_bias);
@@ -326,27 +327,7 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   for (int i = 0; i < MAX_GROUPS && e == hipSuccess; ++i) {
     DecGroup& gr = s->groups[i];
     gr.view.state = s->states + i;
-    // M2M_CHAIN_CU_MASK=<n> (diagnostic, round 6): chain i may only use the CUs whose index within their XCD satisfies
-    // (cu * n / 32) % n == i % n, i.e. n disjoint slices of every XCD - to see whether two chains of 128-workgroup launches already
-    // land side by side on their own (they do: DESIGN 4.3)
-    const char* cm = getenv("M2M_CHAIN_CU_MASK");
-    const int nmask = (cm && cm[0]) ? atoi(cm) : 0;
-    if (nmask >= 2 && nmask <= 8) {
-      uint32_t mask[8];                                   // 256 CUs = 8 XCDs x 32; bit index = the runtime's CU numbering
-      const int mode = getenv("M2M_CHAIN_CU_MASK_MODE") ? atoi(getenv("M2M_CHAIN_CU_MASK_MODE")) : 0;
-      for (int w = 0; w < 8; ++w) {
-        mask[w] = 0;
-        for (int b = 0; b < 32; ++b) {
-          const int cu = w * 32 + b;
-          // mode 0: contiguous slices of each 32-CU group; mode 1: interleaved CUs
-          const int owner = mode == 0 ? ((b * nmask) / 32) % nmask : cu % nmask;
-          if (owner == i % nmask) mask[w] |= 1u << b;
-        }
-      }
-      e = hipExtStreamCreateWithCUMask(&gr.stream, 8, mask);
-    } else {
-      e = hipStreamCreateWithFlags(&gr.stream, hipStreamNonBlocking);
-    }
+    e = hipStreamCreateWithFlags(&gr.stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&gr.ev_done, hipEventDisableTiming);
     if (e == hipSuccess) e = hipHostMalloc((void**)&gr.state_host, sizeof(DecState), hipHostMallocDefault);
   }
@@ -437,23 +418,23 @@ extern "C" int m2m_encode(m2m_session* s, const float* inputs_embeds_dev, int B,
 }
 
 // ----------------------------------------------------------------- decode ---
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && v[0]) ? atoi(v) : dflt;
-}
-
-static bool use_graph() { return env_int("M2M_NO_GRAPH", 0) != 1; }
+// The switches tests and A/B runs flip between two calls on one session: read once at the top of a decode call, never inside it.
+struct DecodeSwitches {
+  int group_rows = env_int("M2M_GROUP_ROWS", 0);                       // clips per chain (0: plan_groups decides)
+  bool graph = env_int("M2M_NO_GRAPH", 0) != 1;                        // 1: every step launched directly
+  int graph_steps = std::max(1, env_int("M2M_GRAPH_STEPS", 8));        // decode steps per graph
+  bool compact = env_int("M2M_COMPACT", 1) != 0;                       // 0: no live-row re-packing
+};
 
 // Split the B encoded clips into independent chains: M2M_GROUP_ROWS clips per chain (default 32:
 // one 32-row MFMA tile of clips per chain), at most MAX_GROUPS chains.  Measured at B = 32 on
 // MI355X: 1 chain 322 ms, 2 chains 315 ms, 4 chains 666 ms (dispatch-bound) - see DESIGN_HISTORY.md 4.4.
-static int plan_groups(m2m_session* s, int rows = -1) {       // rows: the packed slots to decode (default: the whole encoded batch)
+static int plan_groups(m2m_session* s, int rows_env, int rows = -1) {       // rows_env: DecodeSwitches::group_rows; rows: the packed slots to decode (default: the whole encoded batch)
   // Default: TWO chains once there are enough clips to split (B >= 24), one otherwise.  Two graph chains on two
   // streams overlap one chain's latency phases (prologue, merge tail, feed-forward, lm_head / head) with the other's
   // K/V stream: B = 32 -> 2 x 16 clips is +3.7 % over one chain of 32 (tools/chain_sweep.py); more than two chains do
   // not help (the dependent-dispatch rate of the command processor becomes the limit: 4 x 8 = 1 x 32, 8 x 4 is 4x slower).
   const int nrows = rows < 0 ? s->B : rows;
-  const int rows_env = env_int("M2M_GROUP_ROWS", 0);
   int G = rows_env > 0 ? ceil_div(nrows, rows_env) : (nrows >= 24 ? 2 : 1);
   if (G < 1) G = 1;
   if (G > MAX_GROUPS) G = MAX_GROUPS;
@@ -473,7 +454,7 @@ static int plan_groups(m2m_session* s, int rows = -1) {       // rows: the packe
 // One graph = `steps` consecutive decode steps of one chain (kernels read the step index from
 // device memory, so the same graph replays for every position; steps past the end are no-ops).
 static int ensure_graph(m2m_session* s, DecGroup& gr, int steps) {
-  const int key[8] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, decode_finished_skip_on() ? 1 : 0, s->head_mode, s->beam_nb};
+  const int key[8] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, s->finished_skip ? 1 : 0, s->head_mode, s->beam_nb};
   ++gr.graph_clock;
   for (auto& ge : gr.graphs)
     if (memcmp(key, ge.key, sizeof(key)) == 0) { ge.used = gr.graph_clock; gr.graph_exec = ge.exec; return M2M_OK; }
@@ -643,13 +624,14 @@ static int decode_loop(m2m_session* s, const DecodeCall& c, int max_length, int*
   const char* fn = c.fn;
   const bool beam = c.head_mode == HEAD_BEAM;
   const int steps = max_length - 1, rows = beam ? s->B * c.beam_nb : s->B;
-  int G = plan_groups(s, rows);        // beam search: chains split at clip boundaries
-  const bool graph = use_graph();
-  const int U = env_int("M2M_GRAPH_STEPS", 8) < 1 ? 1 : env_int("M2M_GRAPH_STEPS", 8);   // decode steps per graph
+  const DecodeSwitches sw;
+  int G = plan_groups(s, sw.group_rows, rows);        // beam search: chains split at clip boundaries
+  const bool graph = sw.graph;
+  const int U = sw.graph_steps;
   // Live-row re-packing at the host polls (decode.hip "live-row re-packing"): once a quarter of the packed rows have emitted EOS the
   // live ones are moved into the first slots and smaller chains take over.  M2M_COMPACT=0: rows keep their slots (round 4).  Never in
   // beam search: a clip's beams move through each other's cache slots, so a beam call does not consume the encode.
-  const bool compact = !beam && env_int("M2M_COMPACT", 1) != 0;
+  const bool compact = !beam && sw.compact;
   int rc;
   // order every chain after whatever the caller enqueued (encode ran on the caller's stream)
   M2M_CHECK_HIP(hipEventRecord(s->ev_in, caller));
@@ -728,7 +710,7 @@ static int decode_loop(m2m_session* s, const DecodeCall& c, int max_length, int*
         M2M_CHECK_HIP(hipStreamSynchronize(st0));
         s->repacks += 1; s->rows_moved += (int)mv_src.size();
         cur_rows = live;
-        G = plan_groups(s, cur_rows);
+        G = plan_groups(s, sw.group_rows, cur_rows);
         for (int i = 0; i < G; ++i) {
           DecGroup& gr = s->groups[i];
           DecState hs{};
@@ -898,7 +880,7 @@ extern "C" int m2m_decode_forced(m2m_session* s, const int64_t* dec_input_ids_de
   hipStream_t st = (hipStream_t)stream;
   const EncSwitchScope sw_scope(&s->enc_sw);
   M2M_CHECK_HIP(hipMemcpyAsync(s->forced_ids, dec_input_ids_dev, (size_t)s->B * Ld * 8, hipMemcpyDeviceToDevice, st));
-  const char* fwd = getenv("M2M_FORWARD");          // "step": Ld KV-cached decode steps instead (read per call: tests toggle it)
+  const char* fwd = env_str("M2M_FORWARD");         // "step": Ld KV-cached decode steps instead (read per call, here only: tests toggle it on one session)
   const bool stepwise = fwd && strcmp(fwd, "step") == 0;
   if (!stepwise) return forward_batched(s, s->forced_ids, Ld, logits_out_dev, st);
   const DecView all{0, s->B, s->states};
@@ -927,7 +909,8 @@ extern "C" int m2m_bench_kernel(m2m_session* s, int which, int self_len, int ite
   const m2m_model* m = s->m;
   const int Ld = m->g.num_decoder_layers;
   hipStream_t caller = (hipStream_t)stream;
-  const int G = plan_groups(s);
+  const DecodeSwitches sw;
+  const int G = plan_groups(s, sw.group_rows);
   M2M_CHECK_HIP(hipEventRecord(s->ev_in, caller));
   for (int i = 0; i < G; ++i) M2M_CHECK_HIP(hipStreamWaitEvent(s->groups[i].stream, s->ev_in, 0));
   int rc;
@@ -958,8 +941,8 @@ extern "C" int m2m_bench_kernel(m2m_session* s, int which, int self_len, int ite
       const int layer = same_layer ? 0 : i % Ld;
       for (int c = 0; c < G; ++c) {
         const DecGroup& gr = s->groups[c];
-        if (which == M2M_KERNEL_DEC_CROSS_ATTN) { if ((rc = decode_launch_attn(s, gr.view, false, layer, 0, gr.stream, decode_headless()))) return rc; }
-        else if (which == M2M_KERNEL_DEC_SELF_ATTN) { if ((rc = decode_launch_attn(s, gr.view, true, layer, self_len, gr.stream, decode_headless()))) return rc; }
+        if (which == M2M_KERNEL_DEC_CROSS_ATTN) { if ((rc = decode_launch_attn(s, gr.view, false, layer, 0, gr.stream, s->headless))) return rc; }
+        else if (which == M2M_KERNEL_DEC_SELF_ATTN) { if ((rc = decode_launch_attn(s, gr.view, true, layer, self_len, gr.stream, s->headless))) return rc; }
       }
     }
     return M2M_OK;
@@ -990,13 +973,13 @@ extern "C" int m2m_bench_kernel(m2m_session* s, int which, int self_len, int ite
     // (t advances by `iters` from self_len - 1, so self-attention lengths are the real ones)
     M2M_REQUIRE(self_len - 1 + iters < s->max_dec, "m2m_bench_kernel: self_len + iters exceeds max_dec_len");
     const int U = 1;
-    for (int i = 0; i < G; ++i) if (use_graph() && (rc = ensure_graph(s, s->groups[i], U))) return rc;
+    for (int i = 0; i < G; ++i) if (sw.graph && (rc = ensure_graph(s, s->groups[i], U))) return rc;
     M2M_CHECK_HIP(hipEventRecord(e0, caller));
     for (int i = 0; i < G; ++i) M2M_CHECK_HIP(hipStreamWaitEvent(s->groups[i].stream, e0, 0));
     for (int k = 0; k < iters; ++k)
       for (int i = 0; i < G; ++i) {
         DecGroup& gr = s->groups[i];
-        if (use_graph()) M2M_CHECK_HIP(hipGraphLaunch(gr.graph_exec, gr.stream));
+        if (sw.graph) M2M_CHECK_HIP(hipGraphLaunch(gr.graph_exec, gr.stream));
         else if ((rc = decode_launch_step(s, gr.view, false, nullptr, 0, gr.stream))) return rc;
       }
     for (int i = 0; i < G; ++i) {

@@ -2,10 +2,52 @@
 #pragma once
 
 #include "common.h"
+#include "env.h"
+
+#include <string.h>
 
 namespace m2m {
 
 enum { TG_STORE_T = 0, TG_STORE_F32 = 1, TG_ACC_F32 = 2, TG_RESID_F32 = 3 };
+
+// Environment switches of the training path.  CONSTRUCTING one reads the environment — every member's initialiser is the one
+// read of its switch — and that happens at two places: m2m_trainer holds one (sw), so a trainer latches them when it is created,
+// keeps the kernel forms it started with (its graphs bake them in) and no pass or launch reads the environment; and the entry
+// points without a trainer (the single-product test hooks) share process_train_switches().  The launchers below take the struct
+// from their caller.  The one switch of the training path that is NOT here is M2M_TRAIN_ATTN: read per pass (train.hip, Ops::head_on).
+struct TrainSwitches {
+  struct Fp8Parts { bool fwd = true, dx = true, dw = false; };
+  static Fp8Parts fp8_parts(const char* p) { return p ? Fp8Parts{strstr(p, "fwd") != nullptr, strstr(p, "dx") != nullptr, strstr(p, "dw") != nullptr} : Fp8Parts{}; }
+  static int fuse_mode(const char* v) { return !v ? 3 : v[0] == '0' ? 0 : v[0] == 'f' ? 1 : v[0] == 'b' ? 2 : 3; }
+  static bool is(const char* v, const char* word) { return v && strcmp(v, word) == 0; }
+  static bool starts(const char* v, char c) { return v && v[0] == c; }
+  bool side = env_on("M2M_TRAIN_SIDE");                  // 0: everything on the caller's stream
+  bool graph = env_on("M2M_TRAIN_GRAPH");                // 0: no graph replay, every pass issued directly
+  bool graph_caller = env_on("M2M_TRAIN_GRAPH_CALLER");  // 0: an unsplit graph replays on the trainer's own stream
+  bool dw_group = env_on("M2M_TRAIN_DW_GROUP");          // 0: a launch per weight gradient instead of the grouped one (bf16 / fp32 modes)
+  bool tail_side = env_on("M2M_TRAIN_TAIL_SIDE");        // 0: the small reductions of the tail stay on the main stream
+  Fp8Parts fp8 = fp8_parts(env_str("M2M_FP8_PARTS"));    // subset of fwd,dx,dw: which projection products run on MXFP8 (see m2m_trainer)
+  int grad_fmt = is(env_str("M2M_FP8_GRAD"), "e5m2");    // element format of the gradient operands: 0 = e4m3 (default), 1 = e5m2
+  bool fp8_fused_q = env_on("M2M_FP8_FUSED_Q");          // 0: activations through the separate row quantiser
+  bool tuned_gemm = !env_set("M2M_TRAIN_PLAIN_GEMM");    // set (diagnostic): everything through bgemm
+  int dw_kmajor = env_int("M2M_TRAIN_DW_KMAJOR", -1);    // -1 = by size, 0 / 1 = forced
+  bool dw_old = env_set("M2M_TRAIN_DW_OLD");             // set: the split-K bgemm weight gradient
+  bool dw_tr = env_on("M2M_DW_TR");                      // 0: the register-transposing tile of the grouped launch
+  int dw_xcd = env_int("M2M_DW_XCD", 1);                 // 0: the grouped launch in plain workgroup order
+  int dw_tile = env_int("M2M_DW_TILE", 0);               // 64 / 128 (diagnostic): tile of launch_dw_gemm
+  int dw_wgs = env_int("M2M_DW_WGS", 512);               // workgroups launch_dw_gemm aims for
+  bool gate_epi = env_on("M2M_TRAIN_GATE_EPI");          // 0: gated_fwd / gated_bwd kernel launches
+  bool stripes = env_on("M2M_TRAIN_STRIPES");            // 0: no fused scores + softmax
+  int fuse_pv = fuse_mode(env_str("M2M_TRAIN_FUSE_PV")); // 0 = off, 1 / 2 = only the forward ("fwd") / backward ("bwd") pass (diagnostics), 3 = both
+  bool pair_dvdk = env_on("M2M_TRAIN_PAIR_DVDK");        // 0: dV and dK in launches of their own
+  bool fwd_pd = starts(env_str("M2M_TRAIN_FWD_PD"), '1');  // 1: always write the dropped copy of P (measurement)
+  bool fuse_pd = env_on("M2M_TRAIN_FUSE_PD");            // 0: the dropped P through redrop
+  bool st_slim = env_on("M2M_ST_SLIM");                  // 0: never five stripe workgroups per CU
+  bool xcd_order = env_on("M2M_XCD_ORDER");              // 0: plain grids for bgemm, the stripe kernels and the MXFP8 products
+  int ah_waves = env_int("M2M_AH_WAVES", 0);             // 1..4: waves per whole-head attention workgroup (0: by size)
+  int ah_split = env_int("M2M_AH_SPLIT", 0);             // 1..3: waves per query block of the forward kernel (0: two)
+};
+inline const TrainSwitches& process_train_switches() { static const TrainSwitches sw; return sw; }      // read at its first use, once per process
 
 // C[z][M,N] (op)= alpha * A[z][M,K] . B[z][N,K]^T ; z = (b1, b2)
 struct BGemmArgs {
@@ -38,7 +80,7 @@ struct BGemmArgs {
 };
 
 
-int launch_bgemm(int precision, int epi, const BGemmArgs& g, hipStream_t st);
+int launch_bgemm(int precision, int epi, const BGemmArgs& g, hipStream_t st, const TrainSwitches& sw);
 
 // MXFP8 product (mx8.hip): C[M,N] (epi)= A[M,K] . B[N,K]^T, block-scaled fp8 operands (32 elements along K per E8M0 scale)
 struct MxGemmArgs {
@@ -62,8 +104,8 @@ struct MxGemmArgs {
   // workgroups, column tile fastest, so the column tiles of a row block share its rows in ONE XCD's L2; 0: plain 2-D grid
   int xcd_total, xcd_nx;
 };
-int launch_mxgemm(int fmt_a, int fmt_b, int epi, const MxGemmArgs& g, hipStream_t st);      // fmt: 0 = e4m3, 1 = e5m2
-int launch_mxgemm_q(int fmt_a, int epi, const MxGemmArgs& g, hipStream_t st);               // A quantised in the product's own staging
+int launch_mxgemm(int fmt_a, int fmt_b, int epi, const MxGemmArgs& g, hipStream_t st, const TrainSwitches& sw);      // fmt: 0 = e4m3, 1 = e5m2
+int launch_mxgemm_q(int fmt_a, int epi, const MxGemmArgs& g, hipStream_t st, const TrainSwitches& sw);               // A quantised in the product's own staging
 int launch_mxq_rows(int src_kind, const void* src, int64_t ld_s, uint8_t* q, uint8_t* sc, int R, int C, int Cp, int fmt, hipStream_t st);
 int launch_mxq_cols(int src_kind, const void* src, int64_t ld_s, uint8_t* qt, uint8_t* sc, int R, int C, int Rp, int fmt, hipStream_t st);
 
@@ -90,8 +132,8 @@ struct HeadAttnArgs {
                                // is kept.  The forward pass hashes once and writes them; both backward orientations read them instead of hashing again.
 };
 constexpr int AH_MAX_S = 288;  // rows an LDS image holds (9 blocks of 32): 36 KB per [S, 64] bf16 operand, two images + tables per workgroup, two workgroups per CU
-int launch_attn_head_fwd(const HeadAttnArgs& a, int nB, hipStream_t st);
-int launch_attn_head_bwd(const HeadAttnArgs& a, int nB, hipStream_t st);
+int launch_attn_head_fwd(const HeadAttnArgs& a, int nB, hipStream_t st, const TrainSwitches& sw);
+int launch_attn_head_bwd(const HeadAttnArgs& a, int nB, hipStream_t st, const TrainSwitches& sw);
 
 // Adafactor plan (device tables built once per trainer)
 struct AfTensor {

@@ -175,10 +175,9 @@ __global__ __launch_bounds__(256) void bgemm_kernel(BGemmArgs g) {
 }
 
 template <typename T>
-static int launch_bgemm_t(int epi, const BGemmArgs& g_in, hipStream_t st) {
+static int launch_bgemm_t(int epi, const BGemmArgs& g_in, hipStream_t st, bool xcd) {
   BGemmArgs g = g_in;
   dim3 grid((unsigned)ceil_div(g.N, TG_BN), (unsigned)ceil_div(g.M, TG_BM), (unsigned)(g.ksplit > 1 ? g.ksplit : g.nb1 * g.nb2 * (g.A2 ? 2 : 1)));
-  static const bool xcd = [] { const char* v = getenv("M2M_XCD_ORDER"); return !(v && v[0] == '0'); }();
   if (xcd && (int64_t)grid.x * grid.y * grid.z >= 64 && (int64_t)grid.x * grid.y * grid.z < (1 << 30)) {
     g.xcd_nx = (int)grid.x; g.xcd_ny = (int)grid.y; g.xcd_total = (int)(grid.x * grid.y * grid.z);
     grid = dim3((unsigned)(8 * ceil_div(g.xcd_total, 8)));
@@ -470,19 +469,17 @@ __global__ __launch_bounds__(256) void dw_group_kernel(const DwProb* __restrict_
 // C = A^T . B with the split chosen here: enough workgroups to fill the chip, as few k-slices as that allows (every slice
 // writes and re-reads an fp32 image of C).
 int launch_dw_gemm(int precision, const void* A, int64_t lda, int N1, const void* B, int64_t ldb, int N2, int K, float* C, int64_t ldc,
-                   float* kpart, int64_t kpart_floats, hipStream_t st, int accumulate) {
+                   float* kpart, int64_t kpart_floats, hipStream_t st, int accumulate, const TrainSwitches& sw) {
   const int E = precision == M2M_PREC_BF16 ? 8 : 4, BK = precision == M2M_PREC_BF16 ? 64 : 32;
   M2M_REQUIRE(N1 % E == 0 && N2 % E == 0 && lda % E == 0 && ldb % E == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(B) & 15) == 0,
               "dw_gemm: operands must be 16-byte aligned with row lengths that are multiples of %d", E);
-  static const int force_tf = [] { const char* v = getenv("M2M_DW_TILE"); return v ? atoi(v) : 0; }();      // 64 / 128: diagnostic
-  static const int target = [] { const char* v = getenv("M2M_DW_WGS"); return v ? atoi(v) : 512; }();
   const int t128 = ceil_div(N1, 128) * ceil_div(N2, 128);
-  const int tf = force_tf == 64 ? 1 : 2;   // 128x128 measured faster for every weight shape of the model (16 clips: 8.80 vs 9.90 ms per step)
+  const int tf = sw.dw_tile == 64 ? 1 : 2;   // 128x128 measured faster for every weight shape of the model (16 clips: 8.80 vs 9.90 ms per step)
   (void)t128;
   const int bt = 64 * tf;
   const int tiles = ceil_div(N1, bt) * ceil_div(N2, bt);
-  int ks = ceil_div(target, tiles);
+  int ks = ceil_div(sw.dw_wgs, tiles);
   if (ks > 32) ks = 32;
   while (ks > 1 && ((int64_t)ks * N1 * N2 > kpart_floats || K / ks < 2 * BK)) --ks;
   DwGemmArgs g{};
@@ -645,7 +642,7 @@ __global__ __launch_bounds__(64) void mxq_weights_kernel(const W8Tile* __restric
   }
 }
 
-int launch_bgemm(int precision, int epi, const BGemmArgs& g, hipStream_t st) {
+int launch_bgemm(int precision, int epi, const BGemmArgs& g, hipStream_t st, const TrainSwitches& sw) {
   const int E = precision == M2M_PREC_BF16 ? 8 : 4;
   M2M_REQUIRE(g.M >= 1 && g.N >= 1 && g.K >= 1 && g.nb1 >= 1 && g.nb2 >= 1, "bgemm: empty problem");
   M2M_REQUIRE(g.lda % E == 0 && g.ldb % E == 0, "bgemm: operand row strides (%lld, %lld) must be multiples of %d elements (16-byte rows)",
@@ -659,7 +656,7 @@ int launch_bgemm(int precision, int epi, const BGemmArgs& g, hipStream_t st) {
   if (g.ksplit > 1) {
     M2M_REQUIRE(g.nb1 == 1 && g.nb2 == 1 && (epi == TG_STORE_F32 || epi == TG_ACC_F32) && g.Cpart && g.kchunk % TG_BK_MAX == 0,
                 "bgemm: split-K is for plain fp32-store / fp32-accumulate products");
-    int rc = precision == M2M_PREC_BF16 ? launch_bgemm_t<bf16_t>(epi, g, st) : launch_bgemm_t<float>(epi, g, st);
+    int rc = precision == M2M_PREC_BF16 ? launch_bgemm_t<bf16_t>(epi, g, st, sw.xcd_order) : launch_bgemm_t<float>(epi, g, st, sw.xcd_order);
     if (rc != M2M_OK) return rc;
     const int64_t n = (int64_t)g.M * g.N;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), dim3(256), 0, st, g.Cpart,
@@ -667,7 +664,7 @@ int launch_bgemm(int precision, int epi, const BGemmArgs& g, hipStream_t st) {
     M2M_CHECK_HIP(hipGetLastError());
     return M2M_OK;
   }
-  return precision == M2M_PREC_BF16 ? launch_bgemm_t<bf16_t>(epi, g, st) : launch_bgemm_t<float>(epi, g, st);
+  return precision == M2M_PREC_BF16 ? launch_bgemm_t<bf16_t>(epi, g, st, sw.xcd_order) : launch_bgemm_t<float>(epi, g, st, sw.xcd_order);
 }
 
 // ============================================================ element / row kernels ====
@@ -1205,12 +1202,11 @@ __global__ __launch_bounds__(256, SLIM ? 5 : 4) void attn_stripe_kernel(StripeAr
 }
 
 template <typename T>
-static int launch_attn_stripe(bool bwd, const StripeArgs& a_in, int nB, hipStream_t st) {
+static int launch_attn_stripe(bool bwd, const StripeArgs& a_in, int nB, hipStream_t st, const TrainSwitches& sw) {
   StripeArgs a = a_in;
   dim3 grid((unsigned)ceil_div(a.Sq, 32), (unsigned)(nB * a.H));
   a.n_stripes = (int)grid.x;
-  static const bool xcd = [] { const char* v = getenv("M2M_XCD_ORDER"); return !(v && v[0] == '0'); }();
-  if (xcd && grid.x * grid.y >= 64) {
+  if (sw.xcd_order && grid.x * grid.y >= 64) {
     a.xcd_total = (int)(grid.x * grid.y);
     grid = dim3((unsigned)(8 * ceil_div(a.xcd_total, 8)));
   }
@@ -1219,9 +1215,8 @@ static int launch_attn_stripe(bool bwd, const StripeArgs& a_in, int nB, hipStrea
   const size_t row_bytes = (size_t)32 * (ceil_div(a.Sk, 32) * 32 + 16 / sizeof(T)) * sizeof(T);
   const size_t smem = bias_bytes + row_bytes * ((!bwd && drop && a.Pd) ? 2 : 1);      // forward with a dropped copy of P wanted in memory: two row blocks
   // five workgroups per CU when that turns two rounds into one (and their LDS fits): see SLIM above
-  static const bool slim_on = [] { const char* v = getenv("M2M_ST_SLIM"); return !(v && v[0] == '0'); }();
   const int64_t n_wgs = (int64_t)a.n_stripes * nB * a.H;
-  const bool slim = slim_on && sizeof(T) == 2 && n_wgs > 4 * 256 && n_wgs <= 5 * 256 && 5 * (smem + 1024) <= 160 * 1024;
+  const bool slim = sw.st_slim && sizeof(T) == 2 && n_wgs > 4 * 256 && n_wgs <= 5 * 256 && 5 * (smem + 1024) <= 160 * 1024;
 #define M2M_ST_LAUNCH(B_, D_, I_)                                                                              \
   do {                                                                                                         \
     if (slim) {                                                                                                \
@@ -2095,11 +2090,11 @@ struct m2m_trainer {
   int tab_S = -1, tab_L = -1;            // geometry the bucket tables on the device were built for
   // fp8 mode (M2M_PREC_FP8): storage type stays bf16, the projection products run on MXFP8 (mx8.hip)
   bool fp8 = false;
-  // which projection products run on MXFP8 (M2M_FP8_PARTS = subset of fwd,dx,dw).  Default: forward and dX; the weight gradients
-  // take the grouped bf16 launch — on fp8 they need two transposing quantiser launches + a split-K product + a reduce EACH
-  // (16 clips: 8.9 ms per step against 7.5 ms), for the least accuracy-critical third of the products
-  bool fp8_fwd = true, fp8_dx = true, fp8_dw = false;
-  int grad_fmt = 0;                      // element format of the gradient operands: 0 = e4m3 (default), 1 = e5m2 (M2M_FP8_GRAD=e5m2)
+  // sw.fp8.fwd / fp8_dx / fp8_dw: which projection products run on MXFP8 (M2M_FP8_PARTS = subset of fwd,dx,dw).  Default: forward
+  // and dX; the weight gradients take the grouped bf16 launch — on fp8 they need two transposing quantiser launches + a split-K
+  // product + a reduce EACH (16 clips: 8.9 ms per step against 7.5 ms), for the least accuracy-critical third of the products
+  TrainSwitches sw;                      // every environment switch of the trainer, latched by m2m_trainer_create
+  EncSwitches enc_sw;                    // ... and those of the encoder-side kernels its passes launch (put in scope by m2m_train_forward_backward)
   struct LinW { int64_t off; int N, K, Np; int64_t q, qs, qt, qts; };
   std::vector<LinW> lin;                 // every projection matrix (fused groups), by parameter offset
   uint8_t* w8 = nullptr;                 // fp8 weights, both layouts, + scales
@@ -2124,7 +2119,6 @@ struct m2m_trainer {
   // (or, in fp8 mode, on the side stream while the main stream moves on), so nothing may be overwritten before.
   enum { K_DXT = 0, K_DAB, K_DQKV, K_DCQ, K_DCKV, K_KINDS };
   std::vector<void*> ring[K_KINDS];
-  bool use_group = true;                 // one grouped weight-gradient launch per step (bf16 / fp32 modes)
   void* dw_probs_dev = nullptr;          // DwProb tables on the device: [N_SLOTS + 1 table slots][2 phases][128 entries] (see GraphSlot)
   int dw_tiles = 0;
   int64_t drel_slot_floats = 0;          // one self-attention layer's per-stripe diagonal sums (t->drel holds Le + Ld of them, then the scratch)
@@ -2138,7 +2132,6 @@ struct m2m_trainer {
   // streams / graph of the step (trainer-owned: the caller's stream may be the legacy default stream, which cannot capture)
   hipStream_t s_main = nullptr, s_side = nullptr;
   hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_ready = nullptr, ev_free[2] = {nullptr, nullptr};
-  bool use_side = true, use_graph = true;
   int64_t* labels_buf = nullptr;
   int64_t* cond_buf = nullptr;
   float* loss_dev = nullptr;
@@ -2437,11 +2430,8 @@ struct Ops {
   m2m_trainer* t;
   hipStream_t st;
   const float* P;      // master parameters (fp32)
-  bool use_tuned = getenv("M2M_TRAIN_PLAIN_GEMM") == nullptr;   // diagnostic switch: everything through bgemm
-  int dw_kmajor = getenv("M2M_TRAIN_DW_KMAJOR") ? atoi(getenv("M2M_TRAIN_DW_KMAJOR")) : -1;   // -1 = by size, 0 / 1 = forced
   const T* W(int64_t off) const { return (t->precision == M2M_PREC_BF16 ? reinterpret_cast<const T*>(t->Wc) : reinterpret_cast<const T*>(P)) + off; }
 
-  static bool mxq_fused() { static const bool on = [] { const char* v = getenv("M2M_FP8_FUSED_Q"); return !(v && v[0] == '0'); }(); return on; }
   // fp8 mode: the projection matrix that starts at parameter offset `off`, or null (lm_head, non-projection operands)
   const m2m_trainer::LinW* lin8(int64_t off) const {
     if (!t->fp8) return nullptr;
@@ -2553,8 +2543,8 @@ struct Ops {
       M2M_CHECK_HIP(hipMemcpy(tab_dev, probs.data(), bytes, hipMemcpyHostToDevice));
       tab_host.assign(reinterpret_cast<const unsigned char*>(probs.data()), reinterpret_cast<const unsigned char*>(probs.data()) + bytes);
     }
-    static const bool tr_reads = [] { const char* v = getenv("M2M_DW_TR"); return !(v && v[0] == '0'); }();      // 0: the register-transposing tile
-    static const int xcd_order = [] { const char* v = getenv("M2M_DW_XCD"); return v ? atoi(v) : 1; }();
+    const bool tr_reads = t->sw.dw_tr;
+    const int xcd_order = t->sw.dw_xcd;
     const int grid = xcd_order ? 8 * ceil_div(tiles, 8) : tiles;
     if (t->precision == M2M_PREC_BF16 && tr_reads)
       hipLaunchKernelGGL((dw_group_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, st, (const DwProb*)tab_dev, (int)probs.size(), tiles, xcd_order);
@@ -2572,24 +2562,24 @@ struct Ops {
     g.A = A; g.B = B; g.C = C; g.R = R; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.a_kmajor = akm; g.b_kmajor = bkm;
     g.nb1 = 1; g.nb2 = 1; g.alpha = 1.0f;
     if (dropping(drop_site)) { g.drop_thresh = t->drop_thresh; g.drop_scale = t->drop_scale; g.drop_key = key(drop_site).salt; g.drop_step = t->step_key_dev; }
-    if (!akm && !bkm && t->fp8 && t->fp8_fwd) {          // a forward projection Y = X . W^T on MXFP8 operands
+    if (!akm && !bkm && t->fp8 && t->sw.fp8.fwd) {          // a forward projection Y = X . W^T on MXFP8 operands
       const int64_t off = reinterpret_cast<const T*>(B) - W(0);
       if (const m2m_trainer::LinW* w = lin8(off)) {
         MxGemmArgs m{};
         m.A = t->q8a; m.sA = t->s8a; m.B = t->w8 + w->q; m.sB = t->w8 + w->qs; m.C = C; m.R = R; m.M = M; m.N = N; m.K = K;
         m.lda = K; m.ldb = K; m.ldc = ldc; m.drop_thresh = g.drop_thresh; m.drop_scale = g.drop_scale; m.drop_key = g.drop_key; m.drop_step = g.drop_step;
-        if (mxq_fused() && K % 128 == 0 && lda % 8 == 0) {      // activations quantised inside the product's staging: one launch
+        if (t->sw.fp8_fused_q && K % 128 == 0 && lda % 8 == 0) {      // activations quantised inside the product's staging: one launch
           m.Asrc = A; m.ld_src = lda; m.Kvalid = K;
-          return launch_mxgemm_q(0, epi, m, st);
+          return launch_mxgemm_q(0, epi, m, st, t->sw);
         }
         int rc = launch_mxq_rows(1, A, lda, t->q8a, t->s8a, M, K, K, 0, st);
         if (rc != M2M_OK) return rc;
-        return launch_mxgemm(0, 0, epi, m, st);
+        return launch_mxgemm(0, 0, epi, m, st, t->sw);
       }
     }
     // dense NT products with K % 64 == 0 go through the inference path's tuned kernel (128x128 tiles, register-prefetched
     // staging, XCD-aware tile order): every forward projection and every dX product qualifies
-    if (!akm && !bkm && K % 64 == 0 && lda == K && ldb == K && use_tuned) {
+    if (!akm && !bkm && K % 64 == 0 && lda == K && ldb == K && t->sw.tuned_gemm) {
       GemmArgs a{};
       a.A = A; a.W = B; a.M = M; a.N = N; a.K = K; a.out = C; a.ldo = (int)ldc; a.vt_which = -1;
       if (epi == TG_STORE_T) return launch_gemm(t->precision, EPI_STORE, a, st);
@@ -2598,7 +2588,7 @@ struct Ops {
       a.resid = R; a.drop_thresh = g.drop_thresh; a.drop_scale = g.drop_scale; a.drop_key = g.drop_key; a.drop_step = g.drop_step;
       return launch_gemm(t->precision, EPI_RESID, a, st);
     }
-    return launch_bgemm(t->precision, epi, g, st);
+    return launch_bgemm(t->precision, epi, g, st, t->sw);
   }
   // gradient entering a (possibly dropped) branch, in the GEMM-input type
   int cvt_branch(const float* src, void* dst, int64_t n, int site) const {
@@ -2615,7 +2605,7 @@ struct Ops {
     BGemmArgs g{};
     g.A = A; g.B = B; g.C = C; g.R = nullptr; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.a_kmajor = akm; g.b_kmajor = bkm;
     g.nb1 = nB; g.nb2 = t->g.num_heads; g.sA1 = sA1; g.sA2 = sA2; g.sB1 = sB1; g.sB2 = sB2; g.sC1 = sC1; g.sC2 = sC2; g.alpha = 1.0f;
-    return launch_bgemm(t->precision, epi, g, st);
+    return launch_bgemm(t->precision, epi, g, st, t->sw);
   }
   // two products of one shape in one launch (BGemmArgs pair mode): (A, B) -> C and (A2, B2) -> C2; A / A2 and C / C2 share strides
   int mmbh2(int epi, const T* A, const T* A2, int64_t lda, int akm, int64_t sA1, int64_t sA2, const T* B, int64_t ldb, int64_t sB1, int64_t sB2,
@@ -2625,21 +2615,21 @@ struct Ops {
     g.A = A; g.B = B; g.C = C; g.R = nullptr; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.a_kmajor = akm; g.b_kmajor = bkm;
     g.nb1 = nB; g.nb2 = t->g.num_heads; g.sA1 = sA1; g.sA2 = sA2; g.sB1 = sB1; g.sB2 = sB2; g.sC1 = sC1; g.sC2 = sC2; g.alpha = 1.0f;
     g.A2 = A2; g.B2 = B2; g.C2 = C2; g.ldb2 = ldb2; g.sB1_2 = sB1_2; g.sB2_2 = sB2_2;
-    return launch_bgemm(t->precision, epi, g, st);
+    return launch_bgemm(t->precision, epi, g, st, t->sw);
   }
   // dX[M, Kw] (epi) = dY[M, Nw] . W   for a weight stored [Nw][Kw]: an NT product against the transposed copy WT [Kw][Nw]
   int dX(int epi, const void* dY, int64_t ldy, int64_t w_off, int Nw, int Kw, void* C, int64_t ldc, int M) const {
-    if (const m2m_trainer::LinW* w = t->fp8_dx ? lin8(w_off) : nullptr) {    // fp8 mode: dY in e5m2 (gradient format), W^T in e4m3
+    if (const m2m_trainer::LinW* w = t->sw.fp8.dx ? lin8(w_off) : nullptr) {    // fp8 mode: dY in e5m2 (gradient format), W^T in e4m3
       MxGemmArgs m{};
       m.A = t->q8a; m.sA = t->s8a; m.B = t->w8 + w->qt; m.sB = t->w8 + w->qts; m.C = C; m.M = M; m.N = Kw; m.K = w->Np;
       m.lda = w->Np; m.ldb = w->Np; m.ldc = ldc;
-      if (mxq_fused() && Nw % 8 == 0 && ldy % 8 == 0) {
+      if (t->sw.fp8_fused_q && Nw % 8 == 0 && ldy % 8 == 0) {
         m.Asrc = dY; m.ld_src = ldy; m.Kvalid = Nw;
-        return launch_mxgemm_q(t->grad_fmt, epi, m, st);
+        return launch_mxgemm_q(t->sw.grad_fmt, epi, m, st, t->sw);
       }
-      int rc = launch_mxq_rows(1, dY, ldy, t->q8a, t->s8a, M, Nw, w->Np, t->grad_fmt, st);
+      int rc = launch_mxq_rows(1, dY, ldy, t->q8a, t->s8a, M, Nw, w->Np, t->sw.grad_fmt, st);
       if (rc != M2M_OK) return rc;
-      return launch_mxgemm(t->grad_fmt, 0, epi, m, st);
+      return launch_mxgemm(t->sw.grad_fmt, 0, epi, m, st, t->sw);
     }
     return mm(epi, dY, ldy, 0, reinterpret_cast<const T*>(t->WT) + w_off, Nw, 0, C, ldc, M, Kw, Nw);
   }
@@ -2665,9 +2655,9 @@ struct Ops {
     return M2M_OK;
   }
   int dW_on(hipStream_t st, const void* dY, int64_t ldy, int Ny, const void* X, int64_t ldx, int Kx, float* Gout, int M) const {
-    if (Gbase && t->fp8_dw && lin8(Gout - Gbase)) {      // fp8 mode: dY^T (e5m2) . X^T (e4m3), blocks along the M rows
+    if (Gbase && t->sw.fp8.dw && lin8(Gout - Gbase)) {      // fp8 mode: dY^T (e5m2) . X^T (e4m3), blocks along the M rows
       const int Mp8 = (int)align_up(M, 128);
-      int rc = launch_mxq_cols(1, dY, ldy, t->q8ta, t->s8ta, M, Ny, Mp8, t->grad_fmt, st);
+      int rc = launch_mxq_cols(1, dY, ldy, t->q8ta, t->s8ta, M, Ny, Mp8, t->sw.grad_fmt, st);
       if (rc == M2M_OK) rc = launch_mxq_cols(1, X, ldx, t->q8tb, t->s8tb, M, Kx, Mp8, 0, st);
       if (rc != M2M_OK) return rc;
       MxGemmArgs m{};
@@ -2677,18 +2667,17 @@ struct Ops {
       if (ks > 32) ks = 32;
       while (ks > 1 && ((int64_t)ks * Ny * Kx > t->kpart_floats || Mp8 / ks < 128)) --ks;
       if (ks > 1) { m.kchunk = (int)align_up(ceil_div(Mp8, ks), 128); m.ksplit = ceil_div(Mp8, m.kchunk); m.Cpart = t->kpart; }
-      return launch_mxgemm(t->grad_fmt, 0, gacc ? TG_ACC_F32 : TG_STORE_F32, m, st);
+      return launch_mxgemm(t->sw.grad_fmt, 0, gacc ? TG_ACC_F32 : TG_STORE_F32, m, st, t->sw);
     }
     // (the generic kernel's k-major staging — 2-byte LDS scatters — and the transpose-then-NT route it replaced cost
     //  ~30 us per weight gradient at 16 clips; M2M_TRAIN_DW_OLD=1 keeps them for comparison)
-    static const bool old_path = getenv("M2M_TRAIN_DW_OLD") != nullptr;
     const int Ealign = t->precision == M2M_PREC_BF16 ? 8 : 4;
-    if (!old_path && Ny % Ealign == 0 && Kx % Ealign == 0 && ldy % Ealign == 0 && ldx % Ealign == 0)
-      return launch_dw_gemm(t->precision, dY, ldy, Ny, X, ldx, Kx, M, Gout, Kx, t->kpart, t->kpart_floats, st, gacc);
+    if (!t->sw.dw_old && Ny % Ealign == 0 && Kx % Ealign == 0 && ldy % Ealign == 0 && ldx % Ealign == 0)
+      return launch_dw_gemm(t->precision, dY, ldy, Ny, X, ldx, Kx, M, Gout, Kx, t->kpart, t->kpart_floats, st, gacc, t->sw);
     const int Mp = (int)align_up(M, 8);
     BGemmArgs g{};
     g.C = Gout; g.M = Ny; g.N = Kx; g.K = M; g.ldc = Kx; g.nb1 = 1; g.nb2 = 1; g.alpha = 1.0f;
-    if (dw_kmajor == 1 || (dw_kmajor < 0 && M < 8192)) {
+    if (t->sw.dw_kmajor == 1 || (t->sw.dw_kmajor < 0 && M < 8192)) {
       g.A = dY; g.B = X; g.lda = ldy; g.ldb = ldx; g.a_kmajor = 1; g.b_kmajor = 1;
     } else {
       hipLaunchKernelGGL((transpose_kernel<T, T>), dim3(ceil_div(Ny, 64), ceil_div(Mp, 64)), dim3(256), 0, st, (const T*)dY, ldy, (T*)t->tA, (int64_t)Mp, M, Ny, Mp);
@@ -2701,7 +2690,7 @@ struct Ops {
     if (ks > 32) ks = 32;
     while (ks > 1 && ((int64_t)ks * Ny * Kx > t->kpart_floats || ceil_div(M, ks) < 64)) --ks;
     if (ks > 1) { g.ksplit = ks; g.kchunk = (int)align_up(ceil_div(M, ks), TG_BK_MAX); g.ksplit = ceil_div(M, g.kchunk); g.Cpart = t->kpart; }
-    return launch_bgemm(t->precision, gacc ? TG_ACC_F32 : TG_STORE_F32, g, st);
+    return launch_bgemm(t->precision, gacc ? TG_ACC_F32 : TG_STORE_F32, g, st, t->sw);
   }
   int cvt(const float* src, void* dst, int64_t n) const { return launch_cvt(t->precision, src, dst, n, st); }
   // (A row-complete residual product that carries the next sub-layer's RMSNorm in its epilogue — 32 whole rows per workgroup, the
@@ -2745,8 +2734,9 @@ struct Ops {
     return M2M_OK;
   }
   // Whole-head attention kernels (attn_train.hip): bf16 storage, both lengths within an LDS image.  M2M_TRAIN_ATTN=stripes keeps round 2's path.
-  static bool head_on() { const char* v = getenv("M2M_TRAIN_ATTN"); return !(v && v[0] == 's'); }      // (read per pass: tests run both paths in one process)
-  bool head_ok(int Sq, int Sk) const { return sizeof(T) == 2 && head_on() && use_tuned && Sq <= AH_MAX_S && Sk <= AH_MAX_S; }
+  // (the one switch of the trainer read per pass, not at create: tests/test_train_gpu.py runs both paths on trainers that exist already)
+  static bool head_on() { const char* v = env_str("M2M_TRAIN_ATTN"); return !(v && v[0] == 's'); }
+  bool head_ok(int Sq, int Sk) const { return sizeof(T) == 2 && head_on() && t->sw.tuned_gemm && Sq <= AH_MAX_S && Sk <= AH_MAX_S; }
   HeadAttnArgs head_args(const void* Q, int64_t ldq, int64_t sQb, const void* K, int64_t ldk, const void* V, int64_t ldv, int64_t sKb, void* O, float* lse,
                          int Sq, int Sk, const float* tab, int causal, int site, void* keep_bits) const {
     HeadAttnArgs a{};
@@ -2761,9 +2751,8 @@ struct Ops {
     return a;
   }
   // Fused scores + softmax (attn_stripe_kernel) when a wave can hold all keys; K = (key, d) operand, Q = (query, d) operand.
-  static bool stripes_on() { static const bool on = [] { const char* v = getenv("M2M_TRAIN_STRIPES"); return !(v && v[0] == '0'); }(); return on; }
   bool stripe_ok(int Sk) const {      // the bias row + (two, with dropout) 32-row blocks of P must fit the LDS
-    return stripes_on() && Sk <= 32 * ST_NT && 2 * (size_t)32 * (ceil_div(Sk, 32) * 32 + 8) * sizeof(T) + 8192 <= 158 * 1024;
+    return t->sw.stripes && Sk <= 32 * ST_NT && 2 * (size_t)32 * (ceil_div(Sk, 32) * 32 + 8) * sizeof(T) + 8192 <= 158 * 1024;
   }
   // K | V of a layer ([rows, ld], K at column 0 and V at column `inner` of `kv`) -> kt [2][nB*H][64][Sp]
   int kv_transpose(const T* kv, int64_t ld, void* kt, int nB, int S) const {
@@ -2775,9 +2764,6 @@ struct Ops {
     return M2M_OK;
   }
   // M2M_TRAIN_FUSE_PV: 0 = off, fwd / bwd = only that pass (diagnostics), default both
-  static int fuse_mode() { static const int m = [] { const char* v = getenv("M2M_TRAIN_FUSE_PV"); return !v ? 3 : v[0] == '0' ? 0 : v[0] == 'f' ? 1 : v[0] == 'b' ? 2 : 3; }(); return m; }
-  static bool fuse_on() { return fuse_mode() != 0; }
-  static bool pair_on() { static const bool on = [] { const char* v = getenv("M2M_TRAIN_PAIR_DVDK"); return !(v && v[0] == '0'); }(); return on; }
   // Xt / O: the fused product of the stripe kernel (StripeArgs), or null
   int attn_probs(const T* K, int64_t ldk, int64_t sK1, int64_t sK2, const T* Q, int64_t ldq, int64_t sQ1, int64_t sQ2, void* Pm, int nB, int Sq, int Sk,
             int ldp, const float* tab, int causal, int site, const T** Puse, const T* Xt = nullptr, void* O = nullptr, int64_t ldo = 0, int64_t sO1 = 0,
@@ -2785,14 +2771,13 @@ struct Ops {
     const bool dr = dropping(site);
     StripeArgs a{};
     a.X = K; a.ldx = ldk; a.sX1 = sK1; a.sX2 = sK2; a.Y = Q; a.ldy = ldq; a.sY1 = sQ1; a.sY2 = sQ2;
-    static const bool keep_pd = [] { const char* v = getenv("M2M_TRAIN_FWD_PD"); return v && v[0] == '1'; }();      // 1: always write the dropped copy (measurement)
-    a.P = Pm; a.Pd = (dr && (keep_pd || !(Xt && O))) ? t->dS : nullptr;      // fused P.V: the dropped copy never leaves the kernel
+    a.P = Pm; a.Pd = (dr && (t->sw.fwd_pd || !(Xt && O))) ? t->dS : nullptr;      // fused P.V: the dropped copy never leaves the kernel
     a.bias_tab = tab; a.tab_stride = Sq + Sk - 1; a.tab_center = Sq - 1;
     a.H = t->g.num_heads; a.Sq = Sq; a.Sk = Sk; a.ldp = ldp; a.causal = causal;
     a.dk = dr ? key(site) : DropKey{nullptr, 0}; a.thresh = dr ? t->drop_thresh : 0u; a.scale = t->drop_scale;
     a.Xt = Xt; a.xt_ld = align_up(Sk, 32); a.O = O; a.ldo = ldo; a.sO1 = sO1; a.sO2 = sO2;
     *Puse = dr ? (const T*)t->dS : (const T*)Pm;
-    return launch_attn_stripe<T>(false, a, nB, st);
+    return launch_attn_stripe<T>(false, a, nB, st, t->sw);
   }
   // Fused dP + softmax backward: V = (key, d) operand, dO = (query, d) operand; dS out
   int dscores(const T* V, int64_t ldv, int64_t sV1, int64_t sV2, const T* dO, int64_t ldo, int64_t sO1, int64_t sO2, const void* Pm, void* dS, int nB,
@@ -2807,7 +2792,7 @@ struct Ops {
     a.diag_part = want_diag ? drel_slot() : nullptr;
     a.Xt = Xt; a.xt_ld = align_up(Sk, 32); a.O = Out; a.ldo = ld_out; a.sO1 = s1_out; a.sO2 = s2_out;
     a.dk = dr ? key(site) : DropKey{nullptr, 0}; a.thresh = dr ? t->drop_thresh : 0u; a.scale = t->drop_scale;
-    return launch_attn_stripe<T>(true, a, nB, st);
+    return launch_attn_stripe<T>(true, a, nB, st, t->sw);
   }
   // P (kept for the backward) and, with dropout, the dropped copy the P.V product reads (scratch: t->dS); returns it through *Puse
   int softmax(const float* sc, void* Pm, int nB, int Sq, int Sk, int ldp, const float* tab, int causal, int site, const T** Puse) const {
@@ -2822,7 +2807,6 @@ struct Ops {
   // backward: the dropped probabilities again (into t->dS, consumed by the dV product before dS overwrites it)
   // (into_sc: the dropped copy goes to the fp32 score scratch, unused on the stripe path, so that it survives the dS written later
   //  and dV can share a launch with dK)
-  static bool pd_fuse_on() { static const bool on = [] { const char* v = getenv("M2M_TRAIN_FUSE_PD"); return !(v && v[0] == '0'); }(); return on; }
   int redrop(const void* Pm, int64_t n, int site, const T** Puse, bool into_sc = false) const {
     if (!dropping(site)) { *Puse = (const T*)Pm; return M2M_OK; }
     T* dst = into_sc ? (T*)t->sc : (T*)t->dS;
@@ -2911,13 +2895,13 @@ int attn_self_fwd(const Ops<T>& o, const float* x_in, float* x_out, int64_t ln, 
   if (lse && o.head_ok(S, S)) {                                  // whole-head kernel: no P, no K^T | V^T, only O and the row log-sum-exp
     const HeadAttnArgs a = o.head_args(q, 3 * inner, (int64_t)S * 3 * inner, q + inner, 3 * inner, q + 2 * inner, 3 * inner, (int64_t)S * 3 * inner, ao, lse, S, S,
                                        tab, causal, site0 + PL_PROBS_SELF, Pm);
-    RC(launch_attn_head_fwd(a, nB, o.st));
+    RC(launch_attn_head_fwd(a, nB, o.st, o.t->sw));
     RC(o.mm_resid(ao, wo, x_out, M, d, inner, x_in, site0 + PL_SELF_OUT));
     return M2M_OK;
   }
   const T* Pu;
-  const bool fuse = o.stripe_ok(S) && o.fuse_on() && kt;         // P . V inside the stripe kernel, against the transposed V
-  const bool fuse_pv = fuse && (o.fuse_mode() & 1);
+  const bool fuse = o.stripe_ok(S) && t->sw.fuse_pv && kt;         // P . V inside the stripe kernel, against the transposed V
+  const bool fuse_pv = fuse && (t->sw.fuse_pv & 1);
   const T* vt = (const T*)kt + (int64_t)nB * H * DK * align_up(S, 32);
   // (K^T | V^T from the projection's own epilogue was built twice in round 3 — the tile staged through LDS, then the transpose taken
   //  from the matrix core with the operands swapped — and both cost the projection as much as these launches take: 64-byte row
@@ -2961,7 +2945,7 @@ int attn_self_bwd(const Ops<T>& o, const float* x_in, const float* dx_out, float
     a.dQ = (bf16_t*)dq; a.dK = (bf16_t*)(dq + inner); a.dV = (bf16_t*)(dq + 2 * inner);
     a.lddq = a.lddk = a.lddv = 3 * inner; a.sdQb = a.sdKb = a.sdVb = sQ1;
     a.diag_part = buckets ? o.drel_slot() : nullptr;
-    RC(launch_attn_head_bwd(a, nB, o.st));
+    RC(launch_attn_head_bwd(a, nB, o.st, o.t->sw));
     if (buckets) RC(o.bias_grad_stripes(buckets, G + bias_off, nB, S, S, bias_accumulate));
     RC(o.dW(dq, 3 * inner, 3 * inner, h, d, d, G + wqkv, M));                                     // dWqkv = dqkv^T . h
     RC(o.dX(TG_STORE_F32, dq, 3 * inner, wqkv, 3 * inner, d, t->dh, d, M));                       // dh = dqkv . Wqkv
@@ -2970,12 +2954,12 @@ int attn_self_bwd(const Ops<T>& o, const float* x_in, const float* dx_out, float
     return M2M_OK;
   }
   const T* Pu;
-  const bool pair = o.stripe_ok(S) && o.pair_on();            // dV and dK in one launch (after dS exists)
-  const bool pd_fused = pair && o.dropping(site0 + PL_PROBS_SELF) && o.pd_fuse_on();      // the stripe kernel re-emits the dropped P itself
+  const bool pair = o.stripe_ok(S) && t->sw.pair_dvdk;            // dV and dK in one launch (after dS exists)
+  const bool pd_fused = pair && o.dropping(site0 + PL_PROBS_SELF) && t->sw.fuse_pd;      // the stripe kernel re-emits the dropped P itself
   if (pd_fused) Pu = (const T*)t->sc;
   else RC(o.redrop(Pm, (int64_t)nB * H * S * ldp, site0 + PL_PROBS_SELF, &Pu, pair));
   if (!pair) RC(o.mmbh(TG_STORE_T, Pu, ldp, 1, sP1, sP2, dO, inner, 1, sO1, DK, dq + 2 * inner, 3 * inner, sQ1, DK, nB, S, DK, S));  // dV = Pd^T dO
-  const bool fuse = o.stripe_ok(S) && (o.fuse_mode() & 2) && kt;  // dQ = dS . K inside the stripe kernel, against the transposed K
+  const bool fuse = o.stripe_ok(S) && (t->sw.fuse_pv & 2) && kt;  // dQ = dS . K inside the stripe kernel, against the transposed K
   if (o.stripe_ok(S)) {
     RC(o.dscores(q + 2 * inner, 3 * inner, sQ1, DK, dO, inner, sO1, DK, Pm, t->dS, nB, S, S, ldp, site0 + PL_PROBS_SELF, buckets != nullptr,   // dS from dPd = dO V^T
                  fuse ? (const T*)kt : nullptr, dq, 3 * inner, sQ1, DK, buckets == t->dbucket ? 1 : 0, pd_fused ? t->sc : nullptr));
@@ -3006,8 +2990,7 @@ int ff_fwd(const Ops<T>& o, const float* x_in, float* x_out, int64_t ln, int64_t
   RC(o.norm(x_in, ln, h, M));
   // the gate product with the activation in its epilogue (bf16, grids the 128x128 tile takes anyway): a | b and
   // mid = dropout(gelu_new(a) * b) leave the product together — the gated_fwd_kernel launch and its read of the pair are gone
-  static const bool gate_epi = [] { const char* v = getenv("M2M_TRAIN_GATE_EPI"); return !(v && v[0] == '0'); }();
-  if (gate_epi && !t->fp8 && o.use_tuned && t->Wil && gemm_takes_gated_train(t->precision, M, 2 * dff, d)) {
+  if (t->sw.gate_epi && !t->fp8 && t->sw.tuned_gemm && t->Wil && gemm_takes_gated_train(t->precision, M, 2 * dff, d)) {
     GemmArgs a{};
     a.A = h; a.W = reinterpret_cast<const T*>(t->Wil) + wi; a.M = M; a.N = 2 * dff; a.K = d; a.out = mid; a.ldo = dff; a.ab_out = ab; a.vt_which = -1;
     if (o.dropping(site0 + PL_MID)) { a.drop_thresh = t->drop_thresh; a.drop_scale = t->drop_scale; a.drop_key = o.key(site0 + PL_MID).salt; a.drop_step = t->step_key_dev; }
@@ -3030,8 +3013,7 @@ int ff_bwd(const Ops<T>& o, const float* x_in, const float* dx_out, float* dx_in
   RC(o.dW(t->dxT, d, d, mid, dff, dff, G + wo, M));                                               // dWo = dx^T . mid
   // dmid = dx . Wo, turned into the gate pair's gradient by the product's own epilogue where it can (bf16): dmid is never stored,
   // the gated_bwd_kernel launch and its reads are gone
-  static const bool gate_epi = [] { const char* v = getenv("M2M_TRAIN_GATE_EPI"); return !(v && v[0] == '0'); }();
-  if (gate_epi && !t->fp8 && o.use_tuned && gemm_takes_gated_bwd(t->precision, M, dff, d)) {
+  if (t->sw.gate_epi && !t->fp8 && t->sw.tuned_gemm && gemm_takes_gated_bwd(t->precision, M, dff, d)) {
     GemmArgs a{};
     a.A = t->dxT; a.W = reinterpret_cast<const T*>(t->WT) + wo; a.M = M; a.N = dff; a.K = d; a.out = t->dab; a.ldo = 2 * dff; a.ab_out = const_cast<void*>(ab);
     a.vt_which = -1;
@@ -3140,7 +3122,7 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
   o.Gbase = G;
   o.gacc = G && (t->gmode & m2m_trainer::GM_ACC) ? 1 : 0;
   const bool scaled = G && (t->gmode & m2m_trainer::GM_SCALED);
-  o.group = G && t->use_group && !(t->fp8 && t->fp8_dw);
+  o.group = G && t->sw.dw_group && !(t->fp8 && t->sw.fp8.dw);
   o.st2 = (G && !o.group) ? st_side : nullptr;
   int rc;
   // (the bucket tables of this geometry are on the device already: ensure_tables())
@@ -3191,8 +3173,8 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
     RC(launch_embed_rows(t->dec_in, P + t->o_shared, t->xd[0], Md, d, V, g.pad_token_id, st));
   }
   const int64_t sPc1 = (int64_t)H * L * lps, sPc2 = (int64_t)L * lps;
-  const bool fuse_c = o.stripe_ok(S) && o.fuse_on();       // cross-attention: P . V and dQ = dS . K inside the stripe kernels
-  const bool fuse_c_pv = fuse_c && (o.fuse_mode() & 1), fuse_c_dq = fuse_c && (o.fuse_mode() & 2);
+  const bool fuse_c = o.stripe_ok(S) && t->sw.fuse_pv;       // cross-attention: P . V and dQ = dS . K inside the stripe kernels
+  const bool fuse_c_pv = fuse_c && (t->sw.fuse_pv & 1), fuse_c_dq = fuse_c && (t->sw.fuse_pv & 2);
   for (int l = 0; l < Ld; ++l) {
     const DecOff& e = t->dec[l];
     RC(attn_self_fwd<T>(o, t->xd[3 * l], t->xd[3 * l + 1], e.ln0, e.qkv, e.o, t->h0d[l], t->qkvd[l], t->Pd[l], t->aod[l], B, L, t->dtab, 1,
@@ -3208,7 +3190,7 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
     if (head_c) {
       const HeadAttnArgs a = o.head_args(cq, inner, (int64_t)L * inner, ckv, 2 * inner, ckv + inner, 2 * inner, (int64_t)S * 2 * inner, t->aocd[l], t->lse_c[l], L, S,
                                          nullptr, 0, SITE_DEC + 16 * l + PL_PROBS_CROSS, t->Pcd[l]);
-      RC(launch_attn_head_fwd(a, B, o.st));
+      RC(launch_attn_head_fwd(a, B, o.st, o.t->sw));
     } else if (o.stripe_ok(S)) {
       if (fuse_c) RC(o.kv_transpose(ckv, 2 * inner, t->ktc[l], B, S));          // serves P . V here and dQ = dS . K in the backward pass
       RC(o.attn_probs(ckv, 2 * inner, (int64_t)S * 2 * inner, DK, cq, inner, (int64_t)L * inner, DK, t->Pcd[l], B, L, S, lps, nullptr, 0,
@@ -3271,11 +3253,11 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
       a.dO = (const bf16_t*)dO;
       a.dQ = (bf16_t*)dcq; a.lddq = inner; a.sdQb = sQ1;
       a.dK = (bf16_t*)dckv; a.dV = (bf16_t*)(dckv + inner); a.lddk = a.lddv = 2 * inner; a.sdKb = a.sdVb = sK1;
-      RC(launch_attn_head_bwd(a, B, o.st));
+      RC(launch_attn_head_bwd(a, B, o.st, o.t->sw));
     }
     if (!head_cb) {
-      const bool pair_c = o.stripe_ok(S) && o.pair_on();
-      const bool pd_fused_c = pair_c && o.dropping(SITE_DEC + 16 * l + PL_PROBS_CROSS) && o.pd_fuse_on();
+      const bool pair_c = o.stripe_ok(S) && t->sw.pair_dvdk;
+      const bool pd_fused_c = pair_c && o.dropping(SITE_DEC + 16 * l + PL_PROBS_CROSS) && t->sw.fuse_pd;
       if (pd_fused_c) Pu = (const T*)t->sc;
       else RC(o.redrop(t->Pcd[l], (int64_t)B * H * L * lps, SITE_DEC + 16 * l + PL_PROBS_CROSS, &Pu, pair_c));
       if (!pair_c) RC(o.mmbh(TG_STORE_T, Pu, lps, 1, sPc1, sPc2, dO, inner, 1, sQ1, DK, dckv + inner, 2 * inner, sK1, DK, B, S, DK, L));      // dV = Pd^T dO
@@ -3345,8 +3327,7 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
   // The tail of the pass is a set of reductions that do not depend on one another: the grouped weight-gradient launch (0.35 ms,
   // seven rounds of workgroups) and a handful of small ones — conditioning-embedding rows, the norm-weight column sums, the
   // relative-position-bias reductions (~90 us as a chain).  The small ones go to the side stream and run beside the big launch.
-  static const bool tail_side = [] { const char* v = getenv("M2M_TRAIN_TAIL_SIDE"); return !(v && v[0] == '0'); }();
-  const bool fork = o.group && st_side && tail_side;
+  const bool fork = o.group && st_side && t->sw.tail_side;
   hipStream_t small = fork ? st_side : st;
   if (fork) {
     M2M_CHECK_HIP(hipEventRecord(t->ev_ready, st));
@@ -3407,21 +3388,16 @@ extern "C" int m2m_trainer_create(const m2m_t5_geometry* geom, int n_cond, const
   // Gradient operands: e4m3 by default — with a scale per 32 elements the range of e5m2 is not needed, and its third
   // mantissa bit halves the noise every backward product adds (measured on the full model, per-tensor gradient cosine
   // against the fp32 oracle: e5m2 median 0.931 / min 0.908; e4m3: see tests/test_train_gpu.py).  M2M_FP8_GRAD=e5m2 selects e5m2.
-  t->grad_fmt = (getenv("M2M_FP8_GRAD") && strcmp(getenv("M2M_FP8_GRAD"), "e5m2") == 0) ? 1 : 0;
-  if (const char* parts = getenv("M2M_FP8_PARTS")) {
-    t->fp8_fwd = strstr(parts, "fwd") != nullptr; t->fp8_dx = strstr(parts, "dx") != nullptr; t->fp8_dw = strstr(parts, "dw") != nullptr;
-  }
+  // every environment switch the trainer obeys is read here, once: t->sw by its constructor above (M2M_TRAIN_ATTN apart: Ops::head_on)
+  t->enc_sw = read_enc_switches();
   t->max_batch = max_batch; t->max_enc = max_enc_len; t->max_dec = max_dec_len;
   t->cond_rows.assign(cond_rows, cond_rows + n_cond);
   build_layout(t);
   int rc = build_arena(t);
   if (rc == M2M_OK) rc = build_optimizer(t);
   if (rc != M2M_OK) { m2m_trainer_destroy(t); return rc; }
-  // streams / events of the step (M2M_TRAIN_SIDE=0: everything on the caller's stream; M2M_TRAIN_GRAPH=0: no graph replay)
-  { const char* v = getenv("M2M_TRAIN_SIDE"); t->use_side = !(v && v[0] == '0'); }
-  { const char* v = getenv("M2M_TRAIN_GRAPH"); t->use_graph = !(v && v[0] == '0'); }
-  { const char* v = getenv("M2M_TRAIN_DW_GROUP"); t->use_group = !(v && v[0] == '0'); }
-  if (t->use_side) {
+  // streams / events of the step
+  if (t->sw.side) {
     hipError_t e = hipStreamCreateWithFlags(&t->s_main, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&t->s_side, hipStreamNonBlocking);
     hipEvent_t* evs[] = {&t->ev_in, &t->ev_out, &t->ev_ready, &t->ev_free[0], &t->ev_free[1], &t->ev_mid};
@@ -3526,11 +3502,12 @@ extern "C" int m2m_train_forward_backward(m2m_trainer* t, const float* params_de
   M2M_REQUIRE(B >= 1 && B <= t->max_batch && S > t->n_cond && S <= t->max_enc && Ld >= 1 && Ld <= t->max_dec,
               "m2m_train_forward_backward: (B=%d, S=%d, Ld=%d) outside the trainer's (%d, %d, %d)", B, S, Ld, t->max_batch, t->max_enc, t->max_dec);
   hipStream_t caller = (hipStream_t)stream;
+  const EncSwitchScope sw_scope(&t->enc_sw);
   int rc = ensure_tables(t, S, Ld, caller);
   if (rc != M2M_OK) return rc;
-  const bool two = grads_dev && t->use_side && t->s_main && t->s_side;
+  const bool two = grads_dev && t->sw.side && t->s_main && t->s_side;
   // split pass: the stream that carries the decoder-side gradient all-reduce waits for ev_mid, recorded where those gradients are final
-  const bool split = grads_dev && t->sync_stream && t->ev_mid && t->use_group && !(t->fp8 && t->fp8_dw);
+  const bool split = grads_dev && t->sync_stream && t->ev_mid && t->sw.dw_group && !(t->fp8 && t->sw.fp8.dw);
   hipStream_t work = two ? t->s_main : caller;
   const std::function<int()> release = [t, work]() -> int {
     M2M_CHECK_HIP(hipEventRecord(t->ev_mid, work));
@@ -3570,7 +3547,7 @@ extern "C" int m2m_train_forward_backward(m2m_trainer* t, const float* params_de
   slot.calls += 1;
   slot.last_use = ++t->tick;
   t->cur_slot = si;
-  if (t->use_graph && slot.calls >= 2 && !slot.gexec) {                    // second call with this key: capture
+  if (t->sw.graph && slot.calls >= 2 && !slot.gexec) {                    // second call with this key: capture
     // a split pass becomes TWO graphs: the capture is closed and reopened where the decoder-side gradients are final, and the
     // replay records ev_mid between the two launches
     hipGraphExec_t first = nullptr;
@@ -3617,8 +3594,7 @@ extern "C" int m2m_train_forward_backward(m2m_trainer* t, const float* params_de
   // A replayed graph that is not split is launched straight on the CALLER's stream: the inputs were staged there, the loss copy and the
   // optimizer follow there, so neither hand-over event (ev_in / ev_out: a cross-stream dependency on each side of every step) is needed.
   // M2M_TRAIN_GRAPH_CALLER=0: on the trainer's own stream, as the directly issued and the split passes run.
-  static const bool graph_on_caller = [] { const char* v = getenv("M2M_TRAIN_GRAPH_CALLER"); return !(v && v[0] == '0'); }();
-  if (slot.gexec && !split && !release_at_end && graph_on_caller) {
+  if (slot.gexec && !split && !release_at_end && t->sw.graph_caller) {
     M2M_CHECK_HIP(hipGraphLaunch(slot.gexec, caller));
     M2M_CHECK_HIP(hipMemcpyAsync(loss_out_dev, t->loss_dev, 4, hipMemcpyDeviceToDevice, caller));
     if (logits_out_dev)

@@ -177,7 +177,7 @@ print("CHILD OK")
 
 
 def test_vocab_size_through_the_head_kernel():
-    """M2M_HEADLESS=0 (latched per process: a child) decodes every case above through dec_head_kernel: the register batch of 512
+    """M2M_HEADLESS=0 (latched when a session is created; set for a child process) decodes every case above through dec_head_kernel: the register batch of 512
     columns and the loop over the rest, its tie-break, the special ids."""
     env = dict(os.environ, M2M_HEADLESS="0", OMP_NUM_THREADS="8")
     r = subprocess.run([sys.executable, "-c", _CHILD], env=env, capture_output=True, text=True, timeout=600)

@@ -369,7 +369,7 @@ def _large_window_check(precision):
 
 # The writers a 16-clip step reaches besides the default grouped launch (full 128 x 128 tiles of dw_tile_tr): the per-product
 # split-K weight gradients and per-norm / per-layer reductions (M2M_TRAIN_DW_GROUP=0), the MXFP8 split-K weight gradients
-# (M2M_FP8_PARTS=fwd,dx,dw), and the split-K bgemm fallback (M2M_TRAIN_DW_OLD, latched per process: run in a child).
+# (M2M_FP8_PARTS=fwd,dx,dw), and the split-K bgemm fallback (M2M_TRAIN_DW_OLD, latched when a trainer is created; set for a child).
 @pytest.mark.parametrize("precision,env", [("bf16", {}), ("fp32", {}), ("bf16", {"M2M_TRAIN_DW_GROUP": "0"}),
                                            ("fp8", {"M2M_FP8_PARTS": "fwd,dx,dw"}), ("fp8", {})])
 def test_large_window_every_gradient_writer_adds(precision, env, monkeypatch):

@@ -146,7 +146,7 @@ print("IDS", ",".join(str(int(v)) for v in ids.flatten().tolist()), *ids.shape)
 
 def test_seed_reproduces_ids_across_kernel_forms(monkeypatch):
     """Same torch.manual_seed -> identical ids, whether rows are re-packed or not, whatever the chain split, the attention form or
-    the greedy head fold (M2M_HEADLESS is latched per process: a child process).  Another seed changes the ids."""
+    the greedy head fold (M2M_HEADLESS is latched when a session is created; set for a child process).  Another seed changes the ids."""
     model, _, g = build_ragged("fp32")
     x = embeds(40, 40, g.d_model, seed=4)
     monkeypatch.setenv("M2M_COMPACT", "1")

@@ -160,7 +160,7 @@ print("STATS", stats[0], stats[1], int(torch.equal(on, off)), int(torch.equal(on
 def test_repacking_on_a_larger_session_and_with_the_head_kernel(big, B, S, L, headless):
     """decode_move_rows takes the self-cache layer stride from max_batch and the cross plane stride from the encoded B —
     covered here with a session created larger than the batch it decodes (encode B = 9 on a 33-clip session), and the re-packing
-    path with dec_head_kernel kept in the loop (M2M_HEADLESS=0 is latched per process: a child process), where the moved residual
+    path with dec_head_kernel kept in the loop (M2M_HEADLESS=0 is latched when a session is created; set for a child process), where the moved residual
     row is what the next step reads."""
     env = dict(os.environ, M2M_HEADLESS=headless)
     env.pop("M2M_COMPACT", None)
