@@ -312,6 +312,25 @@ int m2m_generate_processed(m2m_session* s, int max_length, const m2m_process_par
                            int64_t* tokens_out_dev, int* out_len_host, void* stream);
 
 /*
+ * The same decode with per-token outputs (hf: generate(return_dict_in_generate=True, output_scores=True) and
+ * compute_transition_scores(normalize_logits=True)).  proc == NULL: no logits processor; sample == NULL: the arg-max (ids equal to
+ * m2m_generate_greedy's); both follow m2m_generate_processed / m2m_generate_sample otherwise.  For the token clip c selects at
+ * step t (column t + 1 of its token row), written while the row is in registers for the select:
+ *   scores_out_dev   (optional) [max_length - 1, B, V] fp32: the row the token was selected from, as HF appends it to `scores` -
+ *                    the raw logits (greedy), the logits after the processors, or after processors, temperature, top-k and top-p
+ *                    with the removed entries at -inf (sampling);
+ *   logprobs_out_dev (optional) [B, max_length - 1] fp32: log_softmax(that row)[token].  Asked for alone, no V-wide row is written.
+ * Both are zeroed on `stream` first; a row that finished before step t (it emits pad) writes nothing and stays 0 - HF runs the
+ * model on finished rows and returns their logits.  The outputs follow the clip, not its slot: the live-row re-packing and the
+ * chain split do not change them.  With both outputs NULL this is the matching unscored export.  Checks and error codes are those
+ * of m2m_generate_processed (when proc is given) and m2m_generate_sample (when sample is given); a vocabulary larger than 4096
+ * returns M2M_ERR_INVALID.  Everything else - out_len, M2M_ERR_RANGE, the re-packing and the session state afterwards - is as for
+ * m2m_generate_greedy.
+ */
+int m2m_generate_scored(m2m_session* s, int max_length, const m2m_process_params* proc, const m2m_sample_params* sample,
+                        int64_t* tokens_out_dev, float* scores_out_dev, float* logprobs_out_dev, int* out_len_host, void* stream);
+
+/*
  * Rows end at different steps (ref: music2midi/model.py:115-135 decodes chunks of inference.batch_size = 128 three-second
  * segments to max_length 1024; a trained checkpoint ends a segment after tens to hundreds of tokens).  Once a quarter of the
  * rows still being decoded have emitted EOS, m2m_generate_greedy (and m2m_generate_sample, m2m_generate_processed) re-packs the live rows into the first slots of the batch at its

@@ -2177,9 +2177,12 @@ __device__ inline unsigned long long lane_bits(const unsigned* w, int v0) {   //
   else return (w[v0 >> 5] >> (v0 & 31)) & ((1ull << NPL) - 1);
 }
 
-template <int NPL, bool GREEDY>
+// SCORED (m2m_generate_scored, dec_scored_kernel): the same head also writes the row the token was selected from and / or the
+// token's log-probability (ScoreParams, t5.h); every addition is under `if constexpr (SCORED)`, so the unscored kernels keep
+// their instructions.
+template <int NPL, bool GREEDY, bool SCORED = false>
 __device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleParams* sp, const ProcessParams* pp,
-                                             unsigned short* s_hist, unsigned* s_bits) {
+                                             unsigned short* s_hist, unsigned* s_bits, const ScoreParams* sc = nullptr) {
   __shared__ int s_unfinished;
   DecState* stp = a.state;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -2207,7 +2210,9 @@ __device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleP
     unsigned short* hist = s_hist + (tid >> 6) * PROC_MAX_LEN;
     unsigned* seen = s_bits + (tid >> 6) * 2 * PROC_BITS;
     unsigned* ban = seen + PROC_BITS;
-    const bool scan = row && live && cur <= PROC_MAX_LEN && !a.finished[b];   // a finished row emits pad whatever its scores
+    bool scan = row && live && cur <= PROC_MAX_LEN && !a.finished[b];   // a finished row emits pad whatever its scores
+    if constexpr (SCORED)   // scores of a call without processors (a neutral block): no history to stage, no bitmap to read
+      scan = scan && (pp->penalty != 1.0f || pp->ngram > 0 || pp->n_bad > 0 || pp->has_bad1 || pp->has_supp || pp->has_begin);
     for (int i = lane; i < PROC_BITS; i += 64) { seen[i] = 0u; ban[i] = 0u; }
     if (scan) {
       const int64_t* hr = a.tokens + (int64_t)a.tok_row[b] * a.max_len;
@@ -2272,6 +2277,7 @@ __device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleP
       }
     }
     int tok;
+    float zsum = 0.f;          // SCORED: the sum of exp(x - m) over the entries the select saw (m: their maximum)
     if constexpr (GREEDY) {
       // arg-max, ties to the lower id (dec_head_kernel; an all -inf row gives id 0, as torch.argmax)
       float best = -INFINITY;
@@ -2286,6 +2292,13 @@ __device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleP
         if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
       }
       tok = bi == 0x7fffffff ? 0 : bi;
+      if constexpr (SCORED) {
+        m = wave_max(m);
+        float zl = 0.f;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) zl += (v0 + j < V) ? expf(x[j] - m) : 0.f;
+        zsum = wave_sum_uniform(zl);
+      }
     } else {
       m = wave_max(m);          // exact: every lane holds the same maximum
       unsigned kk[NPL];         // order-preserving keys; 0 (below every finite logit's) past the vocabulary
@@ -2310,6 +2323,7 @@ __device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleP
         z += w[j];
       }
       z = wave_sum_uniform(z);
+      unsigned cut = 0;          // SCORED: the nucleus cutoff key (0: no top-p filter)
       // TopP: the largest key c with mass(key < c) <= (1 - top_p) * Z, capped at the maximum's key (which always stays)
       if (top_p < 1.0f) {
         const float R = (1.0f - top_p) * z;
@@ -2324,6 +2338,7 @@ __device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleP
         c = min(c, ord_key(m));
 #pragma unroll
         for (int j = 0; j < NPL; ++j) if (kk[j] < c) w[j] = 0.f;
+        if constexpr (SCORED) cut = c;
       }
       // draw: the first kept entry (vocabulary order) whose inclusive cumulative weight exceeds u * Z
       float ls = 0.f;
@@ -2356,10 +2371,42 @@ __device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleP
       tk = __shfl(tk, sel, 64);
       if (tk < 0) tk = a.pad_id;         // no finite weight at all (the overflow flag is raised)
       tok = tk;
+      if constexpr (SCORED) {
+        // HF's warped row: what top-k and top-p removed is -inf (by the keys, not by w: a kept entry's weight may underflow to 0);
+        // the log-probability's sum is over what both filters kept - `total`, not z, which still holds the mass top-p removed
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) if (kk[j] < thr || kk[j] < cut) x[j] = -INFINITY;
+        zsum = total;
+      }
     }
     if (__ballot(bad) && live && lane == 0) stp->overflow = 1;
     // hf generation/utils.py (sample): finished rows emit pad; EOS finishes a row
     int next = fin ? a.pad_id : tok;
+    if constexpr (SCORED) {
+      // a row that finished before this step writes nothing (the caller's buffers are zeroed); t < steps and the clip < rows while live
+      if (live && !fin) {
+        const int clip = a.tok_row[b];
+        if (sc->scores) {
+          float* dst = sc->scores + ((int64_t)t * sc->rows + clip) * V;
+          if (sc->vec4) {            // V % 4 == 0 and an aligned base: 16-byte stores, NPL / 4 per lane over NPL contiguous floats
+#pragma unroll
+            for (int q = 0; q < NPL; q += 4)
+              if (v0 + q < V) *reinterpret_cast<float4*>(dst + v0 + q) = make_float4(x[q], x[q + 1], x[q + 2], x[q + 3]);
+          } else {
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) if (v0 + j < V) dst[v0 + j] = x[j];
+          }
+        }
+        if (sc->logprobs) {          // log_softmax(row)[token]: NaN for a row without a finite entry, as torch's
+          const int tk = (tok >= 0 && tok < V) ? tok : 0;
+          float xs = 0.f;
+#pragma unroll
+          for (int j = 0; j < NPL; ++j) if (v0 + j == tk) xs = x[j];
+          xs = __shfl(xs, tk / NPL, 64);
+          if (lane == 0) sc->logprobs[(int64_t)clip * sc->steps + t] = (xs - m) - logf(zsum);
+        }
+      }
+    }
     if (lane == 0 && live) {
       if (t + 1 < a.max_len) a.tokens[(int64_t)a.tok_row[b] * a.max_len + t + 1] = next;
       const int nf = fin | (next == a.eos_id);
@@ -2415,6 +2462,40 @@ static int launch_dec_process(const DecHeadArgs& h, const SampleParams* sp, cons
   const dim3 grid((unsigned)ceil_div(h.B, SAMPLE_ROWS)), block(64 * SAMPLE_ROWS);
   if (greedy) launch_dec_process_v<true>(h, sp, pp, grid, block, st);
   else launch_dec_process_v<false>(h, sp, pp, grid, block, st);
+  M2M_CHECK_HIP(hipGetLastError());
+  return M2M_OK;
+}
+
+// =========================================================== scored head ====
+// m2m_generate_scored: the processed head (with a neutral ProcessParams block when the call has no processor) that also writes, for
+// every live row, the fp32 row the token was selected from (HF's `scores`: raw, processed or warped logits, removed entries -inf) to
+// scores[t][clip][0:V] and / or log_softmax(that row)[token] to logprobs[clip][t].  The row is in the wavefront's registers when the
+// token is selected, so the log-probability costs one wave-wide max and sum and a 4-byte store; the row itself is only written when
+// asked for.  clip = tok_row[b]: the outputs follow the clip through live-row re-packing and chains of any size.  The output
+// pointers come from the ScoreParams block of the workspace, so one captured graph serves every call.
+template <int NPL, bool GREEDY>
+__global__ __launch_bounds__(64 * SAMPLE_ROWS) void dec_scored_kernel(DecHeadArgs a, const SampleParams* sp, const ProcessParams* pp,
+                                                                      const ScoreParams* sc) {
+  __shared__ unsigned short s_hist[SAMPLE_ROWS * PROC_MAX_LEN];
+  __shared__ unsigned s_bits[SAMPLE_ROWS * 2 * PROC_BITS];
+  process_head<NPL, GREEDY, true>(a, sp, pp, s_hist, s_bits, sc);
+}
+
+template <bool GREEDY>
+static void launch_dec_scored_v(const DecHeadArgs& h, const SampleParams* sp, const ProcessParams* pp, const ScoreParams* sc, dim3 grid,
+                                dim3 block, hipStream_t st) {
+  if (h.V <= 64 * 8) hipLaunchKernelGGL((dec_scored_kernel<8, GREEDY>), grid, block, 0, st, h, sp, pp, sc);
+  else if (h.V <= 64 * 16) hipLaunchKernelGGL((dec_scored_kernel<16, GREEDY>), grid, block, 0, st, h, sp, pp, sc);
+  else if (h.V <= 64 * 32) hipLaunchKernelGGL((dec_scored_kernel<32, GREEDY>), grid, block, 0, st, h, sp, pp, sc);
+  else hipLaunchKernelGGL((dec_scored_kernel<64, GREEDY>), grid, block, 0, st, h, sp, pp, sc);
+}
+
+static int launch_dec_scored(const DecHeadArgs& h, const SampleParams* sp, const ProcessParams* pp, const ScoreParams* sc, bool greedy,
+                             hipStream_t st) {
+  M2M_REQUIRE(h.V >= 1 && h.V <= PROC_MAX_VOCAB, "dec_scored_kernel: vocab_size %d outside [1, %d]", h.V, PROC_MAX_VOCAB);
+  const dim3 grid((unsigned)ceil_div(h.B, SAMPLE_ROWS)), block(64 * SAMPLE_ROWS);
+  if (greedy) launch_dec_scored_v<true>(h, sp, pp, sc, grid, block, st);
+  else launch_dec_scored_v<false>(h, sp, pp, sc, grid, block, st);
   M2M_CHECK_HIP(hipGetLastError());
   return M2M_OK;
 }
@@ -2962,6 +3043,8 @@ int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* log
   if ((rc = launch_dec_gemm(P, a, st))) return rc;
   if (headless) return M2M_OK;             // the arg-max key is consumed by the next step's layer 0 (or by decode_finalize)
   DecHeadArgs h = head_args(s, v, forced, logits_out, Ld);
+  if (!forced && (s->head_mode & HEAD_SCORED))
+    return launch_dec_scored(h, s->sample_dev, s->proc_dev, s->score_dev, !(s->head_mode & HEAD_SAMPLE), st);
   if (!forced && (s->head_mode & HEAD_PROCESSED))
     return launch_dec_process(h, s->sample_dev, s->proc_dev, !(s->head_mode & HEAD_SAMPLE), st);
   if (!forced && s->head_mode == HEAD_SAMPLE) return launch_dec_sample(h, s->sample_dev, st);

@@ -104,6 +104,16 @@ struct ProcessParams {
   unsigned begin[PROC_BITS];           // begin_suppress_tokens
 };
 
+// Per-token outputs of m2m_generate_scored (decode.hip dec_scored_kernel): where the call's outputs go, a device block of the workspace
+// written before the chains start (as SampleParams): the captured step reads the pointers from it.
+struct ScoreParams {
+  float* scores;            // [steps][rows][V] the row each token was selected from, or nullptr
+  float* logprobs;          // [rows][steps] log_softmax(that row)[token], or nullptr
+  int rows, steps;          // the call's clips (the encoded batch) and max_length - 1
+  int vec4;                 // the rows of `scores` are 16-byte aligned (V % 4 == 0, aligned base): float4 stores
+  int pad_;
+};
+
 // Beam search (m2m_generate_beam): the call's parameters, a device block of the workspace written before the chains start (as
 // SampleParams), and the per-clip / per-row state of the beam head (decode.hip dec_beam_kernel).
 struct BeamParams {
@@ -220,12 +230,14 @@ struct m2m_session {
   bool finished_skip = true;   // M2M_FINISHED_SKIP=0: finished rows keep streaming their K/V (the behaviour before round 4; bench.py's ragged_eos "before" leg)
   int kv_resident_layers = -1; // M2M_KV_RESIDENT_LAYERS: layers of cross K/V kept cache-resident when the rest streams non-temporally (-1: by a 180 MB budget)
   int repacks = 0, rows_moved = 0;   // live-row re-packings / rows moved by them in the last m2m_generate_greedy / _sample
-  int head_mode = 0;       // head form of the free-running decode step: 0 greedy (arg-max), 1 sampling, 2 beam, | 4 processed
+  int head_mode = 0;       // head form of the free-running decode step: 0 greedy (arg-max), 1 sampling, 2 beam, | 4 processed, | 8 scored
                            // (set for the length of a call)
   m2m::SampleParams* sample_dev = nullptr;    // [1] in the workspace
   m2m::SampleParams* sample_host = nullptr;   // pinned staging copy
   m2m::ProcessParams* proc_dev = nullptr;     // [1] in the workspace
   m2m::ProcessParams* proc_host = nullptr;    // pinned staging copy
+  m2m::ScoreParams* score_dev = nullptr;      // [1] in the workspace
+  m2m::ScoreParams* score_host = nullptr;     // pinned staging copy
   // beam search (m2m_generate_beam): rows = encoded clips x beam_nb; every buffer below is in the workspace
   int beam_nb = 0;                            // beams per clip during a beam call, 0 otherwise
   m2m::BeamParams* beam_dev = nullptr;        // [1]
@@ -328,6 +340,7 @@ int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int 
 int decode_finalize(m2m_session* s, const DecView& v, hipStream_t st);   // headless greedy loop: write the last token, close the chain
 constexpr int HEAD_GREEDY = 0, HEAD_SAMPLE = 1, HEAD_BEAM = 2;
 constexpr int HEAD_PROCESSED = 4;        // bit: logits processors before the greedy (| 0) or sampling (| HEAD_SAMPLE) select
+constexpr int HEAD_SCORED = 8;           // bit: the processed head that also writes scores / log-probabilities (always with HEAD_PROCESSED)
 constexpr int BEAM_MAX = 32;             // beams per clip: one LDS list of 2 x 32 candidates per beam, ancestries in bytes
 int decode_beam_init(m2m_session* s, const DecView& v, hipStream_t st);
 int decode_beam_finalize(m2m_session* s, int rows, int steps, int64_t* out, float* scores, int max_length, hipStream_t st);

@@ -189,7 +189,7 @@ extern "C" int m2m_model_checksum(const m2m_model* m, uint64_t* out_host, void* 
 namespace {
 struct WsLayout {
   int64_t x_enc, h_enc, qkv_enc, vt_enc, attn_enc, mid_enc, enc_bias, dec_bias, dec_bias_full, cross_vt, cross_kv, self_k, self_v;
-  int64_t x_dec, logits, tokens, finished, tok_row, keys, state, forced, sample, proc, beam, beam_clip, beam_row, anc, hyp_tok, total;
+  int64_t x_dec, logits, tokens, finished, tok_row, keys, state, forced, sample, proc, beam, beam_clip, beam_row, anc, hyp_tok, score, total;
 };
 
 WsLayout ws_layout(const m2m_model* m, int B, int S, int L) {
@@ -228,6 +228,7 @@ WsLayout ws_layout(const m2m_model* m, int B, int S, int L) {
   w.beam_row = take((int64_t)B * sizeof(BeamRow));
   w.anc = take(2 * (int64_t)B * L);
   w.hyp_tok = take((int64_t)B * L * 8);
+  w.score = take(sizeof(ScoreParams));
   w.total = off;
   return w;
 }
@@ -288,6 +289,7 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   s->proc_dev = (ProcessParams*)(b + w.proc);
   s->beam_dev = (BeamParams*)(b + w.beam); s->beam_clip = (BeamClip*)(b + w.beam_clip); s->beam_row = (BeamRow*)(b + w.beam_row);
   s->anc = b + w.anc; s->hyp_tok = (int64_t*)(b + w.hyp_tok);
+  s->score_dev = (ScoreParams*)(b + w.score);
 
   // relative-position bias tables (fp32), built on the host from the bucket function
   const m2m_t5_geometry& g = m->g;
@@ -324,6 +326,7 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   if (e == hipSuccess) e = hipHostMalloc((void**)&s->sample_host, sizeof(SampleParams), hipHostMallocDefault);
   if (e == hipSuccess) e = hipHostMalloc((void**)&s->proc_host, sizeof(ProcessParams), hipHostMallocDefault);
   if (e == hipSuccess) e = hipHostMalloc((void**)&s->beam_host, sizeof(BeamParams), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s->score_host, sizeof(ScoreParams), hipHostMallocDefault);
   for (int i = 0; i < MAX_GROUPS && e == hipSuccess; ++i) {
     DecGroup& gr = s->groups[i];
     gr.view.state = s->states + i;
@@ -357,6 +360,7 @@ extern "C" void m2m_session_destroy(m2m_session* s) {
   if (s->sample_host) (void)hipHostFree(s->sample_host);
   if (s->proc_host) (void)hipHostFree(s->proc_host);
   if (s->beam_host) (void)hipHostFree(s->beam_host);
+  if (s->score_host) (void)hipHostFree(s->score_host);
   delete s;
 }
 
@@ -550,8 +554,8 @@ extern "C" int m2m_generate_sample(m2m_session* s, int max_length, const m2m_sam
 
 // Logits processors (include/music2midi_amd.h): the id lists are checked and laid out into the ProcessParams block on the host; the
 // decode loop runs the processed head (HEAD_PROCESSED, greedy or sampling select).
-static int fill_process_params(const m2m_session* s, int max_length, const m2m_process_params* p, ProcessParams& h) {
-  const char* fn = "m2m_generate_processed";
+static int fill_process_params(const m2m_session* s, int max_length, const m2m_process_params* p, ProcessParams& h,
+                               const char* fn = "m2m_generate_processed") {
   const m2m_t5_geometry& g = s->m->g;
   const int V = g.vocab_size;
   M2M_REQUIRE(V <= PROC_MAX_VOCAB, "%s: vocab_size %d > %d (the processed head keeps a row in one wavefront's registers)", fn, V,
@@ -617,6 +621,40 @@ extern "C" int m2m_generate_processed(m2m_session* s, int max_length, const m2m_
   if ((rc = require_encoded(s, fn))) return rc;
   return decode_call(s, {fn, HEAD_PROCESSED | (sample ? HEAD_SAMPLE : HEAD_GREEDY), 0, tokens_out_dev, nullptr}, max_length, out_len_host,
                      (hipStream_t)stream);
+}
+
+// Per-token outputs (include/music2midi_amd.h): the processed head's scored form (HEAD_SCORED, greedy or sampling select), with a
+// neutral ProcessParams block when the call has no processor; with no output asked for, the matching unscored export.
+extern "C" int m2m_generate_scored(m2m_session* s, int max_length, const m2m_process_params* proc, const m2m_sample_params* sample,
+                                   int64_t* tokens_out_dev, float* scores_out_dev, float* logprobs_out_dev, int* out_len_host,
+                                   void* stream) {
+  const char* fn = "m2m_generate_scored";
+  M2M_REQUIRE(s && tokens_out_dev && out_len_host, "m2m_generate_scored: null argument");
+  if (!scores_out_dev && !logprobs_out_dev) {
+    if (proc) return m2m_generate_processed(s, max_length, proc, sample, tokens_out_dev, out_len_host, stream);
+    if (sample) return m2m_generate_sample(s, max_length, sample, tokens_out_dev, out_len_host, stream);
+    return m2m_generate_greedy(s, max_length, tokens_out_dev, out_len_host, stream);
+  }
+  int rc;
+  if (sample && (rc = fill_sample_params(sample, *s->sample_host, fn))) return rc;
+  const int V = s->m->g.vocab_size;
+  M2M_REQUIRE(V <= PROC_MAX_VOCAB, "%s: vocab_size %d > %d (the scored head keeps a row in one wavefront's registers)", fn, V,
+              PROC_MAX_VOCAB);
+  M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_scored: max_length %d outside [1, %d]", max_length, s->max_dec);
+  if (proc) {
+    if ((rc = fill_process_params(s, max_length, proc, *s->proc_host, fn))) return rc;
+  } else {                                   // no processor: the neutral block (nothing banned, nothing forced)
+    ProcessParams& h = *s->proc_host;
+    h = ProcessParams{};
+    h.penalty = 1.0f; h.forced_bos = -1; h.forced_eos = -1; h.begin_index = 1; h.max_length = max_length;
+  }
+  if ((rc = require_encoded(s, fn))) return rc;
+  ScoreParams& sc = *s->score_host;
+  sc = ScoreParams{};
+  sc.scores = scores_out_dev; sc.logprobs = logprobs_out_dev; sc.rows = s->B; sc.steps = max_length - 1;
+  sc.vec4 = (V % 4 == 0 && ((uintptr_t)scores_out_dev & 15) == 0) ? 1 : 0;
+  return decode_call(s, {fn, HEAD_SCORED | HEAD_PROCESSED | (sample ? HEAD_SAMPLE : HEAD_GREEDY), 0, tokens_out_dev, nullptr}, max_length,
+                     out_len_host, (hipStream_t)stream);
 }
 
 // the decode loop of every head form (s->head_mode, set by decode_call)
@@ -768,6 +806,16 @@ static int decode_call(m2m_session* s, const DecodeCall& c, int max_length, int*
   if (c.head_mode & HEAD_SAMPLE) rc = upload(s->sample_dev, s->sample_host, sizeof(SampleParams), caller, c.fn);
   if (rc == M2M_OK && (c.head_mode & HEAD_PROCESSED)) rc = upload(s->proc_dev, s->proc_host, sizeof(ProcessParams), caller, c.fn);
   if (rc == M2M_OK && c.head_mode == HEAD_BEAM) rc = upload(s->beam_dev, s->beam_host, sizeof(BeamParams), caller, c.fn);
+  if (rc == M2M_OK && (c.head_mode & HEAD_SCORED)) {
+    // finished rows write nothing: the caller's buffers are zeroed on its stream, before the chains start
+    const ScoreParams& sc = *s->score_host;
+    const size_t cells = (size_t)sc.rows * (size_t)sc.steps;
+    hipError_t e = hipSuccess;
+    if (sc.scores && cells) e = hipMemsetAsync(sc.scores, 0, cells * (size_t)s->m->g.vocab_size * sizeof(float), caller);
+    if (e == hipSuccess && sc.logprobs && cells) e = hipMemsetAsync(sc.logprobs, 0, cells * sizeof(float), caller);
+    if (e != hipSuccess) { set_error("%s: hipMemsetAsync: %s", c.fn, hipGetErrorString(e)); rc = M2M_ERR_HIP; }
+    if (rc == M2M_OK) rc = upload(s->score_dev, s->score_host, sizeof(ScoreParams), caller, c.fn);
+  }
   if (rc == M2M_OK) {
     s->head_mode = c.head_mode; s->beam_nb = c.beam_nb;
     rc = decode_loop(s, c, max_length, out_len_host, caller);

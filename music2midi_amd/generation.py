@@ -8,7 +8,8 @@ and the argument checks of its logits warpers (hf: generation/logits_process.py 
 ``no_repeat_ngram_size``, ``bad_words_ids``, ``min_length``, ``min_new_tokens``, ``forced_bos_token_id``,
 ``forced_eos_token_id``, ``suppress_tokens``, ``begin_suppress_tokens``) and ``max_new_tokens`` follow 4.34's
 ``_get_logits_processor`` and its processors' checks.  Beam search and every other keyword raise
-``NotImplementedError`` there; beam search has its own entry point (``T5Transformer.beam_search``), whose keywords
+``NotImplementedError`` there (``return_dict_in_generate``, ``output_scores`` and the project keyword ``output_logprobs`` select
+the per-token outputs of the scored head); beam search has its own entry point (``T5Transformer.beam_search``), whose keywords
 ``resolve_beam_kwargs`` checks.
 """
 from __future__ import annotations
@@ -58,6 +59,9 @@ class GenerateConfig:
     top_p: float = DEFAULT_TOP_P         # 1.0: no nucleus filter
     num_return_sequences: int = 1
     process: "ProcessConfig | None" = None   # None: no logits processor (the plain greedy / sampling head)
+    return_dict: bool = False            # return_dict_in_generate=True: an output with .sequences / .scores / .logprobs
+    output_scores: bool = False          # ... with the row every token was selected from (only with return_dict)
+    output_logprobs: bool = False        # ... with every token's log-probability under that row (only with return_dict)
 
 
 def _is_int(v) -> bool:
@@ -163,7 +167,10 @@ def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_
     ``None`` for temperature / top_k / top_p means "no such warper", as in HF (the warper is only built when the value is
     not None).  With ``do_sample=False`` the sampling keywords are ignored (HF warns and decodes greedily).
     ``max_new_tokens`` sets ``max_length = max_new_tokens + 1`` (the decoder prompt is the start token) and wins over
-    ``max_length``, as in 4.34.  ``vocab_size`` (optional) range-checks the processors' token ids."""
+    ``max_length``, as in 4.34.  ``vocab_size`` (optional) range-checks the processors' token ids.
+    ``return_dict_in_generate`` and ``output_scores`` have 4.34's meaning: without ``return_dict_in_generate=True`` the call
+    returns the plain tensor and ``output_scores`` is ignored.  ``output_logprobs`` (a keyword of this project: the tokens'
+    log-probabilities without the V-wide rows) raises ``ValueError`` unless ``return_dict_in_generate=True``."""
     kw = dict(kwargs)
     max_length = int(kw.pop("max_length", default_max_length))   # range-checked by the library, as before
     max_new = kw.pop("max_new_tokens", None)
@@ -184,15 +191,24 @@ def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_
     n = kw.pop("num_return_sequences", 1)
     if n is None:
         n = 1
+    return_dict = bool(kw.pop("return_dict_in_generate", False))
+    output_scores = bool(kw.pop("output_scores", False)) and return_dict
+    output_logprobs = bool(kw.pop("output_logprobs", False))
     if kw:
         raise NotImplementedError(f"unsupported generate kwargs on the MI355X path: {sorted(kw)}")
+    if output_logprobs and not return_dict:
+        raise ValueError("`output_logprobs=True` needs `return_dict_in_generate=True` (a plain tensor has no place for them)")
+    if (output_scores or output_logprobs) and vocab_size is not None and vocab_size > PROCESS_MAX_VOCAB:
+        raise ValueError(f"per-token scores on the MI355X path need a vocabulary of at most {PROCESS_MAX_VOCAB} ids "
+                         f"(the model has {vocab_size})")
+    out = dict(return_dict=return_dict, output_scores=output_scores, output_logprobs=output_logprobs)
     if not _is_int(n) or n < 1:
         raise ValueError(f"`num_return_sequences` has to be a strictly positive integer, but is {n!r}")
     if not do_sample:
         if n != 1:   # hf: generation/utils.py (greedy mode) raises the same
             raise ValueError("Greedy methods without beam search do not support `num_return_sequences` different than 1 "
                              f"(got {n}).")
-        return GenerateConfig(max_length=max_length, process=process)
+        return GenerateConfig(max_length=max_length, process=process, **out)
     # TemperatureLogitsWarper: a strictly positive float
     if temperature is None:
         temperature = DEFAULT_TEMPERATURE
@@ -212,7 +228,7 @@ def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_
     if not _is_real(top_p) or not (0.0 <= float(top_p) <= 1.0):
         raise ValueError(f"`top_p` has to be a float >= 0 and <= 1, but is {top_p!r}")
     return GenerateConfig(max_length=max_length, do_sample=True, temperature=float(temperature), top_k=operator.index(top_k),
-                          top_p=float(top_p), num_return_sequences=operator.index(n), process=process)
+                          top_p=float(top_p), num_return_sequences=operator.index(n), process=process, **out)
 
 
 BEAM_MAX = 32   # beams per clip the device beam head supports

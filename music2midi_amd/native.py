@@ -114,6 +114,8 @@ _SIGNATURES = {
                                       C.c_void_p]),
     "m2m_generate_processed": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ProcessParams), C.POINTER(SampleParams), C.c_void_p,
                                          C.POINTER(C.c_int), C.c_void_p]),
+    "m2m_generate_scored": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ProcessParams), C.POINTER(SampleParams), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "m2m_generate_beam": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BeamParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                     C.c_void_p]),
     "m2m_session_repack_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -135,6 +135,11 @@ class Seq2SeqOutput(dict):
             raise AttributeError(name) from e
 
 
+class GenerateOutput(Seq2SeqOutput):
+    """``generate(return_dict_in_generate=True)``: ``sequences`` [B * n, L]; ``scores``: a tuple of L - 1 tensors [B * n, V] (the
+    unbound views of one buffer), or ``None``; ``logprobs`` [B * n, L - 1] float32, or ``None``."""
+
+
 # --------------------------------------------------------------------------
 class T5Transformer(nn.Module):
     def __init__(self, config_path, precision: Optional[str] = None):
@@ -318,18 +323,18 @@ class T5Transformer(nn.Module):
             return out
 
     @torch.no_grad()
-    def generate_from_embeds(self, inputs_embeds: torch.Tensor, max_length: int = 20, **kwargs) -> torch.Tensor:
+    def generate_from_embeds(self, inputs_embeds: torch.Tensor, max_length: int = 20, **kwargs):
         """Decode from encoder inputs [B, S, d].  Keywords as :meth:`generate` (``do_sample``, ``temperature``, ``top_k``,
-        ``top_p``, ``num_return_sequences``, the logits processors, ``max_new_tokens``); without ``do_sample=True`` this is the
-        greedy decode."""
+        ``top_p``, ``num_return_sequences``, the logits processors, ``max_new_tokens``, ``return_dict_in_generate`` with
+        ``output_scores`` / ``output_logprobs``); without ``do_sample=True`` this is the greedy decode."""
         cfg = (resolve_generate_kwargs(kwargs, default_max_length=max_length, vocab_size=self.geometry.vocab_size) if kwargs
                else GenerateConfig(max_length=max_length))
         return self._decode(inputs_embeds, cfg)
 
     @torch.no_grad()
-    def _decode(self, inputs_embeds: torch.Tensor, cfg: GenerateConfig) -> torch.Tensor:
+    def _decode(self, inputs_embeds: torch.Tensor, cfg: GenerateConfig):
         """Greedy, sampled or processed decode of encoder inputs [B, S, d] as the resolved ``cfg`` asks."""
-        sp = None
+        sp = pp = None
         if cfg.do_sample:
             # the call's seed: one draw from torch's default CPU generator, so torch.manual_seed(n) makes the call reproducible
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
@@ -351,18 +356,48 @@ class T5Transformer(nn.Module):
             export, params = "m2m_generate_sample", (C.byref(sp),)
         else:
             export, params = "m2m_generate_greedy", ()
+        if cfg.return_dict:    # the scored head writes the outputs as it selects the token (the library zeroes both buffers first)
+            export, params = "m2m_generate_scored", (C.byref(pp) if pp is not None else None, C.byref(sp) if sp is not None else None)
         with self._lock:
             x = inputs_embeds.to(self.transformer.device, torch.float32)
             if cfg.num_return_sequences > 1:      # HF's expansion: the n sequences of a clip are consecutive rows
                 x = x.repeat_interleave(cfg.num_return_sequences, dim=0)
             x = x.contiguous()
             sess, _ = self._encode(x, cfg.max_length)
-            tokens = torch.empty((x.shape[0], cfg.max_length), dtype=torch.long, device=x.device)
+            rows, steps, dev = x.shape[0], cfg.max_length - 1, x.device
+            tokens = torch.empty((rows, cfg.max_length), dtype=torch.long, device=dev)
+            scores = logprobs = None
+            outs = ()
+            if cfg.return_dict:
+                if cfg.output_scores:
+                    scores = torch.empty((steps, rows, self.geometry.vocab_size), dtype=torch.float32, device=dev)
+                if cfg.output_logprobs:
+                    logprobs = torch.empty((rows, steps), dtype=torch.float32, device=dev)
+                outs = tuple(t.data_ptr() if t is not None and t.numel() else None for t in (scores, logprobs))
             out_len = C.c_int(0)
-            with torch.cuda.device(x.device):
-                native.check(getattr(native.load(), export)(sess, cfg.max_length, *params, tokens.data_ptr(), C.byref(out_len),
-                                                            native.stream_handle(x.device)), export)
-            return tokens[:, : out_len.value]
+            with torch.cuda.device(dev):
+                native.check(getattr(native.load(), export)(sess, cfg.max_length, *params, tokens.data_ptr(), *outs, C.byref(out_len),
+                                                            native.stream_handle(dev)), export)
+            n = out_len.value
+            if not cfg.return_dict:
+                return tokens[:, :n]
+            return GenerateOutput(sequences=tokens[:, :n],
+                                  scores=tuple(scores[: n - 1].unbind(0)) if scores is not None else None,
+                                  logprobs=logprobs[:, : n - 1] if logprobs is not None else None)
+
+    @staticmethod
+    def compute_transition_scores(sequences: torch.Tensor, scores, beam_indices=None, normalize_logits: bool = False) -> torch.Tensor:
+        """transformers 4.34's ``GenerationMixin.compute_transition_scores`` for the non-beam case: the score of every generated
+        token, [B, len(scores)] - ``scores[t][b, sequences[b, t - len(scores)]]``, after a ``log_softmax`` over the vocabulary with
+        ``normalize_logits=True`` (then equal to ``generate(output_logprobs=True).logprobs`` up to rounding, wherever a row had
+        not finished: finished rows hold zeros here, see :meth:`generate`).  ``beam_indices`` raises ``NotImplementedError``."""
+        if beam_indices is not None:
+            raise NotImplementedError("compute_transition_scores with beam_indices: beam_search returns sequences_scores only")
+        stacked = torch.stack(tuple(scores)).transpose(0, 1)                  # [B, T, V]
+        if normalize_logits:
+            stacked = torch.nn.functional.log_softmax(stacked, dim=-1)
+        idx = sequences[:, sequences.shape[-1] - stacked.shape[1]:].to(stacked.device)
+        return stacked.gather(2, idx.unsqueeze(-1)).squeeze(-1)
 
     @torch.no_grad()
     def beam_search_from_embeds(self, inputs_embeds: torch.Tensor, num_beams: int, max_length: int = 20,
@@ -460,7 +495,7 @@ class T5Transformer(nn.Module):
 
     _GENERATE_DEFAULT_MAX_LENGTH = 20   # HF GenerationConfig default when max_length is not given
 
-    def generate(self, inputs: ModelInputs, **kwargs) -> torch.Tensor:
+    def generate(self, inputs: ModelInputs, **kwargs):
         """Decode (ref transformer.py:41-45, which forwards every keyword to HF ``generate``).
 
         Greedy by default (``do_sample=False``; the reference itself only ever passes ``max_length``, ref
@@ -473,8 +508,17 @@ class T5Transformer(nn.Module):
         generator).  The logits processors of 4.34 run on the GPU before the greedy or sampled select:
         ``repetition_penalty``, ``no_repeat_ngram_size``, ``bad_words_ids``, ``min_length``, ``min_new_tokens``,
         ``forced_bos_token_id``, ``forced_eos_token_id``, ``suppress_tokens``, ``begin_suppress_tokens``; ``max_new_tokens``
-        sets ``max_length = max_new_tokens + 1``.  Invalid values raise ``ValueError``; beam search (``num_beams != 1``) and
-        any other keyword raise ``NotImplementedError``."""
+        sets ``max_length = max_new_tokens + 1``.  ``return_dict_in_generate=True`` returns an attribute-access dict instead of
+        the tensor: ``sequences`` [B * n, L]; with ``output_scores=True`` ``scores``, a tuple of L - 1 float32 tensors [B * n, V] -
+        the row each token was selected from, as HF appends it (raw logits for greedy, after the processors, after the warpers
+        with removed entries at ``-inf`` for sampling); with ``output_logprobs=True`` (a keyword of this project, the cheap
+        form: no V-wide row is written) ``logprobs`` [B * n, L - 1], ``log_softmax(scores[t])[token]``, what
+        :meth:`compute_transition_scores` with ``normalize_logits=True`` gives.  Both are written by the decode step as it
+        selects the token.  Unlike HF, a row that has emitted EOS is no longer scored: its later positions are 0.0 in both.
+        Without ``return_dict_in_generate=True`` ``output_scores`` is ignored (4.34) and ``output_logprobs`` raises
+        ``ValueError``.  :meth:`beam_search` is unchanged (``sequences_scores`` only), and ``Music2MIDI.generate_notes`` does not
+        carry per-note confidences yet (the tokenizer would have to keep token positions through ``decode``).  Invalid values
+        raise ``ValueError``; beam search (``num_beams != 1``) and any other keyword raise ``NotImplementedError``."""
         cfg = resolve_generate_kwargs(kwargs, default_max_length=self._GENERATE_DEFAULT_MAX_LENGTH,
                                       vocab_size=self.geometry.vocab_size)
         return self._decode(self.encoder_inputs(inputs), cfg)
