@@ -22,6 +22,7 @@
 #include "t5.h"
 
 #include <stdlib.h>
+#include <type_traits>
 
 namespace m2m {
 
@@ -1992,9 +1993,11 @@ __global__ void dec_final_kernel(DecHeadArgs a) {
   if (threadIdx.x == 0) { st->done = 1; st->out_len = t + 1; }
 }
 
-// ========================================================== sampling head ====
-// do_sample=True replaces dec_head_kernel by this kernel (the step is otherwise the non-headless one, as with M2M_HEADLESS=0).  It
-// follows transformers 4.34's logits warpers in their order (hf: generation/utils.py _get_logits_warper, generation/logits_process.py):
+// =========================================================== select heads ====
+// do_sample=True, the logits processors and the per-token outputs replace dec_head_kernel by dec_sample_kernel, dec_process_kernel
+// or dec_scored_kernel (the step is otherwise the non-headless one, as with M2M_HEADLESS=0): one body, select_head, built from the
+// helpers of this section; dec_beam_kernel shares the row load, the embedding write and the step close.  Sampling follows
+// transformers 4.34's logits warpers in their order (hf: generation/utils.py _get_logits_warper, generation/logits_process.py):
 //   TemperatureLogitsWarper  x / T (skipped for T == 1)
 //   TopKLogitsWarper         remove every logit strictly below the k-th largest, k = min(top_k, V) (ties at the boundary stay)
 //   TopPLogitsWarper         sorted ascending, remove the entries whose cumulative softmax is <= 1 - top_p, the largest always stays
@@ -2007,182 +2010,241 @@ __global__ void dec_final_kernel(DecHeadArgs a) {
 // the nucleus boundary are kept or removed together; HF removes them in torch.sort's order.)  Non-finite logits raise the chain's
 // overflow flag (M2M_ERR_RANGE) as the greedy head does; the EOS / pad / finished bookkeeping, the token store and the embedding
 // write are the greedy branch of dec_head_kernel.  The last workgroup of a step (a ticket in DecState) closes it.
+// Per-token outputs (m2m_generate_scored): the processed head (with a neutral ProcessParams block when the call has no processor)
+// also writes, for every live row, the fp32 row the token was selected from (HF's `scores`: raw, processed or warped logits, removed
+// entries -inf) to scores[t][clip][0:V] and / or log_softmax(that row)[token] to logprobs[clip][t]: the row is in registers, so the
+// log-probability costs one wave-wide max and sum and a 4-byte store, and the row itself is only written when asked for.  clip =
+// tok_row[b]: the outputs follow the clip through live-row re-packing and chains of any size.  The output pointers come from the
+// ScoreParams block of the workspace, so one captured graph serves every call.
+static_assert(PROC_MAX_VOCAB == SAMPLE_MAX_VOCAB && SAMPLE_MAX_VOCAB == 64 * 64, "the register row: 64 lanes x at most 64 logits");
 __device__ inline unsigned ord_key(float v) {
   unsigned u = __float_as_uint(v + 0.0f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ inline float wave_sum_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wave_sum(v)))); }
-
-constexpr int SAMPLE_ROWS = 4;   // rows (waves) per dec_sample_kernel workgroup: a chain's rows are spread over ceil(B / 4) workgroups
-
+constexpr int SAMPLE_ROWS = 4;   // rows (waves) per select-head workgroup: a chain's rows are spread over ceil(B / 4) workgroups
+// this lane's NPL logits of a row (0 past V) -> x; true when one is not finite (the reference would emit NaN logits, never a token)
 template <int NPL>
-__global__ __launch_bounds__(64 * SAMPLE_ROWS) void dec_sample_kernel(DecHeadArgs a, const SampleParams* sp) {
-  __shared__ int s_unfinished;
-  DecState* stp = a.state;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int b = blockIdx.x * SAMPLE_ROWS + (tid >> 6);
-  const int V = a.V, v0 = lane * NPL;
-  const bool row = b < a.B;
-  // the row's logits are requested before the loop state is consumed (as in dec_head_kernel)
-  float x[NPL];
-  const float* lg = a.logits + (int64_t)(row ? b : 0) * a.ldl;
+__device__ __forceinline__ bool load_row(const float* lg, int v0, int V, float (&x)[NPL]) {
+  bool bad = false;
 #pragma unroll
-  for (int j = 0; j < NPL; ++j) x[j] = (v0 + j < V) ? lg[v0 + j] : 0.f;
-  const float temp = sp->temperature, top_p = sp->top_p;
-  const int top_k = sp->top_k;
-  const unsigned long long seed_h = splitmix64(sp->seed);
-  const int t = stp->t;
-  const bool live = !(stp->done | (t >= stp->max_steps));
-  if (tid == 0) s_unfinished = 0;
-  __syncthreads();
-  const int k = top_k > 0 ? min(top_k, V) : V;
-  if (row) {
-    const int fin = a.finished[b];
-    bool bad = false;
-    float m = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-      if (v0 + j < V) {
-        bad |= !(fabsf(x[j]) <= 3.0e38f);
-        if (temp != 1.0f) x[j] = x[j] / temp;
-        m = fmaxf(m, x[j]);
-      }
-    }
-    m = wave_max(m);          // exact: every lane holds the same maximum
-    unsigned kk[NPL];         // order-preserving keys; 0 (below every finite logit's) past the vocabulary
-#pragma unroll
-    for (int j = 0; j < NPL; ++j) kk[j] = (v0 + j < V) ? ord_key(x[j]) : 0u;
-    // TopK: the k-th largest key, bit by bit from the top (the largest thr with count(key >= thr) >= k); counts are ballots
-    unsigned thr = 0;
-    if (k < V) {
-      for (int bit = 31; bit >= 0; --bit) {
-        const unsigned cand = thr | (1u << bit);
-        int cnt = 0;
-#pragma unroll
-        for (int j = 0; j < NPL; ++j) cnt += __popcll(__ballot(kk[j] >= cand));
-        if (cnt >= k) thr = cand;
-      }
-    }
-    float w[NPL];
-    float z = 0.f;
-#pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-      w[j] = (v0 + j < V && kk[j] >= thr) ? expf(x[j] - m) : 0.f;
-      z += w[j];
-    }
-    z = wave_sum_uniform(z);
-    // TopP: the largest key c with mass(key < c) <= (1 - top_p) * Z, capped at the maximum's key (which always stays)
-    if (top_p < 1.0f) {
-      const float R = (1.0f - top_p) * z;
-      unsigned c = 0;
-      for (int bit = 31; bit >= 0; --bit) {
-        const unsigned cand = c | (1u << bit);
-        float lm = 0.f;
-#pragma unroll
-        for (int j = 0; j < NPL; ++j) lm += kk[j] < cand ? w[j] : 0.f;
-        if (wave_sum_uniform(lm) <= R) c = cand;
-      }
-      c = min(c, ord_key(m));
-#pragma unroll
-      for (int j = 0; j < NPL; ++j) if (kk[j] < c) w[j] = 0.f;
-    }
-    // draw: the first kept entry (vocabulary order) whose inclusive cumulative weight exceeds u * Z
-    float ls = 0.f;
-#pragma unroll
-    for (int j = 0; j < NPL; ++j) ls += w[j];
-    float incl = ls;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const float up = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += up;
-    }
-    const float total = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, incl), 63));
-    const unsigned long long h = splitmix64(seed_h ^ (((unsigned long long)(unsigned)a.tok_row[b] << 32) | (unsigned)t));
-    const float target = (float)(h >> 40) * 0x1p-24f * total;
-    const unsigned long long over = __ballot(incl > target && ls > 0.f);
-    const unsigned long long any = __ballot(ls > 0.f);
-    const int sel = over ? __ffsll((long long)over) - 1 : (any ? 63 - __clzll((long long)any) : 0);
-    float acc = __shfl_up(incl, 1, 64);
-    if (lane == 0) acc = 0.f;
-    int tok = -1, last = -1;
-#pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-      if (w[j] > 0.f) {
-        acc += w[j];
-        last = v0 + j;
-        if (tok < 0 && acc > target) tok = v0 + j;
-      }
-    }
-    if (tok < 0) tok = last;           // rounding put the target past this lane's last kept entry
-    tok = __shfl(tok, sel, 64);
-    if (tok < 0) tok = a.pad_id;       // no finite weight at all (the overflow flag is raised)
-    if (__ballot(bad) && live && lane == 0) stp->overflow = 1;
-    // hf generation/utils.py (sample): finished rows emit pad; EOS finishes a row
-    int next = fin ? a.pad_id : tok;
-    if (lane == 0 && live) {
-      if (t + 1 < a.max_len) a.tokens[(int64_t)a.tok_row[b] * a.max_len + t + 1] = next;
-      const int nf = fin | (next == a.eos_id);
-      a.finished[b] = nf;
-      if (!nf) atomicAdd(&s_unfinished, 1);
-    }
-    if (next < 0 || next >= V) next = a.pad_id;
-    const float* emb = a.shared + (int64_t)next * a.d;
-    for (int c = lane * 4; c < a.d; c += 256) {
-      const float4 e4 = *reinterpret_cast<const float4*>(emb + c);
-      xq_t* xp = a.x + (int64_t)b * a.d + c;
-      if (live) {
-        *reinterpret_cast<longlong2*>(xp) = make_longlong2(xq_fix_guarded(e4.x, stp), xq_fix_guarded(e4.y, stp));
-        *reinterpret_cast<longlong2*>(xp + 2) = make_longlong2(xq_fix_guarded(e4.z, stp), xq_fix_guarded(e4.w, stp));
-      }
-    }
+  for (int j = 0; j < NPL; ++j) {
+    x[j] = (v0 + j < V) ? lg[v0 + j] : 0.f;
+    bad |= !(fabsf(x[j]) <= 3.0e38f);
   }
-  // the step closes when the last workgroup is through: every workgroup has read t / done above before it takes its ticket
-  __syncthreads();
-  if (tid == 0 && live) {
-    if (s_unfinished) atomicAdd(&stp->smp_unfinished, s_unfinished);
-    __threadfence();
-    if (atomicAdd(&stp->smp_ticket, 1) == (int)gridDim.x - 1) {
-      __threadfence();
-      const int nu = atomicExch(&stp->smp_unfinished, 0);
-      stp->smp_ticket = 0;
-      const int nt = t + 1;
-      stp->t = nt;
-      stp->n_unfinished = nu;
-      if (nu == 0 || nt >= stp->max_steps) { stp->done = 1; stp->out_len = nt + 1; }
-    }
-  }
+  return bad;
 }
-
-static int launch_dec_sample(const DecHeadArgs& h, const SampleParams* sp, hipStream_t st) {
-  M2M_REQUIRE(h.V >= 1 && h.V <= SAMPLE_MAX_VOCAB, "dec_sample_kernel: vocab_size %d outside [1, %d]", h.V, SAMPLE_MAX_VOCAB);
-  const dim3 grid((unsigned)ceil_div(h.B, SAMPLE_ROWS)), block(64 * SAMPLE_ROWS);
-  if (h.V <= 64 * 8) hipLaunchKernelGGL(dec_sample_kernel<8>, grid, block, 0, st, h, sp);
-  else if (h.V <= 64 * 16) hipLaunchKernelGGL(dec_sample_kernel<16>, grid, block, 0, st, h, sp);
-  else if (h.V <= 64 * 32) hipLaunchKernelGGL(dec_sample_kernel<32>, grid, block, 0, st, h, sp);
-  else hipLaunchKernelGGL(dec_sample_kernel<64>, grid, block, 0, st, h, sp);
-  M2M_CHECK_HIP(hipGetLastError());
-  return M2M_OK;
-}
-
-// ======================================================== processed head ====
-// Logits processors (m2m_generate_processed; transformers 4.34 _get_logits_processor, see include/music2midi_amd.h): the sampling
-// head's form with the processors applied to the row in registers before the select - the arg-max (GREEDY) or the warpers and the
-// draw.  Per workgroup (4 rows) 16 KB of LDS hold the rows' histories as 16-bit ids and 4 KB their "seen" / ban bitmaps; the ids
-// that do not depend on the history (suppress, begin-suppress, one-id bad words) come as bitmaps of the parameter block.  The
-// overflow check looks at the raw logits.  The warper and draw code below repeats dec_sample_kernel's: a body shared by inlining
-// changed that kernel's instructions, and the sampling path must stay what it was.
 template <int NPL>
 __device__ inline unsigned long long lane_bits(const unsigned* w, int v0) {   // bits v0 .. v0 + NPL - 1 of a vocabulary bitmap
   if constexpr (NPL == 64) return (unsigned long long)w[v0 >> 5] | ((unsigned long long)w[(v0 >> 5) + 1] << 32);
   else return (w[v0 >> 5] >> (v0 & 31)) & ((1ull << NPL) - 1);
 }
+// Logits processors (m2m_generate_processed; transformers 4.34 _get_logits_processor, see include/music2midi_amd.h) on the row in
+// registers, before the select; every thread of the workgroup calls this (it holds barriers).  Per workgroup (4 rows) 16 KB of LDS
+// hold the rows' histories (input_ids = the start token and t generated ids, cur = cur_len = t + 1) as 16-bit ids, staged from the
+// token matrix (row tok_row[b]: the clip's own row whatever its slot), and 4 KB their bitmaps: one lane-strided pass each sets the
+// "seen" bits (repetition penalty) and the ban bits (n-gram, bad words of two or more ids).  The ids that do not depend on the
+// history (suppress, begin-suppress, one-id bad words) come as bitmaps of the parameter block.
+template <int NPL, bool SCORED>
+__device__ __forceinline__ void apply_processors(const DecHeadArgs& a, const ProcessParams* pp, float (&x)[NPL], int b, bool row,
+                                                 bool live, int cur, int v0) {
+  __shared__ unsigned short s_hist[SAMPLE_ROWS][PROC_MAX_LEN];
+  __shared__ unsigned s_bits[SAMPLE_ROWS][2][PROC_BITS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned long long m_seen = 0, m_ban = 0, m_post = 0;
+  unsigned short* hist = s_hist[wave];
+  unsigned *seen = s_bits[wave][0], *ban = s_bits[wave][1];
+  bool scan = row && live && cur <= PROC_MAX_LEN && !a.finished[b];   // a finished row emits pad whatever its scores
+  if constexpr (SCORED)   // scores of a call without processors (a neutral block): no history to stage, no bitmap to read
+    scan = scan && (pp->penalty != 1.0f || pp->ngram > 0 || pp->n_bad > 0 || pp->has_bad1 || pp->has_supp || pp->has_begin);
+  for (int i = lane; i < PROC_BITS; i += 64) { seen[i] = 0u; ban[i] = 0u; }
+  if (scan) {
+    const int64_t* hr = a.tokens + (int64_t)a.tok_row[b] * a.max_len;
+    for (int p = lane; p < cur; p += 64) hist[p] = (unsigned short)min((unsigned long long)hr[p], (unsigned long long)(PROC_MAX_VOCAB - 1));
+  }
+  __syncthreads();
+  if (scan) {
+    if (pp->penalty != 1.0f)
+      for (int p = lane; p < cur; p += 64) atomicOr(&seen[hist[p] >> 5], 1u << (hist[p] & 31));
+    // NoRepeatNGram: every complete window i .. i + n - 1 whose first n - 1 ids equal the last n - 1 ids bans its last id
+    const int n = pp->ngram;
+    if (n > 0) {
+      const int pre = cur - n + 1;
+      for (int i = lane; i + n <= cur; i += 64) {
+        int k = 0;
+        while (k < n - 1 && hist[i + k] == hist[pre + k]) ++k;
+        if (k == n - 1) atomicOr(&ban[hist[i + n - 1] >> 5], 1u << (hist[i + n - 1] & 31));
+      }
+    }
+    // NoBadWords (sequences of L >= 2 ids): the last id is banned when the history ends with the other L - 1; a sequence longer
+    // than the history is skipped (4.34's SequenceBiasLogitsProcessor)
+    for (int q = lane; q < pp->n_bad; q += 64) {
+      const int o = pp->bad_off[q], L = pp->bad_off[q + 1] - o;
+      if (L > cur) continue;
+      int k = 0;
+      while (k < L - 1 && (int)hist[cur - L + 1 + k] == pp->bad_ids[o + k]) ++k;
+      const int last = pp->bad_ids[o + L - 1];
+      if (k == L - 1) atomicOr(&ban[last >> 5], 1u << (last & 31));
+    }
+  }
+  __syncthreads();
+  if (scan) {
+    m_seen = pp->penalty != 1.0f ? lane_bits<NPL>(seen, v0) : 0ull;
+    m_ban = lane_bits<NPL>(ban, v0) | (pp->has_bad1 ? lane_bits<NPL>(pp->bad1, v0) : 0ull);
+    m_post = (pp->has_supp ? lane_bits<NPL>(pp->supp, v0) : 0ull) |
+             (pp->has_begin && cur == pp->begin_index ? lane_bits<NPL>(pp->begin, v0) : 0ull);
+  }
+  if (!row) return;
+  // 4.34's _get_logits_processor order: repetition, n-gram, bad words, min length, min new tokens, forced BOS, forced EOS,
+  // suppress, begin-suppress
+  const float pen = pp->penalty;
+  const bool eos_ban = cur < pp->min_length || cur - 1 < pp->min_new;
+  const int fbos = cur == 1 ? pp->forced_bos : -1;
+  const int feos = cur == pp->max_length - 1 ? pp->forced_eos : -1;
+#pragma unroll
+  for (int j = 0; j < NPL; ++j) {
+    const int v = v0 + j;
+    if (v < a.V) {
+      if ((m_seen >> j) & 1) x[j] = x[j] < 0.f ? x[j] * pen : x[j] / pen;
+      if (((m_ban >> j) & 1) || (eos_ban && v == a.eos_id)) x[j] = -INFINITY;
+      if (fbos >= 0) x[j] = v == fbos ? 0.f : -INFINITY;
+      if (feos >= 0) x[j] = v == feos ? 0.f : -INFINITY;
+      if ((m_post >> j) & 1) x[j] = -INFINITY;
+    }
+  }
+}
+// arg-max of the row, ties to the lower id (dec_head_kernel; an all -inf row gives id 0, as torch.argmax)
+template <int NPL>
+__device__ __forceinline__ int argmax_row(const float (&x)[NPL], int v0, int V) {
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+#pragma unroll
+  for (int j = 0; j < NPL; ++j)
+    if (v0 + j < V && (x[j] > best || (x[j] == best && v0 + j < bi))) { best = x[j]; bi = v0 + j; }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+  }
+  return bi == 0x7fffffff ? 0 : bi;
+}
+// TopK: the k-th largest key, bit by bit from the top (the largest thr with count(key >= thr) >= k); counts are ballots
+template <int NPL>
+__device__ __forceinline__ unsigned topk_threshold(const unsigned (&kk)[NPL], int k, int V) {
+  unsigned thr = 0;
+  if (k < V) {
+    for (int bit = 31; bit >= 0; --bit) {
+      const unsigned cand = thr | (1u << bit);
+      int cnt = 0;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) cnt += __popcll(__ballot(kk[j] >= cand));
+      if (cnt >= k) thr = cand;
+    }
+  }
+  return thr;
+}
+// TopP: the largest key c with mass(key < c) <= (1 - top_p) * Z, capped at the key of the maximum m (which always stays); the
+// weights below c are zeroed.  -> c (0: no nucleus filter)
+template <int NPL>
+__device__ __forceinline__ unsigned topp_cutoff(const unsigned (&kk)[NPL], float (&w)[NPL], float top_p, float z, float m) {
+  unsigned c = 0;
+  if (top_p < 1.0f) {
+    const float R = (1.0f - top_p) * z;
+    for (int bit = 31; bit >= 0; --bit) {
+      const unsigned cand = c | (1u << bit);
+      float lm = 0.f;
+#pragma unroll
+      for (int j = 0; j < NPL; ++j) lm += kk[j] < cand ? w[j] : 0.f;
+      if (wave_sum_uniform(lm) <= R) c = cand;
+    }
+    c = min(c, ord_key(m));
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) if (kk[j] < c) w[j] = 0.f;
+  }
+  return c;
+}
+// draw: the first kept entry (vocabulary order) whose inclusive cumulative weight exceeds u * total, u the top 24 bits of h;
+// total = the sum of the weights in the draw's own order
+template <int NPL>
+__device__ __forceinline__ int draw_token(const float (&w)[NPL], unsigned long long h, int v0, int pad_id, float& total) {
+  const int lane = threadIdx.x & 63;
+  float ls = 0.f;
+#pragma unroll
+  for (int j = 0; j < NPL; ++j) ls += w[j];
+  float incl = ls;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  total = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, incl), 63));
+  const float target = (float)(h >> 40) * 0x1p-24f * total;
+  const unsigned long long over = __ballot(incl > target && ls > 0.f);
+  const unsigned long long any = __ballot(ls > 0.f);
+  const int sel = over ? __ffsll((long long)over) - 1 : (any ? 63 - __clzll((long long)any) : 0);
+  float acc = __shfl_up(incl, 1, 64);
+  if (lane == 0) acc = 0.f;
+  int tok = -1, last = -1;
+#pragma unroll
+  for (int j = 0; j < NPL; ++j) {
+    if (w[j] > 0.f) {
+      acc += w[j];
+      last = v0 + j;
+      if (tok < 0 && acc > target) tok = v0 + j;
+    }
+  }
+  if (tok < 0) tok = last;           // rounding put the target past this lane's last kept entry
+  tok = __shfl(tok, sel, 64);
+  return tok < 0 ? pad_id : tok;     // no finite weight at all (the overflow flag is raised)
+}
+// hf generation/utils.py (greedy_search, sample): finished rows emit pad; EOS finishes a row.  `store`: one lane of the row's
+// wavefront in a live chain.  -> the id the next step is fed
+__device__ __forceinline__ int emit_token(const DecHeadArgs& a, int b, int t, int fin, int tok, bool store, int* s_unfinished) {
+  const int next = fin ? a.pad_id : tok;
+  if (store) {
+    if (t + 1 < a.max_len) a.tokens[(int64_t)a.tok_row[b] * a.max_len + t + 1] = next;
+    const int nf = fin | (next == a.eos_id);
+    a.finished[b] = nf;
+    if (!nf) atomicAdd(s_unfinished, 1);
+  }
+  return next;
+}
+// one wavefront: the embedding of id `next` (pad for an id outside the vocabulary) into slot b's row of the fixed-point residual
+// stream; a finished chain (!live) stores nothing
+__device__ __forceinline__ void write_embedding_row(const DecHeadArgs& a, int b, int next, bool live) {
+  if (next < 0 || next >= a.V) next = a.pad_id;
+  const float* emb = a.shared + (int64_t)next * a.d;
+  for (int c = (threadIdx.x & 63) * 4; c < a.d; c += 256) {
+    const float4 e4 = *reinterpret_cast<const float4*>(emb + c);
+    xq_t* xp = a.x + (int64_t)b * a.d + c;
+    if (live) {
+      *reinterpret_cast<longlong2*>(xp) = make_longlong2(xq_fix_guarded(e4.x, a.state), xq_fix_guarded(e4.y, a.state));
+      *reinterpret_cast<longlong2*>(xp + 2) = make_longlong2(xq_fix_guarded(e4.z, a.state), xq_fix_guarded(e4.w, a.state));
+    }
+  }
+}
+// One thread per workgroup of a live chain, after the workgroup's barrier, with the workgroup's count of unfinished rows (beam
+// search: clips).  The step closes when the last workgroup is through: every workgroup has read t / done before it takes its ticket.
+__device__ __forceinline__ void close_step(DecState* stp, int t, int unfinished) {
+  if (unfinished) atomicAdd(&stp->smp_unfinished, unfinished);
+  __threadfence();
+  if (atomicAdd(&stp->smp_ticket, 1) == (int)gridDim.x - 1) {
+    __threadfence();
+    const int nu = atomicExch(&stp->smp_unfinished, 0);
+    stp->smp_ticket = 0;
+    const int nt = t + 1;
+    stp->t = nt;
+    stp->n_unfinished = nu;
+    if (nu == 0 || nt >= stp->max_steps) { stp->done = 1; stp->out_len = nt + 1; }
+  }
+}
 
-// SCORED (m2m_generate_scored, dec_scored_kernel): the same head also writes the row the token was selected from and / or the
-// token's log-probability (ScoreParams, t5.h); every addition is under `if constexpr (SCORED)`, so the unscored kernels keep
-// their instructions.
-template <int NPL, bool GREEDY, bool SCORED = false>
-__device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleParams* sp, const ProcessParams* pp,
-                                             unsigned short* s_hist, unsigned* s_bits, const ScoreParams* sc = nullptr) {
+// The select step, one row per wavefront.  GREEDY: arg-max, else the warpers and the draw (sp).  PROCESSED: the logits processors
+// first (pp); without it no ProcessParams is read and no LDS beyond the s_unfinished word is used.  SCORED: the outputs too (sc).
+template <int NPL, bool GREEDY, bool PROCESSED, bool SCORED>
+__device__ __forceinline__ void select_head(const DecHeadArgs& a, const SampleParams* sp, const ProcessParams* pp, const ScoreParams* sc) {
+  static_assert(PROCESSED || !SCORED, "the scored head is the processed head (a neutral ProcessParams block without processors)");
   __shared__ int s_unfinished;
   DecState* stp = a.state;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -2191,9 +2253,7 @@ __device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleP
   const bool row = b < a.B;
   // the row's logits are requested before the loop state is consumed (as in dec_head_kernel)
   float x[NPL];
-  const float* lg = a.logits + (int64_t)(row ? b : 0) * a.ldl;
-#pragma unroll
-  for (int j = 0; j < NPL; ++j) x[j] = (v0 + j < V) ? lg[v0 + j] : 0.f;
+  const bool bad = load_row<NPL>(a.logits + (int64_t)(row ? b : 0) * a.ldl, v0, V, x);   // the RAW logits: the processors' -inf is legal
   const float temp = GREEDY ? 1.0f : sp->temperature, top_p = GREEDY ? 1.0f : sp->top_p;
   const int top_k = GREEDY ? 0 : sp->top_k;
   const unsigned long long seed_h = GREEDY ? 0ull : splitmix64(sp->seed);
@@ -2201,97 +2261,18 @@ __device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleP
   const bool live = !(stp->done | (t >= stp->max_steps));
   if (tid == 0) s_unfinished = 0;
   __syncthreads();
-  // Processors that read the history (input_ids = the start token and t generated ids, cur_len = t + 1): the row's ids are staged
-  // in LDS from the token matrix (row tok_row[b]: the clip's own row whatever its slot), then one lane-strided pass each sets the
-  // "seen" bits (repetition penalty) and the ban bits (n-gram, bad words of two or more ids) of the row's bitmaps.
-  const int cur = t + 1;
-  unsigned long long m_seen = 0, m_ban = 0, m_post = 0;
-  {
-    unsigned short* hist = s_hist + (tid >> 6) * PROC_MAX_LEN;
-    unsigned* seen = s_bits + (tid >> 6) * 2 * PROC_BITS;
-    unsigned* ban = seen + PROC_BITS;
-    bool scan = row && live && cur <= PROC_MAX_LEN && !a.finished[b];   // a finished row emits pad whatever its scores
-    if constexpr (SCORED)   // scores of a call without processors (a neutral block): no history to stage, no bitmap to read
-      scan = scan && (pp->penalty != 1.0f || pp->ngram > 0 || pp->n_bad > 0 || pp->has_bad1 || pp->has_supp || pp->has_begin);
-    for (int i = lane; i < PROC_BITS; i += 64) { seen[i] = 0u; ban[i] = 0u; }
-    if (scan) {
-      const int64_t* hr = a.tokens + (int64_t)a.tok_row[b] * a.max_len;
-      for (int p = lane; p < cur; p += 64) hist[p] = (unsigned short)min((unsigned long long)hr[p], (unsigned long long)(PROC_MAX_VOCAB - 1));
-    }
-    __syncthreads();
-    if (scan) {
-      if (pp->penalty != 1.0f)
-        for (int p = lane; p < cur; p += 64) atomicOr(&seen[hist[p] >> 5], 1u << (hist[p] & 31));
-      // NoRepeatNGram: every complete window i .. i + n - 1 whose first n - 1 ids equal the last n - 1 ids bans its last id
-      const int n = pp->ngram;
-      if (n > 0) {
-        const int pre = cur - n + 1;
-        for (int i = lane; i + n <= cur; i += 64) {
-          int k = 0;
-          while (k < n - 1 && hist[i + k] == hist[pre + k]) ++k;
-          if (k == n - 1) atomicOr(&ban[hist[i + n - 1] >> 5], 1u << (hist[i + n - 1] & 31));
-        }
-      }
-      // NoBadWords (sequences of L >= 2 ids): the last id is banned when the history ends with the other L - 1; a sequence longer
-      // than the history is skipped (4.34's SequenceBiasLogitsProcessor)
-      for (int q = lane; q < pp->n_bad; q += 64) {
-        const int o = pp->bad_off[q], L = pp->bad_off[q + 1] - o;
-        if (L > cur) continue;
-        int k = 0;
-        while (k < L - 1 && (int)hist[cur - L + 1 + k] == pp->bad_ids[o + k]) ++k;
-        const int last = pp->bad_ids[o + L - 1];
-        if (k == L - 1) atomicOr(&ban[last >> 5], 1u << (last & 31));
-      }
-    }
-    __syncthreads();
-    if (scan) {
-      m_seen = pp->penalty != 1.0f ? lane_bits<NPL>(seen, v0) : 0ull;
-      m_ban = lane_bits<NPL>(ban, v0) | (pp->has_bad1 ? lane_bits<NPL>(pp->bad1, v0) : 0ull);
-      m_post = (pp->has_supp ? lane_bits<NPL>(pp->supp, v0) : 0ull) |
-               (pp->has_begin && cur == pp->begin_index ? lane_bits<NPL>(pp->begin, v0) : 0ull);
-    }
-  }
+  if constexpr (PROCESSED) apply_processors<NPL, SCORED>(a, pp, x, b, row, live, t + 1, v0);
   const int k = top_k > 0 ? min(top_k, V) : V;
   if (row) {
     const int fin = a.finished[b];
-    bool bad = false;
     float m = -INFINITY;
-    const float pen = pp->penalty;
-    const bool eos_ban = cur < pp->min_length || cur - 1 < pp->min_new;
-    const int fbos = cur == 1 ? pp->forced_bos : -1;
-    const int feos = cur == pp->max_length - 1 ? pp->forced_eos : -1;
 #pragma unroll
-    for (int j = 0; j < NPL; ++j) {
-      if (v0 + j < V) {
-        bad |= !(fabsf(x[j]) <= 3.0e38f);   // the RAW logits: the -inf the processors write is legal
-        // 4.34's _get_logits_processor order: repetition, n-gram, bad words, min length, min new tokens, forced BOS, forced EOS,
-        // suppress, begin-suppress
-        const int v = v0 + j;
-        if ((m_seen >> j) & 1) x[j] = x[j] < 0.f ? x[j] * pen : x[j] / pen;
-        if (((m_ban >> j) & 1) || (eos_ban && v == a.eos_id)) x[j] = -INFINITY;
-        if (fbos >= 0) x[j] = v == fbos ? 0.f : -INFINITY;
-        if (feos >= 0) x[j] = v == feos ? 0.f : -INFINITY;
-        if ((m_post >> j) & 1) x[j] = -INFINITY;
-        if (temp != 1.0f) x[j] = x[j] / temp;
-        m = fmaxf(m, x[j]);
-      }
-    }
+    for (int j = 0; j < NPL; ++j)
+      if (v0 + j < V) { if (temp != 1.0f) x[j] = x[j] / temp; m = fmaxf(m, x[j]); }
     int tok;
     float zsum = 0.f;          // SCORED: the sum of exp(x - m) over the entries the select saw (m: their maximum)
     if constexpr (GREEDY) {
-      // arg-max, ties to the lower id (dec_head_kernel; an all -inf row gives id 0, as torch.argmax)
-      float best = -INFINITY;
-      int bi = 0x7fffffff;
-#pragma unroll
-      for (int j = 0; j < NPL; ++j)
-        if (v0 + j < V && (x[j] > best || (x[j] == best && v0 + j < bi))) { best = x[j]; bi = v0 + j; }
-#pragma unroll
-      for (int o = 32; o >= 1; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-      }
-      tok = bi == 0x7fffffff ? 0 : bi;
+      tok = argmax_row<NPL>(x, v0, V);
       if constexpr (SCORED) {
         m = wave_max(m);
         float zl = 0.f;
@@ -2304,17 +2285,7 @@ __device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleP
       unsigned kk[NPL];         // order-preserving keys; 0 (below every finite logit's) past the vocabulary
 #pragma unroll
       for (int j = 0; j < NPL; ++j) kk[j] = (v0 + j < V) ? ord_key(x[j]) : 0u;
-      // TopK: the k-th largest key, bit by bit from the top (the largest thr with count(key >= thr) >= k); counts are ballots
-      unsigned thr = 0;
-      if (k < V) {
-        for (int bit = 31; bit >= 0; --bit) {
-          const unsigned cand = thr | (1u << bit);
-          int cnt = 0;
-#pragma unroll
-          for (int j = 0; j < NPL; ++j) cnt += __popcll(__ballot(kk[j] >= cand));
-          if (cnt >= k) thr = cand;
-        }
-      }
+      const unsigned thr = topk_threshold<NPL>(kk, k, V);
       float w[NPL];
       float z = 0.f;
 #pragma unroll
@@ -2323,181 +2294,87 @@ __device__ __forceinline__ void process_head(const DecHeadArgs& a, const SampleP
         z += w[j];
       }
       z = wave_sum_uniform(z);
-      unsigned cut = 0;          // SCORED: the nucleus cutoff key (0: no top-p filter)
-      // TopP: the largest key c with mass(key < c) <= (1 - top_p) * Z, capped at the maximum's key (which always stays)
-      if (top_p < 1.0f) {
-        const float R = (1.0f - top_p) * z;
-        unsigned c = 0;
-        for (int bit = 31; bit >= 0; --bit) {
-          const unsigned cand = c | (1u << bit);
-          float lm = 0.f;
-#pragma unroll
-          for (int j = 0; j < NPL; ++j) lm += kk[j] < cand ? w[j] : 0.f;
-          if (wave_sum_uniform(lm) <= R) c = cand;
-        }
-        c = min(c, ord_key(m));
-#pragma unroll
-        for (int j = 0; j < NPL; ++j) if (kk[j] < c) w[j] = 0.f;
-        if constexpr (SCORED) cut = c;
-      }
-      // draw: the first kept entry (vocabulary order) whose inclusive cumulative weight exceeds u * Z
-      float ls = 0.f;
-#pragma unroll
-      for (int j = 0; j < NPL; ++j) ls += w[j];
-      float incl = ls;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const float up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-      }
-      const float total = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, incl), 63));
+      const unsigned cut = topp_cutoff<NPL>(kk, w, top_p, z, m);
       const unsigned long long h = splitmix64(seed_h ^ (((unsigned long long)(unsigned)a.tok_row[b] << 32) | (unsigned)t));
-      const float target = (float)(h >> 40) * 0x1p-24f * total;
-      const unsigned long long over = __ballot(incl > target && ls > 0.f);
-      const unsigned long long any = __ballot(ls > 0.f);
-      const int sel = over ? __ffsll((long long)over) - 1 : (any ? 63 - __clzll((long long)any) : 0);
-      float acc = __shfl_up(incl, 1, 64);
-      if (lane == 0) acc = 0.f;
-      int tk = -1, last = -1;
-#pragma unroll
-      for (int j = 0; j < NPL; ++j) {
-        if (w[j] > 0.f) {
-          acc += w[j];
-          last = v0 + j;
-          if (tk < 0 && acc > target) tk = v0 + j;
-        }
-      }
-      if (tk < 0) tk = last;             // rounding put the target past this lane's last kept entry
-      tk = __shfl(tk, sel, 64);
-      if (tk < 0) tk = a.pad_id;         // no finite weight at all (the overflow flag is raised)
-      tok = tk;
+      // the log-probability's sum is over what both filters kept - the draw's total, not z, which still holds the mass top-p removed
+      tok = draw_token<NPL>(w, h, v0, a.pad_id, zsum);
       if constexpr (SCORED) {
-        // HF's warped row: what top-k and top-p removed is -inf (by the keys, not by w: a kept entry's weight may underflow to 0);
-        // the log-probability's sum is over what both filters kept - `total`, not z, which still holds the mass top-p removed
+        // HF's warped row: what top-k and top-p removed is -inf (by the keys, not by w: a kept entry's weight may underflow to 0)
 #pragma unroll
         for (int j = 0; j < NPL; ++j) if (kk[j] < thr || kk[j] < cut) x[j] = -INFINITY;
-        zsum = total;
       }
     }
     if (__ballot(bad) && live && lane == 0) stp->overflow = 1;
-    // hf generation/utils.py (sample): finished rows emit pad; EOS finishes a row
-    int next = fin ? a.pad_id : tok;
-    if constexpr (SCORED) {
-      // a row that finished before this step writes nothing (the caller's buffers are zeroed); t < steps and the clip < rows while live
-      if (live && !fin) {
-        const int clip = a.tok_row[b];
-        if (sc->scores) {
-          float* dst = sc->scores + ((int64_t)t * sc->rows + clip) * V;
-          if (sc->vec4) {            // V % 4 == 0 and an aligned base: 16-byte stores, NPL / 4 per lane over NPL contiguous floats
+    // a row that finished before this step writes nothing (the caller's buffers are zeroed); t < steps and the clip < rows while live
+    if (SCORED && live && !fin) {
+      const int clip = a.tok_row[b];
+      if (sc->scores) {
+        float* dst = sc->scores + ((int64_t)t * sc->rows + clip) * V;
+        if (sc->vec4) {            // V % 4 == 0 and an aligned base: 16-byte stores, NPL / 4 per lane over NPL contiguous floats
 #pragma unroll
-            for (int q = 0; q < NPL; q += 4)
-              if (v0 + q < V) *reinterpret_cast<float4*>(dst + v0 + q) = make_float4(x[q], x[q + 1], x[q + 2], x[q + 3]);
-          } else {
+          for (int q = 0; q < NPL; q += 4)
+            if (v0 + q < V) *reinterpret_cast<float4*>(dst + v0 + q) = make_float4(x[q], x[q + 1], x[q + 2], x[q + 3]);
+        } else {
 #pragma unroll
-            for (int j = 0; j < NPL; ++j) if (v0 + j < V) dst[v0 + j] = x[j];
-          }
-        }
-        if (sc->logprobs) {          // log_softmax(row)[token]: NaN for a row without a finite entry, as torch's
-          const int tk = (tok >= 0 && tok < V) ? tok : 0;
-          float xs = 0.f;
-#pragma unroll
-          for (int j = 0; j < NPL; ++j) if (v0 + j == tk) xs = x[j];
-          xs = __shfl(xs, tk / NPL, 64);
-          if (lane == 0) sc->logprobs[(int64_t)clip * sc->steps + t] = (xs - m) - logf(zsum);
+          for (int j = 0; j < NPL; ++j) if (v0 + j < V) dst[v0 + j] = x[j];
         }
       }
-    }
-    if (lane == 0 && live) {
-      if (t + 1 < a.max_len) a.tokens[(int64_t)a.tok_row[b] * a.max_len + t + 1] = next;
-      const int nf = fin | (next == a.eos_id);
-      a.finished[b] = nf;
-      if (!nf) atomicAdd(&s_unfinished, 1);
-    }
-    if (next < 0 || next >= V) next = a.pad_id;
-    const float* emb = a.shared + (int64_t)next * a.d;
-    for (int c = lane * 4; c < a.d; c += 256) {
-      const float4 e4 = *reinterpret_cast<const float4*>(emb + c);
-      xq_t* xp = a.x + (int64_t)b * a.d + c;
-      if (live) {
-        *reinterpret_cast<longlong2*>(xp) = make_longlong2(xq_fix_guarded(e4.x, stp), xq_fix_guarded(e4.y, stp));
-        *reinterpret_cast<longlong2*>(xp + 2) = make_longlong2(xq_fix_guarded(e4.z, stp), xq_fix_guarded(e4.w, stp));
+      if (sc->logprobs) {          // log_softmax(row)[token]: NaN for a row without a finite entry, as torch's
+        const int tk = (tok >= 0 && tok < V) ? tok : 0;
+        float xs = 0.f;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) if (v0 + j == tk) xs = x[j];
+        xs = __shfl(xs, tk / NPL, 64);
+        if (lane == 0) sc->logprobs[(int64_t)clip * sc->steps + t] = (xs - m) - logf(zsum);
       }
     }
+    const int next = emit_token(a, b, t, fin, tok, lane == 0 && live, &s_unfinished);
+    write_embedding_row(a, b, next, live);
   }
-  // the step closes when the last workgroup is through: every workgroup has read t / done above before it takes its ticket
   __syncthreads();
-  if (tid == 0 && live) {
-    if (s_unfinished) atomicAdd(&stp->smp_unfinished, s_unfinished);
-    __threadfence();
-    if (atomicAdd(&stp->smp_ticket, 1) == (int)gridDim.x - 1) {
-      __threadfence();
-      const int nu = atomicExch(&stp->smp_unfinished, 0);
-      stp->smp_ticket = 0;
-      const int nt = t + 1;
-      stp->t = nt;
-      stp->n_unfinished = nu;
-      if (nu == 0 || nt >= stp->max_steps) { stp->done = 1; stp->out_len = nt + 1; }
-    }
-  }
+  if (tid == 0 && live) close_step(stp, t, s_unfinished);
 }
 
+template <int NPL>
+__global__ __launch_bounds__(64 * SAMPLE_ROWS) void dec_sample_kernel(DecHeadArgs a, const SampleParams* sp) {
+  select_head<NPL, false, false, false>(a, sp, nullptr, nullptr);
+}
 template <int NPL, bool GREEDY>
 __global__ __launch_bounds__(64 * SAMPLE_ROWS) void dec_process_kernel(DecHeadArgs a, const SampleParams* sp, const ProcessParams* pp) {
-  __shared__ unsigned short s_hist[SAMPLE_ROWS * PROC_MAX_LEN];
-  __shared__ unsigned s_bits[SAMPLE_ROWS * 2 * PROC_BITS];
-  process_head<NPL, GREEDY>(a, sp, pp, s_hist, s_bits);
+  select_head<NPL, GREEDY, true, false>(a, sp, pp, nullptr);
 }
-
-template <bool GREEDY>
-static void launch_dec_process_v(const DecHeadArgs& h, const SampleParams* sp, const ProcessParams* pp, dim3 grid, dim3 block,
-                                 hipStream_t st) {
-  if (h.V <= 64 * 8) hipLaunchKernelGGL((dec_process_kernel<8, GREEDY>), grid, block, 0, st, h, sp, pp);
-  else if (h.V <= 64 * 16) hipLaunchKernelGGL((dec_process_kernel<16, GREEDY>), grid, block, 0, st, h, sp, pp);
-  else if (h.V <= 64 * 32) hipLaunchKernelGGL((dec_process_kernel<32, GREEDY>), grid, block, 0, st, h, sp, pp);
-  else hipLaunchKernelGGL((dec_process_kernel<64, GREEDY>), grid, block, 0, st, h, sp, pp);
-}
-
-static int launch_dec_process(const DecHeadArgs& h, const SampleParams* sp, const ProcessParams* pp, bool greedy, hipStream_t st) {
-  M2M_REQUIRE(h.V >= 1 && h.V <= PROC_MAX_VOCAB, "dec_process_kernel: vocab_size %d outside [1, %d]", h.V, PROC_MAX_VOCAB);
-  const dim3 grid((unsigned)ceil_div(h.B, SAMPLE_ROWS)), block(64 * SAMPLE_ROWS);
-  if (greedy) launch_dec_process_v<true>(h, sp, pp, grid, block, st);
-  else launch_dec_process_v<false>(h, sp, pp, grid, block, st);
-  M2M_CHECK_HIP(hipGetLastError());
-  return M2M_OK;
-}
-
-// =========================================================== scored head ====
-// m2m_generate_scored: the processed head (with a neutral ProcessParams block when the call has no processor) that also writes, for
-// every live row, the fp32 row the token was selected from (HF's `scores`: raw, processed or warped logits, removed entries -inf) to
-// scores[t][clip][0:V] and / or log_softmax(that row)[token] to logprobs[clip][t].  The row is in the wavefront's registers when the
-// token is selected, so the log-probability costs one wave-wide max and sum and a 4-byte store; the row itself is only written when
-// asked for.  clip = tok_row[b]: the outputs follow the clip through live-row re-packing and chains of any size.  The output
-// pointers come from the ScoreParams block of the workspace, so one captured graph serves every call.
 template <int NPL, bool GREEDY>
 __global__ __launch_bounds__(64 * SAMPLE_ROWS) void dec_scored_kernel(DecHeadArgs a, const SampleParams* sp, const ProcessParams* pp,
                                                                       const ScoreParams* sc) {
-  __shared__ unsigned short s_hist[SAMPLE_ROWS * PROC_MAX_LEN];
-  __shared__ unsigned s_bits[SAMPLE_ROWS * 2 * PROC_BITS];
-  process_head<NPL, GREEDY, true>(a, sp, pp, s_hist, s_bits, sc);
+  select_head<NPL, GREEDY, true, true>(a, sp, pp, sc);
 }
 
-template <bool GREEDY>
-static void launch_dec_scored_v(const DecHeadArgs& h, const SampleParams* sp, const ProcessParams* pp, const ScoreParams* sc, dim3 grid,
-                                dim3 block, hipStream_t st) {
-  if (h.V <= 64 * 8) hipLaunchKernelGGL((dec_scored_kernel<8, GREEDY>), grid, block, 0, st, h, sp, pp, sc);
-  else if (h.V <= 64 * 16) hipLaunchKernelGGL((dec_scored_kernel<16, GREEDY>), grid, block, 0, st, h, sp, pp, sc);
-  else if (h.V <= 64 * 32) hipLaunchKernelGGL((dec_scored_kernel<32, GREEDY>), grid, block, 0, st, h, sp, pp, sc);
-  else hipLaunchKernelGGL((dec_scored_kernel<64, GREEDY>), grid, block, 0, st, h, sp, pp, sc);
-}
-
-static int launch_dec_scored(const DecHeadArgs& h, const SampleParams* sp, const ProcessParams* pp, const ScoreParams* sc, bool greedy,
-                             hipStream_t st) {
-  M2M_REQUIRE(h.V >= 1 && h.V <= PROC_MAX_VOCAB, "dec_scored_kernel: vocab_size %d outside [1, %d]", h.V, PROC_MAX_VOCAB);
-  const dim3 grid((unsigned)ceil_div(h.B, SAMPLE_ROWS)), block(64 * SAMPLE_ROWS);
-  if (greedy) launch_dec_scored_v<true>(h, sp, pp, sc, grid, block, st);
-  else launch_dec_scored_v<false>(h, sp, pp, sc, grid, block, st);
+// launch(integral_constant NPL) for a head that keeps a row in one wavefront's registers: NPL logits per lane, the smallest of 8, 16,
+// 32, 64 with V <= 64 NPL
+template <typename F>
+static int launch_vocab_band(const char* kernel, int V, F launch) {
+  M2M_REQUIRE(V >= 1 && V <= SAMPLE_MAX_VOCAB, "%s: vocab_size %d outside [1, %d]", kernel, V, SAMPLE_MAX_VOCAB);
+  if (V <= 64 * 8) launch(std::integral_constant<int, 8>());
+  else if (V <= 64 * 16) launch(std::integral_constant<int, 16>());
+  else if (V <= 64 * 32) launch(std::integral_constant<int, 32>());
+  else launch(std::integral_constant<int, 64>());
   M2M_CHECK_HIP(hipGetLastError());
   return M2M_OK;
+}
+
+// head_mode: HEAD_SAMPLE, HEAD_PROCESSED | select, HEAD_SCORED | HEAD_PROCESSED | select (select: HEAD_GREEDY or HEAD_SAMPLE)
+static int launch_dec_select(const DecHeadArgs& h, int head_mode, const SampleParams* sp, const ProcessParams* pp, const ScoreParams* sc,
+                             hipStream_t st) {
+  const bool scored = head_mode & HEAD_SCORED, processed = head_mode & HEAD_PROCESSED, greedy = !(head_mode & HEAD_SAMPLE);
+  const dim3 grid((unsigned)ceil_div(h.B, SAMPLE_ROWS)), block(64 * SAMPLE_ROWS);
+  return launch_vocab_band(scored ? "dec_scored_kernel" : processed ? "dec_process_kernel" : "dec_sample_kernel", h.V, [&](auto npl) {
+    constexpr int NPL = decltype(npl)::value;
+    if (scored && greedy) hipLaunchKernelGGL((dec_scored_kernel<NPL, true>), grid, block, 0, st, h, sp, pp, sc);
+    else if (scored) hipLaunchKernelGGL((dec_scored_kernel<NPL, false>), grid, block, 0, st, h, sp, pp, sc);
+    else if (processed && greedy) hipLaunchKernelGGL((dec_process_kernel<NPL, true>), grid, block, 0, st, h, sp, pp);
+    else if (processed) hipLaunchKernelGGL((dec_process_kernel<NPL, false>), grid, block, 0, st, h, sp, pp);
+    else hipLaunchKernelGGL(dec_sample_kernel<NPL>, grid, block, 0, st, h, sp);
+  });
 }
 
 // ============================================================== beam head ====
@@ -2510,7 +2387,7 @@ static int launch_dec_scored(const DecHeadArgs& h, const SampleParams* sp, const
 // A beam is a path through the self K/V caches (DecAttnArgs::anc): new beam i of parent p gets p's ancestry plus p at position t,
 // double-buffered by the parity of t; the token fed at position j of slot s stays in the token matrix at [s][j] (written once).
 // A hypothesis keeps a snapshot of its tokens.  The rows of a done clip are marked finished (their K/V streams stop); the step
-// closes when the last workgroup is through (the sampling head's ticket), the chain is done when every clip is.
+// closes when the last workgroup is through (close_step, the select heads' ticket), the chain is done when every clip is.
 struct DecBeamArgs {
   BeamParams* p;           // the call's parameters (device block; max_hyp_len is written by the finalize kernel)
   BeamClip* clip;          // [clips of the view]
@@ -2581,13 +2458,10 @@ __global__ __launch_bounds__(1024) void dec_beam_kernel(DecHeadArgs a, DecBeamAr
       const float* lg = a.logits + (int64_t)(r0 + r) * a.ldl;
       const int v0 = lane * NPL;
       float x[NPL];
-      bool bad = false;
+      const bool bad = load_row<NPL>(lg, v0, V, x);
       float m = -INFINITY;
 #pragma unroll
-      for (int j = 0; j < NPL; ++j) {
-        x[j] = (v0 + j < V) ? lg[v0 + j] : 0.f;
-        if (v0 + j < V) { bad |= !(fabsf(x[j]) <= 3.0e38f); m = fmaxf(m, x[j]); }
-      }
+      for (int j = 0; j < NPL; ++j) if (v0 + j < V) m = fmaxf(m, x[j]);
       m = wave_max(m);
       float z = 0.f;
 #pragma unroll
@@ -2678,45 +2552,23 @@ __global__ __launch_bounds__(1024) void dec_beam_kernel(DecHeadArgs a, DecBeamAr
       } else if (lane == 0) {
         a.finished[r0 + i] = 1;     // a done clip: its rows stop streaming K/V
       }
-      int next = dn ? a.pad_id : s_tok[i];
-      if (next < 0 || next >= V) next = a.pad_id;
-      const float* emb = a.shared + (int64_t)next * a.d;
-      for (int c = lane * 4; c < a.d; c += 256) {
-        const float4 e4 = *reinterpret_cast<const float4*>(emb + c);
-        xq_t* xp = a.x + (int64_t)(r0 + i) * a.d + c;
-        *reinterpret_cast<longlong2*>(xp) = make_longlong2(xq_fix_guarded(e4.x, stp), xq_fix_guarded(e4.y, stp));
-        *reinterpret_cast<longlong2*>(xp + 2) = make_longlong2(xq_fix_guarded(e4.z, stp), xq_fix_guarded(e4.w, stp));
-      }
+      write_embedding_row(a, r0 + i, dn ? a.pad_id : s_tok[i], true);
     }
   }
-  // E. the step closes when the last workgroup is through (every workgroup has read t / done above before it takes its ticket)
+  // E. the step closes by the select heads' ticket; the count is of clips, not rows
   __syncthreads();
   if (tid == 0 && live) {
     if (s_bad) stp->overflow = 1;
-    if (!s_done) atomicAdd(&stp->smp_unfinished, 1);
-    __threadfence();
-    if (atomicAdd(&stp->smp_ticket, 1) == (int)gridDim.x - 1) {
-      __threadfence();
-      const int nu = atomicExch(&stp->smp_unfinished, 0);
-      stp->smp_ticket = 0;
-      const int nt = t + 1;
-      stp->t = nt;
-      stp->n_unfinished = nu;
-      if (nu == 0 || nt >= stp->max_steps) { stp->done = 1; stp->out_len = nt + 1; }
-    }
+    close_step(stp, t, s_done ? 0 : 1);
   }
 }
 
 static int launch_dec_beam(const DecHeadArgs& h, const DecBeamArgs& bm, int nbeams, hipStream_t st) {
-  M2M_REQUIRE(h.V >= 1 && h.V <= SAMPLE_MAX_VOCAB, "dec_beam_kernel: vocab_size %d outside [1, %d]", h.V, SAMPLE_MAX_VOCAB);
   M2M_REQUIRE(nbeams >= 2 && nbeams <= BEAM_MAX && h.B % nbeams == 0, "dec_beam_kernel: %d rows are not clips of %d beams", h.B, nbeams);
   const dim3 grid((unsigned)(h.B / nbeams)), block(1024);
-  if (h.V <= 64 * 8) hipLaunchKernelGGL(dec_beam_kernel<8>, grid, block, 0, st, h, bm);
-  else if (h.V <= 64 * 16) hipLaunchKernelGGL(dec_beam_kernel<16>, grid, block, 0, st, h, bm);
-  else if (h.V <= 64 * 32) hipLaunchKernelGGL(dec_beam_kernel<32>, grid, block, 0, st, h, bm);
-  else hipLaunchKernelGGL(dec_beam_kernel<64>, grid, block, 0, st, h, bm);
-  M2M_CHECK_HIP(hipGetLastError());
-  return M2M_OK;
+  return launch_vocab_band("dec_beam_kernel", h.V, [&](auto npl) {
+    hipLaunchKernelGGL(dec_beam_kernel<decltype(npl)::value>, grid, block, 0, st, h, bm);
+  });
 }
 
 // before the first step of a chain: beam 0 of every clip starts at score 0, the others at -1e9 (hf _beam_search), empty stores
@@ -3043,12 +2895,8 @@ int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* log
   if ((rc = launch_dec_gemm(P, a, st))) return rc;
   if (headless) return M2M_OK;             // the arg-max key is consumed by the next step's layer 0 (or by decode_finalize)
   DecHeadArgs h = head_args(s, v, forced, logits_out, Ld);
-  if (!forced && (s->head_mode & HEAD_SCORED))
-    return launch_dec_scored(h, s->sample_dev, s->proc_dev, s->score_dev, !(s->head_mode & HEAD_SAMPLE), st);
-  if (!forced && (s->head_mode & HEAD_PROCESSED))
-    return launch_dec_process(h, s->sample_dev, s->proc_dev, !(s->head_mode & HEAD_SAMPLE), st);
-  if (!forced && s->head_mode == HEAD_SAMPLE) return launch_dec_sample(h, s->sample_dev, st);
   if (!forced && s->head_mode == HEAD_BEAM) return launch_dec_beam(h, beam_args(s, v), s->beam_nb, st);
+  if (!forced && s->head_mode != HEAD_GREEDY) return launch_dec_select(h, s->head_mode, s->sample_dev, s->proc_dev, s->score_dev, st);
   hipLaunchKernelGGL(dec_head_kernel, dim3(1), dim3(1024), 0, st, h);
   M2M_CHECK_HIP(hipGetLastError());
   return M2M_OK;

@@ -65,12 +65,13 @@ struct DecState {
   int t_copy;        // headless greedy loop: t of the current step, rewritten every step by the layer-0 cross kernel (the lm_head
                      // kernel, which ADVANCES t at its end, reads this stable copy instead of t itself)
   int zero;          // always 0 (cleared with the rest of the state, never written): what a "never skip" row flag points at
-  int smp_unfinished;  // sampling head (several workgroups per step): unfinished rows summed over the workgroups of the step ...
-  int smp_ticket;      // ... and workgroups done; the last one closes the step and clears both
+  int smp_unfinished;  // select and beam heads (several workgroups per step; decode.hip close_step): unfinished rows or clips summed ...
+  int smp_ticket;      // ... over the step's workgroups, and workgroups done; the last one closes the step and clears both
 };
 
-// Parameters of the sampling head (dec_sample_kernel), a device block of the session workspace: written with an async copy before
-// every m2m_generate_sample, so one captured graph serves every call and every seed.
+// Parameters of the sampling select (decode.hip select_head: dec_sample_kernel and the sampled forms of dec_process_kernel and
+// dec_scored_kernel), a device block of the session workspace: written with an async copy before every sampled call, so one
+// captured graph serves every call and every seed.
 struct SampleParams {
   float temperature;        // > 0; 1 = no scaling
   int top_k;                // 0 = no top-k filter
@@ -344,7 +345,7 @@ constexpr int HEAD_SCORED = 8;           // bit: the processed head that also wr
 constexpr int BEAM_MAX = 32;             // beams per clip: one LDS list of 2 x 32 candidates per beam, ancestries in bytes
 int decode_beam_init(m2m_session* s, const DecView& v, hipStream_t st);
 int decode_beam_finalize(m2m_session* s, int rows, int steps, int64_t* out, float* scores, int max_length, hipStream_t st);
-constexpr int SAMPLE_MAX_VOCAB = 4096;   // dec_sample_kernel keeps a row in the registers of one wavefront (64 lanes x 64 logits)
+constexpr int SAMPLE_MAX_VOCAB = 4096;   // the select and beam heads keep a row in the registers of one wavefront (64 lanes x 64 logits)
 int decode_attn_clips(const m2m_session* s, int nb);
 int decode_ff_rows(const m2m_session* s, int nb);
 int decode_ff_slices(const m2m_session* s, int nb);

@@ -213,6 +213,27 @@ def test_sampling_head_across_the_vocabulary_bands(V):
             assert all(v == g.pad_token_id for v in row[end + 1:]), (b, row)
 
 
+@pytest.mark.parametrize("V", [400, 1024, 2048, 4096])
+def test_sampled_ids_are_the_same_from_every_select_kernel(V):
+    """dec_sample_kernel, dec_process_kernel and dec_scored_kernel are one select body (decode.hip select_head): with the same
+    seed and processors that cannot alter a row they emit the same ids, at one vocabulary in each logits-per-lane band, without
+    warpers and with all three.  The legs: plain do_sample=True (dec_sample_kernel); output_logprobs=True (dec_scored_kernel with
+    the neutral processor block); min_length=1 (dec_process_kernel: resolve_generate_kwargs takes any min_length > 0 as an active
+    processor, and cur_len >= 1 never falls below it, so EOS is never banned).  Not yet run on a GPU, neither on this tree
+    nor on the build before the fold (where it would prove that the three copies agreed): see DESIGN.md section 17."""
+    model, _, g, _ = build_geom(geom_config(V), "fp32", head=tail_head)
+    B, S, L = 5, 19, 32
+    x = embeds(B, S, g.d_model, seed=V % 89).cuda()
+    for seed, kw in enumerate([dict(temperature=1.0, top_k=0, top_p=1.0), dict(temperature=0.7, top_k=50, top_p=0.9)]):
+        def ids(**more):
+            torch.manual_seed(300 + seed)
+            out = model.generate_from_embeds(x, max_length=L, do_sample=True, **kw, **more)
+            return (out.sequences if more.get("return_dict_in_generate") else out).cpu()
+        plain = ids()
+        assert torch.equal(ids(return_dict_in_generate=True, output_logprobs=True), plain), (V, kw)
+        assert torch.equal(ids(min_length=1), plain), (V, kw)
+
+
 def first_step_head(sd, geom, orc_cls, x1, targets):
     """lm_head whose first-step logits are `targets` {row: logit} (every other row 0): the oracle's first-step hidden state h is
     read through an identity head, then row r = targets[r] * h / |h|^2 (the head does not feed back into that step)"""
