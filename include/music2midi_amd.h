@@ -331,6 +331,22 @@ int m2m_generate_scored(m2m_session* s, int max_length, const m2m_process_params
                         int64_t* tokens_out_dev, float* scores_out_dev, float* logprobs_out_dev, int* out_len_host, void* stream);
 
 /*
+ * The same decode constrained to the MIDI token grammar (music2midi_amd/grammar.py; hf: generate(prefix_allowed_tokens_fn=...),
+ * PrefixConstrainedLogitsProcessor): at every step the ids that may not follow the row's prefix go to -inf, after the min_length /
+ * min_new_tokens bans and before forced_bos_token_id (4.34's place for the processor).  Pitch ids are [pitch_offset, pitch_offset +
+ * n_pitch), time ids the n_time ids after them; EOS = 2, ONSET = 3 and OFFSET = 4 as the tokenizer writes them.  The state of a row
+ * (phase, last time index, the sounding pitches of earlier groups and of the current one: 48 bytes per clip in the workspace) is
+ * advanced by the id actually emitted, so a step costs O(1) whatever its position.  grammar == NULL is m2m_generate_scored.
+ * proc, sample and the two outputs are as there (all optional; with both outputs NULL the unscored processed head runs).
+ * M2M_ERR_INVALID: pitch_offset < 5, n_pitch outside [1, 128], n_time < 1, pitch_offset + n_pitch + n_time > vocab_size, vocab_size
+ * > 4096, max_length > 2048, eos_token_id != 2.
+ */
+typedef struct { int pitch_offset, n_pitch, n_time; } m2m_grammar_params;
+int m2m_generate_grammar(m2m_session* s, int max_length, const m2m_grammar_params* grammar, const m2m_process_params* proc,
+                         const m2m_sample_params* sample, int64_t* tokens_out_dev, float* scores_out_dev, float* logprobs_out_dev,
+                         int* out_len_host, void* stream);
+
+/*
  * Rows end at different steps (ref: music2midi/model.py:115-135 decodes chunks of inference.batch_size = 128 three-second
  * segments to max_length 1024; a trained checkpoint ends a segment after tens to hundreds of tokens).  Once a quarter of the
  * rows still being decoded have emitted EOS, m2m_generate_greedy (and m2m_generate_sample, m2m_generate_processed) re-packs the live rows into the first slots of the batch at its

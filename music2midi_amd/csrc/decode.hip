@@ -2045,9 +2045,11 @@ __device__ inline unsigned long long lane_bits(const unsigned* w, int v0) {   //
 // token matrix (row tok_row[b]: the clip's own row whatever its slot), and 4 KB their bitmaps: one lane-strided pass each sets the
 // "seen" bits (repetition penalty) and the ban bits (n-gram, bad words of two or more ids).  The ids that do not depend on the
 // history (suppress, begin-suppress, one-id bad words) come as bitmaps of the parameter block.
-template <int NPL, bool SCORED>
+// m_gram: the ids of this lane the token grammar bans (grammar_banned; 0 without it), applied where 4.34 puts
+// PrefixConstrainedLogitsProcessor: after the two EOS bans, before forced BOS.
+template <int NPL>
 __device__ __forceinline__ void apply_processors(const DecHeadArgs& a, const ProcessParams* pp, float (&x)[NPL], int b, bool row,
-                                                 bool live, int cur, int v0) {
+                                                 bool live, int cur, int v0, unsigned long long m_gram) {
   __shared__ unsigned short s_hist[SAMPLE_ROWS][PROC_MAX_LEN];
   __shared__ unsigned s_bits[SAMPLE_ROWS][2][PROC_BITS];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -2055,8 +2057,8 @@ __device__ __forceinline__ void apply_processors(const DecHeadArgs& a, const Pro
   unsigned short* hist = s_hist[wave];
   unsigned *seen = s_bits[wave][0], *ban = s_bits[wave][1];
   bool scan = row && live && cur <= PROC_MAX_LEN && !a.finished[b];   // a finished row emits pad whatever its scores
-  if constexpr (SCORED)   // scores of a call without processors (a neutral block): no history to stage, no bitmap to read
-    scan = scan && (pp->penalty != 1.0f || pp->ngram > 0 || pp->n_bad > 0 || pp->has_bad1 || pp->has_supp || pp->has_begin);
+  // no processor that looks at the history or at a bitmap (scores or the grammar over a neutral block, min_length alone): nothing to stage
+  scan = scan && (pp->penalty != 1.0f || pp->ngram > 0 || pp->n_bad > 0 || pp->has_bad1 || pp->has_supp || pp->has_begin);
   for (int i = lane; i < PROC_BITS; i += 64) { seen[i] = 0u; ban[i] = 0u; }
   if (scan) {
     const int64_t* hr = a.tokens + (int64_t)a.tok_row[b] * a.max_len;
@@ -2106,11 +2108,72 @@ __device__ __forceinline__ void apply_processors(const DecHeadArgs& a, const Pro
     const int v = v0 + j;
     if (v < a.V) {
       if ((m_seen >> j) & 1) x[j] = x[j] < 0.f ? x[j] * pen : x[j] / pen;
-      if (((m_ban >> j) & 1) || (eos_ban && v == a.eos_id)) x[j] = -INFINITY;
+      if ((((m_ban | m_gram) >> j) & 1) || (eos_ban && v == a.eos_id)) x[j] = -INFINITY;
       if (fbos >= 0) x[j] = v == fbos ? 0.f : -INFINITY;
       if (feos >= 0) x[j] = v == feos ? 0.f : -INFINITY;
       if ((m_post >> j) & 1) x[j] = -INFINITY;
     }
+  }
+}
+// The MIDI token grammar (m2m_generate_grammar; music2midi_amd/grammar.py defines it, t5.h GrammarState holds a clip's state).
+// Bits [lo, hi) of the vocabulary as they fall into this lane's ids v0 .. v0 + NPL - 1 (bit j = id v0 + j).
+template <int NPL>
+__device__ __forceinline__ unsigned long long lane_range_bits(int lo, int hi, int v0) {
+  const int l = max(lo, v0) - v0, h = min(hi, v0 + NPL) - v0;
+  if (h <= l) return 0ull;
+  return (h - l >= 64 ? ~0ull : ((1ull << (h - l)) - 1)) << l;
+}
+// The ids of this lane the grammar BANS after the clip's prefix.  The state is the same for the whole wavefront (one row): every
+// lane loads the same 48 bytes and the first lane's values become scalars; the allowed set is range compares on them plus, for the
+// pitch ids, a 64-bit window of the 128-bit pitch set.  No LDS, no history: the cost does not depend on the position.
+template <int NPL>
+__device__ __forceinline__ unsigned long long grammar_banned(const GrammarParams* gp, const GrammarState* st, int v0, int V) {
+  auto uni = [](unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); };
+  const uint4* q = reinterpret_cast<const uint4*>(st);
+  const uint4 hd = q[0], o4 = q[1], n4 = q[2];
+  const int phase = (int)uni(hd.x), next_time = (int)uni(hd.y);
+  const unsigned o0 = uni(o4.x), o1 = uni(o4.y), o2 = uni(o4.z), o3 = uni(o4.w);
+  const unsigned n0 = uni(n4.x), n1 = uni(n4.y), n2 = uni(n4.z), n3 = uni(n4.w);
+  const int pitch0 = gp->pitch0, time0 = gp->time0, end = gp->end;
+  const bool list_end = phase == GRAM_START || phase == GRAM_ONSET_LIST || phase == GRAM_OFFSET_LIST;   // a group may end here
+  const bool onset = phase == GRAM_ONSET_OPEN || phase == GRAM_ONSET_LIST, offset = phase == GRAM_OFFSET_OPEN || phase == GRAM_OFFSET_LIST;
+  const bool any_old = (o0 | o1 | o2 | o3) != 0u;
+  unsigned long long ok = 0ull;
+  if (list_end) ok |= lane_range_bits<NPL>(GRAM_EOS, GRAM_EOS + 1, v0) | lane_range_bits<NPL>(time0 + next_time, end, v0);
+  if (phase == GRAM_TIME) ok |= lane_range_bits<NPL>(GRAM_ONSET, GRAM_ONSET + 1, v0);
+  if ((phase == GRAM_TIME || phase == GRAM_ONSET_LIST) && any_old) ok |= lane_range_bits<NPL>(GRAM_OFFSET, GRAM_OFFSET + 1, v0);
+  if (onset || offset) {
+    // the pitch set the phase allows: not yet struck in this group, or sounding from an earlier one
+    const unsigned long long w0 = onset ? ~(((unsigned long long)n1 << 32) | n0) : (((unsigned long long)o1 << 32) | o0);
+    const unsigned long long w1 = onset ? ~(((unsigned long long)n3 << 32) | n2) : (((unsigned long long)o3 << 32) | o2);
+    const int p0 = v0 - pitch0;          // pitch of this lane's first id (negative: the pitch ids start inside or past its ids)
+    unsigned long long win = 0ull;       // bit j = pitch p0 + j of the set
+    if (p0 <= -64 || p0 >= GRAM_MAX_PITCH) win = 0ull;
+    else if (p0 < 0) win = w0 << (-p0);
+    else if (p0 == 0) win = w0;
+    else if (p0 < 64) win = (w0 >> p0) | (w1 << (64 - p0));
+    else win = w1 >> (p0 - 64);
+    ok |= win & lane_range_bits<NPL>(pitch0, time0, v0);
+  }
+  return ~ok & lane_range_bits<NPL>(0, V, v0);
+}
+// One lane, after the token store: the transition for the id the row actually emitted (forced, drawn or the arg-max), written back
+// with plain stores.  The function is total: an id that is no time, mode or pitch id (PAD, BOS, EOS, the unused tail) changes nothing.
+__device__ __forceinline__ void grammar_advance(const GrammarParams* gp, GrammarState* st, int tok) {
+  const int phase = st->phase;
+  if (tok >= gp->time0 && tok < gp->end) {
+#pragma unroll
+    for (int i = 0; i < GRAM_MAX_PITCH / 32; ++i) { st->open_old[i] |= st->open_new[i]; st->open_new[i] = 0u; }
+    st->next_time = tok - gp->time0 + 1;
+    st->phase = GRAM_TIME;
+  } else if (tok == GRAM_ONSET) {
+    st->phase = GRAM_ONSET_OPEN;
+  } else if (tok == GRAM_OFFSET) {
+    st->phase = GRAM_OFFSET_OPEN;
+  } else if (tok >= gp->pitch0 && tok < gp->time0) {
+    const int p = tok - gp->pitch0;      // < GRAM_MAX_PITCH (checked by m2m_generate_grammar)
+    if (phase == GRAM_ONSET_OPEN || phase == GRAM_ONSET_LIST) { st->open_new[p >> 5] |= 1u << (p & 31); st->phase = GRAM_ONSET_LIST; }
+    else if (phase == GRAM_OFFSET_OPEN || phase == GRAM_OFFSET_LIST) { st->open_old[p >> 5] &= ~(1u << (p & 31)); st->phase = GRAM_OFFSET_LIST; }
   }
 }
 // arg-max of the row, ties to the lower id (dec_head_kernel; an all -inf row gives id 0, as torch.argmax)
@@ -2242,8 +2305,11 @@ __device__ __forceinline__ void close_step(DecState* stp, int t, int unfinished)
 
 // The select step, one row per wavefront.  GREEDY: arg-max, else the warpers and the draw (sp).  PROCESSED: the logits processors
 // first (pp); without it no ProcessParams is read and no LDS beyond the s_unfinished word is used.  SCORED: the outputs too (sc).
+// PROCESSED heads also read the GrammarParams block (gp): with its enable flag set (m2m_generate_grammar) a live row masks its logits
+// with the token grammar and advances its clip's state (gs, by clip) with the id it emitted; a finished row does neither.
 template <int NPL, bool GREEDY, bool PROCESSED, bool SCORED>
-__device__ __forceinline__ void select_head(const DecHeadArgs& a, const SampleParams* sp, const ProcessParams* pp, const ScoreParams* sc) {
+__device__ __forceinline__ void select_head(const DecHeadArgs& a, const SampleParams* sp, const ProcessParams* pp, const ScoreParams* sc,
+                                            const GrammarParams* gp = nullptr, GrammarState* gs = nullptr) {
   static_assert(PROCESSED || !SCORED, "the scored head is the processed head (a neutral ProcessParams block without processors)");
   __shared__ int s_unfinished;
   DecState* stp = a.state;
@@ -2261,7 +2327,13 @@ __device__ __forceinline__ void select_head(const DecHeadArgs& a, const SamplePa
   const bool live = !(stp->done | (t >= stp->max_steps));
   if (tid == 0) s_unfinished = 0;
   __syncthreads();
-  if constexpr (PROCESSED) apply_processors<NPL, SCORED>(a, pp, x, b, row, live, t + 1, v0);
+  bool gram = false;
+  if constexpr (PROCESSED) {
+    unsigned long long m_gram = 0ull;
+    gram = gp->enable && row && live && !a.finished[b];
+    if (gram) m_gram = grammar_banned<NPL>(gp, gs + a.tok_row[b], v0, V);
+    apply_processors<NPL>(a, pp, x, b, row, live, t + 1, v0, m_gram);
+  }
   const int k = top_k > 0 ? min(top_k, V) : V;
   if (row) {
     const int fin = a.finished[b];
@@ -2329,6 +2401,8 @@ __device__ __forceinline__ void select_head(const DecHeadArgs& a, const SamplePa
       }
     }
     const int next = emit_token(a, b, t, fin, tok, lane == 0 && live, &s_unfinished);
+    if constexpr (PROCESSED)
+      if (gram && lane == 0) grammar_advance(gp, gs + a.tok_row[b], next);
     write_embedding_row(a, b, next, live);
   }
   __syncthreads();
@@ -2340,13 +2414,14 @@ __global__ __launch_bounds__(64 * SAMPLE_ROWS) void dec_sample_kernel(DecHeadArg
   select_head<NPL, false, false, false>(a, sp, nullptr, nullptr);
 }
 template <int NPL, bool GREEDY>
-__global__ __launch_bounds__(64 * SAMPLE_ROWS) void dec_process_kernel(DecHeadArgs a, const SampleParams* sp, const ProcessParams* pp) {
-  select_head<NPL, GREEDY, true, false>(a, sp, pp, nullptr);
+__global__ __launch_bounds__(64 * SAMPLE_ROWS) void dec_process_kernel(DecHeadArgs a, const SampleParams* sp, const ProcessParams* pp,
+                                                                       const GrammarParams* gp, GrammarState* gs) {
+  select_head<NPL, GREEDY, true, false>(a, sp, pp, nullptr, gp, gs);
 }
 template <int NPL, bool GREEDY>
 __global__ __launch_bounds__(64 * SAMPLE_ROWS) void dec_scored_kernel(DecHeadArgs a, const SampleParams* sp, const ProcessParams* pp,
-                                                                      const ScoreParams* sc) {
-  select_head<NPL, GREEDY, true, true>(a, sp, pp, sc);
+                                                                      const ScoreParams* sc, const GrammarParams* gp, GrammarState* gs) {
+  select_head<NPL, GREEDY, true, true>(a, sp, pp, sc, gp, gs);
 }
 
 // launch(integral_constant NPL) for a head that keeps a row in one wavefront's registers: NPL logits per lane, the smallest of 8, 16,
@@ -2364,15 +2439,15 @@ static int launch_vocab_band(const char* kernel, int V, F launch) {
 
 // head_mode: HEAD_SAMPLE, HEAD_PROCESSED | select, HEAD_SCORED | HEAD_PROCESSED | select (select: HEAD_GREEDY or HEAD_SAMPLE)
 static int launch_dec_select(const DecHeadArgs& h, int head_mode, const SampleParams* sp, const ProcessParams* pp, const ScoreParams* sc,
-                             hipStream_t st) {
+                             const GrammarParams* gp, GrammarState* gs, hipStream_t st) {
   const bool scored = head_mode & HEAD_SCORED, processed = head_mode & HEAD_PROCESSED, greedy = !(head_mode & HEAD_SAMPLE);
   const dim3 grid((unsigned)ceil_div(h.B, SAMPLE_ROWS)), block(64 * SAMPLE_ROWS);
   return launch_vocab_band(scored ? "dec_scored_kernel" : processed ? "dec_process_kernel" : "dec_sample_kernel", h.V, [&](auto npl) {
     constexpr int NPL = decltype(npl)::value;
-    if (scored && greedy) hipLaunchKernelGGL((dec_scored_kernel<NPL, true>), grid, block, 0, st, h, sp, pp, sc);
-    else if (scored) hipLaunchKernelGGL((dec_scored_kernel<NPL, false>), grid, block, 0, st, h, sp, pp, sc);
-    else if (processed && greedy) hipLaunchKernelGGL((dec_process_kernel<NPL, true>), grid, block, 0, st, h, sp, pp);
-    else if (processed) hipLaunchKernelGGL((dec_process_kernel<NPL, false>), grid, block, 0, st, h, sp, pp);
+    if (scored && greedy) hipLaunchKernelGGL((dec_scored_kernel<NPL, true>), grid, block, 0, st, h, sp, pp, sc, gp, gs);
+    else if (scored) hipLaunchKernelGGL((dec_scored_kernel<NPL, false>), grid, block, 0, st, h, sp, pp, sc, gp, gs);
+    else if (processed && greedy) hipLaunchKernelGGL((dec_process_kernel<NPL, true>), grid, block, 0, st, h, sp, pp, gp, gs);
+    else if (processed) hipLaunchKernelGGL((dec_process_kernel<NPL, false>), grid, block, 0, st, h, sp, pp, gp, gs);
     else hipLaunchKernelGGL(dec_sample_kernel<NPL>, grid, block, 0, st, h, sp);
   });
 }
@@ -2896,7 +2971,7 @@ int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* log
   if (headless) return M2M_OK;             // the arg-max key is consumed by the next step's layer 0 (or by decode_finalize)
   DecHeadArgs h = head_args(s, v, forced, logits_out, Ld);
   if (!forced && s->head_mode == HEAD_BEAM) return launch_dec_beam(h, beam_args(s, v), s->beam_nb, st);
-  if (!forced && s->head_mode != HEAD_GREEDY) return launch_dec_select(h, s->head_mode, s->sample_dev, s->proc_dev, s->score_dev, st);
+  if (!forced && s->head_mode != HEAD_GREEDY) return launch_dec_select(h, s->head_mode, s->sample_dev, s->proc_dev, s->score_dev, s->gram_dev, s->gram_state, st);
   hipLaunchKernelGGL(dec_head_kernel, dim3(1), dim3(1024), 0, st, h);
   M2M_CHECK_HIP(hipGetLastError());
   return M2M_OK;

@@ -115,6 +115,27 @@ struct ScoreParams {
   int pad_;
 };
 
+// The MIDI token grammar (m2m_generate_grammar, decode.hip grammar_*; music2midi_amd/grammar.py is the definition): the call's
+// parameters, a device block of the workspace written before the chains start by EVERY call of the processed or scored head (enable
+// = 0 without the grammar: one captured graph serves both), and the state of one clip, indexed by the clip (tok_row[b]), not the
+// slot - live-row re-packing does not move it.  The states are zeroed on the caller's stream before the chains start: zero is the
+// start state (no phase entered, every time index allowed, nothing sounding).
+constexpr int GRAM_MAX_PITCH = 128;
+constexpr int GRAM_EOS = 2, GRAM_ONSET = 3, GRAM_OFFSET = 4;     // music2midi_amd/tokenizer.py
+enum { GRAM_START = 0, GRAM_TIME = 1, GRAM_ONSET_OPEN = 2, GRAM_ONSET_LIST = 3, GRAM_OFFSET_OPEN = 4, GRAM_OFFSET_LIST = 5 };
+struct GrammarParams {
+  int enable;               // 0: the head neither reads nor writes a state
+  int pitch0, time0, end;   // pitch ids [pitch0, time0), time ids [time0, end); ids from `end` upwards are never allowed
+};
+struct GrammarState {
+  int phase;                // GRAM_*
+  int next_time;            // last_time + 1: the smallest time index still allowed (0 at the start)
+  int pad_[2];
+  unsigned open_old[GRAM_MAX_PITCH / 32];   // sounding pitches whose onset lies before the current group
+  unsigned open_new[GRAM_MAX_PITCH / 32];   // onsets of the current group
+};
+static_assert(sizeof(GrammarState) == 48, "one clip's grammar state: three 16-byte loads");
+
 // Beam search (m2m_generate_beam): the call's parameters, a device block of the workspace written before the chains start (as
 // SampleParams), and the per-clip / per-row state of the beam head (decode.hip dec_beam_kernel).
 struct BeamParams {
@@ -239,6 +260,9 @@ struct m2m_session {
   m2m::ProcessParams* proc_host = nullptr;    // pinned staging copy
   m2m::ScoreParams* score_dev = nullptr;      // [1] in the workspace
   m2m::ScoreParams* score_host = nullptr;     // pinned staging copy
+  m2m::GrammarParams* gram_dev = nullptr;     // [1] in the workspace
+  m2m::GrammarParams* gram_host = nullptr;    // pinned staging copy, written by decode_call from the call's block
+  m2m::GrammarState* gram_state = nullptr;    // [max_batch] in the workspace, by clip
   // beam search (m2m_generate_beam): rows = encoded clips x beam_nb; every buffer below is in the workspace
   int beam_nb = 0;                            // beams per clip during a beam call, 0 otherwise
   m2m::BeamParams* beam_dev = nullptr;        // [1]

@@ -189,7 +189,7 @@ extern "C" int m2m_model_checksum(const m2m_model* m, uint64_t* out_host, void* 
 namespace {
 struct WsLayout {
   int64_t x_enc, h_enc, qkv_enc, vt_enc, attn_enc, mid_enc, enc_bias, dec_bias, dec_bias_full, cross_vt, cross_kv, self_k, self_v;
-  int64_t x_dec, logits, tokens, finished, tok_row, keys, state, forced, sample, proc, beam, beam_clip, beam_row, anc, hyp_tok, score, total;
+  int64_t x_dec, logits, tokens, finished, tok_row, keys, state, forced, sample, proc, beam, beam_clip, beam_row, anc, hyp_tok, score, gram, gram_state, total;
 };
 
 WsLayout ws_layout(const m2m_model* m, int B, int S, int L) {
@@ -229,6 +229,8 @@ WsLayout ws_layout(const m2m_model* m, int B, int S, int L) {
   w.anc = take(2 * (int64_t)B * L);
   w.hyp_tok = take((int64_t)B * L * 8);
   w.score = take(sizeof(ScoreParams));
+  w.gram = take(sizeof(GrammarParams));
+  w.gram_state = take((int64_t)B * sizeof(GrammarState));
   w.total = off;
   return w;
 }
@@ -290,6 +292,7 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   s->beam_dev = (BeamParams*)(b + w.beam); s->beam_clip = (BeamClip*)(b + w.beam_clip); s->beam_row = (BeamRow*)(b + w.beam_row);
   s->anc = b + w.anc; s->hyp_tok = (int64_t*)(b + w.hyp_tok);
   s->score_dev = (ScoreParams*)(b + w.score);
+  s->gram_dev = (GrammarParams*)(b + w.gram); s->gram_state = (GrammarState*)(b + w.gram_state);
 
   // relative-position bias tables (fp32), built on the host from the bucket function
   const m2m_t5_geometry& g = m->g;
@@ -327,6 +330,8 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   if (e == hipSuccess) e = hipHostMalloc((void**)&s->proc_host, sizeof(ProcessParams), hipHostMallocDefault);
   if (e == hipSuccess) e = hipHostMalloc((void**)&s->beam_host, sizeof(BeamParams), hipHostMallocDefault);
   if (e == hipSuccess) e = hipHostMalloc((void**)&s->score_host, sizeof(ScoreParams), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s->gram_host, sizeof(GrammarParams), hipHostMallocDefault);
+  if (e == hipSuccess) *s->gram_host = GrammarParams{};
   for (int i = 0; i < MAX_GROUPS && e == hipSuccess; ++i) {
     DecGroup& gr = s->groups[i];
     gr.view.state = s->states + i;
@@ -361,6 +366,7 @@ extern "C" void m2m_session_destroy(m2m_session* s) {
   if (s->proc_host) (void)hipHostFree(s->proc_host);
   if (s->beam_host) (void)hipHostFree(s->beam_host);
   if (s->score_host) (void)hipHostFree(s->score_host);
+  if (s->gram_host) (void)hipHostFree(s->gram_host);
   delete s;
 }
 
@@ -506,6 +512,7 @@ struct DecodeCall {
   int head_mode, beam_nb;  // the session's head form for this call
   int64_t* tokens_out;
   float* scores_out;       // beam search: optional sequence scores
+  const GrammarParams* gram = nullptr;   // processed and scored heads: the token grammar of this call, nullptr without one
 };
 }  // namespace
 
@@ -610,27 +617,30 @@ static int fill_process_params(const m2m_session* s, int max_length, const m2m_p
   return M2M_OK;
 }
 
-extern "C" int m2m_generate_processed(m2m_session* s, int max_length, const m2m_process_params* proc, const m2m_sample_params* sample,
-                                      int64_t* tokens_out_dev, int* out_len_host, void* stream) {
-  const char* fn = "m2m_generate_processed";
-  M2M_REQUIRE(s && proc && tokens_out_dev && out_len_host, "m2m_generate_processed: null argument");
+static int generate_processed(m2m_session* s, int max_length, const m2m_process_params* proc, const m2m_sample_params* sample,
+                              int64_t* tokens_out_dev, int* out_len_host, void* stream, const GrammarParams* gram, const char* fn) {
+  M2M_REQUIRE(s && proc && tokens_out_dev && out_len_host, "%s: null argument", fn);
   int rc;
   if (sample && (rc = fill_sample_params(sample, *s->sample_host, fn))) return rc;
-  M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_processed: max_length %d outside [1, %d]", max_length, s->max_dec);
-  if ((rc = fill_process_params(s, max_length, proc, *s->proc_host))) return rc;
+  M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "%s: max_length %d outside [1, %d]", fn, max_length, s->max_dec);
+  if ((rc = fill_process_params(s, max_length, proc, *s->proc_host, fn))) return rc;
   if ((rc = require_encoded(s, fn))) return rc;
-  return decode_call(s, {fn, HEAD_PROCESSED | (sample ? HEAD_SAMPLE : HEAD_GREEDY), 0, tokens_out_dev, nullptr}, max_length, out_len_host,
-                     (hipStream_t)stream);
+  return decode_call(s, {fn, HEAD_PROCESSED | (sample ? HEAD_SAMPLE : HEAD_GREEDY), 0, tokens_out_dev, nullptr, gram}, max_length,
+                     out_len_host, (hipStream_t)stream);
+}
+
+extern "C" int m2m_generate_processed(m2m_session* s, int max_length, const m2m_process_params* proc, const m2m_sample_params* sample,
+                                      int64_t* tokens_out_dev, int* out_len_host, void* stream) {
+  return generate_processed(s, max_length, proc, sample, tokens_out_dev, out_len_host, stream, nullptr, "m2m_generate_processed");
 }
 
 // Per-token outputs (include/music2midi_amd.h): the processed head's scored form (HEAD_SCORED, greedy or sampling select), with a
 // neutral ProcessParams block when the call has no processor; with no output asked for, the matching unscored export.
-extern "C" int m2m_generate_scored(m2m_session* s, int max_length, const m2m_process_params* proc, const m2m_sample_params* sample,
-                                   int64_t* tokens_out_dev, float* scores_out_dev, float* logprobs_out_dev, int* out_len_host,
-                                   void* stream) {
-  const char* fn = "m2m_generate_scored";
-  M2M_REQUIRE(s && tokens_out_dev && out_len_host, "m2m_generate_scored: null argument");
-  if (!scores_out_dev && !logprobs_out_dev) {
+static int generate_scored(m2m_session* s, int max_length, const m2m_process_params* proc, const m2m_sample_params* sample,
+                           int64_t* tokens_out_dev, float* scores_out_dev, float* logprobs_out_dev, int* out_len_host, void* stream,
+                           const GrammarParams* gram, const char* fn) {
+  M2M_REQUIRE(s && tokens_out_dev && out_len_host, "%s: null argument", fn);
+  if (!scores_out_dev && !logprobs_out_dev) {        // (never with a grammar: m2m_generate_grammar takes the processed head then)
     if (proc) return m2m_generate_processed(s, max_length, proc, sample, tokens_out_dev, out_len_host, stream);
     if (sample) return m2m_generate_sample(s, max_length, sample, tokens_out_dev, out_len_host, stream);
     return m2m_generate_greedy(s, max_length, tokens_out_dev, out_len_host, stream);
@@ -640,7 +650,7 @@ extern "C" int m2m_generate_scored(m2m_session* s, int max_length, const m2m_pro
   const int V = s->m->g.vocab_size;
   M2M_REQUIRE(V <= PROC_MAX_VOCAB, "%s: vocab_size %d > %d (the scored head keeps a row in one wavefront's registers)", fn, V,
               PROC_MAX_VOCAB);
-  M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_scored: max_length %d outside [1, %d]", max_length, s->max_dec);
+  M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "%s: max_length %d outside [1, %d]", fn, max_length, s->max_dec);
   if (proc) {
     if ((rc = fill_process_params(s, max_length, proc, *s->proc_host, fn))) return rc;
   } else {                                   // no processor: the neutral block (nothing banned, nothing forced)
@@ -653,8 +663,45 @@ extern "C" int m2m_generate_scored(m2m_session* s, int max_length, const m2m_pro
   sc = ScoreParams{};
   sc.scores = scores_out_dev; sc.logprobs = logprobs_out_dev; sc.rows = s->B; sc.steps = max_length - 1;
   sc.vec4 = (V % 4 == 0 && ((uintptr_t)scores_out_dev & 15) == 0) ? 1 : 0;
-  return decode_call(s, {fn, HEAD_SCORED | HEAD_PROCESSED | (sample ? HEAD_SAMPLE : HEAD_GREEDY), 0, tokens_out_dev, nullptr}, max_length,
-                     out_len_host, (hipStream_t)stream);
+  return decode_call(s, {fn, HEAD_SCORED | HEAD_PROCESSED | (sample ? HEAD_SAMPLE : HEAD_GREEDY), 0, tokens_out_dev, nullptr, gram},
+                     max_length, out_len_host, (hipStream_t)stream);
+}
+
+extern "C" int m2m_generate_scored(m2m_session* s, int max_length, const m2m_process_params* proc, const m2m_sample_params* sample,
+                                   int64_t* tokens_out_dev, float* scores_out_dev, float* logprobs_out_dev, int* out_len_host,
+                                   void* stream) {
+  return generate_scored(s, max_length, proc, sample, tokens_out_dev, scores_out_dev, logprobs_out_dev, out_len_host, stream, nullptr,
+                         "m2m_generate_scored");
+}
+
+// The MIDI token grammar (include/music2midi_amd.h): the processed or scored head with the call's GrammarParams block (DecodeCall::gram:
+// decode_call uploads it and zeroes the clips' states); without a processor the neutral m2m_process_params.
+extern "C" int m2m_generate_grammar(m2m_session* s, int max_length, const m2m_grammar_params* grammar, const m2m_process_params* proc,
+                                    const m2m_sample_params* sample, int64_t* tokens_out_dev, float* scores_out_dev,
+                                    float* logprobs_out_dev, int* out_len_host, void* stream) {
+  const char* fn = "m2m_generate_grammar";
+  if (!grammar) return m2m_generate_scored(s, max_length, proc, sample, tokens_out_dev, scores_out_dev, logprobs_out_dev, out_len_host, stream);
+  M2M_REQUIRE(s && tokens_out_dev && out_len_host, "m2m_generate_grammar: null argument");
+  const m2m_t5_geometry& g = s->m->g;
+  const int V = g.vocab_size;
+  M2M_REQUIRE(V <= PROC_MAX_VOCAB, "%s: vocab_size %d > %d (the processed head keeps a row in one wavefront's registers)", fn, V, PROC_MAX_VOCAB);
+  M2M_REQUIRE(max_length <= PROC_MAX_LEN, "%s: max_length %d > %d", fn, max_length, PROC_MAX_LEN);
+  M2M_REQUIRE(grammar->pitch_offset > GRAM_OFFSET && grammar->pitch_offset <= V, "%s: pitch_offset %d outside [%d, %d]", fn,
+              grammar->pitch_offset, GRAM_OFFSET + 1, V);
+  M2M_REQUIRE(grammar->n_pitch >= 1 && grammar->n_pitch <= GRAM_MAX_PITCH, "%s: n_pitch %d outside [1, %d]", fn, grammar->n_pitch,
+              GRAM_MAX_PITCH);
+  M2M_REQUIRE(grammar->n_time >= 1 && grammar->n_time <= V, "%s: n_time %d outside [1, %d]", fn, grammar->n_time, V);
+  M2M_REQUIRE(grammar->pitch_offset + grammar->n_pitch + grammar->n_time <= V, "%s: pitch_offset + n_pitch + n_time = %d > vocab_size %d",
+              fn, grammar->pitch_offset + grammar->n_pitch + grammar->n_time, V);
+  M2M_REQUIRE(g.eos_token_id == GRAM_EOS, "%s: the grammar ends a sequence with id %d, the model's eos_token_id is %d", fn, GRAM_EOS,
+              g.eos_token_id);
+  GrammarParams gp{};
+  gp.enable = 1; gp.pitch0 = grammar->pitch_offset; gp.time0 = gp.pitch0 + grammar->n_pitch; gp.end = gp.time0 + grammar->n_time;
+  if (scores_out_dev || logprobs_out_dev)
+    return generate_scored(s, max_length, proc, sample, tokens_out_dev, scores_out_dev, logprobs_out_dev, out_len_host, stream, &gp, fn);
+  m2m_process_params neutral{};
+  neutral.repetition_penalty = 1.0f; neutral.forced_bos_token_id = -1; neutral.forced_eos_token_id = -1;
+  return generate_processed(s, max_length, proc ? proc : &neutral, sample, tokens_out_dev, out_len_host, stream, &gp, fn);
 }
 
 // the decode loop of every head form (s->head_mode, set by decode_call)
@@ -805,6 +852,15 @@ static int decode_call(m2m_session* s, const DecodeCall& c, int max_length, int*
   int rc = M2M_OK;
   if (c.head_mode & HEAD_SAMPLE) rc = upload(s->sample_dev, s->sample_host, sizeof(SampleParams), caller, c.fn);
   if (rc == M2M_OK && (c.head_mode & HEAD_PROCESSED)) rc = upload(s->proc_dev, s->proc_host, sizeof(ProcessParams), caller, c.fn);
+  if (rc == M2M_OK && (c.head_mode & HEAD_PROCESSED)) {
+    // the grammar block travels with every processed call (enable = 0 without a grammar); with one, the clips' states restart
+    *s->gram_host = c.gram ? *c.gram : GrammarParams{};
+    rc = upload(s->gram_dev, s->gram_host, sizeof(GrammarParams), caller, c.fn);
+    if (rc == M2M_OK && c.gram && hipMemsetAsync(s->gram_state, 0, (size_t)s->B * sizeof(GrammarState), caller) != hipSuccess) {
+      set_error("%s: hipMemsetAsync: %s", c.fn, hipGetErrorString(hipGetLastError()));
+      rc = M2M_ERR_HIP;
+    }
+  }
   if (rc == M2M_OK && c.head_mode == HEAD_BEAM) rc = upload(s->beam_dev, s->beam_host, sizeof(BeamParams), caller, c.fn);
   if (rc == M2M_OK && (c.head_mode & HEAD_SCORED)) {
     // finished rows write nothing: the caller's buffers are zeroed on its stream, before the chains start

@@ -211,14 +211,15 @@ def all_gather_tokens(tokens: torch.Tensor, max_length: int, pad_id: int = 0) ->
     return out[:, :L_global].contiguous()
 
 
-def generate_sharded(generate_fn, inputs, max_length: int, pad_id: int = 0):
+def generate_sharded(generate_fn, inputs, max_length: int, pad_id: int = 0, **generate_kwargs):
     """Decode a batch of clips across all ranks: rank r runs ``generate_fn`` on its contiguous block of clips
     (``shard_range``) and the token matrices are all-gathered back into clip order — what one process decoding the
     whole batch would have returned.  ``inputs`` is a ``ModelInputs`` whose tensors have the FULL batch on every rank
     (clips are cheap to replicate: 0.9 MB each); without a process group this is ``generate_fn(inputs, max_length=...)``.
+    Further keywords (``midi_grammar=True``) are forwarded to ``generate_fn``.
     Used by ``Music2MIDI.sample_tokens`` and by bench.py, so callers and the benchmark share one sharding path."""
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-        return generate_fn(inputs, max_length=max_length)
+        return generate_fn(inputs, max_length=max_length, **generate_kwargs)
     rank, world = dist.get_rank(), dist.get_world_size()
     n = inputs.input_waveform.shape[0]
     lo, hi = shard_range(n, rank, world)
@@ -226,7 +227,7 @@ def generate_sharded(generate_fn, inputs, max_length: int, pad_id: int = 0):
         local = type(inputs)(input_waveform=inputs.input_waveform[lo:hi],
                              notes_batch=inputs.notes_batch[lo:hi] if inputs.notes_batch is not None else None,
                              cond_index=inputs.cond_index[lo:hi] if inputs.cond_index is not None else None)
-        toks = generate_fn(local, max_length=max_length)
+        toks = generate_fn(local, max_length=max_length, **generate_kwargs)
     else:       # more ranks than clips: this rank contributes nothing
         toks = torch.zeros((0, 1), dtype=torch.long, device=inputs.input_waveform.device)
     return all_gather_tokens(toks, max_length, pad_id)

@@ -9,7 +9,7 @@ and the argument checks of its logits warpers (hf: generation/logits_process.py 
 ``forced_eos_token_id``, ``suppress_tokens``, ``begin_suppress_tokens``) and ``max_new_tokens`` follow 4.34's
 ``_get_logits_processor`` and its processors' checks.  Beam search and every other keyword raise
 ``NotImplementedError`` there (``return_dict_in_generate``, ``output_scores`` and the project keyword ``output_logprobs`` select
-the per-token outputs of the scored head); beam search has its own entry point (``T5Transformer.beam_search``), whose keywords
+the per-token outputs of the scored head; ``midi_grammar`` the token grammar of ``grammar.py``); beam search has its own entry point (``T5Transformer.beam_search``), whose keywords
 ``resolve_beam_kwargs`` checks.
 """
 from __future__ import annotations
@@ -62,6 +62,7 @@ class GenerateConfig:
     return_dict: bool = False            # return_dict_in_generate=True: an output with .sequences / .scores / .logprobs
     output_scores: bool = False          # ... with the row every token was selected from (only with return_dict)
     output_logprobs: bool = False        # ... with every token's log-probability under that row (only with return_dict)
+    midi_grammar: bool = False           # mask every step with the MIDI token grammar (grammar.py), at PrefixConstrainedLogitsProcessor's place
 
 
 def _is_int(v) -> bool:
@@ -161,7 +162,7 @@ def resolve_process_kwargs(kw: dict, vocab_size=None) -> "ProcessConfig | None":
     return ProcessConfig(**p)
 
 
-def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_LENGTH, vocab_size=None) -> GenerateConfig:
+def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_LENGTH, vocab_size=None, grammar=None) -> GenerateConfig:
     """Validate ``generate`` keywords and fill in HF's defaults.  ``kwargs`` is not modified.
 
     ``None`` for temperature / top_k / top_p means "no such warper", as in HF (the warper is only built when the value is
@@ -170,7 +171,10 @@ def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_
     ``max_length``, as in 4.34.  ``vocab_size`` (optional) range-checks the processors' token ids.
     ``return_dict_in_generate`` and ``output_scores`` have 4.34's meaning: without ``return_dict_in_generate=True`` the call
     returns the plain tensor and ``output_scores`` is ignored.  ``output_logprobs`` (a keyword of this project: the tokens'
-    log-probabilities without the V-wide rows) raises ``ValueError`` unless ``return_dict_in_generate=True``."""
+    log-probabilities without the V-wide rows) raises ``ValueError`` unless ``return_dict_in_generate=True``.
+    ``midi_grammar`` (a keyword of this project, a bool) constrains every step to the MIDI token grammar, what HF does with
+    ``prefix_allowed_tokens_fn=grammar.prefix_allowed_tokens_fn()``; ``grammar`` (the tokenizer's ``MidiGrammar``, optional) is
+    checked against the device limits then.  The flag is a field of ``GenerateConfig``, not a processor of ``ProcessConfig``."""
     kw = dict(kwargs)
     max_length = int(kw.pop("max_length", default_max_length))   # range-checked by the library, as before
     max_new = kw.pop("max_new_tokens", None)
@@ -181,6 +185,14 @@ def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_
     process = resolve_process_kwargs(kw, vocab_size)
     if process is not None and max_length > PROCESS_MAX_LENGTH:
         raise ValueError(f"logits processors on the MI355X path take max_length <= {PROCESS_MAX_LENGTH}, got {max_length}")
+    midi_grammar = kw.pop("midi_grammar", False)
+    if not isinstance(midi_grammar, bool):
+        raise ValueError(f"`midi_grammar` has to be a bool, but is {midi_grammar!r}")
+    if midi_grammar:
+        if max_length > PROCESS_MAX_LENGTH:
+            raise ValueError(f"`midi_grammar` on the MI355X path takes max_length <= {PROCESS_MAX_LENGTH}, got {max_length}")
+        if grammar is not None and vocab_size is not None:
+            grammar.check_device_limits(vocab_size)       # pitch ids, special + pitch + time <= vocab_size <= PROCESS_MAX_VOCAB
     do_sample = bool(kw.pop("do_sample", False))
     if int(kw.pop("num_beams", 1)) != 1:
         raise NotImplementedError("generate() does not decode with num_beams > 1 on the MI355X path; "
@@ -201,7 +213,7 @@ def resolve_generate_kwargs(kwargs: dict, default_max_length: int = DEFAULT_MAX_
     if (output_scores or output_logprobs) and vocab_size is not None and vocab_size > PROCESS_MAX_VOCAB:
         raise ValueError(f"per-token scores on the MI355X path need a vocabulary of at most {PROCESS_MAX_VOCAB} ids "
                          f"(the model has {vocab_size})")
-    out = dict(return_dict=return_dict, output_scores=output_scores, output_logprobs=output_logprobs)
+    out = dict(return_dict=return_dict, output_scores=output_scores, output_logprobs=output_logprobs, midi_grammar=midi_grammar)
     if not _is_int(n) or n < 1:
         raise ValueError(f"`num_return_sequences` has to be a strictly positive integer, but is {n!r}")
     if not do_sample:

@@ -301,12 +301,16 @@ class Music2MIDI(nn.Module):
         return loss
 
     # -- inference -----------------------------------------------------------
+    def _grammar_kwargs(self) -> dict:
+        """``midi_grammar=True`` for generate when ``config.inference.midi_grammar`` says so (absent: unconstrained, no keyword)."""
+        return {"midi_grammar": True} if bool(self.config.inference.get("midi_grammar", False)) else {}
+
     @torch.no_grad()
     def evaluate_batch(self, inputs: ModelInputs):
         """(chroma accuracy, decoded MIDI per clip, label MIDI per clip) for one labelled batch — ref
         model.py:55-65.  The decode budget is four tokens per label note of the busiest clip."""
         budget = 4 * max(len(n) for n in inputs.notes_batch)
-        token_ids = self.model.generate(inputs, max_length=budget)
+        token_ids = self.model.generate(inputs, max_length=budget, **self._grammar_kwargs())
         predicted = [numpy_to_midi(n) for n in self.model.tokenizer.decode(token_ids, mode="batched")]
         wanted = [numpy_to_midi(n) for n in inputs.notes_batch]
         return evaluate_batch(wanted, predicted), predicted, wanted
@@ -367,6 +371,6 @@ class Music2MIDI(nn.Module):
             # with a process group (one process per GPU) the chunk's segments are sharded over the ranks and the ids
             # all-gathered back in segment order; a single process decodes the chunk itself
             ids = D.generate_sharded(self.model.generate, ModelInputs(input_waveform=wav, cond_index=self._cond_rows(len(group), cond_index)),
-                                     max_length=1024, pad_id=self.model.geometry.pad_token_id)
+                                     max_length=1024, pad_id=self.model.geometry.pad_token_id, **self._grammar_kwargs())
             token_rows.extend(ids.unbind(0))
         return self.model.tokenizer.decode(token_rows, mode="sequential", duration_per_batch=split_duration)

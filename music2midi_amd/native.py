@@ -74,6 +74,10 @@ class ProcessParams(C.Structure):
                 ("bad_words_ids", C.POINTER(C.c_int32)), ("bad_words_lengths", C.POINTER(C.c_int32)), ("n_bad_words", C.c_int)]
 
 
+class GrammarParams(C.Structure):
+    _fields_ = [("pitch_offset", C.c_int), ("n_pitch", C.c_int), ("n_time", C.c_int)]
+
+
 class BeamParams(C.Structure):
     _fields_ = [("num_beams", C.c_int), ("length_penalty", C.c_float), ("early_stopping", C.c_int),
                 ("num_return_sequences", C.c_int)]
@@ -116,6 +120,8 @@ _SIGNATURES = {
                                          C.POINTER(C.c_int), C.c_void_p]),
     "m2m_generate_scored": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ProcessParams), C.POINTER(SampleParams), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
+    "m2m_generate_grammar": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GrammarParams), C.POINTER(ProcessParams), C.POINTER(SampleParams),
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "m2m_generate_beam": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BeamParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                     C.c_void_p]),
     "m2m_session_repack_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -30,6 +30,12 @@ class MidiTokenizer:
         self.pitch_token_offset = self.config.vocab_size.special
         self.time_token_offset = self.pitch_token_offset + self.config.vocab_size.pitch
 
+    @property
+    def grammar(self):
+        """The token grammar of this vocabulary (``music2midi_amd.grammar.MidiGrammar``): what ``_tokenize`` can write."""
+        from .grammar import MidiGrammar
+        return MidiGrammar.from_vocab(self.config.vocab_size)
+
     # ------------------------------------------------------------------ names
     def to_string(self, tokens) -> List[str]:
         names = []
