@@ -237,7 +237,8 @@ int m2m_generate_sample(m2m_session* s, int max_length, const m2m_sample_params*
 
 /*
  * KV-cached beam search (hf: generation/utils.py _beam_search, generation/beam_search.py BeamSearchScorer / BeamHypotheses,
- * transformers 4.34 read for an encoder-decoder; no logits processors apply to T5): each of the B encoded clips is decoded as
+ * transformers 4.34 read for an encoder-decoder; this export applies no logits processor - the token grammar and the processors
+ * that do not read a row's history come with m2m_generate_beam_processed below): each of the B encoded clips is decoded as
  * num_beams rows.  Every step scores log_softmax(logits) + the running beam score (fp32), takes the clip's top 2 num_beams over
  * num_beams x V (ties to the lower beam-major index) and walks them in rank order: an EOS of rank < num_beams becomes a hypothesis
  * (score sum_logprobs / len ** length_penalty, len = the start token plus the generated tokens, EOS not counted; at most
@@ -345,6 +346,27 @@ typedef struct { int pitch_offset, n_pitch, n_time; } m2m_grammar_params;
 int m2m_generate_grammar(m2m_session* s, int max_length, const m2m_grammar_params* grammar, const m2m_process_params* proc,
                          const m2m_sample_params* sample, int64_t* tokens_out_dev, float* scores_out_dev, float* logprobs_out_dev,
                          int* out_len_host, void* stream);
+
+/*
+ * Beam search under the MIDI token grammar and the logits processors (hf 4.34: generate(num_beams=..., prefix_allowed_tokens_fn=...,
+ * min_length=..., forced_eos_token_id=...), _beam_search with a non-empty logits_processor).  The step is m2m_generate_beam's with
+ * one change: the fp32 log_softmax of a row is processed against its own beam's prefix (cur_len = t + 1) BEFORE the running beam
+ * score is added, in _get_logits_processor's order: one-id bad_words, min_length, min_new_tokens, the grammar's mask (as
+ * m2m_generate_grammar: PrefixConstrainedLogitsProcessor's place), forced_bos_token_id, forced_eos_token_id (every other id -inf,
+ * the forced one 0: it wins over the grammar), suppress_tokens, begin_suppress_tokens.  The grammar state is kept per ROW (48 bytes
+ * each, max_batch of them in the workspace): new beam i takes its parent's state advanced by the id it carries.  A clip may have
+ * fewer than num_beams finite candidates that are not EOS (the forced_eos_token_id step): as in HF its beams are then filled from
+ * candidates at -inf, ties to the lower beam-major flat index, and carry the score -inf from there on; a returned hypothesis may
+ * have the score -inf.  No NaN arises: raw logits are finite or the call returns M2M_ERR_RANGE.
+ * grammar == NULL: no grammar; proc == NULL: no processor; both NULL: this IS m2m_generate_beam.  With a neutral block and no grammar
+ * the ids and scores are m2m_generate_beam's.  M2M_ERR_INVALID without launching anything: every invalid case of m2m_generate_beam
+ * and of m2m_generate_grammar's block, an invalid processor block (as m2m_generate_processed), a processor that reads a row's history
+ * (repetition_penalty != 1, no_repeat_ngram_size > 0, a bad_words sequence of two or more ids: a beam's history is scattered through
+ * the ancestry table), max_length > 2048.  Everything else is as for m2m_generate_beam.
+ */
+int m2m_generate_beam_processed(m2m_session* s, int max_length, const m2m_beam_params* p, const m2m_grammar_params* grammar,
+                                const m2m_process_params* proc, int64_t* tokens_out_dev, float* scores_out_dev, int* out_len_host,
+                                void* stream);
 
 /*
  * Rows end at different steps (ref: music2midi/model.py:115-135 decodes chunks of inference.batch_size = 128 three-second

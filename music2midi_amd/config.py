@@ -131,6 +131,21 @@ def default_config() -> ConfigNode:
     return ConfigNode(DEFAULT_CONFIG)
 
 
+def inference_beams(config) -> dict:
+    """The beam settings of ``config.inference``: ``{}`` when ``num_beams`` is absent or 1 (every call decodes as before), otherwise
+    ``{"num_beams": n, "length_penalty": ..., "early_stopping": ...}`` - the keywords ``Music2MIDI`` passes to
+    ``T5Transformer.beam_search_processed`` (``length_penalty`` defaults to 1.0, ``early_stopping`` to False, as in HF)."""
+    inf = config.inference
+    n = inf.get("num_beams", 1)
+    if n is None:
+        n = 1
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"inference.num_beams has to be a strictly positive integer, but is {n!r}")
+    if n == 1:
+        return {}
+    return {"num_beams": n, "length_penalty": float(inf.get("length_penalty", 1.0)), "early_stopping": inf.get("early_stopping", False)}
+
+
 # T5 hyper-parameters that the reference leaves to the HF defaults
 # (hf: models/t5/configuration_t5.py:44-62): they are not in config.yaml.
 T5_DEFAULTS = {

@@ -2039,6 +2039,39 @@ __device__ inline unsigned long long lane_bits(const unsigned* w, int v0) {   //
   if constexpr (NPL == 64) return (unsigned long long)w[v0 >> 5] | ((unsigned long long)w[(v0 >> 5) + 1] << 32);
   else return (w[v0 >> 5] >> (v0 & 31)) & ((1ull << NPL) - 1);
 }
+// Bits [lo, hi) of the vocabulary as they fall into this lane's ids v0 .. v0 + NPL - 1 (bit j = id v0 + j).
+template <int NPL>
+__device__ __forceinline__ unsigned long long lane_range_bits(int lo, int hi, int v0) {
+  const int l = max(lo, v0) - v0, h = min(hi, v0 + NPL) - v0;
+  if (h <= l) return 0ull;
+  return (h - l >= 64 ? ~0ull : ((1ull << (h - l)) - 1)) << l;
+}
+// The per-lane body of the logits processors, shared by the select heads (apply_processors, on raw logits) and the processed beam
+// head (dec_beam_kernel<NPL, true>, on log-probabilities): bit j of a mask is id v0 + j.  4.34's _get_logits_processor order:
+// repetition (m_seen), n-gram and bad words (m_ban), min length, min new tokens, the token grammar (m_gram: PrefixConstrained-
+// LogitsProcessor's place; one -inf set with the bans before it), forced BOS, forced EOS, suppress and begin-suppress (m_post).
+template <int NPL>
+__device__ __forceinline__ void apply_lane_processors(const ProcessParams* pp, float (&x)[NPL], int cur, int v0, int V, int eos_id,
+                                                      unsigned long long m_seen, unsigned long long m_ban, unsigned long long m_gram,
+                                                      unsigned long long m_post) {
+  const float pen = pp->penalty;
+  const bool eos_ban = cur < pp->min_length || cur - 1 < pp->min_new;
+  const int fbos = cur == 1 ? pp->forced_bos : -1;
+  const int feos = cur == pp->max_length - 1 ? pp->forced_eos : -1;
+  // the processors after the penalty only write -inf or (the forced id) 0: they fold into two masks, in their order
+  unsigned long long ninf = m_ban | m_gram | (eos_ban ? lane_range_bits<NPL>(eos_id, eos_id + 1, v0) : 0ull), zero = 0ull;
+  if (fbos >= 0) { zero = lane_range_bits<NPL>(fbos, fbos + 1, v0); ninf = ~zero; }
+  if (feos >= 0) { zero = lane_range_bits<NPL>(feos, feos + 1, v0); ninf = ~zero; }
+  ninf |= m_post;
+  zero &= ~m_post;
+  ninf &= lane_range_bits<NPL>(0, V, v0);          // ids past the vocabulary keep their 0
+#pragma unroll
+  for (int j = 0; j < NPL; ++j) {
+    if ((m_seen >> j) & 1) x[j] = x[j] < 0.f ? x[j] * pen : x[j] / pen;
+    if ((ninf >> j) & 1) x[j] = -INFINITY;
+    if ((zero >> j) & 1) x[j] = 0.f;
+  }
+}
 // Logits processors (m2m_generate_processed; transformers 4.34 _get_logits_processor, see include/music2midi_amd.h) on the row in
 // registers, before the select; every thread of the workgroup calls this (it holds barriers).  Per workgroup (4 rows) 16 KB of LDS
 // hold the rows' histories (input_ids = the start token and t generated ids, cur = cur_len = t + 1) as 16-bit ids, staged from the
@@ -2097,32 +2130,9 @@ __device__ __forceinline__ void apply_processors(const DecHeadArgs& a, const Pro
              (pp->has_begin && cur == pp->begin_index ? lane_bits<NPL>(pp->begin, v0) : 0ull);
   }
   if (!row) return;
-  // 4.34's _get_logits_processor order: repetition, n-gram, bad words, min length, min new tokens, forced BOS, forced EOS,
-  // suppress, begin-suppress
-  const float pen = pp->penalty;
-  const bool eos_ban = cur < pp->min_length || cur - 1 < pp->min_new;
-  const int fbos = cur == 1 ? pp->forced_bos : -1;
-  const int feos = cur == pp->max_length - 1 ? pp->forced_eos : -1;
-#pragma unroll
-  for (int j = 0; j < NPL; ++j) {
-    const int v = v0 + j;
-    if (v < a.V) {
-      if ((m_seen >> j) & 1) x[j] = x[j] < 0.f ? x[j] * pen : x[j] / pen;
-      if ((((m_ban | m_gram) >> j) & 1) || (eos_ban && v == a.eos_id)) x[j] = -INFINITY;
-      if (fbos >= 0) x[j] = v == fbos ? 0.f : -INFINITY;
-      if (feos >= 0) x[j] = v == feos ? 0.f : -INFINITY;
-      if ((m_post >> j) & 1) x[j] = -INFINITY;
-    }
-  }
+  apply_lane_processors<NPL>(pp, x, cur, v0, a.V, a.eos_id, m_seen, m_ban, m_gram, m_post);
 }
 // The MIDI token grammar (m2m_generate_grammar; music2midi_amd/grammar.py defines it, t5.h GrammarState holds a clip's state).
-// Bits [lo, hi) of the vocabulary as they fall into this lane's ids v0 .. v0 + NPL - 1 (bit j = id v0 + j).
-template <int NPL>
-__device__ __forceinline__ unsigned long long lane_range_bits(int lo, int hi, int v0) {
-  const int l = max(lo, v0) - v0, h = min(hi, v0 + NPL) - v0;
-  if (h <= l) return 0ull;
-  return (h - l >= 64 ? ~0ull : ((1ull << (h - l)) - 1)) << l;
-}
 // The ids of this lane the grammar BANS after the clip's prefix.  The state is the same for the whole wavefront (one row): every
 // lane loads the same 48 bytes and the first lane's values become scalars; the allowed set is range compares on them plus, for the
 // pitch ids, a 64-bit window of the 128-bit pitch set.  No LDS, no history: the cost does not depend on the position.
@@ -2472,6 +2482,13 @@ struct DecBeamArgs {
   int anc_ld;
   int64_t* hyp_tok;        // [rows][max_len] hypothesis snapshots (slot as in `row`)
 };
+// The processed beam head (m2m_generate_beam_processed, dec_beam_kernel<NPL, true>) also reads the ProcessParams and GrammarParams
+// blocks of the call and keeps one grammar state PER ROW (a clip's beams diverge), which follows its parent when the beams reorder.
+struct DecBeamProcArgs : DecBeamArgs {
+  const ProcessParams* pp;
+  const GrammarParams* gp;
+  GrammarState* gs;        // [rows of the view]
+};
 
 __device__ inline float ord_key_inv(unsigned k) {
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
@@ -2509,8 +2526,16 @@ __device__ inline int beam_hyp_add(BeamClip* bc, BeamRow* row, int r0, int nb, d
   return slot;
 }
 
-template <int NPL>
-__global__ __launch_bounds__(1024) void dec_beam_kernel(DecHeadArgs a, DecBeamArgs bm) {
+// PROCESSED (HEAD_BEAM | HEAD_PROCESSED): hf _beam_search with a non-empty logits_processor - the row's log-probabilities are
+// processed (apply_lane_processors: the EOS bans, the grammar of the row's own state, the forced ids, the bitmaps of the block)
+// BEFORE the running score is added, so a forced id scores 0 + the beam score and a banned one -inf.  The processors that read a
+// row's history are not part of this head (m2m_generate_beam_processed refuses them).  Candidates at -inf rank behind every finite
+// one and among themselves by the flat index (ord_key(-inf) is above the key 0 of an exhausted lane), so a clip with fewer than nb
+// finite non-EOS candidates fills its beams from them, in the restatement's order; such a beam carries -inf from there on (-inf +
+// a finite log-probability), and nothing becomes NaN: the raw logits are finite and no +inf arises.  The false form is the kernel
+// as it was: the same arguments, the same instructions.
+template <int NPL, bool PROCESSED = false>
+__global__ __launch_bounds__(1024) void dec_beam_kernel(DecHeadArgs a, std::conditional_t<PROCESSED, DecBeamProcArgs, DecBeamArgs> bm) {
   __shared__ unsigned long long cand[BEAM_MAX][2 * BEAM_MAX];   // per beam: its top 2 nb keys, descending
   __shared__ unsigned long long top[2 * BEAM_MAX];              // the clip's top 2 nb
   __shared__ int s_par[BEAM_MAX], s_tok[BEAM_MAX], s_src[BEAM_MAX];
@@ -2526,6 +2551,15 @@ __global__ __launch_bounds__(1024) void dec_beam_kernel(DecHeadArgs a, DecBeamAr
   const bool work = live && !was_done;
   if (tid == 0) { s_bad = 0; s_done = was_done; }
   if (tid < BEAM_MAX) s_src[tid] = -1;
+  // the clip's nb grammar states to LDS before any is written (phase D): a parent may feed several children and be overwritten by another
+  unsigned* s_gs = nullptr;
+  bool gram = false;
+  if constexpr (PROCESSED) {
+    __shared__ unsigned s_gs_words[BEAM_MAX * (sizeof(GrammarState) / 4)];
+    s_gs = s_gs_words;
+    gram = bm.gp->enable != 0;
+    if (work && gram && tid < nb * (int)(sizeof(GrammarState) / 4)) s_gs[tid] = reinterpret_cast<const unsigned*>(bm.gs + r0)[tid];
+  }
   __syncthreads();
   if (work) {
     // A. per beam (one wave): fp32 log-softmax plus the running score, then the beam's own top 2 nb by repeated arg-max
@@ -2543,8 +2577,22 @@ __global__ __launch_bounds__(1024) void dec_beam_kernel(DecHeadArgs a, DecBeamAr
       for (int j = 0; j < NPL; ++j) if (v0 + j < V) z += expf(x[j] - m);
       z = wave_sum(z);                    // butterfly: the same bits in every lane
       const float lz = logf(z), bs = bm.row[r0 + r].score;
+      if constexpr (PROCESSED) {
+        const ProcessParams* pp = bm.pp;
+        const int cur = t + 1;
 #pragma unroll
-      for (int j = 0; j < NPL; ++j) x[j] = ((x[j] - m) - lz) + bs;
+        for (int j = 0; j < NPL; ++j) x[j] = (x[j] - m) - lz;
+        const unsigned long long m_gram = gram ? grammar_banned<NPL>(bm.gp, bm.gs + r0 + r, v0, V) : 0ull;
+        const unsigned long long m_ban = pp->has_bad1 ? lane_bits<NPL>(pp->bad1, v0) : 0ull;
+        const unsigned long long m_post = (pp->has_supp ? lane_bits<NPL>(pp->supp, v0) : 0ull) |
+                                          (pp->has_begin && cur == pp->begin_index ? lane_bits<NPL>(pp->begin, v0) : 0ull);
+        apply_lane_processors<NPL>(pp, x, cur, v0, V, a.eos_id, 0ull, m_ban, m_gram, m_post);
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) x[j] += bs;
+      } else {
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) x[j] = ((x[j] - m) - lz) + bs;
+      }
       if (__ballot(bad) && lane == 0) s_bad = 1;
       unsigned long long taken = 0ull;
       for (int k = 0; k < K; ++k) {
@@ -2615,6 +2663,17 @@ __global__ __launch_bounds__(1024) void dec_beam_kernel(DecHeadArgs a, DecBeamAr
       }
     }
     const bool dn = s_done != 0;
+    if constexpr (PROCESSED) {
+      // new beam i: its parent's state (the LDS copy) advanced by its token, with plain stores; a clip done at this step writes nothing
+      if (gram && !dn && tid < nb) {
+        constexpr int W = (int)(sizeof(GrammarState) / 4);
+        unsigned* dst = reinterpret_cast<unsigned*>(bm.gs + r0 + tid);
+        const unsigned* src = s_gs + min(max(s_par[tid], 0), nb - 1) * W;
+#pragma unroll
+        for (int w = 0; w < W; ++w) dst[w] = src[w];
+        grammar_advance(bm.gp, bm.gs + r0 + tid, s_tok[tid]);
+      }
+    }
     for (int i = wave; i < nb; i += 16) {
       const int p = dn ? i : s_par[i];
       if (!dn) {
@@ -2638,9 +2697,19 @@ __global__ __launch_bounds__(1024) void dec_beam_kernel(DecHeadArgs a, DecBeamAr
   }
 }
 
-static int launch_dec_beam(const DecHeadArgs& h, const DecBeamArgs& bm, int nbeams, hipStream_t st) {
+// pp == nullptr: the plain head (HEAD_BEAM); otherwise the processed one (HEAD_BEAM | HEAD_PROCESSED) with the blocks and the rows' states
+static int launch_dec_beam(const DecHeadArgs& h, const DecBeamArgs& bm, int nbeams, const ProcessParams* pp, const GrammarParams* gp,
+                           GrammarState* gs, hipStream_t st) {
   M2M_REQUIRE(nbeams >= 2 && nbeams <= BEAM_MAX && h.B % nbeams == 0, "dec_beam_kernel: %d rows are not clips of %d beams", h.B, nbeams);
   const dim3 grid((unsigned)(h.B / nbeams)), block(1024);
+  if (pp) {
+    DecBeamProcArgs bp{};
+    static_cast<DecBeamArgs&>(bp) = bm;
+    bp.pp = pp; bp.gp = gp; bp.gs = gs;
+    return launch_vocab_band("dec_beam_kernel", h.V, [&](auto npl) {
+      hipLaunchKernelGGL((dec_beam_kernel<decltype(npl)::value, true>), grid, block, 0, st, h, bp);
+    });
+  }
   return launch_vocab_band("dec_beam_kernel", h.V, [&](auto npl) {
     hipLaunchKernelGGL(dec_beam_kernel<decltype(npl)::value>, grid, block, 0, st, h, bm);
   });
@@ -2907,7 +2976,7 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
   if (skip_finished && s->finished_skip) { a.fin_skip = s->finished + v.b0; a.fin_stride = 1; }
   else { a.fin_skip = &v.state->zero; a.fin_stride = 0; }
   // beam search: the view's rows are clips x beam_nb beams (the view starts at a clip boundary)
-  const bool beam = s->head_mode == HEAD_BEAM && s->beam_nb > 0;
+  const bool beam = (s->head_mode & HEAD_BEAM) && s->beam_nb > 0;
   if (beam) {
     a.beam_nb = s->beam_nb;
     a.anc = s->anc + (int64_t)v.b0 * s->max_dec; a.anc_par = (int64_t)s->max_batch * s->max_dec; a.anc_ld = s->max_dec;
@@ -2970,7 +3039,10 @@ int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* log
   if ((rc = launch_dec_gemm(P, a, st))) return rc;
   if (headless) return M2M_OK;             // the arg-max key is consumed by the next step's layer 0 (or by decode_finalize)
   DecHeadArgs h = head_args(s, v, forced, logits_out, Ld);
-  if (!forced && s->head_mode == HEAD_BEAM) return launch_dec_beam(h, beam_args(s, v), s->beam_nb, st);
+  if (!forced && (s->head_mode & HEAD_BEAM)) {
+    const bool processed = s->head_mode & HEAD_PROCESSED;       // the grammar states of a beam call are by row: the view's start at b0
+    return launch_dec_beam(h, beam_args(s, v), s->beam_nb, processed ? s->proc_dev : nullptr, s->gram_dev, s->gram_state + v.b0, st);
+  }
   if (!forced && s->head_mode != HEAD_GREEDY) return launch_dec_select(h, s->head_mode, s->sample_dev, s->proc_dev, s->score_dev, s->gram_dev, s->gram_state, st);
   hipLaunchKernelGGL(dec_head_kernel, dim3(1), dim3(1024), 0, st, h);
   M2M_CHECK_HIP(hipGetLastError());

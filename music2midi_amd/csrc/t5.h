@@ -119,7 +119,9 @@ struct ScoreParams {
 // parameters, a device block of the workspace written before the chains start by EVERY call of the processed or scored head (enable
 // = 0 without the grammar: one captured graph serves both), and the state of one clip, indexed by the clip (tok_row[b]), not the
 // slot - live-row re-packing does not move it.  The states are zeroed on the caller's stream before the chains start: zero is the
-// start state (no phase entered, every time index allowed, nothing sounding).
+// start state (no phase entered, every time index allowed, nothing sounding).  The processed beam head (m2m_generate_beam_processed)
+// keeps one state per ROW instead (row c * nb + i: beam i of clip c) in the same region, which holds max_batch states: a clip's
+// beams diverge, and dec_beam_kernel gives new beam i its parent's state advanced by its token.
 constexpr int GRAM_MAX_PITCH = 128;
 constexpr int GRAM_EOS = 2, GRAM_ONSET = 3, GRAM_OFFSET = 4;     // music2midi_amd/tokenizer.py
 enum { GRAM_START = 0, GRAM_TIME = 1, GRAM_ONSET_OPEN = 2, GRAM_ONSET_LIST = 3, GRAM_OFFSET_OPEN = 4, GRAM_OFFSET_LIST = 5 };
@@ -262,7 +264,7 @@ struct m2m_session {
   m2m::ScoreParams* score_host = nullptr;     // pinned staging copy
   m2m::GrammarParams* gram_dev = nullptr;     // [1] in the workspace
   m2m::GrammarParams* gram_host = nullptr;    // pinned staging copy, written by decode_call from the call's block
-  m2m::GrammarState* gram_state = nullptr;    // [max_batch] in the workspace, by clip
+  m2m::GrammarState* gram_state = nullptr;    // [max_batch] in the workspace, by clip (by row in a processed beam call)
   // beam search (m2m_generate_beam): rows = encoded clips x beam_nb; every buffer below is in the workspace
   int beam_nb = 0;                            // beams per clip during a beam call, 0 otherwise
   m2m::BeamParams* beam_dev = nullptr;        // [1]
@@ -364,7 +366,8 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
 int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int t, hipStream_t st);   // live-row re-packing (decode.hip)
 int decode_finalize(m2m_session* s, const DecView& v, hipStream_t st);   // headless greedy loop: write the last token, close the chain
 constexpr int HEAD_GREEDY = 0, HEAD_SAMPLE = 1, HEAD_BEAM = 2;
-constexpr int HEAD_PROCESSED = 4;        // bit: logits processors before the greedy (| 0) or sampling (| HEAD_SAMPLE) select
+constexpr int HEAD_PROCESSED = 4;        // bit: logits processors before the greedy (| 0) or sampling (| HEAD_SAMPLE) select, or on the
+                                         // log-probabilities of the beam head (| HEAD_BEAM: m2m_generate_beam_processed)
 constexpr int HEAD_SCORED = 8;           // bit: the processed head that also writes scores / log-probabilities (always with HEAD_PROCESSED)
 constexpr int BEAM_MAX = 32;             // beams per clip: one LDS list of 2 x 32 candidates per beam, ancestries in bytes
 int decode_beam_init(m2m_session* s, const DecView& v, hipStream_t st);

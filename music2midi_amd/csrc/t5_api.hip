@@ -674,14 +674,8 @@ extern "C" int m2m_generate_scored(m2m_session* s, int max_length, const m2m_pro
                          "m2m_generate_scored");
 }
 
-// The MIDI token grammar (include/music2midi_amd.h): the processed or scored head with the call's GrammarParams block (DecodeCall::gram:
-// decode_call uploads it and zeroes the clips' states); without a processor the neutral m2m_process_params.
-extern "C" int m2m_generate_grammar(m2m_session* s, int max_length, const m2m_grammar_params* grammar, const m2m_process_params* proc,
-                                    const m2m_sample_params* sample, int64_t* tokens_out_dev, float* scores_out_dev,
-                                    float* logprobs_out_dev, int* out_len_host, void* stream) {
-  const char* fn = "m2m_generate_grammar";
-  if (!grammar) return m2m_generate_scored(s, max_length, proc, sample, tokens_out_dev, scores_out_dev, logprobs_out_dev, out_len_host, stream);
-  M2M_REQUIRE(s && tokens_out_dev && out_len_host, "m2m_generate_grammar: null argument");
+// the call's grammar block (m2m_generate_grammar, m2m_generate_beam_processed), checked against the model and laid out for the device
+static int fill_grammar_params(const m2m_session* s, int max_length, const m2m_grammar_params* grammar, GrammarParams& gp, const char* fn) {
   const m2m_t5_geometry& g = s->m->g;
   const int V = g.vocab_size;
   M2M_REQUIRE(V <= PROC_MAX_VOCAB, "%s: vocab_size %d > %d (the processed head keeps a row in one wavefront's registers)", fn, V, PROC_MAX_VOCAB);
@@ -695,8 +689,22 @@ extern "C" int m2m_generate_grammar(m2m_session* s, int max_length, const m2m_gr
               fn, grammar->pitch_offset + grammar->n_pitch + grammar->n_time, V);
   M2M_REQUIRE(g.eos_token_id == GRAM_EOS, "%s: the grammar ends a sequence with id %d, the model's eos_token_id is %d", fn, GRAM_EOS,
               g.eos_token_id);
-  GrammarParams gp{};
+  gp = GrammarParams{};
   gp.enable = 1; gp.pitch0 = grammar->pitch_offset; gp.time0 = gp.pitch0 + grammar->n_pitch; gp.end = gp.time0 + grammar->n_time;
+  return M2M_OK;
+}
+
+// The MIDI token grammar (include/music2midi_amd.h): the processed or scored head with the call's GrammarParams block (DecodeCall::gram:
+// decode_call uploads it and zeroes the clips' states); without a processor the neutral m2m_process_params.
+extern "C" int m2m_generate_grammar(m2m_session* s, int max_length, const m2m_grammar_params* grammar, const m2m_process_params* proc,
+                                    const m2m_sample_params* sample, int64_t* tokens_out_dev, float* scores_out_dev,
+                                    float* logprobs_out_dev, int* out_len_host, void* stream) {
+  const char* fn = "m2m_generate_grammar";
+  if (!grammar) return m2m_generate_scored(s, max_length, proc, sample, tokens_out_dev, scores_out_dev, logprobs_out_dev, out_len_host, stream);
+  M2M_REQUIRE(s && tokens_out_dev && out_len_host, "m2m_generate_grammar: null argument");
+  GrammarParams gp{};
+  int rc;
+  if ((rc = fill_grammar_params(s, max_length, grammar, gp, fn))) return rc;
   if (scores_out_dev || logprobs_out_dev)
     return generate_scored(s, max_length, proc, sample, tokens_out_dev, scores_out_dev, logprobs_out_dev, out_len_host, stream, &gp, fn);
   m2m_process_params neutral{};
@@ -707,7 +715,7 @@ extern "C" int m2m_generate_grammar(m2m_session* s, int max_length, const m2m_gr
 // the decode loop of every head form (s->head_mode, set by decode_call)
 static int decode_loop(m2m_session* s, const DecodeCall& c, int max_length, int* out_len_host, hipStream_t caller) {
   const char* fn = c.fn;
-  const bool beam = c.head_mode == HEAD_BEAM;
+  const bool beam = c.head_mode & HEAD_BEAM;
   const int steps = max_length - 1, rows = beam ? s->B * c.beam_nb : s->B;
   const DecodeSwitches sw;
   int G = plan_groups(s, sw.group_rows, rows);        // beam search: chains split at clip boundaries
@@ -853,15 +861,17 @@ static int decode_call(m2m_session* s, const DecodeCall& c, int max_length, int*
   if (c.head_mode & HEAD_SAMPLE) rc = upload(s->sample_dev, s->sample_host, sizeof(SampleParams), caller, c.fn);
   if (rc == M2M_OK && (c.head_mode & HEAD_PROCESSED)) rc = upload(s->proc_dev, s->proc_host, sizeof(ProcessParams), caller, c.fn);
   if (rc == M2M_OK && (c.head_mode & HEAD_PROCESSED)) {
-    // the grammar block travels with every processed call (enable = 0 without a grammar); with one, the clips' states restart
+    // the grammar block travels with every processed call (enable = 0 without a grammar); with one, the states of the call's rows
+    // restart (one per clip; one per beam row in a processed beam call)
     *s->gram_host = c.gram ? *c.gram : GrammarParams{};
     rc = upload(s->gram_dev, s->gram_host, sizeof(GrammarParams), caller, c.fn);
-    if (rc == M2M_OK && c.gram && hipMemsetAsync(s->gram_state, 0, (size_t)s->B * sizeof(GrammarState), caller) != hipSuccess) {
+    const size_t gram_rows = (size_t)s->B * (size_t)((c.head_mode & HEAD_BEAM) ? c.beam_nb : 1);
+    if (rc == M2M_OK && c.gram && hipMemsetAsync(s->gram_state, 0, gram_rows * sizeof(GrammarState), caller) != hipSuccess) {
       set_error("%s: hipMemsetAsync: %s", c.fn, hipGetErrorString(hipGetLastError()));
       rc = M2M_ERR_HIP;
     }
   }
-  if (rc == M2M_OK && c.head_mode == HEAD_BEAM) rc = upload(s->beam_dev, s->beam_host, sizeof(BeamParams), caller, c.fn);
+  if (rc == M2M_OK && (c.head_mode & HEAD_BEAM)) rc = upload(s->beam_dev, s->beam_host, sizeof(BeamParams), caller, c.fn);
   if (rc == M2M_OK && (c.head_mode & HEAD_SCORED)) {
     // finished rows write nothing: the caller's buffers are zeroed on its stream, before the chains start
     const ScoreParams& sc = *s->score_host;
@@ -883,30 +893,67 @@ static int decode_call(m2m_session* s, const DecodeCall& c, int max_length, int*
 
 // Beam search (hf 4.34 _beam_search / BeamSearchScorer, see include/music2midi_amd.h): the B encoded clips are decoded as B x nb
 // rows (clip-major).  The step's head is dec_beam_kernel; dec_beam_final_kernel writes the output.
+// the checks of a beam call and its BeamParams block (m2m_generate_beam, m2m_generate_beam_processed); `h` is the caller's: the
+// session's staging block is written once every check of the call has passed
+static int fill_beam_params(const m2m_session* s, int max_length, const m2m_beam_params* p, BeamParams& h, const char* fn) {
+  M2M_REQUIRE(p->num_beams >= 2 && p->num_beams <= BEAM_MAX, "%s: num_beams %d outside [2, %d] (one beam is m2m_generate_greedy)", fn,
+              p->num_beams, BEAM_MAX);
+  M2M_REQUIRE(p->num_return_sequences >= 1 && p->num_return_sequences <= p->num_beams,
+              "%s: num_return_sequences %d has to be in [1, num_beams = %d]", fn, p->num_return_sequences, p->num_beams);
+  M2M_REQUIRE(p->early_stopping >= 0 && p->early_stopping <= 2, "%s: early_stopping %d must be 0 (False), 1 (True) or 2 (\"never\")", fn,
+              p->early_stopping);
+  M2M_REQUIRE(isfinite(p->length_penalty), "%s: length_penalty must be finite, got %g", fn, (double)p->length_penalty);
+  const int V = s->m->g.vocab_size;
+  M2M_REQUIRE(V <= SAMPLE_MAX_VOCAB && V >= 2 * p->num_beams, "%s: vocab_size %d outside [2 num_beams, %d] (the beam head keeps a row in "
+              "one wavefront's registers)", fn, V, SAMPLE_MAX_VOCAB);
+  int rc;
+  if ((rc = require_encoded(s, fn))) return rc;
+  M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "%s: max_length %d outside [1, %d]", fn, max_length, s->max_dec);
+  M2M_REQUIRE((int64_t)s->B * p->num_beams <= s->max_batch, "%s: %d clips x %d beams > the session's max_batch %d", fn, s->B, p->num_beams,
+              s->max_batch);
+  h = BeamParams{};
+  h.nb = p->num_beams; h.lp = p->length_penalty; h.early = p->early_stopping; h.n = p->num_return_sequences;
+  h.max_length = max_length; h.max_hyp_len = 0;
+  return M2M_OK;
+}
+
 extern "C" int m2m_generate_beam(m2m_session* s, int max_length, const m2m_beam_params* p, int64_t* tokens_out_dev,
                                  float* scores_out_dev, int* out_len_host, void* stream) {
   const char* fn = "m2m_generate_beam";
   M2M_REQUIRE(s && p && tokens_out_dev && out_len_host, "m2m_generate_beam: null argument");
-  M2M_REQUIRE(p->num_beams >= 2 && p->num_beams <= BEAM_MAX, "m2m_generate_beam: num_beams %d outside [2, %d] (one beam is "
-              "m2m_generate_greedy)", p->num_beams, BEAM_MAX);
-  M2M_REQUIRE(p->num_return_sequences >= 1 && p->num_return_sequences <= p->num_beams,
-              "m2m_generate_beam: num_return_sequences %d has to be in [1, num_beams = %d]", p->num_return_sequences, p->num_beams);
-  M2M_REQUIRE(p->early_stopping >= 0 && p->early_stopping <= 2,
-              "m2m_generate_beam: early_stopping %d must be 0 (False), 1 (True) or 2 (\"never\")", p->early_stopping);
-  M2M_REQUIRE(isfinite(p->length_penalty), "m2m_generate_beam: length_penalty must be finite, got %g", (double)p->length_penalty);
-  const int V = s->m->g.vocab_size;
-  M2M_REQUIRE(V <= SAMPLE_MAX_VOCAB && V >= 2 * p->num_beams, "m2m_generate_beam: vocab_size %d outside [2 num_beams, %d] (the beam "
-              "head keeps a row in one wavefront's registers)", V, SAMPLE_MAX_VOCAB);
   int rc;
-  if ((rc = require_encoded(s, fn))) return rc;
-  M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "m2m_generate_beam: max_length %d outside [1, %d]", max_length, s->max_dec);
-  M2M_REQUIRE((int64_t)s->B * p->num_beams <= s->max_batch, "m2m_generate_beam: %d clips x %d beams > the session's max_batch %d",
-              s->B, p->num_beams, s->max_batch);
-  BeamParams& h = *s->beam_host;
-  h = BeamParams{};
-  h.nb = p->num_beams; h.lp = p->length_penalty; h.early = p->early_stopping; h.n = p->num_return_sequences;
-  h.max_length = max_length; h.max_hyp_len = 0;
+  BeamParams bp{};
+  if ((rc = fill_beam_params(s, max_length, p, bp, fn))) return rc;
+  *s->beam_host = bp;
   return decode_call(s, {fn, HEAD_BEAM, p->num_beams, tokens_out_dev, scores_out_dev}, max_length, out_len_host, (hipStream_t)stream);
+}
+
+// Beam search under the token grammar and the logits processors (include/music2midi_amd.h): the processed beam head (HEAD_BEAM |
+// HEAD_PROCESSED, dec_beam_kernel<NPL, true>) with the call's ProcessParams block (the neutral one without a processor) and its
+// GrammarParams block (enable = 0 without a grammar).  The processors that read a row's history are refused: a beam's history is
+// scattered through the ancestry table.
+extern "C" int m2m_generate_beam_processed(m2m_session* s, int max_length, const m2m_beam_params* p, const m2m_grammar_params* grammar,
+                                           const m2m_process_params* proc, int64_t* tokens_out_dev, float* scores_out_dev,
+                                           int* out_len_host, void* stream) {
+  const char* fn = "m2m_generate_beam_processed";
+  if (!grammar && !proc) return m2m_generate_beam(s, max_length, p, tokens_out_dev, scores_out_dev, out_len_host, stream);
+  M2M_REQUIRE(s && p && tokens_out_dev && out_len_host, "m2m_generate_beam_processed: null argument");
+  int rc;
+  // validate first, then fill: a refused call leaves the session's staging blocks as they were
+  BeamParams bp{};
+  if ((rc = fill_beam_params(s, max_length, p, bp, fn))) return rc;
+  GrammarParams gp{};
+  if (grammar && (rc = fill_grammar_params(s, max_length, grammar, gp, fn))) return rc;
+  m2m_process_params neutral{};
+  neutral.repetition_penalty = 1.0f; neutral.forced_bos_token_id = -1; neutral.forced_eos_token_id = -1;
+  static thread_local ProcessParams h;       // (4.4 KB: not on the stack)
+  if ((rc = fill_process_params(s, max_length, proc ? proc : &neutral, h, fn))) return rc;   // (max_length <= 2048 too)
+  M2M_REQUIRE(h.penalty == 1.0f && h.ngram == 0 && h.n_bad == 0, "%s: repetition_penalty, no_repeat_ngram_size and bad_words sequences of "
+              "two or more ids read a row's history and are not applied under beam search", fn);
+  *s->beam_host = bp;
+  *s->proc_host = h;
+  return decode_call(s, {fn, HEAD_BEAM | HEAD_PROCESSED, p->num_beams, tokens_out_dev, scores_out_dev, grammar ? &gp : nullptr}, max_length,
+                     out_len_host, (hipStream_t)stream);
 }
 
 // Teacher-forced decoder pass over all Ld positions at once (hf: modeling_t5.py:448-509 per block, :898-1066 wrapper):

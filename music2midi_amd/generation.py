@@ -10,7 +10,8 @@ and the argument checks of its logits warpers (hf: generation/logits_process.py 
 ``_get_logits_processor`` and its processors' checks.  Beam search and every other keyword raise
 ``NotImplementedError`` there (``return_dict_in_generate``, ``output_scores`` and the project keyword ``output_logprobs`` select
 the per-token outputs of the scored head; ``midi_grammar`` the token grammar of ``grammar.py``); beam search has its own entry point (``T5Transformer.beam_search``), whose keywords
-``resolve_beam_kwargs`` checks.
+``resolve_beam_kwargs`` checks, and ``T5Transformer.beam_search_processed`` takes the grammar and the processors that do not read a
+row's history under beams (``resolve_beam_process_kwargs``).
 """
 from __future__ import annotations
 
@@ -284,3 +285,31 @@ def resolve_beam_kwargs(num_beams, max_length=DEFAULT_MAX_LENGTH, length_penalty
     return BeamConfig(num_beams=operator.index(num_beams), max_length=operator.index(max_length),
                       length_penalty=float(length_penalty), early_stopping=early_stopping,
                       num_return_sequences=operator.index(num_return_sequences))
+
+
+def resolve_beam_process_kwargs(kwargs: dict, vocab_size=None, grammar=None, max_length=None):
+    """The processor keywords and ``midi_grammar`` of ``T5Transformer.beam_search_processed`` -> ``(ProcessConfig | None,
+    midi_grammar)``.  ``kwargs`` is not modified.  The checks are ``resolve_process_kwargs``'s and ``grammar.check_device_limits``
+    (``ValueError``, as the greedy path raises them; ``max_length``, when given, is held to the processed head's limit too).
+    ``repetition_penalty``, ``no_repeat_ngram_size`` and ``bad_words_ids`` sequences of two or more ids raise
+    ``NotImplementedError``: they read a row's history, which the beam head does not stage; any other keyword does as well."""
+    kw = dict(kwargs)
+    midi_grammar = kw.pop("midi_grammar", False)
+    if not isinstance(midi_grammar, bool):
+        raise ValueError(f"`midi_grammar` has to be a bool, but is {midi_grammar!r}")
+    process = resolve_process_kwargs(kw, vocab_size)
+    if kw:
+        raise NotImplementedError(f"unsupported beam_search_processed kwargs on the MI355X path: {sorted(kw)}")
+    if process is not None:
+        active = [name for name, on in (("repetition_penalty", process.repetition_penalty != 1.0),
+                                        ("no_repeat_ngram_size", process.no_repeat_ngram_size > 0),
+                                        ("bad_words_ids", any(len(w) >= 2 for w in process.bad_words_ids))) if on]
+        if active:
+            raise NotImplementedError(f"beam search on the MI355X path does not apply {', '.join(f'`{a}`' for a in active)} "
+                                      "(bad_words_ids: sequences of two or more ids): they read a row's history, which a beam keeps "
+                                      "scattered through the ancestry table")
+    if (process is not None or midi_grammar) and max_length is not None and max_length > PROCESS_MAX_LENGTH:
+        raise ValueError(f"logits processors and `midi_grammar` on the MI355X path take max_length <= {PROCESS_MAX_LENGTH}, got {max_length}")
+    if midi_grammar and grammar is not None and vocab_size is not None:
+        grammar.check_device_limits(vocab_size)
+    return process, midi_grammar

@@ -21,11 +21,20 @@ from . import distributed as D
 from .accumulation import check_accumulate_grad_batches, micro_step, windows
 from .audio import load_audio as _load_audio
 from .checkpoint import load_t5_state, read_checkpoint
-from .config import load_config
+from .config import inference_beams, load_config
 from .evaluation import evaluate_batch
 from .input import ModelInputs
 from .transformer import T5Transformer
 from .utils import numpy_to_midi
+
+
+def _decode_entry(model, config, grammar_kwargs: dict):
+    """(decode function, its keywords): ``model.generate`` with the grammar keyword, or - with ``config.inference.num_beams`` > 1 -
+    ``model.beam_search_processed`` with the config's beam settings, one returned sequence per clip and the same grammar switch."""
+    beams = inference_beams(config)
+    if not beams:
+        return model.generate, grammar_kwargs
+    return model.beam_search_processed, dict(beams, num_return_sequences=1, **grammar_kwargs)
 
 
 class Music2MIDI(nn.Module):
@@ -310,7 +319,21 @@ class Music2MIDI(nn.Module):
         """(chroma accuracy, decoded MIDI per clip, label MIDI per clip) for one labelled batch — ref
         model.py:55-65.  The decode budget is four tokens per label note of the busiest clip."""
         budget = 4 * max(len(n) for n in inputs.notes_batch)
-        token_ids = self.model.generate(inputs, max_length=budget, **self._grammar_kwargs())
+        decode, decode_kwargs = _decode_entry(self.model, self.config, self._grammar_kwargs())
+        nb = int(decode_kwargs.get("num_beams", 1))
+        if nb == 1:
+            token_ids = decode(inputs, max_length=budget, **decode_kwargs)
+        else:   # beams: chunks of batch_size // num_beams clips, as sample_tokens, so a call's rows stay within inference.batch_size
+            per_call = max(1, int(self.config.inference.get("batch_size", 128)) // nb)
+            n_clips, parts = len(inputs.notes_batch), []
+            for lo in range(0, n_clips, per_call):
+                hi = min(lo + per_call, n_clips)
+                part = type(inputs)(input_waveform=inputs.input_waveform[lo:hi], notes_batch=inputs.notes_batch[lo:hi],
+                                    cond_index=inputs.cond_index[lo:hi] if inputs.cond_index is not None else None)
+                parts.append(decode(part, max_length=budget, **decode_kwargs))
+            width = max(p.shape[1] for p in parts)
+            pad = self.model.geometry.pad_token_id
+            token_ids = torch.cat([torch.nn.functional.pad(p, (0, width - p.shape[1]), value=pad) for p in parts], dim=0)
         predicted = [numpy_to_midi(n) for n in self.model.tokenizer.decode(token_ids, mode="batched")]
         wanted = [numpy_to_midi(n) for n in inputs.notes_batch]
         return evaluate_batch(wanted, predicted), predicted, wanted
@@ -358,9 +381,11 @@ class Music2MIDI(nn.Module):
     @torch.no_grad()
     def sample_tokens(self, waveform: torch.Tensor, split_size: int, split_duration: float,
                       cond_index: Optional[list] = None) -> np.ndarray:
-        """Segments -> chunks of inference.batch_size -> generate(max_length=1024) -> notes."""
+        """Segments -> chunks of inference.batch_size -> generate(max_length=1024) -> notes.  With inference.num_beams > 1 a chunk is
+        batch_size // num_beams clips, decoded by beam_search_processed: the rows of a call stay what the config sized the session for."""
         pieces = torch.split(waveform, split_size)
-        per_call = int(self.config.inference.batch_size)
+        decode, decode_kwargs = _decode_entry(self.model, self.config, self._grammar_kwargs())
+        per_call = max(1, int(self.config.inference.batch_size) // int(decode_kwargs.get("num_beams", 1)))
         token_rows = []
         for first in range(0, len(pieces), per_call):
             group = pieces[first:first + per_call]
@@ -370,7 +395,7 @@ class Music2MIDI(nn.Module):
                 wav[row, : piece.shape[0]] = piece
             # with a process group (one process per GPU) the chunk's segments are sharded over the ranks and the ids
             # all-gathered back in segment order; a single process decodes the chunk itself
-            ids = D.generate_sharded(self.model.generate, ModelInputs(input_waveform=wav, cond_index=self._cond_rows(len(group), cond_index)),
-                                     max_length=1024, pad_id=self.model.geometry.pad_token_id, **self._grammar_kwargs())
+            ids = D.generate_sharded(decode, ModelInputs(input_waveform=wav, cond_index=self._cond_rows(len(group), cond_index)),
+                                     max_length=1024, pad_id=self.model.geometry.pad_token_id, **decode_kwargs)
             token_rows.extend(ids.unbind(0))
         return self.model.tokenizer.decode(token_rows, mode="sequential", duration_per_batch=split_duration)

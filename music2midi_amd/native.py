@@ -124,6 +124,8 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "m2m_generate_beam": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BeamParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                     C.c_void_p]),
+    "m2m_generate_beam_processed": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(BeamParams), C.POINTER(GrammarParams),
+                                              C.POINTER(ProcessParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "m2m_session_repack_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "m2m_decode_forced": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "m2m_trainer_create": (C.c_int, [C.POINTER(T5GeometryC), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,

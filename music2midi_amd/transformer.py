@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import native
 from .config import T5Geometry, load_config
-from .generation import GenerateConfig, resolve_beam_kwargs, resolve_generate_kwargs
+from .generation import GenerateConfig, ProcessConfig, resolve_beam_kwargs, resolve_beam_process_kwargs, resolve_generate_kwargs
 from .input import Conditioning, LogMelSpectrogram, ModelInputs
 from .tokenizer import EOS, MidiTokenizer
 
@@ -332,6 +332,21 @@ class T5Transformer(nn.Module):
                else GenerateConfig(max_length=max_length))
         return self._decode(inputs_embeds, cfg)
 
+    @staticmethod
+    def _process_params(pc: ProcessConfig) -> "native.ProcessParams":
+        """The ``m2m_process_params`` block of the resolved processors (the block keeps its id lists alive)."""
+        def ids(v):
+            return (C.c_int32 * max(len(v), 1))(*v), len(v)
+
+        supp, n_supp = ids(pc.suppress_tokens)
+        begin, n_begin = ids(pc.begin_suppress_tokens)
+        bad, _ = ids([i for w in pc.bad_words_ids for i in w])
+        bad_len, n_bad = ids([len(w) for w in pc.bad_words_ids])
+        pp = native.ProcessParams(pc.repetition_penalty, pc.no_repeat_ngram_size, pc.min_length, pc.min_new_tokens,
+                                  pc.forced_bos_token_id, pc.forced_eos_token_id, supp, n_supp, begin, n_begin, bad, bad_len, n_bad)
+        pp._lists = (supp, begin, bad, bad_len)
+        return pp
+
     @torch.no_grad()
     def _decode(self, inputs_embeds: torch.Tensor, cfg: GenerateConfig):
         """Greedy, sampled or processed decode of encoder inputs [B, S, d] as the resolved ``cfg`` asks."""
@@ -341,17 +356,7 @@ class T5Transformer(nn.Module):
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
             sp = native.SampleParams(cfg.temperature, cfg.top_k, cfg.top_p, seed)
         if cfg.process is not None:
-            pc = cfg.process
-
-            def ids(v):
-                return (C.c_int32 * max(len(v), 1))(*v), len(v)
-
-            supp, n_supp = ids(pc.suppress_tokens)
-            begin, n_begin = ids(pc.begin_suppress_tokens)
-            bad, _ = ids([i for w in pc.bad_words_ids for i in w])
-            bad_len, n_bad = ids([len(w) for w in pc.bad_words_ids])
-            pp = native.ProcessParams(pc.repetition_penalty, pc.no_repeat_ngram_size, pc.min_length, pc.min_new_tokens,
-                                      pc.forced_bos_token_id, pc.forced_eos_token_id, supp, n_supp, begin, n_begin, bad, bad_len, n_bad)
+            pp = self._process_params(cfg.process)
             export, params = "m2m_generate_processed", (C.byref(pp), C.byref(sp) if sp is not None else None)
         elif sp is not None:
             export, params = "m2m_generate_sample", (C.byref(sp),)
@@ -440,12 +445,73 @@ class T5Transformer(nn.Module):
         ``sequences_scores`` (float32 [B * n], length-normalised: sum of log-probs / len ** length_penalty).
         ``early_stopping`` is True, False or "never"; ``num_beams`` is 2..32.  Each clip is encoded once; its beams share
         its cross-attention K/V and read their self-attention K/V through an ancestry table on the GPU.
-        ``generate(num_beams > 1)`` still raises ``NotImplementedError``; beam sampling, group / diverse and constrained beams
-        are not implemented."""
+        ``generate(num_beams > 1)`` still raises ``NotImplementedError``; beam sampling and group / diverse beams are not
+        implemented.  The token grammar and the logits processors under beams: :meth:`beam_search_processed`."""
         encoder_inputs = self.encoder_inputs(inputs)
         return self.beam_search_from_embeds(encoder_inputs, num_beams, max_length=max_length, length_penalty=length_penalty,
                                             early_stopping=early_stopping, num_return_sequences=num_return_sequences,
                                             return_scores=return_scores)
+
+    @torch.no_grad()
+    def beam_search_processed_from_embeds(self, inputs_embeds: torch.Tensor, num_beams: int, max_length: int = 20,
+                                          length_penalty: float = 1.0, early_stopping=False, num_return_sequences: int = 1,
+                                          return_scores: bool = False, midi_grammar: bool = False, **processor_keywords):
+        """Beam search under the token grammar and the logits processors from encoder inputs [B, S, d]; keywords and result as
+        :meth:`beam_search_processed`."""
+        kw = dict(processor_keywords)
+        max_new = kw.pop("max_new_tokens", None)
+        if max_new is not None:                                      # as generate: the decoder prompt is the start token
+            if isinstance(max_new, bool) or not isinstance(max_new, int) or max_new <= 0:
+                raise ValueError(f"`max_new_tokens` must be greater than 0, but is {max_new}.")
+            max_length = max_new + 1
+        cfg = resolve_beam_kwargs(num_beams, max_length, length_penalty, early_stopping, num_return_sequences)
+        kw["midi_grammar"] = midi_grammar
+        pc, gram = resolve_beam_process_kwargs(kw, self.geometry.vocab_size, self.tokenizer.grammar if midi_grammar is True else None,
+                                               max_length=cfg.max_length)
+        pp = self._process_params(pc) if pc is not None else None
+        gp = None
+        if gram:
+            gr = self.tokenizer.grammar
+            if self.geometry.eos_token_id != EOS:
+                raise ValueError(f"`midi_grammar` ends a sequence with the tokenizer's EOS ({EOS}); the model's eos_token_id is "
+                                 f"{self.geometry.eos_token_id}")
+            gp = native.GrammarParams(gr.pitch_offset, gr.n_pitch, gr.n_time)
+        with self._lock:
+            x = inputs_embeds.to(self.transformer.device, torch.float32).contiguous()
+            B, n = x.shape[0], cfg.num_return_sequences
+            sess, _ = self._encode(x, cfg.max_length, rows=B * cfg.num_beams)   # encoded once per clip, decoded as B x nb rows
+            tokens = torch.empty((B * n, cfg.max_length), dtype=torch.long, device=x.device)
+            scores = torch.empty((B * n,), dtype=torch.float32, device=x.device) if return_scores else None
+            out_len = C.c_int(0)
+            p = native.BeamParams(cfg.num_beams, cfg.length_penalty, cfg.early_stopping_code, n)
+            with torch.cuda.device(x.device):
+                native.check(native.load().m2m_generate_beam_processed(
+                    sess, cfg.max_length, C.byref(p), C.byref(gp) if gp is not None else None, C.byref(pp) if pp is not None else None,
+                    tokens.data_ptr(), scores.data_ptr() if return_scores else None, C.byref(out_len),
+                    native.stream_handle(x.device)), "m2m_generate_beam_processed")
+            ids = tokens[:, : out_len.value]
+            return (ids, scores) if return_scores else ids
+
+    def beam_search_processed(self, inputs: ModelInputs, num_beams: int, max_length: int = 20, length_penalty: float = 1.0,
+                              early_stopping=False, num_return_sequences: int = 1, return_scores: bool = False,
+                              midi_grammar: bool = False, **processor_keywords):
+        """:meth:`beam_search` with a non-empty ``logits_processor`` (transformers 4.34 ``generate(num_beams=...,
+        prefix_allowed_tokens_fn=..., min_length=..., forced_eos_token_id=...)``): the most probable WELL-FORMED transcription.
+
+        Every step processes a row's ``log_softmax`` against its own beam's prefix before the beam score is added, in 4.34's
+        order: one-id ``bad_words_ids``, ``min_length``, ``min_new_tokens``, the MIDI token grammar (``midi_grammar=True``, at
+        ``PrefixConstrainedLogitsProcessor``'s place; a per-row state on the GPU that follows its parent when beams reorder),
+        ``forced_bos_token_id``, ``forced_eos_token_id`` (a forced id wins over the grammar), ``suppress_tokens``,
+        ``begin_suppress_tokens``.  ``max_new_tokens`` sets ``max_length = max_new_tokens + 1``.  ``repetition_penalty``,
+        ``no_repeat_ngram_size`` and ``bad_words_ids`` sequences of two or more ids raise ``NotImplementedError`` (they read a row's
+        history); invalid values raise ``ValueError``.  Shapes, order and ``return_scores`` are :meth:`beam_search`'s.  Where a clip
+        has fewer than ``num_beams`` finite candidates (the ``forced_eos_token_id`` step) its beams are filled from candidates at
+        ``-inf`` as in HF, and a returned sequence may have the score ``-inf``.  Without a processor and with
+        ``midi_grammar=False`` the call is :meth:`beam_search`."""
+        encoder_inputs = self.encoder_inputs(inputs)
+        return self.beam_search_processed_from_embeds(encoder_inputs, num_beams, max_length=max_length, length_penalty=length_penalty,
+                                                      early_stopping=early_stopping, num_return_sequences=num_return_sequences,
+                                                      return_scores=return_scores, midi_grammar=midi_grammar, **processor_keywords)
 
     @torch.no_grad()
     def logits_from_embeds(self, inputs_embeds: torch.Tensor, decoder_input_ids: torch.Tensor) -> torch.Tensor:
@@ -531,7 +597,8 @@ class T5Transformer(nn.Module):
         ``music2midi_amd.grammar`` (``self.tokenizer.grammar``): the ids that cannot follow the row's prefix go to ``-inf`` after the
         ``min_length`` / ``min_new_tokens`` bans and before ``forced_bos_token_id`` - exactly HF's
         ``prefix_allowed_tokens_fn=grammar.prefix_allowed_tokens_fn()``, as a per-clip state machine on the GPU; it combines with
-        sampling, every processor and the per-token outputs, and is off by default.  :meth:`beam_search` is unchanged (``sequences_scores`` only), and ``Music2MIDI.generate_notes`` does not
+        sampling, every processor and the per-token outputs, and is off by default.  :meth:`beam_search` is unchanged (``sequences_scores`` only;
+        :meth:`beam_search_processed` is the beam search that takes the grammar), and ``Music2MIDI.generate_notes`` does not
         carry per-note confidences yet (the tokenizer would have to keep token positions through ``decode``).  Invalid values
         raise ``ValueError``; beam search (``num_beams != 1``) and any other keyword raise ``NotImplementedError``."""
         cfg = resolve_generate_kwargs(kwargs, default_max_length=self._GENERATE_DEFAULT_MAX_LENGTH,
