@@ -499,6 +499,32 @@ int m2m_mx8_matmul_f32(const float* a_dev, const float* b_dev, int M, int N, int
  * and by test.  Test utility like the above. */
 int m2m_mx8_matmul_bf16a(const uint16_t* a_bf16_dev, const float* b_dev, int M, int N, int K, int a_is_e5m2, int fused, float* c_dev,
                          void* stream);
+/* The fp8 training step's own routes, one at a time (test utilities like the above: own scratch, `stream` synchronised; bad
+ * arguments answer M2M_ERR_INVALID).  The quantiser hooks return the RAW images; what the kernel does not write stays 0xFF.
+ * m2m_mx8_quantize_cols: the transposing quantiser of the fp8 weight gradient on src [R][C] (fp32, or bf16 when src_is_bf16; row
+ *   stride ld_s >= C elements): qt [C][Rp] FP8 bytes + scales [C][Rp/32] E8M0 bytes, blocks of 32 along the R rows,
+ *   Rp = R rounded up to 128, rows >= R zero.
+ * m2m_mx8_quantize_rows: the row quantiser (what m2m_mx8_matmul_* and the unfused step products run) on the same kind of source:
+ *   q [R][Cp] + scales [R][Cp/32], blocks along the C columns, Cp = C rounded up to 128, columns >= C zero.
+ * m2m_mx8_quantize_weight: the step's weight quantiser on one fp32 matrix W [N][K] (N, K multiples of 128, as the fp8 mode requires):
+ *   q [N][K] + qs [N][K/32] with blocks along K, qt [K][N] + qts [K][N/32] with blocks along N; e4m3. */
+int m2m_mx8_quantize_cols(const void* src_dev, int src_is_bf16, int R, int C, int64_t ld_s, int is_e5m2, uint8_t* qt_dev, uint8_t* scales_dev,
+                          void* stream);
+int m2m_mx8_quantize_rows(const void* src_dev, int src_is_bf16, int R, int C, int64_t ld_s, int is_e5m2, uint8_t* q_dev, uint8_t* scales_dev,
+                          void* stream);
+int m2m_mx8_quantize_weight(const float* w_dev, int N, int K, uint8_t* q_dev, uint8_t* qs_dev, uint8_t* qt_dev, uint8_t* qts_dev, void* stream);
+/* One projection product as the fp8 step issues it, for a weight W [N][K] and M rows (all row-major, dense):
+ *   kind 0, forward:  c [M][N] = x [M][K] . W^T     a = x (bf16), b = W (fp32, through the step's weight quantiser, row image)
+ *   kind 1, dX:       c [M][K] = dy [M][N] . W      a = dy (bf16, e5m2 when grad_is_e5m2), b = W (fp32, transposed image)
+ *   kind 2, dW:       c [N][K] = dy^T . x           a = dy [M][N], b = x [M][K] (both bf16): two transposing quantiser launches, then
+ *                                                    the product over the M rows under the step's split-K policy
+ * fused (kinds 0, 1): a is quantised in the product's operand staging (1) or by the row quantiser (0).  epilogue: 0 = c bf16,
+ * 1 = c fp32, 2 = c fp32 += product, 3 = c fp32 = r + dropout(product) with the step's counter-based hash (drop_p; element index
+ * row * width of c + column, key = splitmix64(step_key + site_salt)); kind 2 takes 1 or 2 only, N and K of kinds 0 and 1 are
+ * multiples of 128.  ksplit_out / kchunk_out (optional, host): the k-split and k-chunk the route used (1 and the whole depth when unsplit). */
+int m2m_mx8_step_product(int kind, const uint16_t* a_bf16_dev, const void* b_dev, int M, int N, int K, int grad_is_e5m2, int fused, int epilogue,
+                         void* c_dev, const float* r_dev, float drop_p, uint64_t step_key, uint64_t site_salt, int* ksplit_out, int* kchunk_out,
+                         void* stream);
 
 /* The training step's whole-head attention kernels on their own (csrc/attn_train.hip; hf: modeling_t5.py:159-170 T5Attention and its
  * autograd backward): q [B, Sq, H*64], k / v [B, Sk, H*64] bf16, row-major; bias_tab [H][Sq + Sk - 1] fp32 by (key - query + Sq - 1)

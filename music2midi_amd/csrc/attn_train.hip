@@ -669,23 +669,6 @@ int launch_attn_head_bwd(const HeadAttnArgs& a, int nB, hipStream_t st, const Tr
 // ---------------------------------------------------------------------------------------------------- test utilities (C ABI)
 using namespace m2m;
 
-namespace {
-// one 64-bit word on the device holding the dropout step key of a test call
-struct StepWord {
-  uint64_t* dev = nullptr;
-  uint64_t last = 0;
-  int set(uint64_t v, hipStream_t st) {
-    if (dev && v == last) return M2M_OK;                    // (repeated calls with one key — tools/attn_head_bench.py — stay asynchronous)
-    if (!dev) M2M_CHECK_HIP(hipMalloc((void**)&dev, 8));
-    M2M_CHECK_HIP(hipStreamSynchronize(st));
-    M2M_CHECK_HIP(hipMemcpyAsync(dev, &v, 8, hipMemcpyHostToDevice, st));
-    M2M_CHECK_HIP(hipStreamSynchronize(st));
-    last = v;
-    return M2M_OK;
-  }
-};
-}  // namespace
-
 extern "C" int m2m_attn_head_fwd_bf16(const uint16_t* q, const uint16_t* k, const uint16_t* v, const float* bias_tab, int B, int H, int Sq, int Sk,
                                       int causal, float drop_p, uint64_t step_key, uint64_t site_salt, uint16_t* out, float* lse, uint32_t* keep_bits,
                                       void* stream) {

@@ -16,6 +16,7 @@
 
 #include <stdlib.h>
 
+#include <algorithm>
 namespace m2m {
 
 typedef int v8i_t __attribute__((ext_vector_type(8)));
@@ -294,9 +295,10 @@ __global__ __launch_bounds__(256) void mxgemm_q_kernel(MxGemmArgs g) {
   }
 }
 
-// Both operands pre-quantised (the activations' fp8 image is written by the kernel that produces them — RMSNorm, gated GELU, the
-// gradient converters), 64 x (64 TN) tile, next k-step's 16-byte chunks prefetched into registers: the operand staging is byte
-// copies only, half the bytes of the bf16 product, and no VALU work in the loop.
+// Both operands pre-quantised (the activations' fp8 image comes from a quantiser launch of its own — launch_mxq_rows with fused
+// quantisation off, launch_mxq_cols for a weight gradient; no producing kernel writes it), 64 x (64 TN) tile, next k-step's 16-byte
+// chunks prefetched into registers: the operand staging is byte copies only, half the bytes of the bf16 product, and no VALU
+// work in the loop.
 template <int FA, int EPI, int TN>
 __global__ __launch_bounds__(256) void mxgemm_p_kernel(MxGemmArgs g) {
   constexpr int BN = 64 * TN;
@@ -511,6 +513,51 @@ int launch_mxq_cols(int src_kind, const void* src, int64_t ld_s, uint8_t* qt, ui
                        : launch_mxq_cols_t<bf16_t>((const bf16_t*)src, ld_s, qt, sc, R, C, Rp, fmt, st);
 }
 
+// ---- the fp8 step's three routes (train.h) ---------------------------------------------------------------------------------
+int mx8_fwd(int epi, const void* X, int64_t ldx, const uint8_t* wq, const uint8_t* wqs, uint8_t* q8a, uint8_t* s8a, void* C, int64_t ldc, const float* R,
+            int M, int N, int K, const MxDrop& drop, const TrainSwitches& sw, hipStream_t st) {
+  MxGemmArgs m{};
+  m.A = q8a; m.sA = s8a; m.B = wq; m.sB = wqs; m.C = C; m.R = R; m.M = M; m.N = N; m.K = K;
+  m.lda = K; m.ldb = K; m.ldc = ldc; m.drop_thresh = drop.thresh; m.drop_scale = drop.scale; m.drop_key = drop.key; m.drop_step = drop.step;
+  if (sw.fp8_fused_q && K % 128 == 0 && ldx % 8 == 0) {      // activations quantised inside the product's staging: one launch
+    m.Asrc = X; m.ld_src = ldx; m.Kvalid = K;
+    return launch_mxgemm_q(0, epi, m, st, sw);
+  }
+  int rc = launch_mxq_rows(1, X, ldx, q8a, s8a, M, K, K, 0, st);
+  if (rc != M2M_OK) return rc;
+  return launch_mxgemm(0, 0, epi, m, st, sw);
+}
+int mx8_dx(int epi, const void* dY, int64_t ldy, int Nw, int Kw, const uint8_t* wqt, const uint8_t* wqts, int Np, uint8_t* q8a, uint8_t* s8a, void* C,
+           int64_t ldc, const float* R, int M, const MxDrop& drop, const TrainSwitches& sw, hipStream_t st) {
+  MxGemmArgs m{};
+  m.A = q8a; m.sA = s8a; m.B = wqt; m.sB = wqts; m.C = C; m.R = R; m.M = M; m.N = Kw; m.K = Np;
+  m.lda = Np; m.ldb = Np; m.ldc = ldc; m.drop_thresh = drop.thresh; m.drop_scale = drop.scale; m.drop_key = drop.key; m.drop_step = drop.step;
+  if (sw.fp8_fused_q && Nw % 8 == 0 && ldy % 8 == 0) {
+    m.Asrc = dY; m.ld_src = ldy; m.Kvalid = Nw;
+    return launch_mxgemm_q(sw.grad_fmt, epi, m, st, sw);
+  }
+  int rc = launch_mxq_rows(1, dY, ldy, q8a, s8a, M, Nw, Np, sw.grad_fmt, st);
+  if (rc != M2M_OK) return rc;
+  return launch_mxgemm(sw.grad_fmt, 0, epi, m, st, sw);
+}
+int mx8_dw(const void* dY, int64_t ldy, int Ny, const void* X, int64_t ldx, int Kx, uint8_t* q8ta, uint8_t* s8ta, uint8_t* q8tb, uint8_t* s8tb, float* kpart,
+           int64_t kpart_floats, float* G, int accumulate, int M, const TrainSwitches& sw, hipStream_t st, int* used_ksplit, int* used_kchunk) {
+  const int Mp8 = (int)align_up(M, 128);
+  int rc = launch_mxq_cols(1, dY, ldy, q8ta, s8ta, M, Ny, Mp8, sw.grad_fmt, st);
+  if (rc == M2M_OK) rc = launch_mxq_cols(1, X, ldx, q8tb, s8tb, M, Kx, Mp8, 0, st);
+  if (rc != M2M_OK) return rc;
+  MxGemmArgs m{};
+  m.A = q8ta; m.sA = s8ta; m.B = q8tb; m.sB = s8tb; m.C = G; m.M = Ny; m.N = Kx; m.K = Mp8; m.lda = Mp8; m.ldb = Mp8; m.ldc = Kx;
+  const int tiles = ceil_div(Ny, 64) * ceil_div(Kx, 64);
+  int ks = 1024 / tiles;
+  if (ks > 32) ks = 32;
+  while (ks > 1 && ((int64_t)ks * Ny * Kx > kpart_floats || Mp8 / ks < 128)) --ks;
+  if (ks > 1) { m.kchunk = (int)align_up(ceil_div(Mp8, ks), 128); m.ksplit = ceil_div(Mp8, m.kchunk); m.Cpart = kpart; }
+  if (used_ksplit) *used_ksplit = m.ksplit > 1 ? m.ksplit : 1;
+  if (used_kchunk) *used_kchunk = m.ksplit > 1 ? m.kchunk : Mp8;
+  return launch_mxgemm(sw.grad_fmt, 0, accumulate ? TG_ACC_F32 : TG_STORE_F32, m, st, sw);
+}
+
 }  // namespace m2m
 
 // ------------------------------------------------------------------ C ABI: one MXFP8 product, for tests and callers ---
@@ -562,4 +609,120 @@ extern "C" int m2m_mx8_matmul_bf16a(const uint16_t* a_bf16_dev, const float* b_d
   (void)hipFree(buf);
   if (rc == M2M_OK && e != hipSuccess) { set_error("m2m_mx8_matmul_bf16a: %s", hipGetErrorString(e)); rc = M2M_ERR_HIP; }
   return rc;
+}
+
+// ------------------------------------------------------------------ C ABI: the fp8 step's own routes, one at a time, for tests ---
+namespace {
+// device scratch of one test call: one allocation, freed when the call returns
+struct Scratch {
+  uint8_t* base = nullptr;
+  int64_t bytes = 0;
+  int64_t take(int64_t n) { const int64_t at = bytes; bytes = align_up(bytes + n, 256); return at; }
+  int alloc() { M2M_CHECK_HIP(hipMalloc((void**)&base, (size_t)(bytes + 256))); return M2M_OK; }
+  ~Scratch() { if (base) (void)hipFree(base); }
+};
+int finish(const char* who, int rc, hipStream_t st) {
+  const hipError_t e = hipStreamSynchronize(st);
+  if (rc == M2M_OK && e != hipSuccess) { set_error("%s: %s", who, hipGetErrorString(e)); rc = M2M_ERR_HIP; }
+  return rc;
+}
+// the four MXFP8 images of one matrix W [N][K] at w8 (0xFF where the kernel writes nothing), through the step's table builder
+int quantize_weight(const float* w_dev, int N, int K, std::vector<W8Tile>& tiles, W8Tile* tiles_dev, uint8_t* w8, int64_t w8_bytes, hipStream_t st) {
+  M2M_CHECK_HIP(hipMemcpyAsync(tiles_dev, tiles.data(), tiles.size() * sizeof(W8Tile), hipMemcpyHostToDevice, st));
+  M2M_CHECK_HIP(hipMemsetAsync(w8, 0xFF, (size_t)w8_bytes, st));
+  return launch_mxq_weights(tiles_dev, (int)tiles.size(), w_dev, w8, st);
+}
+}  // namespace
+
+extern "C" int m2m_mx8_quantize_cols(const void* src_dev, int src_is_bf16, int R, int Cc, int64_t ld_s, int is_e5m2, uint8_t* qt_dev, uint8_t* scales_dev,
+                                     void* stream) {
+  M2M_REQUIRE(src_dev && qt_dev && scales_dev && R >= 1 && Cc >= 1 && ld_s >= Cc && (src_is_bf16 == 0 || src_is_bf16 == 1) && (is_e5m2 == 0 || is_e5m2 == 1),
+              "m2m_mx8_quantize_cols: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int Rp = (int)align_up(R, 128);
+  M2M_CHECK_HIP(hipMemsetAsync(qt_dev, 0xFF, (size_t)Cc * Rp, st));
+  M2M_CHECK_HIP(hipMemsetAsync(scales_dev, 0xFF, (size_t)Cc * (Rp / 32), st));
+  return finish("m2m_mx8_quantize_cols", launch_mxq_cols(src_is_bf16, src_dev, ld_s, qt_dev, scales_dev, R, Cc, Rp, is_e5m2, st), st);
+}
+
+extern "C" int m2m_mx8_quantize_rows(const void* src_dev, int src_is_bf16, int R, int Cc, int64_t ld_s, int is_e5m2, uint8_t* q_dev, uint8_t* scales_dev,
+                                     void* stream) {
+  M2M_REQUIRE(src_dev && q_dev && scales_dev && R >= 1 && Cc >= 1 && ld_s >= Cc && (src_is_bf16 == 0 || src_is_bf16 == 1) && (is_e5m2 == 0 || is_e5m2 == 1),
+              "m2m_mx8_quantize_rows: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const int Cp = (int)align_up(Cc, 128);
+  M2M_CHECK_HIP(hipMemsetAsync(q_dev, 0xFF, (size_t)R * Cp, st));
+  M2M_CHECK_HIP(hipMemsetAsync(scales_dev, 0xFF, (size_t)R * (Cp / 32), st));
+  return finish("m2m_mx8_quantize_rows", launch_mxq_rows(src_is_bf16, src_dev, ld_s, q_dev, scales_dev, R, Cc, Cp, is_e5m2, st), st);
+}
+
+extern "C" int m2m_mx8_quantize_weight(const float* w_dev, int N, int K, uint8_t* q_dev, uint8_t* qs_dev, uint8_t* qt_dev, uint8_t* qts_dev, void* stream) {
+  M2M_REQUIRE(w_dev && q_dev && qs_dev && qt_dev && qts_dev && N >= 128 && K >= 128 && N % 128 == 0 && K % 128 == 0,
+              "m2m_mx8_quantize_weight: bad argument (N and K must be multiples of 128)");
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<W8Tile> tiles;
+  int64_t w8_bytes = 0;
+  const W8Lin w = w8_add_matrix(0, N, K, w8_bytes, tiles);
+  Scratch s;
+  const int64_t o_w8 = s.take(w8_bytes), o_tab = s.take((int64_t)tiles.size() * sizeof(W8Tile));
+  int rc = s.alloc();
+  if (rc != M2M_OK) return rc;
+  uint8_t* w8 = s.base + o_w8;
+  rc = quantize_weight(w_dev, N, K, tiles, (W8Tile*)(s.base + o_tab), w8, w8_bytes, st);
+  if (rc == M2M_OK) {
+    M2M_CHECK_HIP(hipMemcpyAsync(q_dev, w8 + w.q, (size_t)N * K, hipMemcpyDeviceToDevice, st));
+    M2M_CHECK_HIP(hipMemcpyAsync(qs_dev, w8 + w.qs, (size_t)N * (K / 32), hipMemcpyDeviceToDevice, st));
+    M2M_CHECK_HIP(hipMemcpyAsync(qt_dev, w8 + w.qt, (size_t)K * w.Np, hipMemcpyDeviceToDevice, st));
+    M2M_CHECK_HIP(hipMemcpyAsync(qts_dev, w8 + w.qts, (size_t)K * (w.Np / 32), hipMemcpyDeviceToDevice, st));
+  }
+  return finish("m2m_mx8_quantize_weight", rc, st);
+}
+
+extern "C" int m2m_mx8_step_product(int kind, const uint16_t* a_bf16_dev, const void* b_dev, int M, int N, int K, int grad_is_e5m2, int fused, int epilogue,
+                                    void* c_dev, const float* r_dev, float drop_p, uint64_t step_key, uint64_t site_salt, int* ksplit_out,
+                                    int* kchunk_out, void* stream) {
+  M2M_REQUIRE(kind >= 0 && kind <= 2 && a_bf16_dev && b_dev && c_dev && M >= 1 && N >= 1 && K >= 1, "m2m_mx8_step_product: bad argument");
+  M2M_REQUIRE((grad_is_e5m2 == 0 || grad_is_e5m2 == 1) && (fused == 0 || fused == 1) && epilogue >= TG_STORE_T && epilogue <= TG_RESID_F32,
+              "m2m_mx8_step_product: bad format, fused flag or epilogue");
+  M2M_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || epilogue == TG_RESID_F32) && (epilogue != TG_RESID_F32 || r_dev),
+              "m2m_mx8_step_product: dropout belongs to the residual epilogue, which needs r_dev");
+  M2M_REQUIRE(kind != 2 || epilogue == TG_STORE_F32 || epilogue == TG_ACC_F32, "m2m_mx8_step_product: a weight gradient stores or accumulates fp32");
+  M2M_REQUIRE(kind == 2 || (N % 128 == 0 && K % 128 == 0), "m2m_mx8_step_product: the weight's N and K must be multiples of 128");
+  static StepWord word;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = word.set(step_key, st);
+  if (rc != M2M_OK) return rc;
+  TrainSwitches sw = process_train_switches();
+  sw.fp8_fused_q = fused != 0;
+  sw.grad_fmt = grad_is_e5m2;
+  if (kind == 2) {      // dw: a = dY [M][N], b = X [M][K] (bf16), c = G [N][K]
+    const int64_t Mp = align_up(M, 128), kpart_floats = std::max<int64_t>((int64_t)8 << 20, 2 * (int64_t)N * K);
+    Scratch s;
+    const int64_t o_qa = s.take(N * Mp), o_sa = s.take(N * (Mp / 32)), o_qb = s.take(K * Mp), o_sb = s.take(K * (Mp / 32)), o_kp = s.take(kpart_floats * 4);
+    rc = s.alloc();
+    if (rc != M2M_OK) return rc;
+    rc = mx8_dw(a_bf16_dev, N, N, b_dev, K, K, s.base + o_qa, s.base + o_sa, s.base + o_qb, s.base + o_sb, (float*)(s.base + o_kp), kpart_floats,
+                (float*)c_dev, epilogue == TG_ACC_F32, M, sw, st, ksplit_out, kchunk_out);
+    return finish("m2m_mx8_step_product", rc, st);
+  }
+  // fwd: a = X [M][K], c = Y [M][N];  dx: a = dY [M][N], c = dX [M][K];  b = W [N][K] (fp32) through the step's weight quantiser
+  std::vector<W8Tile> tiles;
+  int64_t w8_bytes = 0;
+  const W8Lin w = w8_add_matrix(0, N, K, w8_bytes, tiles);
+  const int64_t wide = std::max<int64_t>(K, w.Np);
+  Scratch s;
+  const int64_t o_w8 = s.take(w8_bytes), o_tab = s.take((int64_t)tiles.size() * sizeof(W8Tile)), o_qa = s.take(M * wide), o_sa = s.take(M * (wide / 32));
+  rc = s.alloc();
+  if (rc != M2M_OK) return rc;
+  uint8_t* w8 = s.base + o_w8;
+  rc = quantize_weight((const float*)b_dev, N, K, tiles, (W8Tile*)(s.base + o_tab), w8, w8_bytes, st);
+  MxDrop drop{};
+  if (drop_p > 0.f) drop = MxDrop{(uint32_t)((double)drop_p * 4294967296.0), 1.0f / (1.0f - drop_p), site_salt, word.dev};
+  if (rc == M2M_OK) {
+    if (kind == 0) rc = mx8_fwd(epilogue, a_bf16_dev, K, w8 + w.q, w8 + w.qs, s.base + o_qa, s.base + o_sa, c_dev, N, r_dev, M, N, K, drop, sw, st);
+    else rc = mx8_dx(epilogue, a_bf16_dev, N, N, K, w8 + w.qt, w8 + w.qts, w.Np, s.base + o_qa, s.base + o_sa, c_dev, K, r_dev, M, drop, sw, st);
+  }
+  if (ksplit_out) *ksplit_out = 1;
+  if (kchunk_out) *kchunk_out = kind == 0 ? K : w.Np;
+  return finish("m2m_mx8_step_product", rc, st);
 }

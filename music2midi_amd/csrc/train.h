@@ -6,6 +6,8 @@
 
 #include <string.h>
 
+#include <vector>
+
 namespace m2m {
 
 enum { TG_STORE_T = 0, TG_STORE_F32 = 1, TG_ACC_F32 = 2, TG_RESID_F32 = 3 };
@@ -108,6 +110,49 @@ int launch_mxgemm(int fmt_a, int fmt_b, int epi, const MxGemmArgs& g, hipStream_
 int launch_mxgemm_q(int fmt_a, int epi, const MxGemmArgs& g, hipStream_t st, const TrainSwitches& sw);               // A quantised in the product's own staging
 int launch_mxq_rows(int src_kind, const void* src, int64_t ld_s, uint8_t* q, uint8_t* sc, int R, int C, int Cp, int fmt, hipStream_t st);
 int launch_mxq_cols(int src_kind, const void* src, int64_t ld_s, uint8_t* qt, uint8_t* sc, int R, int C, int Rp, int fmt, hipStream_t st);
+
+// fp8 mode: the MXFP8 images of one projection matrix W [N][K] (fp32 master at parameter offset `off`), as byte offsets into the
+// trainer's w8 buffer: q [N][K] + qs [N][K/32] with blocks along K (the forward's B operand), qt [K][Np] + qts [K][Np/32] with
+// blocks along N (the B operand of dX = dY . W); Np = align_up(N, 128).  mxq_weights_kernel (train.hip) writes all four from a
+// table of 32 x 64 tiles.  w8_add_matrix is the per-matrix part of the table builder: it places the four images behind
+// `w8_bytes` (advancing it, 256-byte aligned) and appends the matrix's tiles.
+struct W8Lin { int64_t off; int N, K, Np; int64_t q, qs, qt, qts; };
+struct W8Tile { int64_t off; int N, K, Np; int64_t q, qs, qt, qts; int tn, tk; };
+W8Lin w8_add_matrix(int64_t off, int N, int K, int64_t& w8_bytes, std::vector<W8Tile>& tiles);
+int launch_mxq_weights(const W8Tile* tiles_dev, int n_tiles, const float* P, uint8_t* w8, hipStream_t st);
+
+// The three MXFP8 routes of the fp8 step (mx8.hip), called by Ops::mm / dX / dW_on (train.hip) and by the single-product test
+// hook m2m_mx8_step_product: the step and the hook run the same lines.  bf16 operands; fused quantisation and the gradient
+// element format come from sw (fp8_fused_q, grad_fmt).
+struct MxDrop { uint32_t thresh; float scale; uint64_t key; const uint64_t* step; };      // the dropout fields of MxGemmArgs (thresh == 0: off)
+// Y[M,N] (epi)= X[M,K] . W^T: X bf16 [M][ldx], the weight's row image wq / wqs ([N][K]); q8a / s8a: scratch for X's fp8 image
+// ([M][K] + [M][K/32]; untouched when X is quantised in the product's staging)
+int mx8_fwd(int epi, const void* X, int64_t ldx, const uint8_t* wq, const uint8_t* wqs, uint8_t* q8a, uint8_t* s8a, void* C, int64_t ldc, const float* R,
+            int M, int N, int K, const MxDrop& drop, const TrainSwitches& sw, hipStream_t st);
+// dX[M,Kw] (epi)= dY[M,Nw] . W: dY bf16 [M][ldy], the weight's transposed image wqt / wqts ([Kw][Np]); scratch [M][Np] + [M][Np/32]
+int mx8_dx(int epi, const void* dY, int64_t ldy, int Nw, int Kw, const uint8_t* wqt, const uint8_t* wqts, int Np, uint8_t* q8a, uint8_t* s8a, void* C,
+           int64_t ldc, const float* R, int M, const MxDrop& drop, const TrainSwitches& sw, hipStream_t st);
+// G[Ny,Kx] (+)= dY[M,Ny]^T . X[M,Kx]: both operands through the transposing quantiser (scratch q8ta [Ny][Mp] / q8tb [Kx][Mp],
+// Mp = align_up(M, 128), + scales), then a product over the M rows split over k while that fills the chip and kpart
+// (kpart_floats floats) holds the slices.  used_ksplit / used_kchunk (optional): what the policy chose.
+int mx8_dw(const void* dY, int64_t ldy, int Ny, const void* X, int64_t ldx, int Kx, uint8_t* q8ta, uint8_t* s8ta, uint8_t* q8tb, uint8_t* s8tb, float* kpart,
+           int64_t kpart_floats, float* G, int accumulate, int M, const TrainSwitches& sw, hipStream_t st, int* used_ksplit = nullptr,
+           int* used_kchunk = nullptr);
+
+// one 64-bit word on the device holding the dropout step key of a test call (the single-kernel test hooks of the C ABI)
+struct StepWord {
+  uint64_t* dev = nullptr;
+  uint64_t last = 0;
+  int set(uint64_t v, hipStream_t st) {
+    if (dev && v == last) return M2M_OK;                    // (repeated calls with one key — tools/attn_head_bench.py — stay asynchronous)
+    if (!dev) M2M_CHECK_HIP(hipMalloc((void**)&dev, 8));
+    M2M_CHECK_HIP(hipStreamSynchronize(st));
+    M2M_CHECK_HIP(hipMemcpyAsync(dev, &v, 8, hipMemcpyHostToDevice, st));
+    M2M_CHECK_HIP(hipStreamSynchronize(st));
+    last = v;
+    return M2M_OK;
+  }
+};
 
 // Whole-head attention of the training step (attn_train.hip): forward with the row log-sum-exp, two-pass backward
 struct HeadAttnArgs {

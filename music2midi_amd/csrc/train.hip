@@ -588,8 +588,7 @@ __global__ __launch_bounds__(256) void weights_transpose_kernel(const WtBlock* _
 
 // fp8 mode: every projection matrix W [N][K] (fp32 master) -> MXFP8 in BOTH layouts in one launch: row-major with blocks
 // along K (the forward's B operand) and transposed [K][Np] with blocks along N (the B operand of dX = dY . W).
-// One 64-thread workgroup per 32 x 64 tile (table entry); e4m3.
-struct W8Tile { int64_t off; int N, K, Np; int64_t q, qs, qt, qts; int tn, tk; };
+// One 64-thread workgroup per 32 x 64 tile (table entry, W8Tile of train.h); e4m3.
 __device__ inline float w8_scale_exp(float amax) {
   if (!(amax > 0.f)) return -127.f;
   int e;
@@ -640,6 +639,21 @@ __global__ __launch_bounds__(64) void mxq_weights_kernel(const W8Tile* __restric
       w8[tl.qts + (int64_t)(k0 + kl) * (tl.Np / 32) + n0 / 32] = (uint8_t)((int)se + 127);
     }
   }
+}
+W8Lin w8_add_matrix(int64_t off, int N, int K, int64_t& w8_bytes, std::vector<W8Tile>& tiles) {
+  W8Lin w{off, N, K, (int)align_up(N, 128), 0, 0, 0, 0};
+  w.q = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)N * K, 256);
+  w.qs = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)N * (K / 32), 256);
+  w.qt = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)K * w.Np, 256);
+  w.qts = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)K * (w.Np / 32), 256);
+  for (int tn = 0; tn < ceil_div(N, 32); ++tn)
+    for (int tk = 0; tk < ceil_div(K, 64); ++tk) tiles.push_back({off, N, K, w.Np, w.q, w.qs, w.qt, w.qts, tn, tk});
+  return w;
+}
+int launch_mxq_weights(const W8Tile* tiles_dev, int n_tiles, const float* P, uint8_t* w8, hipStream_t st) {
+  hipLaunchKernelGGL(mxq_weights_kernel, dim3(n_tiles), dim3(64), 0, st, tiles_dev, P, w8);
+  M2M_CHECK_HIP(hipGetLastError());
+  return M2M_OK;
 }
 
 int launch_bgemm(int precision, int epi, const BGemmArgs& g, hipStream_t st, const TrainSwitches& sw) {
@@ -2095,8 +2109,8 @@ struct m2m_trainer {
   // product + a reduce EACH (16 clips: 8.9 ms per step against 7.5 ms), for the least accuracy-critical third of the products
   TrainSwitches sw;                      // every environment switch of the trainer, latched by m2m_trainer_create
   EncSwitches enc_sw;                    // ... and those of the encoder-side kernels its passes launch (put in scope by m2m_train_forward_backward)
-  struct LinW { int64_t off; int N, K, Np; int64_t q, qs, qt, qts; };
-  std::vector<LinW> lin;                 // every projection matrix (fused groups), by parameter offset
+  using LinW = W8Lin;
+  std::vector<LinW> lin;                // every projection matrix (fused groups), by parameter offset
   uint8_t* w8 = nullptr;                 // fp8 weights, both layouts, + scales
   void* w8_tiles = nullptr;
   int n_w8_tiles = 0;
@@ -2352,16 +2366,7 @@ int build_arena(m2m_trainer* t) {
   std::vector<W8Tile> w8t;
   int64_t w8_bytes = 0, o_w8 = 0, o_w8t = 0, o_q8a = 0, o_s8a = 0, o_q8ta = 0, o_s8ta = 0, o_q8tb = 0, o_s8tb = 0;
   if (t->fp8) {
-    auto addl = [&](int64_t off, int N, int K) {
-      m2m_trainer::LinW w{off, N, K, (int)align_up(N, 128), 0, 0, 0, 0};
-      w.q = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)N * K, 256);
-      w.qs = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)N * (K / 32), 256);
-      w.qt = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)K * w.Np, 256);
-      w.qts = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)K * (w.Np / 32), 256);
-      t->lin.push_back(w);
-      for (int tn = 0; tn < ceil_div(N, 32); ++tn)
-        for (int tk = 0; tk < ceil_div(K, 64); ++tk) w8t.push_back({off, N, K, w.Np, w.q, w.qs, w.qt, w.qts, tn, tk});
-    };
+    auto addl = [&](int64_t off, int N, int K) { t->lin.push_back(w8_add_matrix(off, N, K, w8_bytes, w8t)); };
     for (const EncOff& e : t->enc) { addl(e.qkv, 3 * (int)inner, (int)d); addl(e.o, (int)d, (int)inner); addl(e.wi, 2 * (int)dff, (int)d); addl(e.wo, (int)d, (int)dff); }
     for (const DecOff& e : t->dec) { addl(e.qkv, 3 * (int)inner, (int)d); addl(e.o, (int)d, (int)inner); addl(e.cq, (int)inner, (int)d);
                                      addl(e.ckv, 2 * (int)inner, (int)d); addl(e.co, (int)d, (int)inner); addl(e.wi, 2 * (int)dff, (int)d); addl(e.wo, (int)d, (int)dff); }
@@ -2564,18 +2569,9 @@ struct Ops {
     if (dropping(drop_site)) { g.drop_thresh = t->drop_thresh; g.drop_scale = t->drop_scale; g.drop_key = key(drop_site).salt; g.drop_step = t->step_key_dev; }
     if (!akm && !bkm && t->fp8 && t->sw.fp8.fwd) {          // a forward projection Y = X . W^T on MXFP8 operands
       const int64_t off = reinterpret_cast<const T*>(B) - W(0);
-      if (const m2m_trainer::LinW* w = lin8(off)) {
-        MxGemmArgs m{};
-        m.A = t->q8a; m.sA = t->s8a; m.B = t->w8 + w->q; m.sB = t->w8 + w->qs; m.C = C; m.R = R; m.M = M; m.N = N; m.K = K;
-        m.lda = K; m.ldb = K; m.ldc = ldc; m.drop_thresh = g.drop_thresh; m.drop_scale = g.drop_scale; m.drop_key = g.drop_key; m.drop_step = g.drop_step;
-        if (t->sw.fp8_fused_q && K % 128 == 0 && lda % 8 == 0) {      // activations quantised inside the product's staging: one launch
-          m.Asrc = A; m.ld_src = lda; m.Kvalid = K;
-          return launch_mxgemm_q(0, epi, m, st, t->sw);
-        }
-        int rc = launch_mxq_rows(1, A, lda, t->q8a, t->s8a, M, K, K, 0, st);
-        if (rc != M2M_OK) return rc;
-        return launch_mxgemm(0, 0, epi, m, st, t->sw);
-      }
+      if (const m2m_trainer::LinW* w = lin8(off))
+        return mx8_fwd(epi, A, lda, t->w8 + w->q, t->w8 + w->qs, t->q8a, t->s8a, C, ldc, R, M, N, K,
+                       MxDrop{g.drop_thresh, g.drop_scale, g.drop_key, g.drop_step}, t->sw, st);
     }
     // dense NT products with K % 64 == 0 go through the inference path's tuned kernel (128x128 tiles, register-prefetched
     // staging, XCD-aware tile order): every forward projection and every dX product qualifies
@@ -2619,18 +2615,8 @@ struct Ops {
   }
   // dX[M, Kw] (epi) = dY[M, Nw] . W   for a weight stored [Nw][Kw]: an NT product against the transposed copy WT [Kw][Nw]
   int dX(int epi, const void* dY, int64_t ldy, int64_t w_off, int Nw, int Kw, void* C, int64_t ldc, int M) const {
-    if (const m2m_trainer::LinW* w = t->sw.fp8.dx ? lin8(w_off) : nullptr) {    // fp8 mode: dY in e5m2 (gradient format), W^T in e4m3
-      MxGemmArgs m{};
-      m.A = t->q8a; m.sA = t->s8a; m.B = t->w8 + w->qt; m.sB = t->w8 + w->qts; m.C = C; m.M = M; m.N = Kw; m.K = w->Np;
-      m.lda = w->Np; m.ldb = w->Np; m.ldc = ldc;
-      if (t->sw.fp8_fused_q && Nw % 8 == 0 && ldy % 8 == 0) {
-        m.Asrc = dY; m.ld_src = ldy; m.Kvalid = Nw;
-        return launch_mxgemm_q(t->sw.grad_fmt, epi, m, st, t->sw);
-      }
-      int rc = launch_mxq_rows(1, dY, ldy, t->q8a, t->s8a, M, Nw, w->Np, t->sw.grad_fmt, st);
-      if (rc != M2M_OK) return rc;
-      return launch_mxgemm(t->sw.grad_fmt, 0, epi, m, st, t->sw);
-    }
+    if (const m2m_trainer::LinW* w = t->sw.fp8.dx ? lin8(w_off) : nullptr)      // fp8 mode: dY in the gradient format, W^T in e4m3
+      return mx8_dx(epi, dY, ldy, Nw, Kw, t->w8 + w->qt, t->w8 + w->qts, w->Np, t->q8a, t->s8a, C, ldc, nullptr, M, MxDrop{}, t->sw, st);
     return mm(epi, dY, ldy, 0, reinterpret_cast<const T*>(t->WT) + w_off, Nw, 0, C, ldc, M, Kw, Nw);
   }
   // G[Ny, Kx] = dY[M, Ny]^T . X[M, Kx]: both operands are transposed once (coalesced, through LDS) into [features][Mp]
@@ -2655,20 +2641,8 @@ struct Ops {
     return M2M_OK;
   }
   int dW_on(hipStream_t st, const void* dY, int64_t ldy, int Ny, const void* X, int64_t ldx, int Kx, float* Gout, int M) const {
-    if (Gbase && t->sw.fp8.dw && lin8(Gout - Gbase)) {      // fp8 mode: dY^T (e5m2) . X^T (e4m3), blocks along the M rows
-      const int Mp8 = (int)align_up(M, 128);
-      int rc = launch_mxq_cols(1, dY, ldy, t->q8ta, t->s8ta, M, Ny, Mp8, t->sw.grad_fmt, st);
-      if (rc == M2M_OK) rc = launch_mxq_cols(1, X, ldx, t->q8tb, t->s8tb, M, Kx, Mp8, 0, st);
-      if (rc != M2M_OK) return rc;
-      MxGemmArgs m{};
-      m.A = t->q8ta; m.sA = t->s8ta; m.B = t->q8tb; m.sB = t->s8tb; m.C = Gout; m.M = Ny; m.N = Kx; m.K = Mp8; m.lda = Mp8; m.ldb = Mp8; m.ldc = Kx;
-      const int tiles = ceil_div(Ny, 64) * ceil_div(Kx, 64);
-      int ks = 1024 / tiles;
-      if (ks > 32) ks = 32;
-      while (ks > 1 && ((int64_t)ks * Ny * Kx > t->kpart_floats || Mp8 / ks < 128)) --ks;
-      if (ks > 1) { m.kchunk = (int)align_up(ceil_div(Mp8, ks), 128); m.ksplit = ceil_div(Mp8, m.kchunk); m.Cpart = t->kpart; }
-      return launch_mxgemm(t->sw.grad_fmt, 0, gacc ? TG_ACC_F32 : TG_STORE_F32, m, st, t->sw);
-    }
+    if (Gbase && t->sw.fp8.dw && lin8(Gout - Gbase))        // fp8 mode: dY^T (gradient format) . X^T (e4m3), blocks along the M rows
+      return mx8_dw(dY, ldy, Ny, X, ldx, Kx, t->q8ta, t->s8ta, t->q8tb, t->s8tb, t->kpart, t->kpart_floats, Gout, gacc, M, t->sw, st);
     // (the generic kernel's k-major staging — 2-byte LDS scatters — and the transpose-then-NT route it replaced cost
     //  ~30 us per weight gradient at 16 clips; M2M_TRAIN_DW_OLD=1 keeps them for comparison)
     const int Ealign = t->precision == M2M_PREC_BF16 ? 8 : 4;
@@ -3144,8 +3118,8 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
     M2M_CHECK_HIP(hipGetLastError());
   }
   if (t->fp8) {
-    hipLaunchKernelGGL(mxq_weights_kernel, dim3(t->n_w8_tiles), dim3(64), 0, st, (const W8Tile*)t->w8_tiles, P, t->w8);
-    M2M_CHECK_HIP(hipGetLastError());
+    const int rc = launch_mxq_weights((const W8Tile*)t->w8_tiles, t->n_w8_tiles, P, t->w8, st);
+    if (rc != M2M_OK) return rc;
   }
 
   // ================= forward =================

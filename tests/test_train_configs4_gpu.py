@@ -176,11 +176,17 @@ def test_fp8_products_of_layers_0_5_11_teacher_forced_at_the_config_shape(c4):
     late product would hide under it.  Here the compounding is taken out: the MX-emulating oracle runs once at the config shape
     (16 x 261 x 256) and records, for ten projections of the first encoder layer, the last encoder layer and the last decoder layer
     (the 12th), the product's bf16 input x, its output gradient dy and its weight; the DEVICE then computes each of the three
-    products from those same tensors — forward y = Qk(x) Qk(W)^T and dX = Qn(dy) Qn(W^T)^T through the kernel the fp8 step runs
-    (mxgemm_q_kernel: bf16 operand quantised in the staging, m2m_mx8_matmul_bf16a fused), dW = Qm(dy^T) Qm(x^T)^T through the
-    quantiser + product pair (m2m_mx8_matmul_f32) — and each is held to the emulation of THAT product: relative l2 <= 3e-4
-    (measured on MI355X: 3.4e-6 ... 4.1e-5 over the 30 products — the matrix core's limited-precision accumulate; the one-layer
-    whole-step bar is cosine 0.98: a product on its own has no flips to compound, so it is held three orders tighter).  The forward outputs are also compared with what the oracle's own pass produced (same tensors: bit-for-bit the
+    products from those same tensors and each is held to the emulation of THAT product: relative l2 <= 3e-4 (measured on MI355X:
+    3.4e-6 ... 4.1e-5 over the 30 products — the matrix core's limited-precision accumulate; the one-layer whole-step bar is cosine
+    0.98: a product on its own has no flips to compound, so it is held three orders tighter).  The legs:
+      fwd      y = Qk(x) Qk(W)^T      m2m_mx8_matmul_bf16a fused: mxgemm_q_kernel, bf16 operand quantised in the staging; the WEIGHT goes
+      dx       Qn(dy) Qn(W^T)^T       through the row quantiser here (W, resp. a pre-transposed W^T), not through the step's weight quantiser
+      dw       Qm(dy^T) Qm(x^T)^T     m2m_mx8_matmul_f32 on PRE-TRANSPOSED operands: row quantiser + unsplit product, not the step's route
+      dx_step  the step's dX route    m2m_mx8_step_product kind 1 (mx8_dx, what Ops::dX calls): weights from mxq_weights_kernel's
+                                      transposed image, dy quantised in the staging
+      dw_step  the step's dW route    m2m_mx8_step_product kind 2 (mx8_dw, what Ops::dW_on calls): the transposing quantiser mxq_cols on
+                                      dy and x, then the split-K product + reduce under the step's own policy
+    The forward outputs are also compared with what the oracle's own pass produced (same tensors: bit-for-bit the
     emulation formula)."""
     import ctypes as C
     from music2midi_amd import native
@@ -210,6 +216,14 @@ def test_fp8_products_of_layers_0_5_11_teacher_forced_at_the_config_shape(c4):
                      "m2m_mx8_matmul_f32")
         return c_d.cpu()
 
+    def dev_step(kind, a, b, M, N, K):      # the fp8 step's own route (include/music2midi_amd.h m2m_mx8_step_product), e4m3 gradients, fp32 store
+        a16 = a.to(torch.bfloat16).cuda().contiguous()
+        b_d = (b.to(torch.bfloat16) if kind == 2 else b).cuda().contiguous()
+        c_d = torch.empty((M, K) if kind == 1 else (N, K), dtype=torch.float32, device="cuda")
+        native.check(lib.m2m_mx8_step_product(kind, a16.data_ptr(), b_d.data_ptr(), M, N, K, 0, 1, 1, c_d.data_ptr(), None, 0.0, 0, 0, None, None,
+                                              native.stream_handle()), "m2m_mx8_step_product")
+        return c_d.cpu()
+
     def agree(got, want):
         g, w = got.reshape(-1).double(), want.reshape(-1).double()
         return float(torch.dot(g, w) / (g.norm() * w.norm() + 1e-300)), float((g - w).norm() / (w.norm() + 1e-300))
@@ -226,13 +240,15 @@ def test_fp8_products_of_layers_0_5_11_teacher_forced_at_the_config_shape(c4):
         want_dx = mx_quant_dequant(dy2, "e4m3") @ mx_quant_dequant(w.T.contiguous(), "e4m3").T
         want_dw = mx_quant_dequant(dy2.T.contiguous(), "e4m3") @ mx_quant_dequant(x2.T.contiguous(), "e4m3").T
         res = {"fwd": agree(dev_bf16a(x2, w), want_y), "dx": agree(dev_bf16a(dy2, w.T.contiguous()), want_dx),
-               "dw": agree(dev_f32(dy2.T.contiguous(), x2.T.contiguous()), want_dw)}
+               "dw": agree(dev_f32(dy2.T.contiguous(), x2.T.contiguous()), want_dw),
+               "dx_step": agree(dev_step(1, dy2, w, dy2.shape[0], w.shape[0], w.shape[1]), want_dx),
+               "dw_step": agree(dev_step(2, dy2, x2, dy2.shape[0], w.shape[0], w.shape[1]), want_dw)}
         print(f"[fp8 product] {name} x {tuple(x2.shape)} dy {tuple(dy2.shape)}: " + "; ".join(f"{k} cos {c:.7f} rel l2 {r:.2e}" for k, (c, r) in res.items()))
         for k, (c, r) in res.items():
             assert np.isfinite(c) and c >= 0.999999 and r <= 3e-4, (name, k, c, r)
             if c < worst[0]:
                 worst = (c, r, f"{name} {k}")
-    print(f"[fp8 product] worst of {3 * len(FP8_PRODUCTS)} products: cosine {worst[0]:.7f} (rel l2 {worst[1]:.2e}) at {worst[2]}")
+    print(f"[fp8 product] worst of {5 * len(FP8_PRODUCTS)} products: cosine {worst[0]:.7f} (rel l2 {worst[1]:.2e}) at {worst[2]}")
 
 
 def test_dropout_step_is_reproducible_and_graph_replay_equals_direct_issue_at_the_config_shape(c4, monkeypatch):
