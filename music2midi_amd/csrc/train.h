@@ -180,7 +180,9 @@ constexpr int AH_MAX_S = 288;  // rows an LDS image holds (9 blocks of 32): 36 K
 int launch_attn_head_fwd(const HeadAttnArgs& a, int nB, hipStream_t st, const TrainSwitches& sw);
 int launch_attn_head_bwd(const HeadAttnArgs& a, int nB, hipStream_t st, const TrainSwitches& sw);
 
-// Adafactor plan (device tables built once per trainer)
+// Adafactor plan (device tables built once per trainer; kernels and launcher: adafactor.hip)
+constexpr int AF_ROWS = 16;      // rows of a matrix per block (32 until round 3: 235 registers in pass A, two blocks per CU; 16 rows run pass A / B / C in
+                                 // 51 / 23 / 61 us instead of 64 / 31 / 69; 8 rows gain nothing more and cost pass A2 its partial sums)
 struct AfTensor {
   int64_t offset;          // into the flat parameter / gradient buffers
   int rows, cols;          // vectors: rows = 1

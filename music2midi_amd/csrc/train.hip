@@ -1,6 +1,7 @@
 // Training-step kernels: what `loss.backward()` + `Adafactor.step()` run for
 // ref: music2midi/model.py:27-43 (training_step -> T5Transformer.forward with labels, ref transformer.py:28-39;
 // optimizer = transformers Adafactor(warmup_init=True) + AdafactorSchedule), written for gfx950.
+// (The Adafactor kernels and their launcher are in adafactor.hip; the plan they run on is built here, build_optimizer.)
 //
 // Layout rules of the training path (train_api.hip drives these kernels):
 //   * every activation is a plain row-major [rows, features] matrix — fp32 for the residual stream, its
@@ -1811,225 +1812,6 @@ __global__ void add_kernel(const float* __restrict__ a, const float* __restrict_
   for (; i < n; i += stride) c[i] = (a ? a[i] : 0.f) + (b ? b[i] : 0.f);
 }
 
-// ============================================================ Adafactor ====
-// transformers.optimization.Adafactor as ref: music2midi/model.py:27-30 builds it:
-//   Adafactor(params, lr=None, eps=(1e-30, 1e-3), clip_threshold=1.0, decay_rate=-0.8, beta1=None, weight_decay=0.0,
-//             scale_parameter=True, relative_step=True, warmup_init=True)
-// per tensor p with gradient g at step t (1-based):
-//   rho   = min(1e-6 * t, 1/sqrt(t))                       (relative step with warm-up init)
-//   lr    = max(1e-3, rms(p)) * rho                        (scale_parameter)
-//   b2    = 1 - t^-0.8
-//   u     = g^2 + 1e-30
-//   2-D:  R <- b2 R + (1-b2) mean_cols(u);  C <- b2 C + (1-b2) mean_rows(u);  upd = g * rsqrt(R / mean(R)) [row] * rsqrt(C) [col]
-//   1-D:  V <- b2 V + (1-b2) u;             upd = g * rsqrt(V)
-//   upd  /= max(1, rms(upd) / 1.0);   p <- p - lr * upd
-// Three passes over (p, g) with the reductions between them; one launch per pass for ALL tensors (block -> (tensor,
-// row block) through a table), every reduction in a fixed order.
-constexpr int AF_ROWS = 16;      // rows of a matrix per block (32 until round 3: 235 registers in pass A, two blocks per CU; 16 rows run pass A / B / C in
-                                 // 51 / 23 / 61 us instead of 64 / 31 / 69; 8 rows gain nothing more and cost pass A2 its partial sums)
-// (vectors: one "row" of up to AF_VEC elements per block)
-
-// pass A: per block: sum p^2, per-row sum of (g^2 + eps1) -> rowsum[tensor rows], per-block column partial sums
-__global__ __launch_bounds__(256) void af_pass_a(const AfBlock* __restrict__ blocks, const AfTensor* __restrict__ tensors,
-                                                 const float* __restrict__ P, const float* __restrict__ G, float* __restrict__ rowsum,
-                                                 float* __restrict__ colpart, float* __restrict__ blk_p2) {
-  __shared__ float sred[256];
-  const AfBlock bk = blocks[blockIdx.x];
-  const AfTensor t = tensors[bk.tensor];
-  const float* p = P + t.offset;
-  const float* g = G + t.offset;
-  float p2 = 0.f;
-  const int r1 = min(bk.row0 + AF_ROWS, t.rows);
-  // thread tid owns columns tid, tid + 256, ... ; rows are walked in order -> fixed summation order per column.  ONE read of
-  // g and p (the first form read g a second time for the row sums, one dependent load per row: 157 us per step): the per-row
-  // partial sums of this thread's columns stay in registers and are reduced by wave, then over the four waves, in a fixed order
-  __shared__ float rred[4][AF_ROWS];
-  float rs[AF_ROWS];
-#pragma unroll
-  for (int j = 0; j < AF_ROWS; ++j) rs[j] = 0.f;
-  for (int c = threadIdx.x; c < t.cols; c += 256) {
-    float gv[AF_ROWS], pv[AF_ROWS];
-#pragma unroll
-    for (int j = 0; j < AF_ROWS; ++j) {
-      const int r = min(bk.row0 + j, r1 - 1);          // clamped: every load of the tile is in flight at once
-      gv[j] = g[(int64_t)r * t.cols + c];
-      pv[j] = p[(int64_t)r * t.cols + c];
-    }
-    float cs = 0.f;
-#pragma unroll
-    for (int j = 0; j < AF_ROWS; ++j) {
-      if (bk.row0 + j < r1) {
-        const float q = gv[j] * gv[j] + 1e-30f;
-        cs += q;
-        rs[j] += q;
-        p2 += pv[j] * pv[j];
-      }
-    }
-    colpart[bk.col_off + c] = cs;
-  }
-  {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < AF_ROWS; ++j) {
-      const float v = wave_sum(rs[j]);
-      if (lane == 0) rred[wave][j] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < AF_ROWS && bk.row0 + (int)threadIdx.x < r1)
-      rowsum[t.row_off + bk.row0 + threadIdx.x] = (rred[0][threadIdx.x] + rred[1][threadIdx.x]) + (rred[2][threadIdx.x] + rred[3][threadIdx.x]);
-  }
-  sred[threadIdx.x] = p2;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sred[threadIdx.x] += sred[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) blk_p2[blockIdx.x] = sred[0];
-}
-
-// pass A2: one block per tensor: finish rms(p), update the factored second moments, derive the row / column factors
-__global__ __launch_bounds__(256) void af_pass_a2(const AfTensor* __restrict__ tensors, const float* __restrict__ rowsum,
-                                                  const float* __restrict__ colpart, const float* __restrict__ blk_p2,
-                                                  float* __restrict__ state, float* __restrict__ rfac, float* __restrict__ cfac,
-                                                  float* __restrict__ tstat, float beta2t) {
-  __shared__ float sred[256];
-  const AfTensor t = tensors[blockIdx.x];
-  float acc = 0.f;
-  for (int b = threadIdx.x; b < t.nblocks; b += 256) acc += blk_p2[t.block0 + b];
-  sred[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) { if (threadIdx.x < s) sred[threadIdx.x] += sred[threadIdx.x + s]; __syncthreads(); }
-  const float p_rms = sqrtf(sred[0] / (float)((int64_t)t.rows * t.cols));
-  __syncthreads();
-  float* R = state + t.state_off;               // [rows] (matrix) or [cols] full second moment (vector: rows == 1)
-  float* C = R + t.rows;                        // [cols] (matrix only)
-  if (t.rows > 1) {
-    // rows
-    float racc = 0.f;
-    for (int r = threadIdx.x; r < t.rows; r += 256) {
-      const float v = beta2t * R[r] + (1.f - beta2t) * (rowsum[t.row_off + r] / (float)t.cols);
-      R[r] = v;
-      racc += v;
-    }
-    sred[threadIdx.x] = racc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if (threadIdx.x < s) sred[threadIdx.x] += sred[threadIdx.x + s]; __syncthreads(); }
-    const float rmean = sred[0] / (float)t.rows;
-    __syncthreads();
-    for (int r = threadIdx.x; r < t.rows; r += 256) rfac[t.row_off + r] = rsqrtf(R[r] / rmean);
-    for (int c = threadIdx.x; c < t.cols; c += 256) {
-      float cs = 0.f;
-      int b = 0;
-      for (; b + 8 <= t.nblocks; b += 8) {            // eight partial rows in flight (the plain loop paid a memory round trip per row block: 28 us per step)
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = colpart[t.col_off + (int64_t)(b + u) * t.cols + c];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) cs += v[u];
-      }
-      for (; b < t.nblocks; ++b) cs += colpart[t.col_off + (int64_t)b * t.cols + c];
-      const float v = beta2t * C[c] + (1.f - beta2t) * (cs / (float)t.rows);
-      C[c] = v;
-      cfac[t.cfac_off + c] = rsqrtf(v);
-    }
-  } else {
-    for (int c = threadIdx.x; c < t.cols; c += 256) {
-      const float v = beta2t * R[c] + (1.f - beta2t) * colpart[t.col_off + c];     // one block, one row: colpart = g^2 + eps
-      R[c] = v;
-      cfac[t.cfac_off + c] = rsqrtf(v);
-    }
-    if (threadIdx.x == 0) rfac[t.row_off] = 1.0f;
-  }
-  if (threadIdx.x == 0) tstat[2 * blockIdx.x] = p_rms;
-}
-
-// pass B: per block sum of upd^2, upd = g * rfac[row] * cfac[col]
-__global__ __launch_bounds__(256) void af_pass_b(const AfBlock* __restrict__ blocks, const AfTensor* __restrict__ tensors,
-                                                 const float* __restrict__ G, const float* __restrict__ rfac, const float* __restrict__ cfac,
-                                                 float* __restrict__ blk_u2) {
-  __shared__ float sred[256];
-  const AfBlock bk = blocks[blockIdx.x];
-  const AfTensor t = tensors[bk.tensor];
-  const float* g = G + t.offset;
-  const int r1 = min(bk.row0 + AF_ROWS, t.rows);
-  float u2 = 0.f;
-  for (int c = threadIdx.x; c < t.cols; c += 256) {
-    const float cf = cfac[t.cfac_off + c];
-    float gv[AF_ROWS];
-#pragma unroll
-    for (int j = 0; j < AF_ROWS; ++j) gv[j] = g[(int64_t)min(bk.row0 + j, r1 - 1) * t.cols + c];
-#pragma unroll
-    for (int j = 0; j < AF_ROWS; ++j) {
-      if (bk.row0 + j < r1) {
-        const float u = gv[j] * rfac[t.row_off + bk.row0 + j] * cf;
-        u2 += u * u;
-      }
-    }
-  }
-  sred[threadIdx.x] = u2;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) { if (threadIdx.x < s) sred[threadIdx.x] += sred[threadIdx.x + s]; __syncthreads(); }
-  if (threadIdx.x == 0) blk_u2[blockIdx.x] = sred[0];
-}
-// pass B2: per tensor: step size = lr / max(1, rms(upd))
-__global__ __launch_bounds__(256) void af_pass_b2(const AfTensor* __restrict__ tensors, const float* __restrict__ blk_u2,
-                                                  float* __restrict__ tstat, float rho) {
-  __shared__ float sred[256];
-  const AfTensor t = tensors[blockIdx.x];
-  float acc = 0.f;
-  for (int b = threadIdx.x; b < t.nblocks; b += 256) acc += blk_u2[t.block0 + b];
-  sred[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) { if (threadIdx.x < s) sred[threadIdx.x] += sred[threadIdx.x + s]; __syncthreads(); }
-  if (threadIdx.x == 0) {
-    const float u_rms = sqrtf(sred[0] / (float)((int64_t)t.rows * t.cols));
-    const float lr = fmaxf(1e-3f, tstat[2 * blockIdx.x]) * rho;
-    tstat[2 * blockIdx.x + 1] = lr / fmaxf(1.0f, u_rms);
-  }
-}
-// pass C: p -= step * g * rfac[row] * cfac[col]
-__global__ __launch_bounds__(256) void af_pass_c(const AfBlock* __restrict__ blocks, const AfTensor* __restrict__ tensors,
-                                                 float* __restrict__ P, const float* __restrict__ G, const float* __restrict__ rfac,
-                                                 const float* __restrict__ cfac, const float* __restrict__ tstat) {
-  const AfBlock bk = blocks[blockIdx.x];
-  const AfTensor t = tensors[bk.tensor];
-  float* p = P + t.offset;
-  const float* g = G + t.offset;
-  const float step = tstat[2 * bk.tensor + 1];
-  const int r1 = min(bk.row0 + AF_ROWS, t.rows);
-  // eight rows of a column in flight per thread (a row-by-row loop kept one load pair per thread in flight: 78 us for the pass's 366 MB; 70 us this way, same arithmetic)
-  for (int c = threadIdx.x; c < t.cols; c += 256) {
-    const float cf = cfac[t.cfac_off + c];
-    for (int r = bk.row0; r < r1; r += 8) {
-      float gv[8], pv[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int64_t at = (int64_t)min(r + j, r1 - 1) * t.cols + c;
-        gv[j] = g[at];
-        pv[j] = p[at];
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (r + j < r1) p[(int64_t)(r + j) * t.cols + c] = pv[j] - gv[j] * (rfac[t.row_off + r + j] * step) * cf;
-    }
-  }
-}
-
-int launch_adafactor(const AfPlan& pl, float* P, const float* G, int step, hipStream_t st) {
-  const double t = (double)step;
-  const float beta2t = (float)(1.0 - pow(t, -0.8));
-  const double rho_d = fmin(1e-6 * t, 1.0 / sqrt(t));
-  const float rho = (float)rho_d;
-  hipLaunchKernelGGL(af_pass_a, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, P, G, pl.rowsum, pl.colpart, pl.blk_a);
-  hipLaunchKernelGGL(af_pass_a2, dim3(pl.n_tensors), dim3(256), 0, st, pl.tensors, pl.rowsum, pl.colpart, pl.blk_a, pl.state, pl.rfac,
-                     pl.cfac, pl.tstat, beta2t);
-  hipLaunchKernelGGL(af_pass_b, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, G, pl.rfac, pl.cfac, pl.blk_b);
-  hipLaunchKernelGGL(af_pass_b2, dim3(pl.n_tensors), dim3(256), 0, st, pl.tensors, pl.blk_b, pl.tstat, rho);
-  hipLaunchKernelGGL(af_pass_c, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, P, G, pl.rfac, pl.cfac, pl.tstat);
-  M2M_CHECK_HIP(hipGetLastError());
-  return M2M_OK;
-}
-
 
 // declared in enc_kernels.hip (the forward RMSNorm is the inference kernel)
 int launch_rmsnorm(int precision, const float* x, const float* w, void* out, int M, int d, float eps, hipStream_t st);
@@ -2429,6 +2211,31 @@ int build_arena(m2m_trainer* t) {
   return M2M_OK;
 }
 
+// ------------------------------------------------------------ operand views of the attention products
+// A matrix per (clip b, head h): element (row, col) at p + b * sb + h * sh + row * ld + col, in elements of its own type.  An activation
+// split into heads ({p, ld, sb}: HeadAttnArgs' convention) has its heads DK columns apart.  km: stored k-major, a product reads it transposed.
+struct Mat {
+  const void* p;
+  int64_t ld, sb, sh = DK;
+  int km = 0;
+  Mat t() const { Mat m = *this; m.km = 1; return m; }
+};
+struct MatProd { Mat A, B, C; };      // C = A . B^T
+// What the attention core of a layer works on (attn_core_fwd / attn_core_bwd)
+struct AttnDesc {
+  Mat q, k, v;                 // V sits `inner` columns behind K
+  int Sq, Sk, causal, site;    // site: the dropout site of the probabilities
+  const float* tab;            // bias table, or null
+  void *Pm, *kt, *ao;          // the layer's P (whole-head kernels: its keep words), its K^T | V^T image, its output rows [nB * Sq, inner]
+  float* lse;
+  // backward only
+  const void* dO;              // layout of ao
+  Mat dq, dk, dv;
+  const int* buckets;          // bias gradient (null: none): bucket table, destination, and `accumulate` as bias_grad* take it
+  float* Gbias;
+  int bias_accumulate;
+};
+
 // ------------------------------------------------------------ typed helpers
 template <typename T>
 struct Ops {
@@ -2595,24 +2402,21 @@ struct Ops {
     M2M_CHECK_HIP(hipGetLastError());
     return M2M_OK;
   }
-  // batched over (clip b, head h): operand X of clip b / head h starts at X + b*s1 + h*s2 (elements of its own type)
-  int mmbh(int epi, const T* A, int64_t lda, int akm, int64_t sA1, int64_t sA2, const T* B, int64_t ldb, int bkm, int64_t sB1, int64_t sB2,
-           void* C, int64_t ldc, int64_t sC1, int64_t sC2, int nB, int M, int N, int K) const {
+  // the layouts only this trainer knows: P / dS / the fp32 scores [nB][H][Sq][ldp] with ldp = align_up(Sk, 8), and the activations
+  Mat pmat(const void* p, int Sq, int Sk) const { const int64_t ldp = align_up(Sk, 8); return Mat{p, ldp, t->g.num_heads * Sq * ldp, Sq * ldp}; }
+  // column group i of n in a projection's output [rows, n * inner] with Sx rows per clip (q | k | v: n = 3; k | v: n = 2; ao, dO, cq: n = 1)
+  Mat part(const void* p, int n, int i, int Sx) const { return Mat{(const T*)p + i * t->inner, n * t->inner, (int64_t)Sx * n * t->inner}; }
+  // C[M,N] (epi)= A[M,K] . B[N,K]^T batched over (clip, head); m2 (BGemmArgs pair mode): a second product of the same shape in the same
+  // launch, whose A and C share pitch, strides and orientation with the first
+  int mmbh(int epi, const MatProd& m, int nB, int M, int N, int K, const MatProd* m2 = nullptr) const {
     BGemmArgs g{};
-    g.A = A; g.B = B; g.C = C; g.R = nullptr; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.a_kmajor = akm; g.b_kmajor = bkm;
-    g.nb1 = nB; g.nb2 = t->g.num_heads; g.sA1 = sA1; g.sA2 = sA2; g.sB1 = sB1; g.sB2 = sB2; g.sC1 = sC1; g.sC2 = sC2; g.alpha = 1.0f;
+    g.A = m.A.p; g.B = m.B.p; g.C = const_cast<void*>(m.C.p); g.R = nullptr; g.M = M; g.N = N; g.K = K; g.lda = m.A.ld; g.ldb = m.B.ld; g.ldc = m.C.ld;
+    g.a_kmajor = m.A.km; g.b_kmajor = m.B.km;
+    g.nb1 = nB; g.nb2 = t->g.num_heads; g.sA1 = m.A.sb; g.sA2 = m.A.sh; g.sB1 = m.B.sb; g.sB2 = m.B.sh; g.sC1 = m.C.sb; g.sC2 = m.C.sh; g.alpha = 1.0f;
+    if (m2) { g.A2 = m2->A.p; g.B2 = m2->B.p; g.C2 = const_cast<void*>(m2->C.p); g.ldb2 = m2->B.ld; g.sB1_2 = m2->B.sb; g.sB2_2 = m2->B.sh; }
     return launch_bgemm(t->precision, epi, g, st, t->sw);
   }
-  // two products of one shape in one launch (BGemmArgs pair mode): (A, B) -> C and (A2, B2) -> C2; A / A2 and C / C2 share strides
-  int mmbh2(int epi, const T* A, const T* A2, int64_t lda, int akm, int64_t sA1, int64_t sA2, const T* B, int64_t ldb, int64_t sB1, int64_t sB2,
-            const T* B2, int64_t ldb2, int64_t sB1_2, int64_t sB2_2, int bkm, void* C, void* C2, int64_t ldc, int64_t sC1, int64_t sC2, int nB, int M, int N,
-            int K) const {
-    BGemmArgs g{};
-    g.A = A; g.B = B; g.C = C; g.R = nullptr; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.a_kmajor = akm; g.b_kmajor = bkm;
-    g.nb1 = nB; g.nb2 = t->g.num_heads; g.sA1 = sA1; g.sA2 = sA2; g.sB1 = sB1; g.sB2 = sB2; g.sC1 = sC1; g.sC2 = sC2; g.alpha = 1.0f;
-    g.A2 = A2; g.B2 = B2; g.C2 = C2; g.ldb2 = ldb2; g.sB1_2 = sB1_2; g.sB2_2 = sB2_2;
-    return launch_bgemm(t->precision, epi, g, st, t->sw);
-  }
+  int mmbh2(int epi, const MatProd& m, const MatProd& m2, int nB, int M, int N, int K) const { return mmbh(epi, m, nB, M, N, K, &m2); }
   // dX[M, Kw] (epi) = dY[M, Nw] . W   for a weight stored [Nw][Kw]: an NT product against the transposed copy WT [Kw][Nw]
   int dX(int epi, const void* dY, int64_t ldy, int64_t w_off, int Nw, int Kw, void* C, int64_t ldc, int M) const {
     if (const m2m_trainer::LinW* w = t->sw.fp8.dx ? lin8(w_off) : nullptr)      // fp8 mode: dY in the gradient format, W^T in e4m3
@@ -2711,71 +2515,76 @@ struct Ops {
   // (the one switch of the trainer read per pass, not at create: tests/test_train_gpu.py runs both paths on trainers that exist already)
   static bool head_on() { const char* v = env_str("M2M_TRAIN_ATTN"); return !(v && v[0] == 's'); }
   bool head_ok(int Sq, int Sk) const { return sizeof(T) == 2 && head_on() && t->sw.tuned_gemm && Sq <= AH_MAX_S && Sk <= AH_MAX_S; }
-  HeadAttnArgs head_args(const void* Q, int64_t ldq, int64_t sQb, const void* K, int64_t ldk, const void* V, int64_t ldv, int64_t sKb, void* O, float* lse,
-                         int Sq, int Sk, const float* tab, int causal, int site, void* keep_bits) const {
+  HeadAttnArgs head_args(const AttnDesc& d, bool bwd) const {
     HeadAttnArgs a{};
-    const int inner = t->inner;
-    a.Q = (const bf16_t*)Q; a.K = (const bf16_t*)K; a.V = (const bf16_t*)V; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.sQb = sQb; a.sKb = sKb; a.sVb = sKb;
-    a.O = (bf16_t*)O; a.ldo = inner; a.sOb = (int64_t)Sq * inner; a.lse = lse;
-    a.bias_tab = tab; a.tab_stride = Sq + Sk - 1; a.tab_center = Sq - 1;
-    a.H = t->g.num_heads; a.Sq = Sq; a.Sk = Sk; a.causal = causal; a.ldp = (int)align_up(Sk, 8);
-    const bool dr = dropping(site);
-    a.dk = dr ? key(site) : DropKey{nullptr, 0}; a.thresh = dr ? t->drop_thresh : 0u; a.scale = t->drop_scale;
-    a.keep_bits = (uint32_t*)keep_bits;      // (the layer's probability buffer, unused on this path: B*H*Sq*Sk/8 bytes of its B*H*Sq*ldp*2)
+    const int Sq = d.Sq, Sk = d.Sk;
+    a.Q = (const bf16_t*)d.q.p; a.K = (const bf16_t*)d.k.p; a.V = (const bf16_t*)d.v.p; a.ldq = d.q.ld; a.ldk = d.k.ld; a.ldv = d.v.ld;
+    a.sQb = d.q.sb; a.sKb = d.k.sb; a.sVb = d.v.sb;
+    a.O = (bf16_t*)d.ao; a.ldo = t->inner; a.sOb = (int64_t)Sq * t->inner; a.lse = d.lse;
+    a.bias_tab = d.tab; a.tab_stride = Sq + Sk - 1; a.tab_center = Sq - 1;
+    a.H = t->g.num_heads; a.Sq = Sq; a.Sk = Sk; a.causal = d.causal; a.ldp = (int)align_up(Sk, 8);
+    const bool dr = dropping(d.site);
+    a.dk = dr ? key(d.site) : DropKey{nullptr, 0}; a.thresh = dr ? t->drop_thresh : 0u; a.scale = t->drop_scale;
+    a.keep_bits = (uint32_t*)d.Pm;           // (the layer's probability buffer, unused on this path: B*H*Sq*Sk/8 bytes of its B*H*Sq*ldp*2)
+    if (bwd) {
+      a.dO = (const bf16_t*)d.dO; a.dQ = (bf16_t*)d.dq.p; a.dK = (bf16_t*)d.dk.p; a.dV = (bf16_t*)d.dv.p;
+      a.lddq = d.dq.ld; a.lddk = d.dk.ld; a.lddv = d.dv.ld; a.sdQb = d.dq.sb; a.sdKb = d.dk.sb; a.sdVb = d.dv.sb;
+      a.diag_part = d.buckets ? drel_slot() : nullptr;
+    }
     return a;
   }
   // Fused scores + softmax (attn_stripe_kernel) when a wave can hold all keys; K = (key, d) operand, Q = (query, d) operand.
   bool stripe_ok(int Sk) const {      // the bias row + (two, with dropout) 32-row blocks of P must fit the LDS
     return t->sw.stripes && Sk <= 32 * ST_NT && 2 * (size_t)32 * (ceil_div(Sk, 32) * 32 + 8) * sizeof(T) + 8192 <= 158 * 1024;
   }
-  // K | V of a layer ([rows, ld], K at column 0 and V at column `inner` of `kv`) -> kt [2][nB*H][64][Sp]
-  int kv_transpose(const T* kv, int64_t ld, void* kt, int nB, int S) const {
+  // K | V of a layer (V `inner` columns behind K) -> kt [2][nB*H][64][Sp]
+  int kv_transpose(const Mat& k, void* kt, int nB, int S) const {
     const int H = t->g.num_heads, Sp = (int)align_up(S, 32);
     constexpr int Et = 16 / sizeof(T);
-    hipLaunchKernelGGL(kv_transpose_kernel<T>, dim3(ceil_div((Sp / Et) * (DK / Et), 256), nB * H, 2), dim3(256), 0, st, kv, ld, (int64_t)t->inner, (T*)kt, S, Sp, H,
-                       (int64_t)nB * H * DK * Sp);
+    hipLaunchKernelGGL(kv_transpose_kernel<T>, dim3(ceil_div((Sp / Et) * (DK / Et), 256), nB * H, 2), dim3(256), 0, st, (const T*)k.p, k.ld, (int64_t)t->inner, (T*)kt, S, Sp,
+                       H, (int64_t)nB * H * DK * Sp);
     M2M_CHECK_HIP(hipGetLastError());
     return M2M_OK;
   }
-  // M2M_TRAIN_FUSE_PV: 0 = off, fwd / bwd = only that pass (diagnostics), default both
-  // Xt / O: the fused product of the stripe kernel (StripeArgs), or null
-  int attn_probs(const T* K, int64_t ldk, int64_t sK1, int64_t sK2, const T* Q, int64_t ldq, int64_t sQ1, int64_t sQ2, void* Pm, int nB, int Sq, int Sk,
-            int ldp, const float* tab, int causal, int site, const T** Puse, const T* Xt = nullptr, void* O = nullptr, int64_t ldo = 0, int64_t sO1 = 0,
-            int64_t sO2 = 0) const {
-    const bool dr = dropping(site);
+  // what the two stripe launches of a layer share: X = (key, d) operand, Y = (query, d) operand, the probabilities, the dropout key, and the
+  // fused product of the rows a workgroup has just formed: Xt its transposed second operand (or null: a launch of its own), `out` its result
+  StripeArgs stripe_args(const AttnDesc& d, const Mat& X, const Mat& Y, const T* Xt, const Mat& out) const {
+    const bool dr = dropping(d.site);
     StripeArgs a{};
-    a.X = K; a.ldx = ldk; a.sX1 = sK1; a.sX2 = sK2; a.Y = Q; a.ldy = ldq; a.sY1 = sQ1; a.sY2 = sQ2;
-    a.P = Pm; a.Pd = (dr && (t->sw.fwd_pd || !(Xt && O))) ? t->dS : nullptr;      // fused P.V: the dropped copy never leaves the kernel
-    a.bias_tab = tab; a.tab_stride = Sq + Sk - 1; a.tab_center = Sq - 1;
-    a.H = t->g.num_heads; a.Sq = Sq; a.Sk = Sk; a.ldp = ldp; a.causal = causal;
-    a.dk = dr ? key(site) : DropKey{nullptr, 0}; a.thresh = dr ? t->drop_thresh : 0u; a.scale = t->drop_scale;
-    a.Xt = Xt; a.xt_ld = align_up(Sk, 32); a.O = O; a.ldo = ldo; a.sO1 = sO1; a.sO2 = sO2;
-    *Puse = dr ? (const T*)t->dS : (const T*)Pm;
+    a.X = X.p; a.ldx = X.ld; a.sX1 = X.sb; a.sX2 = X.sh; a.Y = Y.p; a.ldy = Y.ld; a.sY1 = Y.sb; a.sY2 = Y.sh;
+    a.P = d.Pm; a.H = t->g.num_heads; a.Sq = d.Sq; a.Sk = d.Sk; a.ldp = (int)align_up(d.Sk, 8); a.causal = d.causal;
+    a.dk = dr ? key(d.site) : DropKey{nullptr, 0}; a.thresh = dr ? t->drop_thresh : 0u; a.scale = t->drop_scale;
+    a.Xt = Xt; a.xt_ld = align_up(d.Sk, 32); a.O = const_cast<void*>(out.p); a.ldo = out.ld; a.sO1 = out.sb; a.sO2 = out.sh;
+    return a;
+  }
+  // M2M_TRAIN_FUSE_PV: 0 = off, fwd / bwd = only that pass (diagnostics), default both
+  // Fused scores + softmax (K, Q); vt: the transposed V for the fused P . V into ao, or null
+  int attn_probs(const AttnDesc& d, int nB, const T* vt, const T** Puse) const {
+    const bool dr = dropping(d.site);
+    StripeArgs a = stripe_args(d, d.k, d.q, vt, part(d.ao, 1, 0, d.Sq));
+    a.Pd = (dr && (t->sw.fwd_pd || !vt)) ? t->dS : nullptr;      // fused P.V: the dropped copy never leaves the kernel
+    a.bias_tab = d.tab; a.tab_stride = d.Sq + d.Sk - 1; a.tab_center = d.Sq - 1;
+    *Puse = dr ? (const T*)t->dS : (const T*)d.Pm;
     return launch_attn_stripe<T>(false, a, nB, st, t->sw);
   }
-  // Fused dP + softmax backward: V = (key, d) operand, dO = (query, d) operand; dS out
-  int dscores(const T* V, int64_t ldv, int64_t sV1, int64_t sV2, const T* dO, int64_t ldo, int64_t sO1, int64_t sO2, const void* Pm, void* dS, int nB,
-              int Sq, int Sk, int ldp, int site, bool want_diag = false, const T* Xt = nullptr, void* Out = nullptr, int64_t ld_out = 0, int64_t s1_out = 0,
-              int64_t s2_out = 0, int causal = 0, void* Pd_out = nullptr) const {
-    const bool dr = dropping(site);
-    StripeArgs a{};
-    a.Pd = dr ? Pd_out : nullptr;        // the dropped probabilities again, for the dV product (instead of a drop_copy launch)
-    a.X = V; a.ldx = ldv; a.sX1 = sV1; a.sX2 = sV2; a.Y = dO; a.ldy = ldo; a.sY1 = sO1; a.sY2 = sO2;
-    a.P = const_cast<void*>(Pm); a.dS = dS; a.H = t->g.num_heads; a.Sq = Sq; a.Sk = Sk; a.ldp = ldp;
-    a.causal = causal;                   // only lets the kernel skip key tiles above the diagonal (P is zero there anyway)
-    a.diag_part = want_diag ? drel_slot() : nullptr;
-    a.Xt = Xt; a.xt_ld = align_up(Sk, 32); a.O = Out; a.ldo = ld_out; a.sO1 = s1_out; a.sO2 = s2_out;
-    a.dk = dr ? key(site) : DropKey{nullptr, 0}; a.thresh = dr ? t->drop_thresh : 0u; a.scale = t->drop_scale;
+  // Fused dP + softmax backward (V, dO) -> dS; kt: the transposed K for the fused dQ = dS . K, or null; Pd_out: where the dropped
+  // probabilities go again, for the dV product (instead of a drop_copy launch), or null.  (causal only lets the kernel skip key tiles
+  // above the diagonal: P is zero there anyway)
+  int dscores(const AttnDesc& d, int nB, const T* kt, void* Pd_out) const {
+    StripeArgs a = stripe_args(d, d.v, part(d.dO, 1, 0, d.Sq), kt, d.dq);
+    a.Pd = dropping(d.site) ? Pd_out : nullptr;
+    a.dS = t->dS;
+    a.diag_part = d.buckets ? drel_slot() : nullptr;
     return launch_attn_stripe<T>(true, a, nB, st, t->sw);
   }
   // P (kept for the backward) and, with dropout, the dropped copy the P.V product reads (scratch: t->dS); returns it through *Puse
-  int softmax(const float* sc, void* Pm, int nB, int Sq, int Sk, int ldp, const float* tab, int causal, int site, const T** Puse) const {
-    const int H = t->g.num_heads, rows = nB * H * Sq;
-    const bool dr = dropping(site);
-    hipLaunchKernelGGL(softmax_fwd_kernel<T>, dim3(ceil_div(rows, 4)), dim3(256), 0, st, sc, (T*)Pm, rows, H, Sq, Sk, ldp, tab, Sq + Sk - 1,
-                       Sq - 1, causal, dr ? (T*)t->dS : (T*)nullptr, dr ? key(site) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u, t->drop_scale);
+  int softmax(const AttnDesc& d, int nB, const T** Puse) const {
+    const int H = t->g.num_heads, Sq = d.Sq, Sk = d.Sk, rows = nB * H * Sq;
+    const bool dr = dropping(d.site);
+    hipLaunchKernelGGL(softmax_fwd_kernel<T>, dim3(ceil_div(rows, 4)), dim3(256), 0, st, t->sc, (T*)d.Pm, rows, H, Sq, Sk, (int)align_up(Sk, 8), d.tab, Sq + Sk - 1,
+                       Sq - 1, d.causal, dr ? (T*)t->dS : (T*)nullptr, dr ? key(d.site) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u, t->drop_scale);
     M2M_CHECK_HIP(hipGetLastError());
-    *Puse = dr ? (const T*)t->dS : (const T*)Pm;
+    *Puse = dr ? (const T*)t->dS : (const T*)d.Pm;
     return M2M_OK;
   }
   // backward: the dropped probabilities again (into t->dS, consumed by the dV product before dS overwrites it)
@@ -2789,10 +2598,10 @@ struct Ops {
     *Puse = dst;
     return M2M_OK;
   }
-  int softmax_bwd(const void* Pm, const float* dP, void* dS, int rows, int Sk, int ldp, int site) const {
-    const bool dr = dropping(site);
-    hipLaunchKernelGGL(softmax_bwd_kernel<T>, dim3(ceil_div(rows, 4)), dim3(256), 0, st, (const T*)Pm, dP, (T*)dS, rows, Sk, ldp,
-                       dr ? key(site) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u, t->drop_scale);
+  int softmax_bwd(const AttnDesc& d, int nB) const {      // dS (t->dS) from P and dPd (t->sc)
+    const bool dr = dropping(d.site);
+    hipLaunchKernelGGL(softmax_bwd_kernel<T>, dim3(ceil_div(nB * t->g.num_heads * d.Sq, 4)), dim3(256), 0, st, (const T*)d.Pm, t->sc, (T*)t->dS,
+                       nB * t->g.num_heads * d.Sq, d.Sk, (int)align_up(d.Sk, 8), dr ? key(d.site) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u, t->drop_scale);
     M2M_CHECK_HIP(hipGetLastError());
     return M2M_OK;
   }
@@ -2856,42 +2665,91 @@ struct Ops {
 enum { SITE_ENC = 0, SITE_DEC = 1000, SITE_EMB = 900, SITE_FIN = 901,
        PL_PROBS_SELF = 1, PL_SELF_OUT = 2, PL_PROBS_CROSS = 3, PL_CROSS_OUT = 4, PL_MID = 5, PL_FF_OUT = 6 };
 
+// The attention of one layer between its projections, self or cross: q / k / v -> ao.  The ONE place that chooses among the
+// whole-head kernels (attn_train.hip), the fused stripe kernels and the unfused product + softmax path past 512 keys.
+// (a.lse and a.kt are never null for a layer of the arena — build_arena carves both for every layer — so neither guard decides)
+template <typename T>
+int attn_core_fwd(const Ops<T>& o, const AttnDesc& a, int nB) {
+  m2m_trainer* t = o.t;
+  const int Sq = a.Sq, Sk = a.Sk;
+  int rc;
+  if (a.lse && o.head_ok(Sq, Sk))                                   // whole-head kernel: no P, no K^T | V^T, only O and the row log-sum-exp
+    return launch_attn_head_fwd(o.head_args(a, false), nB, o.st, t->sw);
+  const T* Pu;
+  const bool stripes = o.stripe_ok(Sk);
+  const bool fuse = stripes && t->sw.fuse_pv && a.kt;               // any bit: the image serves P . V here and dQ = dS . K in the backward pass
+  const bool fuse_pv = fuse && (t->sw.fuse_pv & 1);                 // P . V inside the stripe kernel, against the transposed V
+  const T* vt = (const T*)a.kt + (int64_t)nB * t->g.num_heads * DK * align_up(Sk, 32);
+  // (K^T | V^T from the projection's own epilogue was built twice in round 3 — the tile staged through LDS, then the transpose taken
+  //  from the matrix core with the operands swapped — and both cost the projection as much as these launches take: 64-byte row
+  //  pieces instead of whole lines; removed again)
+  if (fuse) RC(o.kv_transpose(a.k, a.kt, nB, Sk));
+  if (stripes) {
+    RC(o.attn_probs(a, nB, fuse_pv ? vt : nullptr, &Pu));
+  } else {
+    RC(o.mmbh(TG_STORE_F32, {a.q, a.k, o.pmat(t->sc, Sq, Sk)}, nB, Sq, Sk, DK));
+    RC(o.softmax(a, nB, &Pu));
+  }
+  if (!fuse_pv) RC(o.mmbh(TG_STORE_T, {o.pmat(Pu, Sq, Sk), a.v.t(), o.part(a.ao, 1, 0, Sq)}, nB, Sq, DK, Sk));
+  return M2M_OK;
+}
+
+// ... and backward: a.dO -> a.dq | a.dk | a.dv, and the bias gradient where the layer has one
+template <typename T>
+int attn_core_bwd(const Ops<T>& o, const AttnDesc& a, int nB) {
+  m2m_trainer* t = o.t;
+  const int Sq = a.Sq, Sk = a.Sk;
+  int rc;
+  if (a.lse && o.head_ok(Sq, Sk)) {                                 // whole-head kernel: dQ | dK | dV (and the bias gradient's diagonal sums) in one launch
+    RC(launch_attn_head_bwd(o.head_args(a, true), nB, o.st, t->sw));
+    if (a.buckets) RC(o.bias_grad_stripes(a.buckets, a.Gbias, nB, Sq, Sk, a.bias_accumulate));
+    return M2M_OK;
+  }
+  const bool stripes = o.stripe_ok(Sk);
+  const bool pair = stripes && t->sw.pair_dvdk;                     // dV and dK in one launch (after dS exists)
+  const bool pd_fused = pair && o.dropping(a.site) && t->sw.fuse_pd;      // the stripe kernel re-emits the dropped P itself
+  const bool fuse = stripes && (t->sw.fuse_pv & 2) && a.kt;         // dQ = dS . K inside the stripe kernel, against the transposed K
+  const Mat dO = o.part(a.dO, 1, 0, Sq), dS = o.pmat(t->dS, Sq, Sk);
+  const T* Pu;
+  if (pd_fused) Pu = (const T*)t->sc;
+  else RC(o.redrop(a.Pm, nB * dS.sb, a.site, &Pu, pair));
+  const Mat Pd = o.pmat(Pu, Sq, Sk);
+  if (!pair) RC(o.mmbh(TG_STORE_T, {Pd.t(), dO.t(), a.dv}, nB, Sk, DK, Sq));                    // dV = Pd^T dO
+  if (stripes) {
+    RC(o.dscores(a, nB, fuse ? (const T*)a.kt : nullptr, pd_fused ? t->sc : nullptr));          // dS from dPd = dO V^T
+    if (a.buckets) RC(o.bias_grad_stripes(a.buckets, a.Gbias, nB, Sq, Sk, a.bias_accumulate));
+  } else {
+    RC(o.mmbh(TG_STORE_F32, {dO, a.v, o.pmat(t->sc, Sq, Sk)}, nB, Sq, Sk, DK));                // dPd = dO V^T
+    RC(o.softmax_bwd(a, nB));
+    if (a.buckets) RC(o.bias_grad(t->dS, a.buckets, a.Gbias, nB, Sq, Sk, (int)dS.ld, a.bias_accumulate));
+  }
+  if (!fuse) RC(o.mmbh(TG_STORE_T, {dS, a.k.t(), a.dq}, nB, Sq, DK, Sk));                  // dQ = dS K
+  if (pair) RC(o.mmbh2(TG_STORE_T, {Pd.t(), dO.t(), a.dv}, {dS.t(), a.q.t(), a.dk}, nB, Sk, DK, Sq));      // dV = Pd^T dO | dK = dS^T Q
+  else RC(o.mmbh(TG_STORE_T, {dS.t(), a.q.t(), a.dk}, nB, Sk, DK, Sq));                    // dK = dS^T Q
+  return M2M_OK;
+}
+
+// the descriptor of a self-attention layer: q | k | v from the layer's one projection, dq | dk | dv into its gradient (t->dqkv)
+template <typename T>
+AttnDesc self_desc(const Ops<T>& o, const void* qkv, int S, const float* tab, int causal, int site0, const void* Pm, const void* kt, float* lse, const void* ao) {
+  AttnDesc a{};
+  a.q = o.part(qkv, 3, 0, S); a.k = o.part(qkv, 3, 1, S); a.v = o.part(qkv, 3, 2, S);
+  a.dq = o.part(o.t->dqkv, 3, 0, S); a.dk = o.part(o.t->dqkv, 3, 1, S); a.dv = o.part(o.t->dqkv, 3, 2, S);
+  a.Sq = a.Sk = S; a.tab = tab; a.causal = causal; a.site = site0 + PL_PROBS_SELF;
+  a.Pm = const_cast<void*>(Pm); a.kt = const_cast<void*>(kt); a.lse = lse; a.ao = const_cast<void*>(ao);
+  return a;
+}
+
 // self-attention block, forward: x_in -> x_out = x_in + Attn(norm(x_in)).  Buffers of this layer are passed in.
 template <typename T>
 int attn_self_fwd(const Ops<T>& o, const float* x_in, float* x_out, int64_t ln, int64_t wqkv, int64_t wo, void* h, void* qkv, void* Pm, void* ao,
                   int nB, int S, const float* tab, int causal, int site0, void* kt, float* lse) {
   m2m_trainer* t = o.t;
-  const int d = t->g.d_model, inner = t->inner, M = nB * S, ldp = (int)align_up(S, 8), H = t->g.num_heads;
+  const int d = t->g.d_model, inner = t->inner, M = nB * S;
   int rc;
   RC(o.norm(x_in, ln, h, M));
   RC(o.mm(TG_STORE_T, h, d, 0, o.W(wqkv), d, 0, qkv, 3 * inner, M, 3 * inner, d));
-  const T* q = (const T*)qkv;
-  if (lse && o.head_ok(S, S)) {                                  // whole-head kernel: no P, no K^T | V^T, only O and the row log-sum-exp
-    const HeadAttnArgs a = o.head_args(q, 3 * inner, (int64_t)S * 3 * inner, q + inner, 3 * inner, q + 2 * inner, 3 * inner, (int64_t)S * 3 * inner, ao, lse, S, S,
-                                       tab, causal, site0 + PL_PROBS_SELF, Pm);
-    RC(launch_attn_head_fwd(a, nB, o.st, o.t->sw));
-    RC(o.mm_resid(ao, wo, x_out, M, d, inner, x_in, site0 + PL_SELF_OUT));
-    return M2M_OK;
-  }
-  const T* Pu;
-  const bool fuse = o.stripe_ok(S) && t->sw.fuse_pv && kt;         // P . V inside the stripe kernel, against the transposed V
-  const bool fuse_pv = fuse && (t->sw.fuse_pv & 1);
-  const T* vt = (const T*)kt + (int64_t)nB * H * DK * align_up(S, 32);
-  // (K^T | V^T from the projection's own epilogue was built twice in round 3 — the tile staged through LDS, then the transpose taken
-  //  from the matrix core with the operands swapped — and both cost the projection as much as these launches take: 64-byte row
-  //  pieces instead of whole lines; removed again)
-  if (fuse) RC(o.kv_transpose(q + inner, 3 * inner, kt, nB, S));
-  if (o.stripe_ok(S)) {
-    RC(o.attn_probs(q + inner, 3 * inner, (int64_t)S * 3 * inner, DK, q, 3 * inner, (int64_t)S * 3 * inner, DK, Pm, nB, S, S, ldp, tab, causal,
-               site0 + PL_PROBS_SELF, &Pu, fuse_pv ? vt : nullptr, ao, inner, (int64_t)S * inner, DK));
-  } else {
-    RC(o.mmbh(TG_STORE_F32, q, 3 * inner, 0, (int64_t)S * 3 * inner, DK, q + inner, 3 * inner, 0, (int64_t)S * 3 * inner, DK, t->sc, ldp,
-              (int64_t)H * S * ldp, (int64_t)S * ldp, nB, S, S, DK));
-    RC(o.softmax(t->sc, Pm, nB, S, S, ldp, tab, causal, site0 + PL_PROBS_SELF, &Pu));
-  }
-  if (!fuse_pv)
-    RC(o.mmbh(TG_STORE_T, Pu, ldp, 0, (int64_t)H * S * ldp, (int64_t)S * ldp, q + 2 * inner, 3 * inner, 1, (int64_t)S * 3 * inner, DK, ao,
-              inner, (int64_t)S * inner, DK, nB, S, DK, S));
+  RC(attn_core_fwd<T>(o, self_desc<T>(o, qkv, S, tab, causal, site0, Pm, kt, lse, ao), nB));
   RC(o.mm_resid(ao, wo, x_out, M, d, inner, x_in, site0 + PL_SELF_OUT));
   return M2M_OK;
 }
@@ -2902,56 +2760,68 @@ int attn_self_bwd(const Ops<T>& o, const float* x_in, const float* dx_out, float
                   const void* h, const void* qkv, const void* Pm, const void* ao, int nB, int S, const int* buckets, int64_t bias_off,
                   int bias_accumulate, int site0, const void* kt, float* lse, const float* tab) {
   m2m_trainer* t = o.t;
-  const int d = t->g.d_model, inner = t->inner, M = nB * S, ldp = (int)align_up(S, 8), H = t->g.num_heads;
+  const int d = t->g.d_model, inner = t->inner, M = nB * S;
   int rc;
   RC(o.begin_sub(1u << m2m_trainer::K_DXT | 1u << m2m_trainer::K_DQKV));
   RC(o.cvt_branch(dx_out, t->dxT, (int64_t)M * d, site0 + PL_SELF_OUT));
   RC(o.dW(t->dxT, d, d, ao, inner, inner, G + wo, M));                                            // dWo = dx^T . ao
   RC(o.dX(TG_STORE_T, t->dxT, d, wo, d, inner, t->dO, inner, M));                                 // dO = dx . Wo
-  const T* q = (const T*)qkv;
-  const T* dO = (const T*)t->dO;
-  T* dq = (T*)t->dqkv;
-  const int64_t sP1 = (int64_t)H * S * ldp, sP2 = (int64_t)S * ldp, sQ1 = (int64_t)S * 3 * inner, sO1 = (int64_t)S * inner;
-  if (lse && o.head_ok(S, S)) {                                  // whole-head kernel: dQ | dK | dV (and the bias gradient's diagonal sums) in one launch
-    HeadAttnArgs a = o.head_args(q, 3 * inner, sQ1, q + inner, 3 * inner, q + 2 * inner, 3 * inner, sQ1, const_cast<void*>(ao), lse, S, S, tab,
-                                 buckets == t->dbucket ? 1 : 0, site0 + PL_PROBS_SELF, const_cast<void*>((const void*)Pm));
-    a.dO = (const bf16_t*)dO;
-    a.dQ = (bf16_t*)dq; a.dK = (bf16_t*)(dq + inner); a.dV = (bf16_t*)(dq + 2 * inner);
-    a.lddq = a.lddk = a.lddv = 3 * inner; a.sdQb = a.sdKb = a.sdVb = sQ1;
-    a.diag_part = buckets ? o.drel_slot() : nullptr;
-    RC(launch_attn_head_bwd(a, nB, o.st, o.t->sw));
-    if (buckets) RC(o.bias_grad_stripes(buckets, G + bias_off, nB, S, S, bias_accumulate));
-    RC(o.dW(dq, 3 * inner, 3 * inner, h, d, d, G + wqkv, M));                                     // dWqkv = dqkv^T . h
-    RC(o.dX(TG_STORE_F32, dq, 3 * inner, wqkv, 3 * inner, d, t->dh, d, M));                       // dh = dqkv . Wqkv
-    RC(o.norm_bwd(x_in, ln, t->dh, dx_out, dx_in, G, M));
-    RC(o.end_sub());
-    return M2M_OK;
-  }
-  const T* Pu;
-  const bool pair = o.stripe_ok(S) && t->sw.pair_dvdk;            // dV and dK in one launch (after dS exists)
-  const bool pd_fused = pair && o.dropping(site0 + PL_PROBS_SELF) && t->sw.fuse_pd;      // the stripe kernel re-emits the dropped P itself
-  if (pd_fused) Pu = (const T*)t->sc;
-  else RC(o.redrop(Pm, (int64_t)nB * H * S * ldp, site0 + PL_PROBS_SELF, &Pu, pair));
-  if (!pair) RC(o.mmbh(TG_STORE_T, Pu, ldp, 1, sP1, sP2, dO, inner, 1, sO1, DK, dq + 2 * inner, 3 * inner, sQ1, DK, nB, S, DK, S));  // dV = Pd^T dO
-  const bool fuse = o.stripe_ok(S) && (t->sw.fuse_pv & 2) && kt;  // dQ = dS . K inside the stripe kernel, against the transposed K
-  if (o.stripe_ok(S)) {
-    RC(o.dscores(q + 2 * inner, 3 * inner, sQ1, DK, dO, inner, sO1, DK, Pm, t->dS, nB, S, S, ldp, site0 + PL_PROBS_SELF, buckets != nullptr,   // dS from dPd = dO V^T
-                 fuse ? (const T*)kt : nullptr, dq, 3 * inner, sQ1, DK, buckets == t->dbucket ? 1 : 0, pd_fused ? t->sc : nullptr));
-    if (buckets) RC(o.bias_grad_stripes(buckets, G + bias_off, nB, S, S, bias_accumulate));
-  } else {
-    RC(o.mmbh(TG_STORE_F32, dO, inner, 0, sO1, DK, q + 2 * inner, 3 * inner, 0, sQ1, DK, t->sc, ldp, sP1, sP2, nB, S, S, DK));      // dPd = dO V^T
-    RC(o.softmax_bwd(Pm, t->sc, t->dS, nB * H * S, S, ldp, site0 + PL_PROBS_SELF));
-    if (buckets) RC(o.bias_grad(t->dS, buckets, G + bias_off, nB, S, S, ldp, bias_accumulate));
-  }
-  const T* dS = (const T*)t->dS;
-  if (!fuse) RC(o.mmbh(TG_STORE_T, dS, ldp, 0, sP1, sP2, q + inner, 3 * inner, 1, sQ1, DK, dq, 3 * inner, sQ1, DK, nB, S, DK, S));   // dQ = dS K
-  if (pair)                                                                                                                          // dV = Pd^T dO | dK = dS^T Q
-    RC(o.mmbh2(TG_STORE_T, Pu, dS, ldp, 1, sP1, sP2, dO, inner, sO1, DK, q, 3 * inner, sQ1, DK, 1, dq + 2 * inner, dq + inner, 3 * inner, sQ1, DK, nB, S, DK, S));
-  else
-    RC(o.mmbh(TG_STORE_T, dS, ldp, 1, sP1, sP2, q, 3 * inner, 1, sQ1, DK, dq + inner, 3 * inner, sQ1, DK, nB, S, DK, S));            // dK = dS^T Q
-  RC(o.dW(dq, 3 * inner, 3 * inner, h, d, d, G + wqkv, M));                                       // dWqkv = dqkv^T . h
-  RC(o.dX(TG_STORE_F32, dq, 3 * inner, wqkv, 3 * inner, d, t->dh, d, M));                         // dh = dqkv . Wqkv
+  AttnDesc a = self_desc<T>(o, qkv, S, tab, buckets == t->dbucket ? 1 : 0, site0, Pm, kt, lse, ao);
+  a.dO = t->dO; a.buckets = buckets; a.Gbias = G + bias_off; a.bias_accumulate = bias_accumulate;
+  RC(attn_core_bwd<T>(o, a, nB));
+  RC(o.dW(t->dqkv, 3 * inner, 3 * inner, h, d, d, G + wqkv, M));                                  // dWqkv = dqkv^T . h
+  RC(o.dX(TG_STORE_F32, t->dqkv, 3 * inner, wqkv, 3 * inner, d, t->dh, d, M));                    // dh = dqkv . Wqkv
   RC(o.norm_bwd(x_in, ln, t->dh, dx_out, dx_in, G, M));
+  RC(o.end_sub());
+  return M2M_OK;
+}
+
+// the descriptor of decoder layer l's cross-attention (hf: modeling_t5.py:319-342: K/V from the encoder output, zero bias, no mask)
+template <typename T>
+AttnDesc cross_desc(const Ops<T>& o, int l, int L, int S) {
+  m2m_trainer* t = o.t;
+  AttnDesc a{};
+  a.q = o.part(t->cqd[l], 1, 0, L); a.k = o.part(t->ckvd[l], 2, 0, S); a.v = o.part(t->ckvd[l], 2, 1, S);
+  a.dq = o.part(t->dcq, 1, 0, L); a.dk = o.part(t->dckv, 2, 0, S); a.dv = o.part(t->dckv, 2, 1, S);
+  a.Sq = L; a.Sk = S; a.site = SITE_DEC + 16 * l + PL_PROBS_CROSS;
+  a.Pm = t->Pcd[l]; a.kt = t->ktc[l]; a.lse = t->lse_c[l]; a.ao = t->aocd[l];
+  return a;
+}
+
+// cross-attention block of decoder layer l, forward: x_in -> x_out = x_in + Attn(norm(x_in), hE)
+template <typename T>
+int attn_cross_fwd(const Ops<T>& o, const float* x_in, float* x_out, int l, int nB, int L, int S) {
+  m2m_trainer* t = o.t;
+  const DecOff& e = t->dec[l];
+  const int d = t->g.d_model, inner = t->inner, Md = nB * L, Me = nB * S;
+  int rc;
+  RC(o.norm(x_in, e.ln1, t->h1d[l], Md));
+  RC(o.mm(TG_STORE_T, t->h1d[l], d, 0, o.W(e.cq), d, 0, t->cqd[l], inner, Md, inner, d));
+  RC(o.mm(TG_STORE_T, t->hE, d, 0, o.W(e.ckv), d, 0, t->ckvd[l], 2 * inner, Me, 2 * inner, d));
+  RC(attn_core_fwd<T>(o, cross_desc<T>(o, l, L, S), nB));
+  RC(o.mm_resid(t->aocd[l], e.co, x_out, Md, d, inner, x_in, SITE_DEC + 16 * l + PL_CROSS_OUT));
+  return M2M_OK;
+}
+
+// ... and backward: dx_out -> dx_in, and the layer's share of the encoder output's gradient into t->dhE (acc_dhE: added to what it holds)
+template <typename T>
+int attn_cross_bwd(const Ops<T>& o, const float* x_in, const float* dx_out, float* dx_in, float* G, int l, int nB, int L, int S, bool acc_dhE) {
+  m2m_trainer* t = o.t;
+  const DecOff& e = t->dec[l];
+  const int d = t->g.d_model, inner = t->inner, Md = nB * L, Me = nB * S;
+  int rc;
+  RC(o.begin_sub(1u << m2m_trainer::K_DXT | 1u << m2m_trainer::K_DCQ | 1u << m2m_trainer::K_DCKV));
+  RC(o.cvt_branch(dx_out, t->dxT, (int64_t)Md * d, SITE_DEC + 16 * l + PL_CROSS_OUT));
+  RC(o.dW(t->dxT, d, d, t->aocd[l], inner, inner, G + e.co, Md));
+  RC(o.dX(TG_STORE_T, t->dxT, d, e.co, d, inner, t->dO, inner, Md));
+  AttnDesc a = cross_desc<T>(o, l, L, S);
+  a.dO = t->dO;
+  RC(attn_core_bwd<T>(o, a, nB));
+  RC(o.dW(t->dcq, inner, inner, t->h1d[l], d, d, G + e.cq, Md));
+  RC(o.dX(TG_STORE_F32, t->dcq, inner, e.cq, inner, d, t->dh, d, Md));
+  RC(o.norm_bwd(x_in, e.ln1, t->dh, dx_out, dx_in, G, Md));
+  RC(o.dW(t->dckv, 2 * inner, 2 * inner, t->hE, d, d, G + e.ckv, Me));                            // dWckv = dckv^T . hE
+  RC(o.dX(acc_dhE ? TG_ACC_F32 : TG_STORE_F32, t->dckv, 2 * inner, e.ckv, 2 * inner, d, t->dhE, d, Me));      // dhE (+)= dckv . Wckv
   RC(o.end_sub());
   return M2M_OK;
 }
@@ -3090,8 +2960,8 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
                        int L, float* loss_out, float* G, float* logits_out, hipStream_t st, hipStream_t st_side,
                        const std::function<int()>* at_split = nullptr) {
   const m2m_t5_geometry& g = t->g;
-  const int d = g.d_model, inner = t->inner, V = g.vocab_size, H = g.num_heads, Le = g.num_layers, Ld = g.num_decoder_layers;
-  const int Me = B * S, Md = B * L, lps = (int)align_up(S, 8), ldv = (int)align_up(V, 8);
+  const int d = g.d_model, V = g.vocab_size, H = g.num_heads, Le = g.num_layers, Ld = g.num_decoder_layers;
+  const int Me = B * S, Md = B * L, ldv = (int)align_up(V, 8);
   Ops<T> o{t, st, P};
   o.Gbase = G;
   o.gacc = G && (t->gmode & m2m_trainer::GM_ACC) ? 1 : 0;
@@ -3146,38 +3016,11 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
   } else {
     RC(launch_embed_rows(t->dec_in, P + t->o_shared, t->xd[0], Md, d, V, g.pad_token_id, st));
   }
-  const int64_t sPc1 = (int64_t)H * L * lps, sPc2 = (int64_t)L * lps;
-  const bool fuse_c = o.stripe_ok(S) && t->sw.fuse_pv;       // cross-attention: P . V and dQ = dS . K inside the stripe kernels
-  const bool fuse_c_pv = fuse_c && (t->sw.fuse_pv & 1), fuse_c_dq = fuse_c && (t->sw.fuse_pv & 2);
   for (int l = 0; l < Ld; ++l) {
     const DecOff& e = t->dec[l];
     RC(attn_self_fwd<T>(o, t->xd[3 * l], t->xd[3 * l + 1], e.ln0, e.qkv, e.o, t->h0d[l], t->qkvd[l], t->Pd[l], t->aod[l], B, L, t->dtab, 1,
                         SITE_DEC + 16 * l, t->ktd[l], t->lse_d[l]));
-    // cross-attention (hf: modeling_t5.py:319-342: K/V from the encoder output, zero bias, no mask)
-    RC(o.norm(t->xd[3 * l + 1], e.ln1, t->h1d[l], Md));
-    RC(o.mm(TG_STORE_T, t->h1d[l], d, 0, o.W(e.cq), d, 0, t->cqd[l], inner, Md, inner, d));
-    RC(o.mm(TG_STORE_T, t->hE, d, 0, o.W(e.ckv), d, 0, t->ckvd[l], 2 * inner, Me, 2 * inner, d));
-    const T* cq = (const T*)t->cqd[l];
-    const T* ckv = (const T*)t->ckvd[l];
-    const T* Pu;
-    const bool head_c = o.head_ok(L, S);
-    if (head_c) {
-      const HeadAttnArgs a = o.head_args(cq, inner, (int64_t)L * inner, ckv, 2 * inner, ckv + inner, 2 * inner, (int64_t)S * 2 * inner, t->aocd[l], t->lse_c[l], L, S,
-                                         nullptr, 0, SITE_DEC + 16 * l + PL_PROBS_CROSS, t->Pcd[l]);
-      RC(launch_attn_head_fwd(a, B, o.st, o.t->sw));
-    } else if (o.stripe_ok(S)) {
-      if (fuse_c) RC(o.kv_transpose(ckv, 2 * inner, t->ktc[l], B, S));          // serves P . V here and dQ = dS . K in the backward pass
-      RC(o.attn_probs(ckv, 2 * inner, (int64_t)S * 2 * inner, DK, cq, inner, (int64_t)L * inner, DK, t->Pcd[l], B, L, S, lps, nullptr, 0,
-                 SITE_DEC + 16 * l + PL_PROBS_CROSS, &Pu, fuse_c_pv ? (const T*)t->ktc[l] + (int64_t)B * H * DK * align_up(S, 32) : nullptr, t->aocd[l], inner,
-                 (int64_t)L * inner, DK));
-    } else {
-      RC(o.mmbh(TG_STORE_F32, cq, inner, 0, (int64_t)L * inner, DK, ckv, 2 * inner, 0, (int64_t)S * 2 * inner, DK, t->sc, lps, sPc1, sPc2, B, L, S, DK));
-      RC(o.softmax(t->sc, t->Pcd[l], B, L, S, lps, nullptr, 0, SITE_DEC + 16 * l + PL_PROBS_CROSS, &Pu));
-    }
-    if (!head_c && !fuse_c_pv)
-      RC(o.mmbh(TG_STORE_T, Pu, lps, 0, sPc1, sPc2, ckv + inner, 2 * inner, 1, (int64_t)S * 2 * inner, DK, t->aocd[l], inner,
-                (int64_t)L * inner, DK, B, L, DK, S));
-    RC(o.mm_resid(t->aocd[l], e.co, t->xd[3 * l + 2], Md, d, inner, t->xd[3 * l + 1], SITE_DEC + 16 * l + PL_CROSS_OUT));
+    RC(attn_cross_fwd<T>(o, t->xd[3 * l + 1], t->xd[3 * l + 2], l, B, L, S));
     RC(ff_fwd<T>(o, t->xd[3 * l + 2], t->xd[3 * l + 3], e.ln2, e.wi, e.wo, t->h2d[l], t->abd[l], t->midd[l], Md, SITE_DEC + 16 * l));
   }
   RC(o.norm_drop(t->xd[3 * Ld], t->o_dln, t->hD, Md, SITE_DEC + SITE_FIN));
@@ -3209,54 +3052,9 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
     RC(ff_bwd<T>(o, t->xd[3 * l + 2], dcur, dnext, G, e.ln2, e.wi, e.wo, t->h2d[l], t->abd[l], t->midd[l], Md, SITE_DEC + 16 * l));
     std::swap(dcur, dnext);
     // ---- cross-attention backward: dcur = d x[3l+2] ----
-    RC(o.begin_sub(1u << m2m_trainer::K_DXT | 1u << m2m_trainer::K_DCQ | 1u << m2m_trainer::K_DCKV));
-    RC(o.cvt_branch(dcur, t->dxT, (int64_t)Md * d, SITE_DEC + 16 * l + PL_CROSS_OUT));
-    RC(o.dW(t->dxT, d, d, t->aocd[l], inner, inner, G + e.co, Md));
-    RC(o.dX(TG_STORE_T, t->dxT, d, e.co, d, inner, t->dO, inner, Md));
-    const T* cq = (const T*)t->cqd[l];
-    const T* ckv = (const T*)t->ckvd[l];
-    const T* dO = (const T*)t->dO;
-    T* dckv = (T*)t->dckv;
-    T* dcq = (T*)t->dcq;
-    const int64_t sK1 = (int64_t)S * 2 * inner, sQ1 = (int64_t)L * inner;
-    const T* Pu;
-    const bool head_cb = o.head_ok(L, S);
-    if (head_cb) {
-      HeadAttnArgs a = o.head_args(cq, inner, sQ1, ckv, 2 * inner, ckv + inner, 2 * inner, sK1, t->aocd[l], t->lse_c[l], L, S, nullptr, 0,
-                                   SITE_DEC + 16 * l + PL_PROBS_CROSS, t->Pcd[l]);
-      a.dO = (const bf16_t*)dO;
-      a.dQ = (bf16_t*)dcq; a.lddq = inner; a.sdQb = sQ1;
-      a.dK = (bf16_t*)dckv; a.dV = (bf16_t*)(dckv + inner); a.lddk = a.lddv = 2 * inner; a.sdKb = a.sdVb = sK1;
-      RC(launch_attn_head_bwd(a, B, o.st, o.t->sw));
-    }
-    if (!head_cb) {
-      const bool pair_c = o.stripe_ok(S) && t->sw.pair_dvdk;
-      const bool pd_fused_c = pair_c && o.dropping(SITE_DEC + 16 * l + PL_PROBS_CROSS) && t->sw.fuse_pd;
-      if (pd_fused_c) Pu = (const T*)t->sc;
-      else RC(o.redrop(t->Pcd[l], (int64_t)B * H * L * lps, SITE_DEC + 16 * l + PL_PROBS_CROSS, &Pu, pair_c));
-      if (!pair_c) RC(o.mmbh(TG_STORE_T, Pu, lps, 1, sPc1, sPc2, dO, inner, 1, sQ1, DK, dckv + inner, 2 * inner, sK1, DK, B, S, DK, L));      // dV = Pd^T dO
-      if (o.stripe_ok(S)) {
-        RC(o.dscores(ckv + inner, 2 * inner, sK1, DK, dO, inner, sQ1, DK, t->Pcd[l], t->dS, B, L, S, lps, SITE_DEC + 16 * l + PL_PROBS_CROSS, false,
-                     fuse_c_dq ? (const T*)t->ktc[l] : nullptr, dcq, inner, sQ1, DK, 0, pd_fused_c ? t->sc : nullptr));
-      } else {
-        RC(o.mmbh(TG_STORE_F32, dO, inner, 0, sQ1, DK, ckv + inner, 2 * inner, 0, sK1, DK, t->sc, lps, sPc1, sPc2, B, L, S, DK));             // dPd = dO V^T
-        RC(o.softmax_bwd(t->Pcd[l], t->sc, t->dS, B * H * L, S, lps, SITE_DEC + 16 * l + PL_PROBS_CROSS));
-      }
-      const T* dS = (const T*)t->dS;
-      if (!fuse_c_dq) RC(o.mmbh(TG_STORE_T, dS, lps, 0, sPc1, sPc2, ckv, 2 * inner, 1, sK1, DK, dcq, inner, sQ1, DK, B, L, DK, S));               // dQ = dS K
-      if (pair_c)                                                                                                                              // dV | dK
-        RC(o.mmbh2(TG_STORE_T, Pu, dS, lps, 1, sPc1, sPc2, dO, inner, sQ1, DK, cq, inner, sQ1, DK, 1, dckv + inner, dckv, 2 * inner, sK1, DK, B, S, DK, L));
-      else
-        RC(o.mmbh(TG_STORE_T, dS, lps, 1, sPc1, sPc2, cq, inner, 1, sQ1, DK, dckv, 2 * inner, sK1, DK, B, S, DK, L));                          // dK = dS^T Q
-    }
-    RC(o.dW(dcq, inner, inner, t->h1d[l], d, d, G + e.cq, Md));
-    RC(o.dX(TG_STORE_F32, dcq, inner, e.cq, inner, d, t->dh, d, Md));
     o.after_site = SITE_DEC + 16 * l + PL_SELF_OUT;
-    RC(o.norm_bwd(t->xd[3 * l + 1], e.ln1, t->dh, dcur, dnext, G, Md));
+    RC(attn_cross_bwd<T>(o, t->xd[3 * l + 1], dcur, dnext, G, l, B, L, S, l != Ld - 1));
     std::swap(dcur, dnext);
-    RC(o.dW(dckv, 2 * inner, 2 * inner, t->hE, d, d, G + e.ckv, Me));                               // dWckv = dckv^T . hE
-    RC(o.dX(l == Ld - 1 ? TG_STORE_F32 : TG_ACC_F32, dckv, 2 * inner, e.ckv, 2 * inner, d, t->dhE, d, Me));                  // dhE (+)= dckv . Wckv
-    RC(o.end_sub());
     // ---- causal self-attention backward ----
     o.after_site = l > 0 ? SITE_DEC + 16 * (l - 1) + PL_FF_OUT : -2;
     RC(attn_self_bwd<T>(o, t->xd[3 * l], dcur, dnext, G, e.ln0, e.qkv, e.o, t->h0d[l], t->qkvd[l], t->Pd[l], t->aod[l], B, L, t->dbucket, t->o_drb,

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Host time of one m2m_train_forward_backward call (enqueue only) against the step's GPU time.  python tools/train_host_time.py [bf16|fp8]"""
+"""Host time of one m2m_train_forward_backward call (enqueue only) against the step's GPU time.  python tools/train_host_time.py [bf16|fp8] [B,B,...]"""
 import sys, time
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
@@ -15,7 +15,7 @@ cfg = default_config(); geom = T5Geometry(cfg.model.t5)
 sd = synth.t5_state_dict(geom, 0)
 model = T5Transformer(cfg.to_dict(), precision="fp32"); load_t5_state(model, sd, strict=False); model = model.cuda()
 S, Ld, n = 261, 256, 20
-for B in (4, 8, 16, 64):
+for B in ([int(v) for v in sys.argv[2].split(",")] if len(sys.argv) > 2 else (4, 8, 16, 64)):
     tr = NativeTrainer(model, B, S, Ld, precision=prec)
     x = torch.from_numpy(synth.normal(1, "x", (B, S, 384), 2.0)).cuda()
     cond = torch.from_numpy(synth.cond_index_batch(0, B)).cuda()

@@ -1,0 +1,68 @@
+#!/usr/bin/env python3
+"""SHA-256 over loss, logits and the flat gradient buffer of one forward_backward call, per kernel family of the training attention,
+and the launches of the captured graph.  For host-side changes of the training pass: run once per build and compare the lines.
+
+    M2M_LIBRARY=<the other build> python tools/train_step_digest.py > a.txt;  python tools/train_step_digest.py > b.txt;  diff a.txt b.txt
+
+Weights, inputs and the dropout seed are fixed; the bits depend on the ROCm build, so the digests are compared, never stored.
+(tiny model; the trainer's switches are latched when it is created, so every case sets its environment before it creates one)"""
+import hashlib
+import os
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from music2midi_amd import synth  # noqa: E402
+from music2midi_amd.checkpoint import load_t5_state  # noqa: E402
+from music2midi_amd.config import T5Geometry, load_config  # noqa: E402
+from music2midi_amd.training import NativeTrainer  # noqa: E402
+from music2midi_amd.transformer import T5Transformer  # noqa: E402
+from test_t5_gpu import tiny_config  # noqa: E402
+
+SWITCHES = ("M2M_TRAIN_GRAPH", "M2M_TRAIN_ATTN", "M2M_TRAIN_FUSE_PV", "M2M_TRAIN_PAIR_DVDK")
+# (precision, B, F, Ld, dropout, environment): stripes; unfused past 512 keys; whole-head; the same on stripes; mixed (402 > AH_MAX_S); fp8
+SHAPES = [("fp32", 3, 21, 14, 0.0, {}), ("fp32", 3, 21, 14, 0.1, {}), ("fp32", 1, 530, 5, 0.0, {}), ("fp32", 1, 530, 5, 0.1, {}),
+          ("bf16", 2, 70, 33, 0.1, {}), ("bf16", 2, 70, 33, 0.1, {"M2M_TRAIN_ATTN": "stripes"}), ("bf16", 2, 400, 37, 0.1, {}),
+          ("fp8", 3, 21, 14, 0.0, {})]
+CASES = SHAPES + [(*c[:5], {**c[5], "M2M_TRAIN_GRAPH": "0"}) for c in SHAPES]
+# the legs where the separate dV / dQ / dK products run
+CASES += [("fp32", 3, 21, 14, 0.1, {"M2M_TRAIN_FUSE_PV": "0"}), ("fp32", 3, 21, 14, 0.1, {"M2M_TRAIN_PAIR_DVDK": "0"})]
+
+
+def main():
+    cfg = tiny_config()
+    geom = T5Geometry(load_config(cfg).model.t5)
+    sd = synth.t5_state_dict(geom, seed=0)
+    synth.perturb_layer_norms(sd, 0)
+    model = T5Transformer(cfg, precision="fp32")
+    load_t5_state(model, sd, strict=False)
+    model = model.cuda()
+    for prec, B, F, Ld, p, env in CASES:
+        for k in SWITCHES:
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        x = torch.zeros((B, F + 2, geom.d_model))
+        x[:, 2:] = torch.from_numpy(synth.normal(5, "feats", (B, F, geom.d_model), 2.0))
+        cond = torch.from_numpy(synth.cond_index_batch(2, B)).cuda()
+        labels = (torch.from_numpy((synth.uniform01(4, "labels", B * Ld) * 330).astype(np.int64).reshape(B, Ld)) + 3).cuda()
+        x = x.cuda()
+        tr = NativeTrainer(model, B, F + 2, Ld, precision=prec)
+        h = hashlib.sha256()
+        if p:
+            tr.set_dropout(p, seed=1234)
+        for call in range(3):                                    # a graph build replays the captured graph from its second call on
+            loss, logits = tr.forward_backward(x, cond, labels, want_logits=True)
+            torch.cuda.synchronize()
+            for a in (loss, logits, tr.grads):
+                h.update(a.cpu().numpy().tobytes())
+        what = " ".join(f"{k}={v}" for k, v in env.items()) or "-"
+        print(f"{prec} B={B} F={F} Ld={Ld} p={p} {what}: graph nodes {tr.graph_nodes()} sha256 {h.hexdigest()}", flush=True)
+        tr.close()
+
+
+if __name__ == "__main__":
+    main()
