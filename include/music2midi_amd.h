@@ -122,6 +122,63 @@ int m2m_cond_rows_f32(const float* const* tables_dev_host, const int* table_rows
                       int64_t out_batch_stride, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Training augmentation: peak normalisation + pitch shift of a waveform batch, replaces
+ * ref: music2midi/dataset.py:131-133,157-160 (librosa.util.normalize, librosa.effects.pitch_shift).
+ * The definition is music2midi_amd/audio.py (normalize, pitch_shift): n_fft 2048, hop 512, periodic Hann,
+ * zero-padded centred frames; phase-vocoder stretch by rate = 2^(-step/12); polyphase resampling by
+ * up/down = rate (denominator <= 1000) through a Kaiser(5.0) windowed sinc of 20 max(up, down) + 1 taps; fix_length.
+ * ------------------------------------------------------------------------- */
+typedef struct m2m_augment m2m_augment;
+
+#define M2M_AUGMENT_MAX_STEP 12            /* |step| <= 12 semitones */
+#define M2M_AUGMENT_MAX_SAMPLES (1 << 22)  /* T <= 2^22 */
+
+/* The handle owns the window, the FFT twiddles and one resampling filter per step in -12..12 (device and host copies). */
+int  m2m_augment_create(m2m_augment** out);
+void m2m_augment_destroy(m2m_augment* a);
+
+/* What audio.pitch_shift computes on the way for a clip of T samples shifted by `step` semitones.  Host arithmetic only:
+ * `a` may be NULL, nothing is launched.  step 0 reports up = down = 1, taps = 0 and the unstretched extents. */
+typedef struct {
+  int frames;            /* 1 + T / 512 */
+  int stretched_frames;  /* len(np.arange(0, frames, rate)) */
+  int stretched_len;     /* int(round(T / rate)) */
+  int up, down;          /* Fraction(rate).limit_denominator(1000) */
+  int taps;              /* 20 max(up, down) + 1 */
+  int cap_frames;        /* 2 * frames: rows per clip of the stretched-STFT workspace region (the extent at step +12) */
+  int cap_len;           /* 2 * T: floats per clip of the stretched-waveform workspace region */
+} m2m_augment_plan_t;
+int m2m_augment_plan(const m2m_augment* a, int T, int step, m2m_augment_plan_t* out);
+/* The resampling filter of `step` (fp32, as scipy's resample_poly hands it to upfirdn for fp32 input): the first n of its taps to
+ * out_host.  Host arithmetic only; returns the number of taps (0 for step 0) or a negative error. */
+int m2m_augment_filter(int step, float* out_host, int n);
+
+/* Bytes of workspace_dev for a call with B clips of T samples (any steps), or a negative error. */
+int64_t m2m_augment_workspace_bytes(int B, int T);
+
+/* Optional copies of the intermediates, each dense over the batch (device pointers; a NULL member is skipped):
+ *   stft            [B][frames][1025] complex fp32 (re, im) of the (normalised) clip
+ *   stretched_stft  [B][cap_frames][1025] complex fp32: rows < the clip's stretched_frames are meaningful
+ *   stretched_wave  [B][cap_len] fp32: samples < the clip's stretched_len are meaningful
+ * The rest of a region, and all of a step-0 clip's part (it is copied, not transformed), is unspecified. */
+typedef struct {
+  float* stft;
+  float* stretched_stft;
+  float* stretched_wave;
+} m2m_augment_stages;
+
+/*
+ * out_dev[b] = pitch_shift(normalize_host[b] ? normalize(wav_dev[b]) : wav_dev[b], steps_host[b]),  wav_dev / out_dev [B, T] fp32.
+ * steps_host [B] int semitones, normalize_host [B] bytes (NULL = no clip is normalised): host arrays, read before the call returns.
+ * A step-0 clip is copied (bit-equal); normalisation divides by max |y| (bit-equal to the host function, skipped below FLT_MIN).
+ * Every clip's result is independent of the other clips of the batch.  Nothing is synchronised and nothing returns to the host.
+ * M2M_ERR_INVALID before anything is launched: B outside 1..65535, T outside 1..2^22, a |step| > 12, out_dev overlapping wav_dev.
+ */
+int m2m_pitch_shift_f32(const m2m_augment* a, const float* wav_dev, int B, int T, const int* steps_host,
+                        const unsigned char* normalize_host, float* out_dev, void* workspace_dev,
+                        const m2m_augment_stages* stages, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * T5 encoder-decoder weights, replaces what ref: music2midi/transformer.py:14-16
  * builds (T5Config + T5ForConditionalGeneration) once a state dict is loaded.
  * ------------------------------------------------------------------------- */

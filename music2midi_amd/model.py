@@ -240,7 +240,7 @@ class Music2MIDI(nn.Module):
             tr.dropout = -1.0                                # the mask sequence restarts from the restored step (see _native_trainer)
 
     def fit_batches(self, batches, optimizer=None, world_size: int = 1, ckpt_path=None, save_path=None, save_every_n_steps: int = 0,
-                    accumulate_grad_batches=None):
+                    accumulate_grad_batches=None, augment=None):
         """Minimal stand-in for ``pl.Trainer.fit`` (ref train.py:40-41): step over an iterable of ModelInputs.  ``ckpt_path``
         resumes a run (weights + Adafactor state + step counter) as ``trainer.fit(..., ckpt_path=)`` does; ``save_path`` is
         (re)written every ``save_every_n_steps`` steps and at the end.  The host never waits for a step: losses stay on the device
@@ -249,7 +249,14 @@ class Music2MIDI(nn.Module):
         Gradient accumulation (``accumulate_grad_batches``, default ``config.trainer.accumulate_grad_batches``; see
         ``music2midi_amd.accumulation``): the optimizer steps — and the gradients are all-reduced — once per window of N batches
         and after the last batch; ``global_step``, ``save_every_n_steps`` and ``log_every_n_steps`` count optimizer steps, so
-        checkpoints fall on window boundaries.  The returned losses are per batch, unscaled.  The override holds for this call only."""
+        checkpoints fall on window boundaries.  The returned losses are per batch, unscaled.  The override holds for this call only.
+        ``augment`` (a ``np.random.Generator``, or ``True`` for ``default_rng(0)``): every batch goes through
+        ``music2midi_amd.augment.augment`` first — the reference dataset's normalise / transpose draws (ref dataset.py:130-133), the
+        audio shifted on the device; ``None`` leaves the batches as they are."""
+        if augment is not None and augment is not False:
+            from .augment import augment as augment_batch
+            rng = np.random.default_rng(0) if augment is True else augment
+            batches = (augment_batch(batch, rng) for batch in batches)
         if accumulate_grad_batches is not None:
             check_accumulate_grad_batches(accumulate_grad_batches)
         previous = self._accumulate_override

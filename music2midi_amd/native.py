@@ -40,6 +40,15 @@ class FrontendPlan(C.Structure):
 FE_FORMS = ("v2_nj6", "v2_nj8", "v1_taps_lds", "v1_taps_global")   # FrontendPlan.form -> name (M2M_FE_FORM_*)
 
 
+class AugmentPlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in
+                ("frames", "stretched_frames", "stretched_len", "up", "down", "taps", "cap_frames", "cap_len")]
+
+
+class AugmentStages(C.Structure):
+    _fields_ = [("stft", C.c_void_p), ("stretched_stft", C.c_void_p), ("stretched_wave", C.c_void_p)]
+
+
 class T5GeometryC(C.Structure):
     _fields_ = [(n, C.c_int) for n in
                 ("d_model", "d_ff", "num_layers", "num_decoder_layers", "num_heads", "d_kv", "vocab_size",
@@ -101,6 +110,13 @@ _SIGNATURES = {
     "m2m_frontend_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(FrontendPlan)]),
     "m2m_cond_rows_f32": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p,
                                     C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "m2m_augment_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "m2m_augment_destroy": (None, [C.c_void_p]),
+    "m2m_augment_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(AugmentPlan)]),
+    "m2m_augment_filter": (C.c_int, [C.c_int, C.c_void_p, C.c_int]),
+    "m2m_augment_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "m2m_pitch_shift_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(AugmentStages), C.c_void_p]),
     "m2m_model_create": (C.c_int, [C.POINTER(T5GeometryC), C.POINTER(T5Weights), C.c_int, C.c_void_p,
                                    C.POINTER(C.c_void_p)]),
     "m2m_model_destroy": (None, [C.c_void_p]),
