@@ -179,6 +179,51 @@ int m2m_pitch_shift_f32(const m2m_augment* a, const float* wav_dev, int B, int T
                         const m2m_augment_stages* stages, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Scoring of decoded tokens: token ids -> notes -> melody -> the counts of the chroma accuracy, replaces for labelled decodes
+ * ref: music2midi/tokenizer.py:169-200 (decode), music2midi/utils.py:5-20 and music2midi/evaluation.py:10-75.
+ * The definitions are music2midi_amd/tokenizer.py (_decode_tokens, _decode), utils.py (numpy_to_midi) and evaluation.py; the
+ * results are EQUAL to theirs (integers; the frame arithmetic repeats the host's float64 operations).  No handle, no workspace,
+ * no environment switch; both calls enqueue on `stream` and return nothing to the host.  Every M2M_ERR_INVALID below is
+ * answered on the arguments alone, before the first HIP call.
+ * ------------------------------------------------------------------------- */
+#define M2M_SCORE_MAX_TOKENS 2048          /* ids per row */
+#define M2M_SCORE_MAX_ROWS 65535
+#define M2M_SCORE_MAX_FRAMES (1 << 22)     /* frames of 10 ms per timeline: 11.6 hours */
+#define M2M_SCORE_MAX_LABELS (1 << 24)     /* label notes per call */
+
+/* len(np.arange(0, end_seconds, 1 / 100)) as the kernels compute it: ceil(end_seconds / (1.0 / 100.0)) in double; 0 for an end
+ * that is not positive.  Host arithmetic, exported so that the formula can be tested without a GPU. */
+int64_t m2m_score_frame_count(double end_seconds);
+
+/*
+ * MidiTokenizer.decode without the host: row r of ids_dev [R, L] int64 (row r at ids_dev + r * row_stride) is one state machine
+ * over (time index, mode, pitch); ids 0 / 1 are skipped, 2 ends the row, 3 / 4 are ONSET / OFFSET, [pitch_offset, time_offset) are
+ * pitches and EVERY id >= time_offset is a time; row r adds r * steps_per_row to its time indices (0: "batched").
+ * notes_out_dev [R, L, 3] int32: (onset index, offset index, pitch) of the closed notes of the row in emission order;
+ * counts_out_dev [R] int32 their number (L is a true bound: every emission consumes an id), or -1 for a row holding an id outside
+ * [0, vocab_size) - nothing is written for it.  Entries beyond a row's count are unspecified.
+ * M2M_ERR_INVALID: R outside 1..65535, L outside 1..2048, row_stride < L, vocab_size outside 1..4096, pitch_offset < 5, a pitch
+ * range outside 1..128 ids, time_offset > vocab_size, steps_per_row < 0, a time index or an element offset beyond int32.
+ */
+int m2m_score_detokenize(const int64_t* ids_dev, int R, int L, int64_t row_stride, int64_t steps_per_row, int pitch_offset,
+                         int time_offset, int vocab_size, int32_t* notes_out_dev, int32_t* counts_out_dev, void* stream);
+
+/*
+ * evaluation.extract_midi_melody + the integer core of melody_chroma_accuracy, per timeline.  The output notes are
+ * m2m_score_detokenize's (seconds = index * time_step); row r belongs to timeline r, or every row to timeline 0 when sequential.
+ * labels_dev [3, n_labels] float64: starts, ends, pitches (whole numbers 0..127) of the label notes, those of timeline t at
+ * [label_offsets_dev[t], label_offsets_dev[t + 1]) (int32 [n_timelines + 1]); a note with end <= start does not exist.
+ * frame_cap: the caller's upper bound on n_frames of any timeline (it sizes the grid).
+ * out_dev [n_timelines, 3] int32, zeroed on `stream` first: correct = frames where both melodies sound and differ by a multiple of
+ * 12, voiced = frames where the label melody sounds, frames = n_frames - or -1 (and no counts) for a timeline beyond frame_cap.
+ * M2M_ERR_INVALID: R, L as above, n_timelines other than R (1 when sequential), time_step outside (0, 3600], n_labels outside
+ * 0..2^24, frame_cap outside 1..2^22, a null pointer.
+ */
+int m2m_score_chroma_counts(const int32_t* notes_dev, const int32_t* counts_dev, int R, int L, int sequential, double time_step,
+                            const double* labels_dev, const int32_t* label_offsets_dev, int n_labels, int n_timelines, int frame_cap,
+                            int32_t* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * T5 encoder-decoder weights, replaces what ref: music2midi/transformer.py:14-16
  * builds (T5Config + T5ForConditionalGeneration) once a state dict is loaded.
  * ------------------------------------------------------------------------- */

@@ -1,2 +1,2 @@
-from music2midi_amd.evaluation import (evaluate_batch, extract_midi_melody,  # noqa: F401
-                                       melody_chroma_accuracy)
+from music2midi_amd.evaluation import (evaluate_batch, evaluate_tokens,  # noqa: F401
+                                       extract_midi_melody, melody_chroma_accuracy)

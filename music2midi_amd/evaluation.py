@@ -81,3 +81,13 @@ def evaluate_batch(targets: Iterable, outputs: Iterable) -> float:
         return 0.0
     ts, os_ = zip(*pairs)
     return melody_chroma_accuracy(np.concatenate(ts), np.concatenate(os_))
+
+
+def evaluate_tokens(tokenizer, token_ids, notes_batch, mode: str = "batched", duration_per_batch=None) -> float:
+    """``evaluate_batch(numpy_to_midi(labels), numpy_to_midi(tokenizer.decode(token_ids, mode, duration_per_batch)))`` for token ids
+    that are on the GPU, computed there (``music2midi_amd.scoring``, csrc/score.hip): the same float, not a close one - for integer
+    pitches the 50-cent octave-folded test is "the pitches differ by a multiple of 12", so the score is a ratio of two frame counts.
+    ``notes_batch``: one label array per row, or ONE array in ``sequential`` mode.  ``ValueError`` for labels the device path does
+    not take (``scoring.labels_eligible``)."""
+    from .scoring import chroma_counts
+    return chroma_counts(tokenizer, token_ids, notes_batch, mode, duration_per_batch).score

@@ -22,7 +22,7 @@ from .accumulation import check_accumulate_grad_batches, micro_step, windows
 from .audio import load_audio as _load_audio
 from .checkpoint import load_t5_state, read_checkpoint
 from .config import inference_beams, load_config
-from .evaluation import evaluate_batch
+from .evaluation import evaluate_batch, evaluate_tokens
 from .input import ModelInputs
 from .transformer import T5Transformer
 from .utils import numpy_to_midi
@@ -35,6 +35,41 @@ def _decode_entry(model, config, grammar_kwargs: dict):
     if not beams:
         return model.generate, grammar_kwargs
     return model.beam_search_processed, dict(beams, num_return_sequences=1, **grammar_kwargs)
+
+
+def _labelled_token_ids(model, config, grammar_kwargs: dict, inputs) -> torch.Tensor:
+    """The decode of one labelled batch that ``evaluate_batch`` and ``score_batch`` share: four tokens per label note of the busiest
+    clip; with beams, chunks of batch_size // num_beams clips, as sample_tokens, so a call's rows stay within inference.batch_size."""
+    budget = 4 * max(len(n) for n in inputs.notes_batch)
+    decode, decode_kwargs = _decode_entry(model, config, grammar_kwargs)
+    nb = int(decode_kwargs.get("num_beams", 1))
+    if nb == 1:
+        return decode(inputs, max_length=budget, **decode_kwargs)
+    per_call = max(1, int(config.inference.get("batch_size", 128)) // nb)
+    n_clips, parts = len(inputs.notes_batch), []
+    for lo in range(0, n_clips, per_call):
+        hi = min(lo + per_call, n_clips)
+        part = type(inputs)(input_waveform=inputs.input_waveform[lo:hi], notes_batch=inputs.notes_batch[lo:hi],
+                            cond_index=inputs.cond_index[lo:hi] if inputs.cond_index is not None else None)
+        parts.append(decode(part, max_length=budget, **decode_kwargs))
+    width = max(p.shape[1] for p in parts)
+    pad = model.geometry.pad_token_id
+    return torch.cat([torch.nn.functional.pad(p, (0, width - p.shape[1]), value=pad) for p in parts], dim=0)
+
+
+def _score_on_host(tokenizer, token_ids, notes_batch):
+    """(chroma accuracy, decoded MIDI per clip, label MIDI per clip): detokenise, build the MIDI objects and score, on the host."""
+    predicted = [numpy_to_midi(n) for n in tokenizer.decode(token_ids, mode="batched")]
+    wanted = [numpy_to_midi(n) for n in notes_batch]
+    return evaluate_batch(wanted, predicted), predicted, wanted
+
+
+def _on_device_scorable(token_ids, label_arrays) -> bool:
+    """The device path takes ids that are on a GPU and labels ``scoring.labels_eligible`` accepts; everything else is the host's."""
+    if not (isinstance(token_ids, torch.Tensor) and token_ids.is_cuda):
+        return False
+    from .scoring import labels_eligible
+    return labels_eligible(label_arrays)
 
 
 class Music2MIDI(nn.Module):
@@ -160,7 +195,7 @@ class Music2MIDI(nn.Module):
         loss = loss[0].clone()                                # the trainer's loss word is rewritten by the next pass
         self.logged = {"train/loss": loss, "batch_size": int(x.shape[0])}
         if (self.global_step + 1) % int(self.config.trainer.log_every_n_steps) == 0:
-            self.logged["train/score"] = float(self.evaluate_batch(inputs)[0])
+            self.logged["train/score"] = float(self.score_batch(inputs))
         return loss
 
     def logged_metrics(self) -> dict:
@@ -310,7 +345,7 @@ class Music2MIDI(nn.Module):
         reference does).  Lightning's ``self.log`` does not exist here: the two values are kept in
         ``self.logged`` under the reference's metric names, already reduced over the ranks (``sync_dist=True``)."""
         loss = self.model(inputs).loss
-        score = self.evaluate_batch(inputs)[0]
+        score = self.score_batch(inputs)
         self.logged = D.reduce_logged({"val/loss": loss, "val/score": float(score), "batch_size": int(inputs.input_waveform.shape[0])},
                                       device=self.device)
         self.logged["batch_size"] = int(self.logged["batch_size"])
@@ -325,25 +360,18 @@ class Music2MIDI(nn.Module):
     def evaluate_batch(self, inputs: ModelInputs):
         """(chroma accuracy, decoded MIDI per clip, label MIDI per clip) for one labelled batch — ref
         model.py:55-65.  The decode budget is four tokens per label note of the busiest clip."""
-        budget = 4 * max(len(n) for n in inputs.notes_batch)
-        decode, decode_kwargs = _decode_entry(self.model, self.config, self._grammar_kwargs())
-        nb = int(decode_kwargs.get("num_beams", 1))
-        if nb == 1:
-            token_ids = decode(inputs, max_length=budget, **decode_kwargs)
-        else:   # beams: chunks of batch_size // num_beams clips, as sample_tokens, so a call's rows stay within inference.batch_size
-            per_call = max(1, int(self.config.inference.get("batch_size", 128)) // nb)
-            n_clips, parts = len(inputs.notes_batch), []
-            for lo in range(0, n_clips, per_call):
-                hi = min(lo + per_call, n_clips)
-                part = type(inputs)(input_waveform=inputs.input_waveform[lo:hi], notes_batch=inputs.notes_batch[lo:hi],
-                                    cond_index=inputs.cond_index[lo:hi] if inputs.cond_index is not None else None)
-                parts.append(decode(part, max_length=budget, **decode_kwargs))
-            width = max(p.shape[1] for p in parts)
-            pad = self.model.geometry.pad_token_id
-            token_ids = torch.cat([torch.nn.functional.pad(p, (0, width - p.shape[1]), value=pad) for p in parts], dim=0)
-        predicted = [numpy_to_midi(n) for n in self.model.tokenizer.decode(token_ids, mode="batched")]
-        wanted = [numpy_to_midi(n) for n in inputs.notes_batch]
-        return evaluate_batch(wanted, predicted), predicted, wanted
+        token_ids = _labelled_token_ids(self.model, self.config, self._grammar_kwargs(), inputs)
+        return _score_on_host(self.model.tokenizer, token_ids, inputs.notes_batch)
+
+    @torch.no_grad()
+    def score_batch(self, inputs: ModelInputs) -> float:
+        """``evaluate_batch(inputs)[0]`` without the host: the same decode, then detokenising, melody and counts on the device
+        (``evaluation.evaluate_tokens``) - the same float.  Labels the device path does not take, or ids that are not on a GPU,
+        are scored on the host from the same ids."""
+        token_ids = _labelled_token_ids(self.model, self.config, self._grammar_kwargs(), inputs)
+        if _on_device_scorable(token_ids, inputs.notes_batch):
+            return evaluate_tokens(self.model.tokenizer, token_ids, inputs.notes_batch)
+        return float(_score_on_host(self.model.tokenizer, token_ids, inputs.notes_batch)[0])
 
     def generate(self, audio_path: Optional[Union[str, Path]] = None, audio_y: Optional[np.ndarray] = None,
                  sr: Optional[int] = None, cond_index: Optional[list] = None):
@@ -367,13 +395,17 @@ class Music2MIDI(nn.Module):
 
     def generate_notes(self, audio_path=None, audio_y=None, sr=None, cond_index=None) -> np.ndarray:
         """Note array [n, 4] (onset_s, offset_s, pitch, velocity) for a whole recording."""
+        padded, seg = self._padded_segments(audio_path, audio_y, sr)
+        return self.sample_tokens(padded, seg, split_duration=self.config.dataset.segment_duration, cond_index=cond_index)
+
+    def _padded_segments(self, audio_path, audio_y, sr):
+        """(the recording on the device, zero-padded to whole segments; samples per segment)"""
         samples = self._resolve_audio(audio_path, audio_y, sr)
         seg = self._segment_length()
         n_segments = -(-len(samples) // seg)                       # ceil
         padded = np.zeros(n_segments * seg, dtype=np.float32)
         padded[: len(samples)] = samples
-        return self.sample_tokens(torch.from_numpy(padded).to(self.device), seg,
-                                  split_duration=self.config.dataset.segment_duration, cond_index=cond_index)
+        return torch.from_numpy(padded).to(self.device), seg
 
     def _cond_rows(self, n_rows: int, cond_index: Optional[list]) -> torch.Tensor:
         """[n_rows, n_embeds] int64: the same (genre, difficulty) pair for every segment; zeros when None."""
@@ -390,6 +422,12 @@ class Music2MIDI(nn.Module):
                       cond_index: Optional[list] = None) -> np.ndarray:
         """Segments -> chunks of inference.batch_size -> generate(max_length=1024) -> notes.  With inference.num_beams > 1 a chunk is
         batch_size // num_beams clips, decoded by beam_search_processed: the rows of a call stay what the config sized the session for."""
+        token_rows = self.sample_token_rows(waveform, split_size, cond_index)
+        return self.model.tokenizer.decode(token_rows, mode="sequential", duration_per_batch=split_duration)
+
+    @torch.no_grad()
+    def sample_token_rows(self, waveform: torch.Tensor, split_size: int, cond_index: Optional[list] = None) -> list:
+        """The token row of every segment, in segment order, not detokenised (rows of different chunks may differ in width)."""
         pieces = torch.split(waveform, split_size)
         decode, decode_kwargs = _decode_entry(self.model, self.config, self._grammar_kwargs())
         per_call = max(1, int(self.config.inference.batch_size) // int(decode_kwargs.get("num_beams", 1)))
@@ -405,4 +443,22 @@ class Music2MIDI(nn.Module):
             ids = D.generate_sharded(decode, ModelInputs(input_waveform=wav, cond_index=self._cond_rows(len(group), cond_index)),
                                      max_length=1024, pad_id=self.model.geometry.pad_token_id, **decode_kwargs)
             token_rows.extend(ids.unbind(0))
-        return self.model.tokenizer.decode(token_rows, mode="sequential", duration_per_batch=split_duration)
+        return token_rows
+
+    def score_recording(self, label_notes: np.ndarray, audio_path=None, audio_y=None, sr=None, cond_index=None) -> float:
+        """Chroma accuracy of a whole recording against its label notes: ``generate_notes``' segmentation and chunked decode, then
+        the sequential detokenising and the scoring on the device.  Equals
+        ``evaluate_batch([numpy_to_midi(label_notes)], [self.generate(...)])``; labels the device path does not take, or ids that
+        are not on a GPU, are scored on the host from the same ids.  One GPU only."""
+        if D.dist.is_available() and D.dist.is_initialized() and D.dist.get_world_size() > 1:
+            raise NotImplementedError("score_recording runs on one GPU: with a process group, score generate()'s notes on the host")
+        padded, seg = self._padded_segments(audio_path, audio_y, sr)
+        rows = self.sample_token_rows(padded, seg, cond_index=cond_index)
+        duration = self.config.dataset.segment_duration
+        width = max(int(r.shape[0]) for r in rows)
+        pad = self.model.geometry.pad_token_id
+        token_ids = torch.stack([torch.nn.functional.pad(r, (0, width - int(r.shape[0])), value=pad) for r in rows])
+        if _on_device_scorable(token_ids, [label_notes]):
+            return evaluate_tokens(self.model.tokenizer, token_ids, label_notes, mode="sequential", duration_per_batch=duration)
+        decoded = self.model.tokenizer.decode(rows, mode="sequential", duration_per_batch=duration)
+        return float(evaluate_batch([numpy_to_midi(label_notes)], [numpy_to_midi(decoded)]))

@@ -117,6 +117,11 @@ _SIGNATURES = {
     "m2m_augment_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "m2m_pitch_shift_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.POINTER(AugmentStages), C.c_void_p]),
+    "m2m_score_frame_count": (C.c_int64, [C.c_double]),
+    "m2m_score_detokenize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "m2m_score_chroma_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "m2m_model_create": (C.c_int, [C.POINTER(T5GeometryC), C.POINTER(T5Weights), C.c_int, C.c_void_p,
                                    C.POINTER(C.c_void_p)]),
     "m2m_model_destroy": (None, [C.c_void_p]),

@@ -1,0 +1,234 @@
+"""Scoring of decoded tokens on the device: detokenise, melody, the counts of the chroma accuracy.
+
+Everything ``Music2MIDI.evaluate_batch`` does after ``generate`` - ``MidiTokenizer.decode``, ``numpy_to_midi``,
+``evaluation.evaluate_batch`` - is integer work on ids that are already in HBM.  Those host functions stay the definition; here the
+same pipeline runs as two HIP kernels (csrc/score.hip) on the current stream and returns what the host returns, exactly: the same
+notes, the same counts, the same float.
+
+    detokenize(tokenizer, token_ids [R, L] cuda int64, mode, duration_per_batch)   -> DeviceNotes   (.to_numpy() == tokenizer.decode(...))
+    chroma_counts(tokenizer, token_ids, notes_batch, mode, duration_per_batch)     -> ChromaCounts  (.correct .voiced .frames .score)
+    labels_eligible(notes_batch)                                                   -> bool
+
+``batched``: row i is clip i, scored against ``notes_batch[i]``; ``sequential``: the rows are the segments of one recording, scored
+against ONE label array.  ``cutoff_time`` is not supported.  There is no fallback in this module: a missing library or a refused
+call raises ``native.NativeError``, labels the device path cannot take raise ``ValueError`` (callers that want the host path
+instead ask ``labels_eligible`` first, as ``Music2MIDI.score_batch`` does).
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import native
+
+FS = 100                                 # frames per second of the metric (evaluation.extract_midi_melody's default, the only one)
+MAX_TOKENS = 2048
+MAX_FRAMES = 1 << 22                     # M2M_SCORE_MAX_FRAMES: 11.6 hours per timeline
+MAX_VOCAB = 4096
+
+
+def frame_count(end_seconds: float) -> int:
+    """``len(np.arange(0, end_seconds, 1 / 100))`` as the kernels compute it (host arithmetic of the library, no GPU)."""
+    return int(native.load().m2m_score_frame_count(float(end_seconds)))
+
+
+def _steps_per_row(tokenizer, mode: str, duration_per_batch) -> int:
+    if mode == "batched":
+        return 0
+    if mode == "sequential":
+        if duration_per_batch is None:
+            raise ValueError('duration_per_batch is required for mode="sequential"')
+        return int(round(duration_per_batch / tokenizer.time_step))
+    raise ValueError(f"Invalid argument mode={mode}")
+
+
+def _vocab_size(tokenizer, vocab_size: Optional[int]) -> int:
+    """The ids the model can emit: the argument, else the T5 vocabulary the tokenizer's config names, else the device limit."""
+    if vocab_size is None:
+        vocab_size = getattr(tokenizer, "model_vocab_size", None)
+    return MAX_VOCAB if vocab_size is None else int(vocab_size)
+
+
+class DeviceNotes:
+    """The notes of every row, on the device: ``notes`` [R, L, 3] int32 (onset index, offset index, pitch), the first
+    ``counts[r]`` of row r in emission order; ``counts`` [R] int32, -1 for a row that held an id outside the vocabulary."""
+
+    def __init__(self, notes: torch.Tensor, counts: torch.Tensor, mode: str, time_step: float, default_velocity, steps_per_row: int):
+        self.notes, self.counts, self.mode = notes, counts, mode
+        self.time_step, self.default_velocity, self.steps_per_row = time_step, default_velocity, steps_per_row
+
+    def to_numpy(self) -> Union[List[np.ndarray], np.ndarray]:
+        """What ``tokenizer.decode(token_ids, mode, duration_per_batch)`` returns: a list of [n, 4] float64 arrays, or their
+        concatenation in ``sequential`` mode."""
+        counts = self.counts.cpu().numpy()
+        _raise_for_bad_rows(counts)
+        notes = self.notes.cpu().numpy()
+        parts = []
+        for r, c in enumerate(counts):
+            out = np.zeros((int(c), 4), dtype=np.float64)
+            out[:, :3] = notes[r, :c]
+            out[:, 3] = self.default_velocity
+            out[:, :2] = out[:, :2] * self.time_step
+            parts.append(out)
+        return parts if self.mode == "batched" else np.concatenate(parts)
+
+
+def _raise_for_bad_rows(counts: np.ndarray) -> None:
+    bad = np.flatnonzero(counts < 0)
+    if len(bad):
+        raise ValueError(f"token row {int(bad[0])} holds an id outside [0, vocab_size): nothing was decoded for it")
+
+
+def detokenize(tokenizer, token_ids: torch.Tensor, mode: str = "batched", duration_per_batch: Optional[float] = None,
+               vocab_size: Optional[int] = None) -> DeviceNotes:
+    """``tokenizer.decode`` on the device, one workgroup per row; nothing is copied to the host until ``to_numpy()``."""
+    steps = _steps_per_row(tokenizer, mode, duration_per_batch)
+    velocity = tokenizer.config.default_velocity
+    if not velocity > 0:
+        raise ValueError(f"default_velocity = {velocity}: the decoder opens a note only with a positive velocity")
+    if not (isinstance(token_ids, torch.Tensor) and token_ids.is_cuda and token_ids.dim() == 2 and token_ids.dtype == torch.int64):
+        raise ValueError("detokenize: token_ids must be a CUDA int64 tensor [rows, length]")
+    R, L = token_ids.shape
+    device = token_ids.device
+    if R == 0:
+        if mode == "sequential":
+            raise ValueError("need at least one row to concatenate")
+        return DeviceNotes(torch.zeros((0, 1, 3), dtype=torch.int32, device=device), torch.zeros(0, dtype=torch.int32, device=device),
+                           mode, tokenizer.time_step, velocity, steps)
+    if L == 0:                                               # PAD is skipped: one column of it decodes as the empty row does
+        token_ids, L = token_ids.new_zeros((R, 1)), 1
+    if token_ids.stride(1) != 1:
+        token_ids = token_ids.contiguous()
+    with torch.cuda.device(device):
+        # (sizes the library will refuse are not allocated for: it answers on the arguments alone)
+        fits = R <= 65535 and L <= MAX_TOKENS
+        notes = torch.empty((R, L, 3) if fits else (1, 1, 3), dtype=torch.int32, device=device)
+        counts = torch.empty(R if fits else 1, dtype=torch.int32, device=device)
+        native.check(native.load().m2m_score_detokenize(
+            token_ids.data_ptr(), R, L, token_ids.stride(0), steps, int(tokenizer.pitch_token_offset), int(tokenizer.time_token_offset),
+            _vocab_size(tokenizer, vocab_size), notes.data_ptr(), counts.data_ptr(), native.stream_handle(device)), "m2m_score_detokenize")
+    return DeviceNotes(notes, counts, mode, tokenizer.time_step, velocity, steps)
+
+
+# ----------------------------------------------------------------------------------------------------------------- labels
+class _Ineligible(ValueError):
+    pass
+
+
+def _kept_labels(label_arrays: Sequence) -> tuple:
+    """(the notes ``numpy_to_midi`` keeps (``end > start``) of every array as one [n, 4] float64 array, their count per array);
+    ``_Ineligible`` when the device path cannot score against them.  The rule, for the kept notes: every value finite,
+    ``start >= 0``, ``0 <= int(pitch) <= 127``, ``int(velocity) >= 1`` - a velocity in (0, 1) is truncated to 0 by ``numpy_to_midi``
+    and sounds in no frame on the host, so it is left to the host - and an end within the frame cap.  All arrays are checked in
+    one pass (a batch is a hundred small arrays)."""
+    arrays = []
+    for i, notes in enumerate(label_arrays):
+        try:
+            a = np.asarray(notes, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise _Ineligible(f"timeline {i}: not a numeric array") from None
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise _Ineligible(f"timeline {i}: shape {a.shape} is not [n, 4]")
+        arrays.append(a)
+    flat = np.concatenate(arrays) if arrays else np.zeros((0, 4))
+    owner = np.repeat(np.arange(len(arrays)), [len(a) for a in arrays])
+    with np.errstate(invalid="ignore"):
+        keep = flat[:, 1] > flat[:, 0]
+    flat, owner = flat[keep], owner[keep]
+    pitch = np.trunc(flat[:, 2])
+    for why, wrong in (("a value that is not finite", ~np.isfinite(flat).all(axis=1)), ("a negative start", flat[:, 0] < 0),
+                       ("a pitch outside 0..127", (pitch < 0) | (pitch > 127)), ("a velocity below 1", flat[:, 3] < 1)):
+        if wrong.any():
+            raise _Ineligible(f"timeline {int(owner[np.argmax(wrong)])}: {why}")
+    if len(flat) and frame_count(float(flat[:, 1].max())) > MAX_FRAMES:
+        raise _Ineligible(f"timeline {int(owner[np.argmax(flat[:, 1])])}: an end beyond {MAX_FRAMES} frames")
+    return flat, np.bincount(owner, minlength=len(arrays))
+
+
+def labels_eligible(notes_batch: Sequence) -> bool:
+    """True when ``chroma_counts`` can take every label array of the batch."""
+    try:
+        _kept_labels(notes_batch)
+    except _Ineligible:
+        return False
+    return True
+
+
+def _pack_labels(label_arrays: Sequence) -> tuple:
+    """([3, N] float64 starts / ends / int(pitch) of the notes with end > start, [T + 1] int32 offsets, frames bound)."""
+    try:
+        flat, per_array = _kept_labels(label_arrays)
+    except _Ineligible as e:
+        raise ValueError(f"chroma_counts: the labels are not eligible for the device path: {e}") from None
+    packed = np.ascontiguousarray(flat[:, :3].T)
+    packed[2] = np.trunc(packed[2])
+    offsets = np.concatenate([[0], np.cumsum(per_array)]).astype(np.int32)
+    bound = frame_count(float(packed[1].max())) if packed.shape[1] else 0
+    return packed, offsets, bound
+
+
+class ChromaCounts:
+    """int64 ``correct``, ``voiced``, ``frames`` per timeline; ``score`` = sum(correct) / sum(voiced) in float64 (0.0 without a
+    voiced frame), the value of ``evaluation.evaluate_batch``; ``scores`` the same ratio per timeline."""
+
+    def __init__(self, correct: np.ndarray, voiced: np.ndarray, frames: np.ndarray):
+        self.correct, self.voiced, self.frames = correct, voiced, frames
+
+    @property
+    def score(self) -> float:
+        voiced = self.voiced.sum()
+        return float(self.correct.sum() / voiced) if voiced else 0.0
+
+    @property
+    def scores(self) -> np.ndarray:
+        out = np.zeros(len(self.voiced), dtype=np.float64)
+        np.divide(self.correct, self.voiced, out=out, where=self.voiced > 0)
+        return out
+
+
+def _enqueue_counts(dn: DeviceNotes, labels_dev: torch.Tensor, offsets_dev: torch.Tensor, frame_cap: int) -> torch.Tensor:
+    """The counts kernel on the current stream, for labels that are on the device already: [T, 3] int32 (correct, voiced, frames)."""
+    R, L = int(dn.notes.shape[0]), int(dn.notes.shape[1])
+    T, n_labels = int(offsets_dev.shape[0]) - 1, int(labels_dev.shape[1])
+    device = dn.notes.device
+    out = torch.empty((T, 3), dtype=torch.int32, device=device)
+    native.check(native.load().m2m_score_chroma_counts(
+        dn.notes.data_ptr(), dn.counts.data_ptr(), R, L, 1 if dn.mode == "sequential" else 0, float(dn.time_step),
+        labels_dev.data_ptr() if n_labels else None, offsets_dev.data_ptr(), n_labels, T, int(frame_cap), out.data_ptr(),
+        native.stream_handle(device)), "m2m_score_chroma_counts")
+    return out
+
+
+def chroma_counts(tokenizer, token_ids: torch.Tensor, notes_batch, mode: str = "batched", duration_per_batch: Optional[float] = None,
+                  vocab_size: Optional[int] = None) -> ChromaCounts:
+    """The counts of ``evaluation.evaluate_batch(labels, decoded)`` for ids on the device.  ``notes_batch``: one label array per
+    row (``batched``), or ONE array for the whole recording (``sequential``).  One small copy to the host at the end."""
+    labels = [notes_batch] if mode == "sequential" else list(notes_batch)
+    dn = detokenize(tokenizer, token_ids, mode, duration_per_batch, vocab_size)
+    R = int(dn.counts.shape[0])
+    T = 1 if mode == "sequential" else R
+    if len(labels) != T:
+        raise ValueError(f"chroma_counts: {len(labels)} label arrays for {T} timelines")
+    packed, offsets, label_frames = _pack_labels(labels)
+    if R == 0:
+        empty = np.zeros(0, dtype=np.int64)
+        return ChromaCounts(empty, empty.copy(), empty.copy())
+    # the largest time index a row can hold bounds the output's frames: the grid is sized for it and for the labels
+    vocab = _vocab_size(tokenizer, vocab_size)
+    top_index = (R - 1) * dn.steps_per_row + max(0, vocab - 1 - int(tokenizer.time_token_offset))
+    frame_cap = max(1, label_frames, frame_count(top_index * tokenizer.time_step))
+    if frame_cap > MAX_FRAMES:
+        raise ValueError(f"chroma_counts: a timeline of up to {frame_cap} frames exceeds the device limit of {MAX_FRAMES}")
+    device = dn.notes.device
+    with torch.cuda.device(device):
+        lab = torch.from_numpy(packed).to(device)
+        off = torch.from_numpy(offsets).to(device)
+        out = _enqueue_counts(dn, lab, off, frame_cap)
+        host = torch.cat([out.reshape(-1), dn.counts]).cpu().numpy()
+    _raise_for_bad_rows(host[3 * T:])
+    res = host[:3 * T].reshape(T, 3).astype(np.int64)
+    if (res[:, 2] < 0).any():
+        raise native.NativeError(f"m2m_score_chroma_counts: a timeline is longer than its bound of {frame_cap} frames")
+    return ChromaCounts(res[:, 0].copy(), res[:, 1].copy(), res[:, 2].copy())

@@ -29,6 +29,12 @@ class MidiTokenizer:
         self.time_step = self.config.midi_quantize_ms / 1000
         self.pitch_token_offset = self.config.vocab_size.special
         self.time_token_offset = self.pitch_token_offset + self.config.vocab_size.pitch
+        # the ids the model can emit (the T5 vocabulary: it may leave ids unused past the time ids, which decode as times);
+        # None when the config names no model.  Read by music2midi_amd.scoring only.
+        try:
+            self.model_vocab_size = int(config.model.t5.vocab_size)
+        except (AttributeError, KeyError, TypeError):
+            self.model_vocab_size = None
 
     @property
     def grammar(self):
