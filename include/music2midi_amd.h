@@ -224,6 +224,55 @@ int m2m_score_chroma_counts(const int32_t* notes_dev, const int32_t* counts_dev,
                             int32_t* out_dev, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Audio ingest: the sample bytes of a WAVE file -> mono fp32 -> another sample rate, zero-padded; replaces, for the files it
+ * takes, the host step of ref: music2midi/model.py:83-84 (librosa.load).  The definitions are music2midi_amd/audio.py (read_wav,
+ * load_audio's y.mean(axis=1), resample = scipy.signal.resample_poly); the results are EQUAL to theirs for finite samples.
+ * No handle, no workspace, no environment switch; both calls enqueue on `stream` and return nothing to the host.  Every
+ * M2M_ERR_INVALID below is answered on the arguments alone, before the first HIP call.
+ * ------------------------------------------------------------------------- */
+#define M2M_INGEST_MAX_FRAMES (1 << 28)    /* frames / samples of one call's input */
+#define M2M_INGEST_MAX_CHANNELS 7          /* from 8 channels up numpy's mean sums pairwise: those files stay on the host */
+#define M2M_INGEST_MAX_RATIO 1000          /* up, down <= 1000: Fraction.limit_denominator(1000) */
+#define M2M_INGEST_MAX_OUT (1 << 30)       /* samples of one call's output buffer */
+
+enum {                                     /* sample formats: read_wav's */
+  M2M_PCM_U8 = 0,                          /* (u8 - 128) / 128 */
+  M2M_PCM_S16 = 1,                         /* i16 / 32768 */
+  M2M_PCM_S24 = 2,                         /* sign-extended 24 bits / 8388608 */
+  M2M_PCM_S32 = 3,                         /* (float)((double)i32 / 2147483648) */
+  M2M_PCM_F32 = 4,
+  M2M_PCM_F64 = 5                          /* (float)f64 */
+};
+
+/* ceil(n_in * up / down), the length of resample_poly's output; M2M_ERR_INVALID for n_in outside 0..2^28 or up / down outside
+ * 1..1000.  Host arithmetic, exported so that the formula can be tested without a GPU. */
+int64_t m2m_ingest_resampled_length(int64_t n_in, int up, int down);
+/* J = 20 max(up, down) / up + 1: taps per phase of the phase-major filter below.  Host arithmetic. */
+int m2m_ingest_phase_taps(int up, int down);
+
+/*
+ * out_dev[f] = mean over the channels of frame f, fp32 [n_frames]: the samples converted as above, summed in channel order in
+ * fp32 from +0 and divided by the fp32 channel count - np.mean(axis=1) of read_wav's array for 1..7 channels.
+ * bytes_dev: n_frames * channels interleaved little-endian samples; ANY address (a `data` chunk starts at any even offset, 24-bit
+ * samples are never aligned): an address that is no multiple of the sample width is read byte by byte.
+ * M2M_ERR_INVALID: n_frames outside 1..2^28, channels outside 1..7, an unknown format, a null pointer, out_dev overlapping the input.
+ */
+int m2m_ingest_pcm(const void* bytes_dev, int64_t n_frames, int channels, int format, float* out_dev, void* stream);
+
+/*
+ * out_dev[n] = sum_m x_dev[m] h[n down - m up + half] for n < n_out = ceil(n_in up / down), x zero outside [0, n_in), and 0 for
+ * n_out <= n < capacity: scipy.signal.resample_poly(x, up, down) for fp32 x, zero-padded to `capacity` samples.  One fp32
+ * accumulator per output, taps in ascending m, a rounded multiply then a rounded add (no FMA): upfirdn's order.
+ * h = up * firwin(2 half + 1, 1 / max(up, down), window=("kaiser", 5.0)) in fp32 is designed by the caller (the library designs
+ * no filter) and handed over phase-major: h_phase_dev [up][J] fp32, J = m2m_ingest_phase_taps(up, down),
+ * h_phase_dev[p][J - 1 - j] = h[p + j up], 0 where p + j up > 2 half.  up == down copies (bit-equal); h_phase_dev may be NULL then.
+ * M2M_ERR_INVALID: n_in outside 1..2^28, up / down outside 1..1000 or not in lowest terms (unless equal), half other than
+ * 10 max(up, down), capacity below n_out or above 2^30, a null pointer, out_dev [capacity] overlapping x_dev [n_in].
+ */
+int m2m_ingest_resample_f32(const float* x_dev, int64_t n_in, int up, int down, const float* h_phase_dev, int half, float* out_dev,
+                            int64_t capacity, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * T5 encoder-decoder weights, replaces what ref: music2midi/transformer.py:14-16
  * builds (T5Config + T5ForConditionalGeneration) once a state dict is loaded.
  * ------------------------------------------------------------------------- */

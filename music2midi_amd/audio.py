@@ -15,13 +15,15 @@
 
 Host-side numpy: this is the step BEFORE the hot path; the reference runs it in
 DataLoader workers on the CPU as well.
+``read_wav`` + ``mean(axis=1)`` + ``resample`` have a device form that gives the same samples
+(``ingest.py``, opt-in through ``inference.device_ingest``); these functions stay its definition.
 """
 from __future__ import annotations
 
 import struct
 from math import gcd
 from pathlib import Path
-from typing import Tuple
+from typing import NamedTuple, Tuple
 
 import numpy as np
 
@@ -30,19 +32,29 @@ _WAVE_FORMAT_IEEE_FLOAT = 3
 _WAVE_FORMAT_EXTENSIBLE = 0xFFFE
 
 
-def read_wav(path) -> Tuple[np.ndarray, int]:
-    """RIFF/WAVE -> (float32 [n_frames, n_channels] in [-1, 1), sample rate)."""
-    raw = Path(path).read_bytes()
+class WavLayout(NamedTuple):
+    """What the RIFF header says: the format tag (the sub-format of ``WAVE_FORMAT_EXTENSIBLE``), channels, sample rate, bits per
+    sample, and where the body of the ``data`` chunk lies in the file (clipped to the file's length)."""
+    tag: int
+    n_ch: int
+    rate: int
+    bits: int
+    data_offset: int
+    data_size: int
+
+
+def wav_layout(path, raw) -> WavLayout:
+    """Walk the chunks of ``raw`` (the file's bytes, or a read-only mmap of it: only the headers and ``fmt `` are touched).
+    ``read_wav`` and the device ingest (``ingest.py``) share this; ``path`` only names the file in the errors."""
     if len(raw) < 12 or raw[:4] != b"RIFF" or raw[8:12] != b"WAVE":
         raise ValueError(f"{path}: not a RIFF/WAVE file (compressed formats need librosa/ffmpeg, which are not installed)")
     pos, fmt, data = 12, None, None
     while pos + 8 <= len(raw):
-        cid, size = raw[pos:pos + 4], struct.unpack("<I", raw[pos + 4:pos + 8])[0]
-        body = raw[pos + 8:pos + 8 + size]
+        cid, size = bytes(raw[pos:pos + 4]), struct.unpack("<I", raw[pos + 4:pos + 8])[0]
         if cid == b"fmt ":
-            fmt = body
+            fmt = bytes(raw[pos + 8:pos + 8 + size])
         elif cid == b"data":
-            data = body
+            data = (pos + 8, max(0, min(size, len(raw) - (pos + 8))))
         pos += 8 + size + (size & 1)              # chunks are word aligned
     if fmt is None or data is None or len(fmt) < 16:
         raise ValueError(f"{path}: missing 'fmt ' or 'data' chunk")
@@ -51,32 +63,47 @@ def read_wav(path) -> Tuple[np.ndarray, int]:
         tag = struct.unpack("<H", fmt[24:26])[0]  # first two bytes of the sub-format GUID
     if n_ch < 1 or rate < 1:
         raise ValueError(f"{path}: bad channel count / sample rate")
+    return WavLayout(tag, n_ch, int(rate), bits, data[0], data[1])
+
+
+def wav_sample_format(path, tag: int, bits: int) -> str:
+    """One of ``u8 s16 s24 s32 f32 f64`` - the conversions ``read_wav`` knows - or the ``ValueError`` it raises for the rest."""
     width = bits // 8
-    n = len(data) // (width * n_ch) * n_ch
     if tag == _WAVE_FORMAT_PCM:
-        if width == 1:
-            y = (np.frombuffer(data, np.uint8, n).astype(np.float32) - 128.0) / 128.0
-        elif width == 2:
-            y = np.frombuffer(data, "<i2", n).astype(np.float32) / 32768.0
-        elif width == 3:
-            b = np.frombuffer(data, np.uint8, n * 3).reshape(-1, 3).astype(np.int32)
-            v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
-            v = np.where(v & 0x800000, v - 0x1000000, v)
-            y = v.astype(np.float32) / 8388608.0
-        elif width == 4:
-            y = (np.frombuffer(data, "<i4", n).astype(np.float64) / 2147483648.0).astype(np.float32)
-        else:
-            raise ValueError(f"{path}: unsupported PCM sample width {bits} bits")
-    elif tag == _WAVE_FORMAT_IEEE_FLOAT:
-        if width == 4:
-            y = np.frombuffer(data, "<f4", n).astype(np.float32)
-        elif width == 8:
-            y = np.frombuffer(data, "<f8", n).astype(np.float32)
-        else:
-            raise ValueError(f"{path}: unsupported float sample width {bits} bits")
+        if width in (1, 2, 3, 4):
+            return ("u8", "s16", "s24", "s32")[width - 1]
+        raise ValueError(f"{path}: unsupported PCM sample width {bits} bits")
+    if tag == _WAVE_FORMAT_IEEE_FLOAT:
+        if width in (4, 8):
+            return "f32" if width == 4 else "f64"
+        raise ValueError(f"{path}: unsupported float sample width {bits} bits")
+    raise ValueError(f"{path}: unsupported WAVE format tag {tag} (only PCM and IEEE float)")
+
+
+def read_wav(path) -> Tuple[np.ndarray, int]:
+    """RIFF/WAVE -> (float32 [n_frames, n_channels] in [-1, 1), sample rate)."""
+    raw = Path(path).read_bytes()
+    lay = wav_layout(path, raw)
+    data = raw[lay.data_offset:lay.data_offset + lay.data_size]
+    n_ch, width = lay.n_ch, lay.bits // 8
+    n = len(data) // (width * n_ch) * n_ch
+    kind = wav_sample_format(path, lay.tag, lay.bits)
+    if kind == "u8":
+        y = (np.frombuffer(data, np.uint8, n).astype(np.float32) - 128.0) / 128.0
+    elif kind == "s16":
+        y = np.frombuffer(data, "<i2", n).astype(np.float32) / 32768.0
+    elif kind == "s24":
+        b = np.frombuffer(data, np.uint8, n * 3).reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        v = np.where(v & 0x800000, v - 0x1000000, v)
+        y = v.astype(np.float32) / 8388608.0
+    elif kind == "s32":
+        y = (np.frombuffer(data, "<i4", n).astype(np.float64) / 2147483648.0).astype(np.float32)
+    elif kind == "f32":
+        y = np.frombuffer(data, "<f4", n).astype(np.float32)
     else:
-        raise ValueError(f"{path}: unsupported WAVE format tag {tag} (only PCM and IEEE float)")
-    return y.reshape(-1, n_ch), int(rate)
+        y = np.frombuffer(data, "<f8", n).astype(np.float32)
+    return y.reshape(-1, n_ch), int(lay.rate)
 
 
 def resample(y: np.ndarray, orig_sr: float, target_sr: float) -> np.ndarray:

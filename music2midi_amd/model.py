@@ -398,10 +398,30 @@ class Music2MIDI(nn.Module):
         padded, seg = self._padded_segments(audio_path, audio_y, sr)
         return self.sample_tokens(padded, seg, split_duration=self.config.dataset.segment_duration, cond_index=cond_index)
 
+    def _device_ingest(self, audio_path, audio_y) -> bool:
+        """The device ingest takes the call when ``config.inference.device_ingest`` is set (absent: off), the audio comes as a
+        path, the model is on a GPU and ``ingest.eligible`` accepts the file; everything else is the host's ``load_audio``."""
+        if audio_path is None or audio_y is not None or not bool(self.config.inference.get("device_ingest", False)):
+            return False
+        if self.device.type != "cuda":
+            return False
+        from . import ingest
+        return ingest.eligible(audio_path, self.config.model.sample_rate)
+
     def _padded_segments(self, audio_path, audio_y, sr):
-        """(the recording on the device, zero-padded to whole segments; samples per segment)"""
-        samples = self._resolve_audio(audio_path, audio_y, sr)
+        """(the recording on the device, zero-padded to whole segments; samples per segment).  With
+        ``config.inference.device_ingest: true`` an eligible WAVE file given as ``audio_path`` is decoded, downmixed, resampled and
+        padded on the device (``ingest.load_audio_device``): the samples ``audio.read_wav`` + scipy's ``resample_poly`` give, bit for
+        bit.  The key wins over an installed librosa - the device path restates the scipy definition, not librosa's soxr resampler,
+        so with librosa present the two paths differ.  Files the device path does not take (compressed containers, 8 or more
+        channels, unknown sample formats) go through the host as without the key."""
         seg = self._segment_length()
+        if self._device_ingest(audio_path, audio_y):
+            from . import ingest
+            if sr is not None:
+                assert sr == self.config.model.sample_rate
+            return ingest.load_audio_device(audio_path, self.config.model.sample_rate, device=self.device, pad_to=seg), seg
+        samples = self._resolve_audio(audio_path, audio_y, sr)
         n_segments = -(-len(samples) // seg)                       # ceil
         padded = np.zeros(n_segments * seg, dtype=np.float32)
         padded[: len(samples)] = samples

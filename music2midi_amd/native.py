@@ -122,6 +122,11 @@ _SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     "m2m_score_chroma_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "m2m_ingest_resampled_length": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "m2m_ingest_phase_taps": (C.c_int, [C.c_int, C.c_int]),
+    "m2m_ingest_pcm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "m2m_ingest_resample_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                          C.c_void_p]),
     "m2m_model_create": (C.c_int, [C.POINTER(T5GeometryC), C.POINTER(T5Weights), C.c_int, C.c_void_p,
                                    C.POINTER(C.c_void_p)]),
     "m2m_model_destroy": (None, [C.c_void_p]),
