@@ -16,11 +16,10 @@ enum { TG_STORE_T = 0, TG_STORE_F32 = 1, TG_ACC_F32 = 2, TG_RESID_F32 = 3 };
 // read of its switch — and that happens at two places: m2m_trainer holds one (sw), so a trainer latches them when it is created,
 // keeps the kernel forms it started with (its graphs bake them in) and no pass or launch reads the environment; and the entry
 // points without a trainer (the single-product test hooks) share process_train_switches().  The launchers below take the struct
-// from their caller.  The one switch of the training path that is NOT here is M2M_TRAIN_ATTN: read per pass (train.hip, Ops::head_on).
+// from their caller.
 struct TrainSwitches {
   struct Fp8Parts { bool fwd = true, dx = true, dw = false; };
   static Fp8Parts fp8_parts(const char* p) { return p ? Fp8Parts{strstr(p, "fwd") != nullptr, strstr(p, "dx") != nullptr, strstr(p, "dw") != nullptr} : Fp8Parts{}; }
-  static int fuse_mode(const char* v) { return !v ? 3 : v[0] == '0' ? 0 : v[0] == 'f' ? 1 : v[0] == 'b' ? 2 : 3; }
   static bool is(const char* v, const char* word) { return v && strcmp(v, word) == 0; }
   static bool starts(const char* v, char c) { return v && v[0] == c; }
   bool side = env_on("M2M_TRAIN_SIDE");                  // 0: everything on the caller's stream
@@ -40,10 +39,7 @@ struct TrainSwitches {
   int dw_wgs = env_int("M2M_DW_WGS", 512);               // workgroups launch_dw_gemm aims for
   bool gate_epi = env_on("M2M_TRAIN_GATE_EPI");          // 0: gated_fwd / gated_bwd kernel launches
   bool stripes = env_on("M2M_TRAIN_STRIPES");            // 0: no fused scores + softmax
-  int fuse_pv = fuse_mode(env_str("M2M_TRAIN_FUSE_PV")); // 0 = off, 1 / 2 = only the forward ("fwd") / backward ("bwd") pass (diagnostics), 3 = both
-  bool pair_dvdk = env_on("M2M_TRAIN_PAIR_DVDK");        // 0: dV and dK in launches of their own
-  bool fwd_pd = starts(env_str("M2M_TRAIN_FWD_PD"), '1');  // 1: always write the dropped copy of P (measurement)
-  bool fuse_pd = env_on("M2M_TRAIN_FUSE_PD");            // 0: the dropped P through redrop
+  bool attn_head = !starts(env_str("M2M_TRAIN_ATTN"), 's');   // stripes: bf16 / fp8 attention on the stripe kernels, not the whole-head ones
   bool st_slim = env_on("M2M_ST_SLIM");                  // 0: never five stripe workgroups per CU
   bool xcd_order = env_on("M2M_XCD_ORDER");              // 0: plain grids for bgemm, the stripe kernels and the MXFP8 products
   int ah_waves = env_int("M2M_AH_WAVES", 0);             // 1..4: waves per whole-head attention workgroup (0: by size)

@@ -814,8 +814,8 @@ __global__ __launch_bounds__(256) void kv_transpose_kernel(const T* __restrict__
 // accumulators: T^T = X . Y^T with the KEYS as tile rows (X = K or V, [Sk, 64]) and the QUERIES as tile columns
 // (Y = Q or dO), so a lane owns ONE query (column l & 31) and its row reductions are in-lane plus one exchange with lane ^ 32
 // (the orientation of the inference flash kernel).  Forward: + T5 bias (per-head row of the (key - query) table, staged in
-// LDS), causal mask, softmax, P (and its dropped copy) written in T.  Backward: dP = V . dO^T, dS = P o (dP~ - sum P o dP~)
-// with dP~ the dropout-masked dP.  Replaces a batched GEMM that wrote the fp32 image + a row kernel that read it back
+// LDS), causal mask, softmax, P written in T (its dropped copy stays in LDS, the operand of the fused P~ . V).
+// Backward: dP = V . dO^T, dS = P o (dP~ - sum P o dP~) with dP~ the dropout-masked dP.  Replaces a batched GEMM that wrote the fp32 image + a row kernel that read it back
 // (35 MB each way per call at 16 clips): 15.6 + 25.7 us -> one launch (forward), 15.6 + 18 us -> one launch (backward).
 #ifdef M2M_ST_STAMP      // diagnostic builds only: phase times of one workgroup of the stripe kernel (100 MHz s_memrealtime)
 __device__ unsigned long long g_st_stamp[4][12];
@@ -829,12 +829,12 @@ struct StripeArgs {
   const void *X, *Y;                 // (key, d) at X + b*sX1 + h*sX2 + key*ldx + d;  (query, d) at Y + b*sY1 + h*sY2 + q*ldy + d
   int64_t ldx, sX1, sX2, ldy, sY1, sY2;
   void* P;                           // [nB*H][Sq][ldp] T: forward out / backward in
-  void* Pd;                          // forward: dropped copy of P, or null
+  void* Pd;                          // backward with dropout: the dropped P again, out (the dV product's operand)
   void* dS;                          // backward out
   float* diag_part;                  // backward, self-attention with bias: [nB*H][stripes][Sk + 31] diagonal sums of dS per stripe, or null
-  // optional fused product with the rows this workgroup has just formed: forward O = P~ . V, backward dQ = dS . K.  Xt is the
+  // the fused product with the rows this workgroup has just formed: forward O = P~ . V, backward dQ = dS . K.  Xt is the
   // second operand TRANSPOSED ([nB*H][64][xt_ld], zero beyond Sk: kv_transpose_kernel), (query, d) of the result at
-  // O + b*sO1 + h*sO2 + q*ldo + d; null: the product is a launch of its own
+  // O + b*sO1 + h*sO2 + q*ldo + d
   const void* Xt;
   int64_t xt_ld;
   void* O;
@@ -848,6 +848,8 @@ struct StripeArgs {
   int n_stripes, xcd_total;          // set by launch_attn_stripe: stripes per (clip, head); > 0: 1-D launch in XCD-contiguous order
 };
 constexpr int ST_NT = 16;            // key tiles per stripe: Sk <= 512 (the X operand of a (clip, head) is staged in LDS)
+// the LDS of a workgroup at the largest stripe: the 32-row block of P / dS in fp32 (32 x 516 x 4 B) + the longest bias row + 1 KB static
+static_assert((size_t)32 * (ST_NT * 32 + 4) * 4 + (2 * ST_NT * 32 + 31) * 4 + 16 + 1024 < 158 * 1024, "a stripe's rows and bias row must fit the LDS");
 // softmax exponential: accurate in the fp32 (parity) mode; multiply + v_exp_f32 where the result is rounded to bf16
 template <typename T> __device__ inline float m2m_exp_t(float x) {
   if constexpr (sizeof(T) == 2) return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
@@ -889,7 +891,6 @@ __global__ __launch_bounds__(256, SLIM ? 5 : 4) void attn_stripe_kernel(StripeAr
   // rows in 16-byte chunks instead of 8-byte pieces of 32 different rows per store (forward 18.7 -> us, backward 25.3 -> us)
   const int LP = nt * 32 + 16 / (int)sizeof(T);                                   // row pitch, elements
   T* pl = reinterpret_cast<T*>(st_smem + (has_bias ? ((size_t)(a.tab_stride + 32) * 4 + 15) / 16 * 16 : 0));
-  T* pl2 = pl + 32 * LP;                                                          // forward with dropout: the dropped copy
   const int q = q0 + r, qc = min(q, a.Sq - 1);
   const T* X = reinterpret_cast<const T*>(a.X) + b * a.sX1 + hh * a.sX2;
   const T* Y = reinterpret_cast<const T*>(a.Y) + b * a.sY1 + hh * a.sY2;
@@ -940,6 +941,8 @@ __global__ __launch_bounds__(256, SLIM ? 5 : 4) void attn_stripe_kernel(StripeAr
       // The dropped probabilities again (the dV product's operand; a scratch buffer in the forward pass) — what drop_copy_kernel
       // produced in a launch of its own, 18 launches / 0.28 ms of a step: masked straight from the staged P rows into memory, chunk by
       // chunk, before the passes overwrite them.  No second row block, so the five-per-CU variant stays available with dropout on.
+      // (a.Pd is set exactly when DROP, so the test below never decides; it stays because without it this compiler allots the bf16
+      //  instantiations more registers: 20 -> 44 bytes of scratch at four workgroups per CU, 71 -> 73 VGPRs in the SLIM form)
       if (a.Pd) {
         T* dst2 = reinterpret_cast<T*>(a.Pd) + blk;
         for (int c = threadIdx.x; c < 32 * cpr; c += 256) {
@@ -978,7 +981,7 @@ __global__ __launch_bounds__(256, SLIM ? 5 : 4) void attn_stripe_kernel(StripeAr
   };
   // fused product rows . Xt^T (see StripeArgs): waves 0 and 1 take the two 32-wide halves of d, 8 k-steps' fragments in flight at a time
   auto rows_times_xt = [&](const T* rows) {
-    if (!a.Xt || wave >= 2) return;
+    if (wave >= 2) return;
     const T* xt = reinterpret_cast<const T*>(a.Xt) + ((int64_t)bh * DK + wave * 32 + r) * a.xt_ld + 8 * h2;
     f32x16 acc = zero_acc();
     const int nks = nt * 2;                           // k-steps of 16 keys
@@ -1049,10 +1052,7 @@ __global__ __launch_bounds__(256, SLIM ? 5 : 4) void attn_stripe_kernel(StripeAr
       if (kt >= nt) break;                             // wave-uniform
       if (a.causal && kt * 32 > q0 + 31) {             // fully masked tile: zeros, no product, no exponentials
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          st_store4<T>(pl + r * LP + kt * 32 + 8 * g + 4 * h2, 0.f, 0.f, 0.f, 0.f);
-          if constexpr (DROP) st_store4<T>(pl2 + r * LP + kt * 32 + 8 * g + 4 * h2, 0.f, 0.f, 0.f, 0.f);
-        }
+        for (int g = 0; g < 4; ++g) st_store4<T>(pl + r * LP + kt * 32 + 8 * g + 4 * h2, 0.f, 0.f, 0.f, 0.f);
         continue;
       }
       const f32x16 acc = tile(j);
@@ -1069,15 +1069,6 @@ __global__ __launch_bounds__(256, SLIM ? 5 : 4) void attn_stripe_kernel(StripeAr
           pv[e] = to_f32(from_f32<T>(m2m_exp_t<T>(v - m) * inv));
         }
         st_store4<T>(pl + r * LP + k0, pv[0], pv[1], pv[2], pv[3]);          // keys >= kend are zeros
-        if constexpr (DROP) {
-          if (a.Pd) {                                   // the dropped copy is wanted in memory: a second row block
-            float dv[4];
-            const uint32_t kb = drop_keep4(key, prow + k0, a.thresh);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) dv[e] = ((kb >> e) & 1u) ? pv[e] * a.scale : 0.f;
-            st_store4<T>(pl2 + r * LP + k0, dv[0], dv[1], dv[2], dv[3]);
-          }
-        }
       }
     }
     ST_STAMP(5);
@@ -1085,43 +1076,37 @@ __global__ __launch_bounds__(256, SLIM ? 5 : 4) void attn_stripe_kernel(StripeAr
     ST_STAMP(6);
     {
       T* dst = reinterpret_cast<T*>(a.P) + blk;
-      T* dst2 = (DROP && a.Pd) ? reinterpret_cast<T*>(a.Pd) + blk : nullptr;
       for (int c = threadIdx.x; c < 32 * cpr; c += 256) {
         const int row = c / cpr, col = (c - row * cpr) * EC;
-        if (q0 + row < a.Sq) {
-          *reinterpret_cast<uint4*>(dst + (int64_t)row * a.ldp + col) = *reinterpret_cast<const uint4*>(pl + row * LP + col);
-          if (DROP && dst2) *reinterpret_cast<uint4*>(dst2 + (int64_t)row * a.ldp + col) = *reinterpret_cast<const uint4*>(pl2 + row * LP + col);
-        }
+        if (q0 + row < a.Sq) *reinterpret_cast<uint4*>(dst + (int64_t)row * a.ldp + col) = *reinterpret_cast<const uint4*>(pl + row * LP + col);
       }
     }
     if constexpr (DROP) {
       // The dropped probabilities are only the operand of the fused product (the backward pass re-forms them): no second row block —
       // half the LDS, four (or five) workgroups per CU instead of three — the rows are masked IN PLACE once they have been copied out,
       // every lane rewriting the elements it wrote
-      if (!a.Pd && a.Xt) {
-        __syncthreads();
+      __syncthreads();
 #pragma unroll
-        for (int j = 0; j < TPW; ++j) {
-          const int kt = wave + 4 * j;
-          if (kt >= nt) break;                             // wave-uniform
-          if (a.causal && kt * 32 > q0 + 31) continue;     // zeros stay zeros
+      for (int j = 0; j < TPW; ++j) {
+        const int kt = wave + 4 * j;
+        if (kt >= nt) break;                             // wave-uniform
+        if (a.causal && kt * 32 > q0 + 31) continue;     // zeros stay zeros
 #pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int k0 = kt * 32 + 8 * g + 4 * h2;
-            const float4 pv = st_load4<T>(pl + r * LP + k0);
-            const float pe[4] = {pv.x, pv.y, pv.z, pv.w};
-            const uint32_t kb4 = drop_keep4(key, prow + k0, a.thresh);
-            float dv[4];
+        for (int g = 0; g < 4; ++g) {
+          const int k0 = kt * 32 + 8 * g + 4 * h2;
+          const float4 pv = st_load4<T>(pl + r * LP + k0);
+          const float pe[4] = {pv.x, pv.y, pv.z, pv.w};
+          const uint32_t kb4 = drop_keep4(key, prow + k0, a.thresh);
+          float dv[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) dv[e] = ((kb4 >> e) & 1u) ? pe[e] * a.scale : 0.f;
-            st_store4<T>(pl + r * LP + k0, dv[0], dv[1], dv[2], dv[3]);
-          }
+          for (int e = 0; e < 4; ++e) dv[e] = ((kb4 >> e) & 1u) ? pe[e] * a.scale : 0.f;
+          st_store4<T>(pl + r * LP + k0, dv[0], dv[1], dv[2], dv[3]);
         }
-        __syncthreads();
       }
+      __syncthreads();
     }
     ST_STAMP(7);
-    rows_times_xt((DROP && a.Pd) ? pl2 : pl);         // O = P~ . V
+    rows_times_xt(pl);                               // O = P~ . V
     ST_STAMP(9);
   } else {
     T* prd = pl + r * LP;                            // this lane's query row of P, in LDS
@@ -1228,7 +1213,7 @@ static int launch_attn_stripe(bool bwd, const StripeArgs& a_in, int nB, hipStrea
   const bool drop = a.thresh != 0, bias = !bwd && a.bias_tab != nullptr;
   const size_t bias_bytes = bias ? ((size_t)(a.tab_stride + 32) * 4 + 15) / 16 * 16 : 0;
   const size_t row_bytes = (size_t)32 * (ceil_div(a.Sk, 32) * 32 + 16 / sizeof(T)) * sizeof(T);
-  const size_t smem = bias_bytes + row_bytes * ((!bwd && drop && a.Pd) ? 2 : 1);      // forward with a dropped copy of P wanted in memory: two row blocks
+  const size_t smem = bias_bytes + row_bytes;
   // five workgroups per CU when that turns two rounds into one (and their LDS fits): see SLIM above
   const int64_t n_wgs = (int64_t)a.n_stripes * nB * a.H;
   const bool slim = sw.st_slim && sizeof(T) == 2 && n_wgs > 4 * 256 && n_wgs <= 5 * 256 && 5 * (smem + 1024) <= 160 * 1024;
@@ -2512,9 +2497,7 @@ struct Ops {
     return M2M_OK;
   }
   // Whole-head attention kernels (attn_train.hip): bf16 storage, both lengths within an LDS image.  M2M_TRAIN_ATTN=stripes keeps round 2's path.
-  // (the one switch of the trainer read per pass, not at create: tests/test_train_gpu.py runs both paths on trainers that exist already)
-  static bool head_on() { const char* v = env_str("M2M_TRAIN_ATTN"); return !(v && v[0] == 's'); }
-  bool head_ok(int Sq, int Sk) const { return sizeof(T) == 2 && head_on() && t->sw.tuned_gemm && Sq <= AH_MAX_S && Sk <= AH_MAX_S; }
+  bool head_ok(int Sq, int Sk) const { return sizeof(T) == 2 && t->sw.attn_head && t->sw.tuned_gemm && Sq <= AH_MAX_S && Sk <= AH_MAX_S; }
   HeadAttnArgs head_args(const AttnDesc& d, bool bwd) const {
     HeadAttnArgs a{};
     const int Sq = d.Sq, Sk = d.Sk;
@@ -2534,9 +2517,7 @@ struct Ops {
     return a;
   }
   // Fused scores + softmax (attn_stripe_kernel) when a wave can hold all keys; K = (key, d) operand, Q = (query, d) operand.
-  bool stripe_ok(int Sk) const {      // the bias row + (two, with dropout) 32-row blocks of P must fit the LDS
-    return t->sw.stripes && Sk <= 32 * ST_NT && 2 * (size_t)32 * (ceil_div(Sk, 32) * 32 + 8) * sizeof(T) + 8192 <= 158 * 1024;
-  }
+  bool stripe_ok(int Sk) const { return t->sw.stripes && Sk <= 32 * ST_NT; }      // (the LDS bound: at ST_NT)
   // K | V of a layer (V `inner` columns behind K) -> kt [2][nB*H][64][Sp]
   int kv_transpose(const Mat& k, void* kt, int nB, int S) const {
     const int H = t->g.num_heads, Sp = (int)align_up(S, 32);
@@ -2547,7 +2528,7 @@ struct Ops {
     return M2M_OK;
   }
   // what the two stripe launches of a layer share: X = (key, d) operand, Y = (query, d) operand, the probabilities, the dropout key, and the
-  // fused product of the rows a workgroup has just formed: Xt its transposed second operand (or null: a launch of its own), `out` its result
+  // fused product of the rows a workgroup has just formed: Xt its transposed second operand, `out` its result
   StripeArgs stripe_args(const AttnDesc& d, const Mat& X, const Mat& Y, const T* Xt, const Mat& out) const {
     const bool dr = dropping(d.site);
     StripeArgs a{};
@@ -2557,22 +2538,18 @@ struct Ops {
     a.Xt = Xt; a.xt_ld = align_up(d.Sk, 32); a.O = const_cast<void*>(out.p); a.ldo = out.ld; a.sO1 = out.sb; a.sO2 = out.sh;
     return a;
   }
-  // M2M_TRAIN_FUSE_PV: 0 = off, fwd / bwd = only that pass (diagnostics), default both
-  // Fused scores + softmax (K, Q); vt: the transposed V for the fused P . V into ao, or null
-  int attn_probs(const AttnDesc& d, int nB, const T* vt, const T** Puse) const {
-    const bool dr = dropping(d.site);
+  // Fused scores + softmax (K, Q) -> P, and O = P~ . V into ao against the transposed V (the dropped P~ never leaves the kernel)
+  int attn_probs(const AttnDesc& d, int nB, const T* vt) const {
     StripeArgs a = stripe_args(d, d.k, d.q, vt, part(d.ao, 1, 0, d.Sq));
-    a.Pd = (dr && (t->sw.fwd_pd || !vt)) ? t->dS : nullptr;      // fused P.V: the dropped copy never leaves the kernel
     a.bias_tab = d.tab; a.tab_stride = d.Sq + d.Sk - 1; a.tab_center = d.Sq - 1;
-    *Puse = dr ? (const T*)t->dS : (const T*)d.Pm;
     return launch_attn_stripe<T>(false, a, nB, st, t->sw);
   }
-  // Fused dP + softmax backward (V, dO) -> dS; kt: the transposed K for the fused dQ = dS . K, or null; Pd_out: where the dropped
-  // probabilities go again, for the dV product (instead of a drop_copy launch), or null.  (causal only lets the kernel skip key tiles
-  // above the diagonal: P is zero there anyway)
-  int dscores(const AttnDesc& d, int nB, const T* kt, void* Pd_out) const {
+  // Fused dP + softmax backward (V, dO) -> dS (t->dS), dQ = dS . K against the transposed K, the diagonal sums of the bias gradient
+  // and, with dropout, the dropped probabilities again into the fp32 score scratch (t->sc, unused on this tier: they survive dS, so
+  // dV shares a launch with dK).  (causal only lets the kernel skip key tiles above the diagonal: P is zero there anyway)
+  int dscores(const AttnDesc& d, int nB, const T* kt) const {
     StripeArgs a = stripe_args(d, d.v, part(d.dO, 1, 0, d.Sq), kt, d.dq);
-    a.Pd = dropping(d.site) ? Pd_out : nullptr;
+    a.Pd = dropping(d.site) ? t->sc : nullptr;
     a.dS = t->dS;
     a.diag_part = d.buckets ? drel_slot() : nullptr;
     return launch_attn_stripe<T>(true, a, nB, st, t->sw);
@@ -2588,14 +2565,11 @@ struct Ops {
     return M2M_OK;
   }
   // backward: the dropped probabilities again (into t->dS, consumed by the dV product before dS overwrites it)
-  // (into_sc: the dropped copy goes to the fp32 score scratch, unused on the stripe path, so that it survives the dS written later
-  //  and dV can share a launch with dK)
-  int redrop(const void* Pm, int64_t n, int site, const T** Puse, bool into_sc = false) const {
+  int redrop(const void* Pm, int64_t n, int site, const T** Puse) const {
     if (!dropping(site)) { *Puse = (const T*)Pm; return M2M_OK; }
-    T* dst = into_sc ? (T*)t->sc : (T*)t->dS;
-    hipLaunchKernelGGL(drop_copy_kernel<T>, dim3(grid_1d(n)), dim3(256), 0, st, (const T*)Pm, dst, n, key(site), t->drop_thresh, t->drop_scale);
+    hipLaunchKernelGGL(drop_copy_kernel<T>, dim3(grid_1d(n)), dim3(256), 0, st, (const T*)Pm, (T*)t->dS, n, key(site), t->drop_thresh, t->drop_scale);
     M2M_CHECK_HIP(hipGetLastError());
-    *Puse = dst;
+    *Puse = (const T*)t->dS;
     return M2M_OK;
   }
   int softmax_bwd(const AttnDesc& d, int nB) const {      // dS (t->dS) from P and dPd (t->sc)
@@ -2666,31 +2640,26 @@ enum { SITE_ENC = 0, SITE_DEC = 1000, SITE_EMB = 900, SITE_FIN = 901,
        PL_PROBS_SELF = 1, PL_SELF_OUT = 2, PL_PROBS_CROSS = 3, PL_CROSS_OUT = 4, PL_MID = 5, PL_FF_OUT = 6 };
 
 // The attention of one layer between its projections, self or cross: q / k / v -> ao.  The ONE place that chooses among the
-// whole-head kernels (attn_train.hip), the fused stripe kernels and the unfused product + softmax path past 512 keys.
-// (a.lse and a.kt are never null for a layer of the arena — build_arena carves both for every layer — so neither guard decides)
+// whole-head kernels (attn_train.hip), the fused stripe kernels and the unfused product + softmax path past 512 keys: three
+// straight-line bodies per direction, the same choice in both.
 template <typename T>
 int attn_core_fwd(const Ops<T>& o, const AttnDesc& a, int nB) {
   m2m_trainer* t = o.t;
   const int Sq = a.Sq, Sk = a.Sk;
   int rc;
-  if (a.lse && o.head_ok(Sq, Sk))                                   // whole-head kernel: no P, no K^T | V^T, only O and the row log-sum-exp
+  if (o.head_ok(Sq, Sk))                                            // whole-head kernel: no P, no K^T | V^T, only O and the row log-sum-exp
     return launch_attn_head_fwd(o.head_args(a, false), nB, o.st, t->sw);
-  const T* Pu;
-  const bool stripes = o.stripe_ok(Sk);
-  const bool fuse = stripes && t->sw.fuse_pv && a.kt;               // any bit: the image serves P . V here and dQ = dS . K in the backward pass
-  const bool fuse_pv = fuse && (t->sw.fuse_pv & 1);                 // P . V inside the stripe kernel, against the transposed V
-  const T* vt = (const T*)a.kt + (int64_t)nB * t->g.num_heads * DK * align_up(Sk, 32);
-  // (K^T | V^T from the projection's own epilogue was built twice in round 3 — the tile staged through LDS, then the transpose taken
-  //  from the matrix core with the operands swapped — and both cost the projection as much as these launches take: 64-byte row
-  //  pieces instead of whole lines; removed again)
-  if (fuse) RC(o.kv_transpose(a.k, a.kt, nB, Sk));
-  if (stripes) {
-    RC(o.attn_probs(a, nB, fuse_pv ? vt : nullptr, &Pu));
-  } else {
-    RC(o.mmbh(TG_STORE_F32, {a.q, a.k, o.pmat(t->sc, Sq, Sk)}, nB, Sq, Sk, DK));
-    RC(o.softmax(a, nB, &Pu));
+  if (o.stripe_ok(Sk)) {                                            // stripe kernel: P, and O = P~ . V against the transposed V
+    // (K^T | V^T from the projection's own epilogue was built twice in round 3 — the tile staged through LDS, then the transpose taken
+    //  from the matrix core with the operands swapped — and both cost the projection as much as this launch takes: 64-byte row
+    //  pieces instead of whole lines; removed again)
+    RC(o.kv_transpose(a.k, a.kt, nB, Sk));                          // (its K^T half serves dQ = dS . K in the backward pass)
+    return o.attn_probs(a, nB, (const T*)a.kt + (int64_t)nB * t->g.num_heads * DK * align_up(Sk, 32));
   }
-  if (!fuse_pv) RC(o.mmbh(TG_STORE_T, {o.pmat(Pu, Sq, Sk), a.v.t(), o.part(a.ao, 1, 0, Sq)}, nB, Sq, DK, Sk));
+  const T* Pu;                                                      // unfused: scores -> softmax (+ the dropped copy) -> P~ . V
+  RC(o.mmbh(TG_STORE_F32, {a.q, a.k, o.pmat(t->sc, Sq, Sk)}, nB, Sq, Sk, DK));
+  RC(o.softmax(a, nB, &Pu));
+  RC(o.mmbh(TG_STORE_T, {o.pmat(Pu, Sq, Sk), a.v.t(), o.part(a.ao, 1, 0, Sq)}, nB, Sq, DK, Sk));
   return M2M_OK;
 }
 
@@ -2700,32 +2669,27 @@ int attn_core_bwd(const Ops<T>& o, const AttnDesc& a, int nB) {
   m2m_trainer* t = o.t;
   const int Sq = a.Sq, Sk = a.Sk;
   int rc;
-  if (a.lse && o.head_ok(Sq, Sk)) {                                 // whole-head kernel: dQ | dK | dV (and the bias gradient's diagonal sums) in one launch
+  if (o.head_ok(Sq, Sk)) {                                          // whole-head kernel: dQ | dK | dV (and the bias gradient's diagonal sums) in one launch
     RC(launch_attn_head_bwd(o.head_args(a, true), nB, o.st, t->sw));
     if (a.buckets) RC(o.bias_grad_stripes(a.buckets, a.Gbias, nB, Sq, Sk, a.bias_accumulate));
     return M2M_OK;
   }
-  const bool stripes = o.stripe_ok(Sk);
-  const bool pair = stripes && t->sw.pair_dvdk;                     // dV and dK in one launch (after dS exists)
-  const bool pd_fused = pair && o.dropping(a.site) && t->sw.fuse_pd;      // the stripe kernel re-emits the dropped P itself
-  const bool fuse = stripes && (t->sw.fuse_pv & 2) && a.kt;         // dQ = dS . K inside the stripe kernel, against the transposed K
   const Mat dO = o.part(a.dO, 1, 0, Sq), dS = o.pmat(t->dS, Sq, Sk);
-  const T* Pu;
-  if (pd_fused) Pu = (const T*)t->sc;
-  else RC(o.redrop(a.Pm, nB * dS.sb, a.site, &Pu, pair));
-  const Mat Pd = o.pmat(Pu, Sq, Sk);
-  if (!pair) RC(o.mmbh(TG_STORE_T, {Pd.t(), dO.t(), a.dv}, nB, Sk, DK, Sq));                    // dV = Pd^T dO
-  if (stripes) {
-    RC(o.dscores(a, nB, fuse ? (const T*)a.kt : nullptr, pd_fused ? t->sc : nullptr));          // dS from dPd = dO V^T
+  if (o.stripe_ok(Sk)) {                                            // stripe kernel: dS, dQ, the dropped P again; then dV | dK as one launch
+    RC(o.dscores(a, nB, (const T*)a.kt));
     if (a.buckets) RC(o.bias_grad_stripes(a.buckets, a.Gbias, nB, Sq, Sk, a.bias_accumulate));
-  } else {
-    RC(o.mmbh(TG_STORE_F32, {dO, a.v, o.pmat(t->sc, Sq, Sk)}, nB, Sq, Sk, DK));                // dPd = dO V^T
-    RC(o.softmax_bwd(a, nB));
-    if (a.buckets) RC(o.bias_grad(t->dS, a.buckets, a.Gbias, nB, Sq, Sk, (int)dS.ld, a.bias_accumulate));
+    const Mat Pd = o.pmat(o.dropping(a.site) ? (const void*)t->sc : a.Pm, Sq, Sk);
+    RC(o.mmbh2(TG_STORE_T, {Pd.t(), dO.t(), a.dv}, {dS.t(), a.q.t(), a.dk}, nB, Sk, DK, Sq));      // dV = Pd^T dO | dK = dS^T Q
+    return M2M_OK;
   }
-  if (!fuse) RC(o.mmbh(TG_STORE_T, {dS, a.k.t(), a.dq}, nB, Sq, DK, Sk));                  // dQ = dS K
-  if (pair) RC(o.mmbh2(TG_STORE_T, {Pd.t(), dO.t(), a.dv}, {dS.t(), a.q.t(), a.dk}, nB, Sk, DK, Sq));      // dV = Pd^T dO | dK = dS^T Q
-  else RC(o.mmbh(TG_STORE_T, {dS.t(), a.q.t(), a.dk}, nB, Sk, DK, Sq));                    // dK = dS^T Q
+  const T* Pu;                                                      // unfused: every product and row kernel a launch of its own
+  RC(o.redrop(a.Pm, nB * dS.sb, a.site, &Pu));
+  RC(o.mmbh(TG_STORE_T, {o.pmat(Pu, Sq, Sk).t(), dO.t(), a.dv}, nB, Sk, DK, Sq));                 // dV = Pd^T dO (before dS overwrites Pd)
+  RC(o.mmbh(TG_STORE_F32, {dO, a.v, o.pmat(t->sc, Sq, Sk)}, nB, Sq, Sk, DK));                     // dPd = dO V^T
+  RC(o.softmax_bwd(a, nB));
+  if (a.buckets) RC(o.bias_grad(t->dS, a.buckets, a.Gbias, nB, Sq, Sk, (int)dS.ld, a.bias_accumulate));
+  RC(o.mmbh(TG_STORE_T, {dS, a.k.t(), a.dq}, nB, Sq, DK, Sk));                                    // dQ = dS K
+  RC(o.mmbh(TG_STORE_T, {dS.t(), a.q.t(), a.dk}, nB, Sk, DK, Sq));                                // dK = dS^T Q
   return M2M_OK;
 }
 
@@ -3160,7 +3124,7 @@ extern "C" int m2m_trainer_create(const m2m_t5_geometry* geom, int n_cond, const
   // Gradient operands: e4m3 by default — with a scale per 32 elements the range of e5m2 is not needed, and its third
   // mantissa bit halves the noise every backward product adds (measured on the full model, per-tensor gradient cosine
   // against the fp32 oracle: e5m2 median 0.931 / min 0.908; e4m3: see tests/test_train_gpu.py).  M2M_FP8_GRAD=e5m2 selects e5m2.
-  // every environment switch the trainer obeys is read here, once: t->sw by its constructor above (M2M_TRAIN_ATTN apart: Ops::head_on)
+  // every environment switch the trainer obeys is read here, once: t->sw by its constructor above
   t->enc_sw = read_enc_switches();
   t->max_batch = max_batch; t->max_enc = max_enc_len; t->max_dec = max_dec_len;
   t->cond_rows.assign(cond_rows, cond_rows + n_cond);

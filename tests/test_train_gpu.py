@@ -213,11 +213,16 @@ def test_music2midi_training_surface_learns_and_serves_the_new_weights():
 
 # (F = 530: past the stripe kernels' 512 keys, in the encoder's self-attention and the cross-attention the softmax kernel writes the
 #  dropped copy of P and the backward pass drops P again for the dV product; the oracle's two losses differ by 7.4 at that shape)
-@pytest.mark.parametrize("precision,B,F,Ld", [pytest.param("fp32", 3, 21, 14, id="fp32"), pytest.param("fp32", 1, 530, 5, id="fp32-unfused")])
-def test_dropout_step_matches_autograd_with_the_same_masks(precision, B, F, Ld):
+#  (fp32-unfused-small: M2M_TRAIN_STRIPES=0 puts EVERY layer on the unfused tier, so the decoder's causal self-attention — five keys
+#  at F = 530, a stripe launch — runs softmax_fwd_kernel with `causal`, softmax_bwd_kernel and bias_diag_kernel for its table too)
+@pytest.mark.parametrize("precision,B,F,Ld,env", [pytest.param("fp32", 3, 21, 14, {}, id="fp32"), pytest.param("fp32", 1, 530, 5, {}, id="fp32-unfused"),
+                                                  pytest.param("fp32", 3, 21, 14, {"M2M_TRAIN_STRIPES": "0"}, id="fp32-unfused-small")])
+def test_dropout_step_matches_autograd_with_the_same_masks(precision, B, F, Ld, env, monkeypatch):
     """Dropout 0.1 at every place hf: modeling_t5.py has it.  The device's masks are a counter-based hash, so the oracle
     regenerates exactly the same masks (oracle/train.py DropoutMasks) and autograd must give the same loss and gradients."""
     from oracle.train import DropoutMasks
+    for k, v in env.items():                                                  # latched when the trainer is created
+        monkeypatch.setenv(k, v)
     model, tr, orc, params, geom, x, feats, cond, labels = _setup(tiny_config(), precision, B, F, Ld)
     tr.set_dropout(0.1, seed=1234)
     loss, logits = tr.forward_backward(x.cuda(), cond.cuda(), labels.cuda(), want_logits=True)
@@ -621,15 +626,15 @@ def test_whole_head_attention_step_against_autograd_and_the_stripe_path(cfg_name
     cfg = tiny_config() if cfg_name == "tiny" else copy.deepcopy(DEFAULT_CONFIG)
     monkeypatch.setenv("M2M_TRAIN_GRAPH", "0")
     torch.set_num_threads(min(16, os.cpu_count() or 16))
+    monkeypatch.setenv("M2M_TRAIN_ATTN", "head")                 # latched when a trainer is created
     model, tr_head, orc, params, geom, x, feats, cond, labels = _setup(cfg, "bf16", B, F, Ld)
+    monkeypatch.setenv("M2M_TRAIN_ATTN", "stripes")
     tr_stripe = NativeTrainer(model, B, F + 2, Ld, precision="bf16")
     for tr in (tr_head, tr_stripe):
         if p:
             tr.set_dropout(p, seed=31)
-    monkeypatch.setenv("M2M_TRAIN_ATTN", "head")
     la, _ = tr_head.forward_backward(x.cuda(), cond.cuda(), labels.cuda())
     la = la.item()
-    monkeypatch.setenv("M2M_TRAIN_ATTN", "stripes")
     lb, _ = tr_stripe.forward_backward(x.cuda(), cond.cuda(), labels.cuda())
     lb = lb.item()
     loss_o, _, grads_o = orc.loss_and_grads(feats, cond, labels, DropoutMasks(p, 31, 0) if p else None)
@@ -663,6 +668,32 @@ def test_whole_head_attention_step_against_autograd_and_the_stripe_path(cfg_name
     assert wh < 1.3 * wst + 1e-2                                 # no further from autograd than the stored-probability path is
     assert med < 4e-2 and worst < 8e-2
     tr_head.close(); tr_stripe.close()
+
+
+def test_the_attention_family_is_latched_when_the_trainer_is_created(monkeypatch):
+    """M2M_TRAIN_ATTN is read when a trainer is created, like every other switch: changing it afterwards moves neither the directly
+    issued first call nor the graph captured at the second and replayed at the third.  bf16 (2, 70, 33): three key tiles, a ragged
+    last stripe, both kernel families apply."""
+    from music2midi_amd.training import NativeTrainer
+    B, F, Ld = 2, 70, 33
+    monkeypatch.setenv("M2M_TRAIN_ATTN", "stripes")
+    model, tr_a, orc, params, geom, x, feats, cond, labels = _setup(tiny_config(), "bf16", B, F, Ld)
+    tr_c = NativeTrainer(model, B, F + 2, Ld, precision="bf16")
+    monkeypatch.setenv("M2M_TRAIN_ATTN", "head")
+    tr_b = NativeTrainer(model, B, F + 2, Ld, precision="bf16")
+    args = (x.cuda(), cond.cuda(), labels.cuda())
+    for call in range(3):                                        # direct, captured, replayed
+        outs = []
+        for tr, now in ((tr_a, "head"), (tr_c, "stripes"), (tr_b, "stripes")):
+            monkeypatch.setenv("M2M_TRAIN_ATTN", now)
+            loss, _ = tr.forward_backward(*args)
+            outs.append((loss.clone(), tr.grads.clone()))
+        assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]), f"call {call}: the variable moved a trainer that exists"
+    print(f"graph nodes: created under stripes {tr_a.graph_nodes()} / {tr_c.graph_nodes()}, under head {tr_b.graph_nodes()}")
+    assert tr_a.graph_nodes() == tr_c.graph_nodes()
+    assert tr_b.graph_nodes() != tr_a.graph_nodes()              # the switch selects something
+    for tr in (tr_a, tr_c, tr_b):
+        tr.close()
 
 
 def test_trainer_rejects_more_label_positions_than_the_embedding_gradient_lists():
