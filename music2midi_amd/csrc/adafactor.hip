@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void af_pass_a(const AfBlock* __restrict__ blo
 __global__ __launch_bounds__(256) void af_pass_a2(const AfTensor* __restrict__ tensors, const float* __restrict__ rowsum,
                                                   const float* __restrict__ colpart, const float* __restrict__ blk_p2,
                                                   float* __restrict__ state, float* __restrict__ rfac, float* __restrict__ cfac,
-                                                  float* __restrict__ tstat, float beta2t) {
+                                                  float* __restrict__ tstat, float beta2t, float omb2t) {
   __shared__ float sred[256];
   const AfTensor t = tensors[blockIdx.x];
   float acc = 0.f;
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void af_pass_a2(const AfTensor* __restrict__ t
     // rows
     float racc = 0.f;
     for (int r = threadIdx.x; r < t.rows; r += 256) {
-      const float v = beta2t * R[r] + (1.f - beta2t) * (rowsum[t.row_off + r] / (float)t.cols);
+      const float v = beta2t * R[r] + omb2t * (rowsum[t.row_off + r] / (float)t.cols);
       R[r] = v;
       racc += v;
     }
@@ -118,13 +118,13 @@ __global__ __launch_bounds__(256) void af_pass_a2(const AfTensor* __restrict__ t
         for (int u = 0; u < 8; ++u) cs += v[u];
       }
       for (; b < t.nblocks; ++b) cs += colpart[t.col_off + (int64_t)b * t.cols + c];
-      const float v = beta2t * C[c] + (1.f - beta2t) * (cs / (float)t.rows);
+      const float v = beta2t * C[c] + omb2t * (cs / (float)t.rows);
       C[c] = v;
       cfac[t.cfac_off + c] = rsqrtf(v);
     }
   } else {
     for (int c = threadIdx.x; c < t.cols; c += 256) {
-      const float v = beta2t * R[c] + (1.f - beta2t) * colpart[t.col_off + c];     // one block, one row: colpart = g^2 + eps
+      const float v = beta2t * R[c] + omb2t * colpart[t.col_off + c];     // one block, one row: colpart = g^2 + eps
       R[c] = v;
       cfac[t.cfac_off + c] = rsqrtf(v);
     }
@@ -208,11 +208,14 @@ __global__ __launch_bounds__(256) void af_pass_c(const AfBlock* __restrict__ blo
 int launch_adafactor(const AfPlan& pl, float* P, const float* G, int step, hipStream_t st) {
   const double t = (double)step;
   const float beta2t = (float)(1.0 - pow(t, -0.8));
+  // 1 - beta2 = t^-0.8 rounded from the double, as the reference's add_(.., alpha=1.0 - beta2t) has it: 1.f - beta2t keeps only the bits
+  // above half an ulp of 1, a relative error of up to 3e-8 * t^0.8 (4e-5 at t = 9 999) on every newly added second moment
+  const float omb2t = (float)pow(t, -0.8);
   const double rho_d = fmin(1e-6 * t, 1.0 / sqrt(t));
   const float rho = (float)rho_d;
   hipLaunchKernelGGL(af_pass_a, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, P, G, pl.rowsum, pl.colpart, pl.blk_a);
   hipLaunchKernelGGL(af_pass_a2, dim3(pl.n_tensors), dim3(256), 0, st, pl.tensors, pl.rowsum, pl.colpart, pl.blk_a, pl.state, pl.rfac,
-                     pl.cfac, pl.tstat, beta2t);
+                     pl.cfac, pl.tstat, beta2t, omb2t);
   hipLaunchKernelGGL(af_pass_b, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, G, pl.rfac, pl.cfac, pl.blk_b);
   hipLaunchKernelGGL(af_pass_b2, dim3(pl.n_tensors), dim3(256), 0, st, pl.tensors, pl.blk_b, pl.tstat, rho);
   hipLaunchKernelGGL(af_pass_c, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, P, G, pl.rfac, pl.cfac, pl.tstat);

@@ -12,6 +12,7 @@ import torch
 from music2midi_amd import synth
 from music2midi_amd.config import DEFAULT_CONFIG
 
+import adafactor_ref as ar
 from test_t5_gpu import tiny_config
 from test_train_gpu import FP8_FLOORS, _notes_batches, _rel, _setup, fp8_agreement
 
@@ -84,10 +85,26 @@ def test_fp32_accumulated_gradients_and_step_match_the_oracle(dropout):
     tr.grads.copy_(acc)
     p_ref = {k: v.detach().clone() for k, v in params.items()}
     AdafactorOracle(p_ref).step(ref)
+    p_old = tr.params.cpu()
     tr.optimizer_step()
     worst_p = max(_rel(tr.params[off:off + int(np.prod(shape))].view(shape).cpu(), p_ref[k]) for k, (off, shape) in tr.layout.items())
     print(f"  after one Adafactor step: worst parameter rel err {worst_p:.2e}")
     assert worst_p < 2e-5
+    # the line above is the size of the step itself (lr = rms(p) 1e-6 at t = 1): also resolve the update, per tensor, against the
+    # float64 step from the device's own parameters and accumulated gradient (tests/adafactor_ref.py; the bar of test_adafactor_gpu.py)
+    p_new, g_dev = tr.params.cpu(), acc.cpu()
+    upd = ar.Worst("update error", ar.update_bar("warmup"))
+    for k, (off, shape) in tr.layout.items():
+        old, new, g = (b[off:off + int(np.prod(shape))].view(shape) for b in (p_old, p_new, g_dev))
+        delta, _ = ar.ref_step(old, g, ar.fresh_state(tuple(shape)), 1)
+        e = ar.update_error(new, old, delta)
+        if e is None:                                                    # an all-zero gradient: nothing may move
+            assert torch.equal(new, old), k
+        else:
+            upd.add(e, k, 1)
+    print("  " + upd.report("that step against the float64 update"))
+    assert len(upd.items) == len(tr.layout)                             # (every tensor has a gradient in a real pass)
+    upd.check("accumulated step")
 
 
 def test_bf16_accumulated_gradients_track_the_fp32_oracle():
