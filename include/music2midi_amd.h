@@ -273,6 +273,46 @@ int m2m_ingest_resample_f32(const float* x_dev, int64_t n_in, int up, int down, 
                             int64_t capacity, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Tokenising of note labels: the note arrays of a batch -> token ids, replaces for the batches it takes
+ * ref: music2midi/tokenizer.py:86-141 (MidiTokenizer.__call__, _tokenize).  The definition is music2midi_amd/tokenizer.py
+ * (_quantize, _tokenize); the ids are EQUAL to its (integer placement; the quantisation repeats the host's float64 operations).
+ * No handle, no workspace, no environment switch; the call enqueues on `stream` and returns nothing to the host.  Every
+ * M2M_ERR_INVALID below is answered on the arguments alone, before the first HIP call.
+ * ------------------------------------------------------------------------- */
+#define M2M_TOKENIZE_MAX_NOTES 1024        /* notes per clip */
+#define M2M_TOKENIZE_MAX_TIME 4096         /* time ids of the vocabulary */
+#define M2M_TOKENIZE_MAX_ROWS 65535
+
+/* MidiTokenizer._quantize: min(rint(nextafter(seconds / time_step, +inf)), n_time - 1) in double, the function the kernel calls;
+ * -1 for seconds that are negative or NaN, a time_step outside (0, 3600] or n_time outside 1..4096.  Host arithmetic, exported so
+ * that the formula can be tested without a GPU. */
+int m2m_tokenize_quantize(double seconds, double time_step, int n_time);
+/* 1 + 2k + min(2k, T) + 2 min(k, T): the longest row k = n_notes notes can give over T = n_time time ids (6k + 1 when every onset
+ * and offset has an index of its own); -1 for k < 0 or T < 1.  Host arithmetic. */
+int64_t m2m_tokenize_row_bound(int n_notes, int n_time);
+
+/*
+ * MidiTokenizer.__call__(notes_batch, cutoff_time) without the host loop, one workgroup per clip.
+ * notes_dev [3, n_notes] float64: onsets (s), offsets (s), pitches of all clips, those of clip r at
+ * [offsets_dev[r], offsets_dev[r + 1]) (int32 [B + 1]) in array order; the velocity is not part of the vocabulary.
+ * Per clip: notes with onset < cutoff_time are kept (has_cutoff = 0: all); offset = max(offset, onset + time_step); both times go
+ * through m2m_tokenize_quantize; for every distinct index in increasing order the row takes time_offset + index, then ONSET (3) and
+ * the pitch ids of the notes starting there, then OFFSET (4) and those of the notes ending there, both in array order; EOS (2) ends
+ * the row.  A pitch id is (int64)(float)(pitch + pitch_offset), a time id (int64)(float)(index + time_offset): the host builds a
+ * float32 tensor and truncates it.  labels = 1 writes -100 for every id equal to pad_id (Music2MIDI._labels).
+ * ids_out_dev [B, row_stride] int64: row r holds its lengths_out_dev[r] ids, then `fill` up to `width`; columns from `width` on are
+ * not touched.  A row longer than `width` is cut at `width` and keeps its true length in lengths_out_dev [B] int32, so the caller
+ * can tell.  lengths_out_dev[r] = -1, and the row all `fill`, for a clip with a value that cannot be placed - an onset, offset or
+ * pitch that is not finite, a negative onset, |pitch| > 32768 - or with offsets outside 0..n_notes or more than 1024 notes apart.
+ * M2M_ERR_INVALID: B outside 1..65535, n_notes outside 0..1024 B, time_step outside (0, 3600], n_time outside 1..4096,
+ * pitch_offset < 5, time_offset outside pitch_offset..2^30, has_cutoff / labels other than 0 or 1, width < 1, row_stride < width,
+ * a null pointer.
+ */
+int m2m_tokenize_notes(const double* notes_dev, const int32_t* offsets_dev, int n_notes, int B, double time_step, int pitch_offset,
+                       int time_offset, int n_time, int has_cutoff, double cutoff_time, int64_t fill, int labels, int64_t pad_id,
+                       int64_t* ids_out_dev, int width, int64_t row_stride, int32_t* lengths_out_dev, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * T5 encoder-decoder weights, replaces what ref: music2midi/transformer.py:14-16
  * builds (T5Config + T5ForConditionalGeneration) once a state dict is loaded.
  * ------------------------------------------------------------------------- */

@@ -153,7 +153,14 @@ class Music2MIDI(nn.Module):
     LABEL_BUCKET = 16
 
     def _labels(self, notes_batch) -> torch.Tensor:
+        """The labels of one batch: ``tokenizer(notes_batch)`` with PAD -> -100, padded to the bucket.  With
+        ``config.trainer.device_labels: true`` (absent: off), the model on a GPU and notes ``tokenize.notes_eligible`` accepts, the
+        same tensor is written on the device by one kernel (``T5Transformer.device_labels``) and stays there."""
         t5 = self.model
+        if bool(self.config.get("trainer", {}).get("device_labels", False)):
+            labels = t5.device_labels(notes_batch, bucket=self.LABEL_BUCKET, enabled=True)
+            if labels is not None:
+                return labels
         labels = t5.tokenizer(notes_batch)
         labels[labels == t5.geometry.pad_token_id] = -100
         pad = -labels.shape[1] % self.LABEL_BUCKET

@@ -127,6 +127,10 @@ _SIGNATURES = {
     "m2m_ingest_pcm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "m2m_ingest_resample_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
                                           C.c_void_p]),
+    "m2m_tokenize_quantize": (C.c_int, [C.c_double, C.c_double, C.c_int]),
+    "m2m_tokenize_row_bound": (C.c_int64, [C.c_int, C.c_int]),
+    "m2m_tokenize_notes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_double, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "m2m_model_create": (C.c_int, [C.POINTER(T5GeometryC), C.POINTER(T5Weights), C.c_int, C.c_void_p,
                                    C.POINTER(C.c_void_p)]),
     "m2m_model_destroy": (None, [C.c_void_p]),

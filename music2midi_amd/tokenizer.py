@@ -1,8 +1,11 @@
 """MIDI note <-> token-id codec with the reference's vocabulary and call surface
 (ref: music2midi/tokenizer.py:18-267): ``MidiTokenizer(config)``, ``__call__``,
 ``decode(mode="batched"|"sequential")``, ``to_string``, constants PAD/BOS/EOS/
-ONSET/OFFSET.  CPU-side and numpy-only (no numba, no ``np.float_``); it is not
-on the accelerated path, but callers of ``generate()`` need it unchanged.
+ONSET/OFFSET.  CPU-side and numpy-only (no numba, no ``np.float_``).  This module
+is the definition of both directions; each has a device form that equals it:
+``decode`` in ``music2midi_amd.scoring`` (csrc/score.hip) and ``__call__`` in
+``music2midi_amd.tokenize`` (csrc/tokenize.hip, ``trainer.device_labels``).
+Callers of ``generate()`` need this one unchanged.
 
 Vocabulary (ref: config.yaml:33-37): ids 0-4 special, then ``pitch`` note ids,
 then ``time`` step ids of ``midi_quantize_ms`` each.

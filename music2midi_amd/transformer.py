@@ -550,6 +550,26 @@ class T5Transformer(nn.Module):
                              "m2m_bench_kernel")
             return float(us.value), int(nbytes.value)
 
+    # -- labels ----------------------------------------------------------------
+    _label_stream = None
+
+    def device_labels(self, notes_batch, bucket: int = 1, enabled: Optional[bool] = None):
+        """With ``config.trainer.device_labels: true`` (absent: off; ``enabled`` is the key as the caller's own config has it, None:
+        this module's), the model on a GPU and notes ``tokenize.notes_eligible`` accepts:
+        ``tokenizer(notes_batch)`` with PAD -> -100, rounded up to ``bucket`` columns with -100, written on the device
+        (``music2midi_amd.tokenize``) - equal to the tensor the host builds.  Otherwise None, and the caller takes the host path.
+        The kernel runs on a side stream of this model, so the read-back of the row lengths waits for that stream alone and not for
+        the training step in flight; the current stream is ordered behind the kernel's event before it reads the labels."""
+        device = self.transformer.device
+        if enabled is None:
+            enabled = bool(self.config.get("trainer", {}).get("device_labels", False))
+        if device.type != "cuda" or not enabled:
+            return None
+        from .tokenize import training_labels
+        if self._label_stream is None or self._label_stream.device != device:
+            self._label_stream = torch.cuda.Stream(device=device)
+        return training_labels(self.tokenizer, notes_batch, device, self.geometry.pad_token_id, bucket, self._label_stream)
+
     # -- reference API -------------------------------------------------------
     def forward(self, inputs: ModelInputs, **kwargs):
         """Teacher-forced pass (ref transformer.py:28-39): labels from the tokenizer, pad -> -100,
@@ -559,9 +579,11 @@ class T5Transformer(nn.Module):
         if kwargs:
             raise NotImplementedError(f"unsupported forward kwargs on the MI355X path: {sorted(kwargs)}")
         g = self.geometry
-        labels = self.tokenizer(inputs.notes_batch)
-        labels[labels == g.pad_token_id] = -100
-        labels = labels.to(self.transformer.device)
+        labels = self.device_labels(inputs.notes_batch)
+        if labels is None:
+            labels = self.tokenizer(inputs.notes_batch)
+            labels[labels == g.pad_token_id] = -100
+            labels = labels.to(self.transformer.device)
         encoder_inputs = self.encoder_inputs(inputs)
         dec_in = torch.full_like(labels, g.decoder_start_token_id)
         dec_in[:, 1:] = labels[:, :-1]
