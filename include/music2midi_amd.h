@@ -273,6 +273,47 @@ int m2m_ingest_resample_f32(const float* x_dev, int64_t n_in, int up, int down, 
                             int64_t capacity, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Training dataset: the segments of a batch, each cut from a different recording whose sample bytes lie in device memory, decoded,
+ * downmixed and resampled by ONE launch - what ref: music2midi/dataset.py:124-129 (librosa.load(offset=, duration=)) does per
+ * item on the host.  The definition is Music2MIDIDataset.crop_host (music2midi_amd/dataset.py): read_wav, the slice, y.mean(axis=1),
+ * resample.  Every sample is EQUAL to what m2m_ingest_pcm followed by m2m_ingest_resample_f32 give for the clip's bytes alone: the
+ * clip is resampled on its own, frames outside it do not exist for the filter.
+ * No handle, no environment switch; the call enqueues on `stream` and returns nothing to the host.  Every M2M_ERR_INVALID below is
+ * answered on the arguments alone, before the first HIP call.
+ * ------------------------------------------------------------------------- */
+#define M2M_DATASET_MAX_CLIPS 65535
+#define M2M_DATASET_LDS_WINDOW 4096        /* floats of LDS for the input frames of one tile of 256 outputs (16 KiB) */
+
+typedef struct {
+  const void* bytes_dev;                   /* the clip's FIRST frame: n_frames * channels interleaved samples, any address */
+  const float* h_phase_dev;                /* the phase-major filter of up / down as m2m_ingest_resample_f32 takes it; NULL when up == down */
+  int64_t n_frames;                        /* frames of the clip, not of the recording */
+  int32_t channels;                        /* 1..7 */
+  int32_t format;                          /* M2M_PCM_* */
+  int32_t up, down;                        /* in lowest terms, or equal */
+  int32_t half;                            /* 10 max(up, down) */
+  int32_t reserved;                        /* 0 */
+} m2m_dataset_clip;
+
+/* Input frames one tile of 256 outputs can touch: (up - 1 + 255 down) / up + J, J = m2m_ingest_phase_taps; 0 for up == down (no
+ * filter, no window); M2M_ERR_INVALID for up / down outside 1..1000.  A ratio whose window exceeds M2M_DATASET_LDS_WINDOW is not
+ * taken by the call below: the caller crops those recordings on the host.  Host arithmetic. */
+int m2m_dataset_crop_window(int up, int down);
+
+/*
+ * out_dev[c * row_stride + n], c < n_clips, n < T: resample_poly(mean over the channels of clip c, up, down)[n] for
+ * n < n_out(c) = ceil(n_frames up / down), exact zero for n_out(c) <= n < T.  Nothing outside these n_clips rows of T floats is written.
+ * clips_host [n_clips] is copied to table_dev (device scratch of n_clips * sizeof(m2m_dataset_clip) bytes, 8-byte aligned) on
+ * `stream`, then one launch of (ceil(T / 256), n_clips) workgroups follows; clips_host may be reused when the call returns.
+ * M2M_ERR_INVALID: n_clips outside 1..65535, T outside 1..2^30, row_stride < T, a null pointer, table_dev misaligned; per clip:
+ * n_frames outside 1..2^28, channels outside 1..7, an unknown format, n_frames * channels * width >= 2^31, up / down outside
+ * 1..1000 or not in lowest terms (unless equal), half other than 10 max(up, down), a missing filter, n_out > T, a window above
+ * M2M_DATASET_LDS_WINDOW, reserved != 0, the rows of out_dev overlapping the clip's bytes, its filter or table_dev.
+ */
+int m2m_dataset_crop_f32(const m2m_dataset_clip* clips_host, int n_clips, void* table_dev, float* out_dev, int64_t row_stride,
+                         int64_t T, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Tokenising of note labels: the note arrays of a batch -> token ids, replaces for the batches it takes
  * ref: music2midi/tokenizer.py:86-141 (MidiTokenizer.__call__, _tokenize).  The definition is music2midi_amd/tokenizer.py
  * (_quantize, _tokenize); the ids are EQUAL to its (integer placement; the quantisation repeats the host's float64 operations).

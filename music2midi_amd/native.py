@@ -49,6 +49,12 @@ class AugmentStages(C.Structure):
     _fields_ = [("stft", C.c_void_p), ("stretched_stft", C.c_void_p), ("stretched_wave", C.c_void_p)]
 
 
+class DatasetClip(C.Structure):
+    """m2m_dataset_clip: one clip of m2m_dataset_crop_f32."""
+    _fields_ = [("bytes_dev", C.c_void_p), ("h_phase_dev", C.c_void_p), ("n_frames", C.c_int64), ("channels", C.c_int32),
+                ("format", C.c_int32), ("up", C.c_int32), ("down", C.c_int32), ("half", C.c_int32), ("reserved", C.c_int32)]
+
+
 class T5GeometryC(C.Structure):
     _fields_ = [(n, C.c_int) for n in
                 ("d_model", "d_ff", "num_layers", "num_decoder_layers", "num_heads", "d_kv", "vocab_size",
@@ -127,6 +133,8 @@ _SIGNATURES = {
     "m2m_ingest_pcm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "m2m_ingest_resample_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
                                           C.c_void_p]),
+    "m2m_dataset_crop_window": (C.c_int, [C.c_int, C.c_int]),
+    "m2m_dataset_crop_f32": (C.c_int, [C.POINTER(DatasetClip), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "m2m_tokenize_quantize": (C.c_int, [C.c_double, C.c_double, C.c_int]),
     "m2m_tokenize_row_bound": (C.c_int64, [C.c_int, C.c_int]),
     "m2m_tokenize_notes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
