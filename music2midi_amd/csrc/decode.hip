@@ -92,6 +92,22 @@ __device__ inline float4 xq_load4(const xq_t* p) {   // p 16-byte aligned
   return make_float4(xq_flt(a.x), xq_flt(a.y), xq_flt(b.x), xq_flt(b.y));
 }
 
+// ---- residual rows of an MFMA tile, staged through LDS (dec_ff_kernel and dec_gemm_kernel) ----
+// The MFMA operand pattern gives lane (r, g) 64-byte pieces of row r: read from memory that way, one wave instruction touches
+// 32 different 128-byte lines, uses a quarter of each, and every line is asked for by four instructions - and these are the loads
+// the kernel's first barrier waits for.  Instead the block loads its rows cooperatively as raw fixed-point words, 16 bytes per
+// lane with consecutive lanes on consecutive addresses (a wave instruction = 1 KB of one row, whole lines), in front of every
+// other request (loads retire in order), stores them to LDS, and each lane reads back exactly the 16 elements it used to read
+// from memory: the conversions and every sum see the same values in the same order.  Same-box A/B against the earlier form
+// (DESIGN 4.3): dec_ff_kernel 7.03 -> 6.61 us per launch, lm_head 4.91 -> 4.87 us at 16 clips and 5.27 -> 4.90 at 64;
+// dec_ff_multi_kernel gained 1.6 %, inside the run-to-run spread, and reads its rows from memory as before.
+// Place, in 16-byte chunks, of chunk cc of tile row r (< 16) in an image of cpr chunks per row (cpr a multiple of 16, so rows
+// start on a 256-byte bank row).  Lane (r, g) reads chunks base + 4 g + q: the XOR with the row's two halves swapped keeps the
+// four 16-lane groups of a 16-byte LDS read on 16 different bank slots (a group holds lanes whose r >> 2 differ wherever their g
+// differs), and the 8 consecutive lanes of a 16-byte LDS write stay on 8 different slots.
+typedef long long xq2_t __attribute__((ext_vector_type(2)));   // one 16-byte chunk of a row (a plain vector: it stays in registers)
+__device__ inline int row_stage_at(int r, int cc, int cpr) { return r * cpr + (cc ^ (((r & 3) << 2) | (r >> 2))); }
+
 // ---- headless greedy loop: the arg-max travels as a packed 64-bit key ----
 // The lm_head workgroups reduce their 16 columns per row and atomicMax a key into keys[row]; the NEXT step's layer-0
 // self-attention workgroups decode it (token id -> embedding row = their input), the layer-0 cross-attention kernel
@@ -175,27 +191,50 @@ __global__ __launch_bounds__(64 * DG_MAXW) void dec_gemm_kernel(DecGemmArgs a) {
   const T* W = reinterpret_cast<const T*>(a.W);
   const int kbeg = wave * (32 * NS) + 8 * g;
   const bool row_ok = (b0 + r) < a.B;
-  const int arow = b0 + (row_ok ? r : 0);           // padding rows read row b0 and are never stored
   const T* wr = W + (int64_t)(n0 + r) * K + kbeg;
   // epilogue coordinates of this thread (threads 0..255 own one output each)
   const int orow = (tid >> 4) & 15, ocol = tid & 15;
   const int ob = b0 + orow, on = n0 + ocol;
 
+  // the tile's rows first (row_stage_at above): a pass of the block's 64 nw lanes covers RPI = 4 / NS rows, thread tid takes chunk
+  // scc of tile rows srow, srow + RPI, ...; rows past the batch re-read its last row (clamped, never a branch around a load)
+  constexpr int RPI = 4 / NS, NXL = 4 * NS;
+  __shared__ __align__(16) xq2_t xs[16 * (NS == 1 ? 64 : 256)];   // K <= 128 (NS = 1) / 512: dec_gemm_shape
+  const int cpr = K >> 1;                                             // 16-byte chunks per row
+  int srow = 0;
+#pragma unroll
+  for (int i = 1; i < RPI; ++i) srow += tid >= i * cpr ? 1 : 0;
+  const int scc = tid - srow * cpr;
+  xq2_t xst[NXL];
+#pragma unroll
+  for (int i = 0; i < NXL; ++i)
+    xst[i] = *reinterpret_cast<const xq2_t*>(a.x + (int64_t)min(b0 + RPI * i + srow, a.B - 1) * a.ldx + 2 * scc);
+  __builtin_amdgcn_sched_barrier(0);               // the latency-critical rows go out FIRST (loads retire in order)
+  float4 g0[NS], g1[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    g0[s] = *reinterpret_cast<const float4*>(a.ln_w + kbeg + 32 * s);
+    g1[s] = *reinterpret_cast<const float4*>(a.ln_w + kbeg + 32 * s + 4);
+  }
   Frag<T> wf[NS];
 #pragma unroll
   for (int s = 0; s < NS; ++s) wf[s] = load_frag(wr + 32 * s);
+  __builtin_amdgcn_sched_barrier(0);
   asm volatile("" ::"s"(done));   // materialise the flag now, under the vector loads (else it is sunk to the epilogue)
+#pragma unroll
+  for (int i = 0; i < NXL; ++i) xs[row_stage_at(RPI * i + srow, scc, cpr)] = xst[i];
+  __syncthreads();
 
   f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
   {
-    const xq_t* xr = a.x + (int64_t)arow * a.ldx + kbeg;
-    float4 x0[NS], x1[NS], g0[NS], g1[NS];
+    float4 x0[NS], x1[NS];
 #pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      x0[s] = xq_load4(xr + 32 * s);
-      x1[s] = xq_load4(xr + 32 * s + 4);
-      g0[s] = *reinterpret_cast<const float4*>(a.ln_w + kbeg + 32 * s);
-      g1[s] = *reinterpret_cast<const float4*>(a.ln_w + kbeg + 32 * s + 4);
+    for (int s = 0; s < NS; ++s) {   // lane (r, g): elements kbeg + 32 s + [0, 8) of row r (padding rows hold the last row: rs = 0 below)
+      const int cc = (kbeg >> 1) + 16 * s;
+      const xq2_t q0 = xs[row_stage_at(r, cc, cpr)], q1 = xs[row_stage_at(r, cc + 1, cpr)];
+      const xq2_t q2 = xs[row_stage_at(r, cc + 2, cpr)], q3 = xs[row_stage_at(r, cc + 3, cpr)];
+      x0[s] = make_float4(xq_flt(q0.x), xq_flt(q0.y), xq_flt(q1.x), xq_flt(q1.y));
+      x1[s] = make_float4(xq_flt(q2.x), xq_flt(q2.y), xq_flt(q3.x), xq_flt(q3.y));
     }
     float ss = 0.f;
 #pragma unroll
@@ -308,8 +347,9 @@ static int launch_dec_gemm(int precision, const DecGemmArgs& a, hipStream_t st) 
 // them), so the rows of x — 8 bytes per element, the largest operand — are fetched once per
 // workgroup; in phase 2 wave w owns output columns [64 w, 64 w + 64).  One extra workgroup per row
 // block adds the residual rows themselves and zeroes the third buffer of the rotation.  A CU pulls only ~25-30 GB/s
-// from beyond its L2, so the kernel's time is the bytes one workgroup requests (x 49 KB + weights
-// 74 KB at d_model 384); every global load is issued before the first use.
+// from beyond its L2, so the kernel's time is the bytes one workgroup requests (at d_model 384 in bf16: x 24 KB with 8-row tiles,
+// 48 KB with 16-row tiles - real rows only, whole lines, staged through LDS: row_stage_at - + weights 74 KB, 147 KB in fp32);
+// every global load is issued before the first use, the rows first.
 struct DecFfArgs {
   const xq_t* x;         // [B, d] residual stream after the attention sub-layers (complete)
   xq_t* x_out;           // [B, d] zero on entry: x + FF(x) is accumulated into it
@@ -339,9 +379,11 @@ constexpr int FF_HP = FF_C + 8; // LDS row pitch of the activation slice (elemen
 template <typename T, int KS, int FF_R>
 __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2))) void dec_ff_kernel(DecFfArgs a) {
   M2M_STAMP_DECL
+  constexpr int CPR = 32 * KS;                         // 16-byte chunks per row
   __shared__ float ss_s[KS][16];
   __shared__ float red[KS][4][16 * 17];
   __shared__ __align__(16) T hs[16 * FF_HP];
+  __shared__ __align__(16) xq2_t xs[FF_R * CPR];       // the block's raw rows (row_stage_at): FF_R x d_model x 8 bytes, 24 KB at 8 x 384
   M2M_STAMP(4, 0);
   const int done = chain_done(a.state);
   const int tid = threadIdx.x, lane = tid & 63, ks = tid >> 6;
@@ -380,17 +422,20 @@ __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2)))
   }
   const int kbeg = ks * 64 + 8 * g;
   const bool row_ok = r < FF_R && (b0 + r) < a.B;
-  const int arow = b0 + (row_ok ? r : 0);            // padding rows read row b0; their activations are zeroed
   const T* Wi = reinterpret_cast<const T*>(a.Wi);
   const T* Wo = reinterpret_cast<const T*>(a.Wo);
 
-  const xq_t* xr = a.x + (int64_t)arow * K + kbeg;
-  longlong2 xraw[2][4];   // raw fixed-point rows: converted only after every load has been issued
+  // The block's FF_R rows, raw, through LDS.  The block has 64 KS lanes = two rows of chunks per pass: thread tid takes chunk scc of
+  // tile rows srow, srow + 2, ...  Rows past the batch re-read its last row (clamped, never a branch around a load); rs = 0 for them.
+  const int srow = tid >= CPR ? 1 : 0, scc = tid - srow * CPR;
+  xq2_t xst[FF_R / 2];
+#pragma unroll
+  for (int i = 0; i < FF_R / 2; ++i)
+    xst[i] = (M2M_FF_ABL & 2) ? xq2_t{1 << 28, 1 << 27} : *reinterpret_cast<const xq2_t*>(a.x + (int64_t)min(b0 + 2 * i + srow, a.B - 1) * K + 2 * scc);
+  __builtin_amdgcn_sched_barrier(0);               // the latency-critical rows go out FIRST (loads retire in order)
   float4 g0[2], g1[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) xraw[s][q] = (M2M_FF_ABL & 2) ? make_longlong2(1 << 28, 1 << 27) : *reinterpret_cast<const longlong2*>(xr + 32 * s + 2 * q);
     g0[s] = *reinterpret_cast<const float4*>(a.ln_w + kbeg + 32 * s);
     g1[s] = *reinterpret_cast<const float4*>(a.ln_w + kbeg + 32 * s + 4);
   }
@@ -407,11 +452,21 @@ __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2)))
   // compiler would otherwise sink to the first use, in front of the barrier on the critical path)
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("" ::"s"(done));
+#pragma unroll
+  for (int i = 0; i < FF_R / 2; ++i) xs[row_stage_at(2 * i + srow, scc, CPR)] = xst[i];
+  __syncthreads();
+  // Lane (r, g) takes its operand pieces: elements kbeg + 32 s + 2 q + {0, 1} of row r, converted only here.  With 8-row tiles the
+  // lanes r >= 8 are padding: they re-read the piece of lane (r - 8, g ^ 1), which sits in their own 16-lane LDS read group (the
+  // same address: a broadcast, no bank conflict).
+  const int lr = r & (FF_R - 1), lcc = (kbeg >> 1) ^ (r >= FF_R ? 4 : 0);
   float4 x0[2], x1[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    x0[s] = make_float4(xq_flt(xraw[s][0].x), xq_flt(xraw[s][0].y), xq_flt(xraw[s][1].x), xq_flt(xraw[s][1].y));
-    x1[s] = make_float4(xq_flt(xraw[s][2].x), xq_flt(xraw[s][2].y), xq_flt(xraw[s][3].x), xq_flt(xraw[s][3].y));
+    xq2_t xraw[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) xraw[q] = xs[row_stage_at(lr, lcc + 16 * s + q, CPR)];
+    x0[s] = make_float4(xq_flt(xraw[0].x), xq_flt(xraw[0].y), xq_flt(xraw[1].x), xq_flt(xraw[1].y));
+    x1[s] = make_float4(xq_flt(xraw[2].x), xq_flt(xraw[2].y), xq_flt(xraw[3].x), xq_flt(xraw[3].y));
   }
 
   // ---- phase 1: RMSNorm + up projection of this slice ----
@@ -564,6 +619,8 @@ __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2)))
   const T* Wo = reinterpret_cast<const T*>(a.Wo);
   const int s0 = c * NSL;                                   // first slice of this workgroup
 
+  // (rows read from memory in the operand pattern: staging them through LDS as the first kernel does gave 12.28 -> 12.09 us per
+  // launch at 64 clips, inside the run-to-run spread - DESIGN 4.3)
   const xq_t* xr = a.x + (int64_t)arow * K + kbeg;
   longlong2 xraw[2][4];
   float4 g0[2], g1[2];
