@@ -209,6 +209,22 @@ int m2m_score_detokenize(const int64_t* ids_dev, int R, int L, int64_t row_strid
                          int time_offset, int vocab_size, int32_t* notes_out_dev, int32_t* counts_out_dev, void* stream);
 
 /*
+ * The same decode with a confidence per note (the definition: music2midi_amd/confidence.py, note_logprobs).  logprobs_dev [R, L]
+ * float32 (row r at logprobs_dev + r * lp_row_stride) holds the log-probability of every id, column-aligned with ids_dev.  Every
+ * note and every OFFSET event takes (lp[time] + lp[mode]) + lp[pitch] of the three tokens that made it - the latest time token, the
+ * latest ONSET / OFFSET token, the latest pitch token - as rounded float32 additions in that order; a closed note carries its own
+ * sum (on) and the sum of the event that closed it (off).  A note is dropped iff on + off < min_logprob is true in float32: a NaN
+ * total is kept, -inf keeps every note.  notes_dev / counts_dev hold the kept notes only, in m2m_score_detokenize's layout (the
+ * one m2m_score_chroma_counts reads); note_lp_dev [R, L, 2] float32 holds (on, off) of note n of row r at [r, n].
+ * The limits, the -1 count of a row with an id outside the vocabulary and every M2M_ERR_INVALID are m2m_score_detokenize's; also
+ * M2M_ERR_INVALID: lp_row_stride < L, a log-probability offset beyond int32, a null logprobs_dev or note_lp_dev.
+ */
+int m2m_score_detokenize_scored(const int64_t* ids_dev, int R, int L, int64_t row_stride, int64_t steps_per_row,
+                                int pitch_offset, int time_offset, int vocab_size,
+                                const float* logprobs_dev, int64_t lp_row_stride, float min_logprob,
+                                int32_t* notes_dev, int32_t* counts_dev, float* note_lp_dev, void* stream);
+
+/*
  * evaluation.extract_midi_melody + the integer core of melody_chroma_accuracy, per timeline.  The output notes are
  * m2m_score_detokenize's (seconds = index * time_step); row r belongs to timeline r, or every row to timeline 0 when sequential.
  * labels_dev [3, n_labels] float64: starts, ends, pitches (whole numbers 0..127) of the label notes, those of timeline t at

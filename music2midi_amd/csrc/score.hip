@@ -10,6 +10,9 @@
 //           event to its pitch's chain.  All lanes then close the notes: note n takes the first event of its pitch's chain, after
 //           the one it was linked to, whose time is later than its onset - the event that closes it on the host, where an OFFSET
 //           closes every open earlier note of the pitch.  A block scan compacts the closed notes in emission order.
+//           The scored form (m2m_score_detokenize_scored) is the same body with the tokens' log-probabilities staged next to the
+//           ids: the walking lane files (lp[time] + lp[mode]) + lp[pitch] with every note and every OFFSET event, the closing pass
+//           gives a note its event's sum and drops it when on + off < min_logprob, before the scan.
 //   counts  grid (frame tiles, timelines).  A workgroup reads its timeline's notes twice: the largest per-note frame count is
 //           n_frames (monotone in the end time), then every note raises the pitch of the frames it covers inside the tile with LDS
 //           integer maxima, labels and output side by side; the n_frames - 1 cut and the two counts follow from the tile in LDS, one
@@ -45,9 +48,14 @@ __device__ inline int sc_pos_capped(double t, int cap) {
   return f >= (double)cap ? cap : (int)f;
 }
 
+// SCORED: lp is the log-probability of every id, column-aligned.  Every sum below is one rounded float32 add, in the order of
+// music2midi_amd/confidence.py (note_logprobs): (time + mode) + pitch per emission, on + off per note; contraction is off above.
+template <bool SCORED>
 __global__ __launch_bounds__(SC_THREADS) void sc_detok_kernel(const int64_t* __restrict__ ids, int L, int64_t row_stride,
                                                               int64_t steps_per_row, int pitch_offset, int time_offset, int vocab_size,
-                                                              int32_t* __restrict__ notes, int32_t* __restrict__ counts) {
+                                                              const float* __restrict__ lp, int64_t lp_row_stride, float min_logprob,
+                                                              int32_t* __restrict__ notes, int32_t* __restrict__ counts,
+                                                              float* __restrict__ note_lp) {
   __shared__ __attribute__((aligned(16))) uint16_t tok[SC_MAX_L];
   __shared__ int note_t[SC_MAX_L];          // onset index of note n
   __shared__ int note_e[SC_MAX_L];          // offset index, -1 = never closed
@@ -58,6 +66,12 @@ __global__ __launch_bounds__(SC_THREADS) void sc_detok_kernel(const int64_t* __r
   __shared__ short first_off[128], last_off[128];
   __shared__ int scan[SC_THREADS];
   __shared__ int s_bad, s_notes;
+  // scored only (24 KiB on top of the 39.5 KiB above: 63.5 KiB of the 64 KiB a workgroup may declare)
+  constexpr int SC_LP = SCORED ? SC_MAX_L : 4;
+  __shared__ __attribute__((aligned(16))) float tok_lp[SC_LP];   // lp of id i; after the walk: the offset part of note n
+  __shared__ float note_on[SC_LP];          // onset part of note n
+  __shared__ float off_lp[SC_LP];           // sum of OFFSET event k
+  float* const note_off = tok_lp;
 
   const int r = blockIdx.x, tid = threadIdx.x;
   const int64_t* row = ids + (int64_t)r * row_stride;
@@ -73,6 +87,7 @@ __global__ __launch_bounds__(SC_THREADS) void sc_detok_kernel(const int64_t* __r
       if (v < 0 || v >= (int64_t)vocab_size) { bad = true; v = SC_EOS; }
     }
     tok[i] = (uint16_t)v;
+    if constexpr (SCORED) tok_lp[i] = i < L ? lp[(int64_t)r * lp_row_stride + i] : 0.0f;
   }
   if (bad) s_bad = 1;
   __syncthreads();
@@ -84,10 +99,16 @@ __global__ __launch_bounds__(SC_THREADS) void sc_detok_kernel(const int64_t* __r
   if (tid == 0) {
     const int start = (int)((int64_t)r * steps_per_row);
     int time_idx = -1, mode = -1, pitch = -1, nn = 0, no = 0;
+    float time_lp = 0.0f, mode_lp = 0.0f, pitch_lp = 0.0f;          // lp of the latest time / mode / pitch token
     bool done = false;
     for (int i = 0; i < Lp && !done; i += 8) {
       const uint4 w = *reinterpret_cast<const uint4*>(&tok[i]);
       const uint32_t words[4] = {w.x, w.y, w.z, w.w};
+      float lps[8] = {};
+      if constexpr (SCORED) {
+        const float4 a = *reinterpret_cast<const float4*>(&tok_lp[i]), b = *reinterpret_cast<const float4*>(&tok_lp[i + 4]);
+        lps[0] = a.x; lps[1] = a.y; lps[2] = a.z; lps[3] = a.w; lps[4] = b.x; lps[5] = b.y; lps[6] = b.z; lps[7] = b.w;
+      }
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const int t = (int)((words[k >> 1] >> (16 * (k & 1))) & 0xFFFFu);
@@ -97,14 +118,21 @@ __global__ __launch_bounds__(SC_THREADS) void sc_detok_kernel(const int64_t* __r
         else if (t == SC_OFFSET) mode = 0;
         if (t >= time_offset) { time_idx = start + (t - time_offset); mode = -1; pitch = -1; }
         else if (t >= pitch_offset) pitch = t - pitch_offset;
+        if constexpr (SCORED) {
+          if (t >= time_offset) time_lp = lps[k];
+          else if (t >= pitch_offset) pitch_lp = lps[k];
+          else if (t <= SC_OFFSET) mode_lp = lps[k];                // ONSET, OFFSET
+        }
         if (time_idx == -1 || mode == -1 || pitch == -1) continue;
         if (mode == 1) {
           note_t[nn] = time_idx;
           note_p[nn] = (unsigned char)pitch;
           note_link[nn] = last_off[pitch];
+          if constexpr (SCORED) note_on[nn] = (time_lp + mode_lp) + pitch_lp;
           ++nn;
         } else {
           off_t[no] = time_idx;
+          if constexpr (SCORED) off_lp[no] = (time_lp + mode_lp) + pitch_lp;
           off_next[no] = -1;
           const int l = last_off[pitch];
           if (l < 0) first_off[pitch] = (short)no;
@@ -125,7 +153,15 @@ __global__ __launch_bounds__(SC_THREADS) void sc_detok_kernel(const int64_t* __r
     const int l = note_link[n], on = note_t[n];
     int k = l < 0 ? first_off[note_p[n]] : off_next[l];
     while (k >= 0 && off_t[k] <= on) k = off_next[k];
-    note_e[n] = k >= 0 ? off_t[k] : -1;
+    int e = k >= 0 ? off_t[k] : -1;
+    if constexpr (SCORED) {
+      if (k >= 0) {                           // the filter: dropped iff on + off < min_logprob (a NaN total is kept)
+        const float off = off_lp[k];
+        if (note_on[n] + off < min_logprob) e = -1;
+        note_off[n] = off;                    // tok_lp is dead: the walk ended before the barrier above
+      }
+    }
+    note_e[n] = e;
   }
   __syncthreads();
 
@@ -154,6 +190,11 @@ __global__ __launch_bounds__(SC_THREADS) void sc_detok_kernel(const int64_t* __r
       out[pos * 3 + 0] = note_t[n];
       out[pos * 3 + 1] = note_e[n];
       out[pos * 3 + 2] = note_p[n];
+      if constexpr (SCORED) {
+        float* out_lp = note_lp + (int64_t)r * L * 2;
+        out_lp[pos * 2 + 0] = note_on[n];
+        out_lp[pos * 2 + 1] = note_off[n];
+      }
       ++pos;
     }
   }
@@ -253,25 +294,50 @@ extern "C" int64_t m2m_score_frame_count(double end_seconds) {
   return f >= 9.0e18 ? INT64_MAX : (int64_t)f;
 }
 
+// the checks the two detokenise exports share: 0, or M2M_ERR_INVALID with the message set under the export's name
+static int sc_detok_args(const char* who, int R, int L, int64_t row_stride, int64_t steps_per_row, int pitch_offset, int time_offset,
+                         int vocab_size) {
+  M2M_REQUIRE(R >= 1 && R <= M2M_SCORE_MAX_ROWS, "%s: %d rows out of range (1..%d)", who, R, M2M_SCORE_MAX_ROWS);
+  M2M_REQUIRE(L >= 1 && L <= M2M_SCORE_MAX_TOKENS, "%s: L=%d out of range (1..%d)", who, L, M2M_SCORE_MAX_TOKENS);
+  M2M_REQUIRE(row_stride >= L, "%s: row stride %lld below L=%d", who, (long long)row_stride, L);
+  M2M_REQUIRE(vocab_size >= 1 && vocab_size <= 4096, "%s: vocab_size %d out of range (1..4096)", who, vocab_size);
+  M2M_REQUIRE(pitch_offset >= 5, "%s: pitch_offset %d below the 5 special ids", who, pitch_offset);
+  M2M_REQUIRE(time_offset > pitch_offset && time_offset - pitch_offset <= 128, "%s: %d pitch ids out of range (1..128)", who,
+              time_offset - pitch_offset);
+  M2M_REQUIRE(time_offset <= vocab_size, "%s: time_offset %d beyond vocab_size %d", who, time_offset, vocab_size);
+  M2M_REQUIRE(steps_per_row >= 0 && steps_per_row <= INT32_MAX, "%s: steps_per_row %lld out of range", who, (long long)steps_per_row);
+  M2M_REQUIRE((int64_t)(R - 1) * steps_per_row + (int64_t)(vocab_size - time_offset) <= (int64_t)INT32_MAX,
+              "%s: time index of row %d does not fit in int32 (steps_per_row %lld)", who, R - 1, (long long)steps_per_row);
+  M2M_REQUIRE((int64_t)(R - 1) * row_stride + L <= (int64_t)INT32_MAX, "%s: the id tensor does not fit in int32 elements", who);
+  return M2M_OK;
+}
+
 extern "C" int m2m_score_detokenize(const int64_t* ids_dev, int R, int L, int64_t row_stride, int64_t steps_per_row, int pitch_offset,
                                     int time_offset, int vocab_size, int32_t* notes_out_dev, int32_t* counts_out_dev, void* stream) {
   // every refusal is made on the arguments alone, before the first HIP call
-  M2M_REQUIRE(R >= 1 && R <= M2M_SCORE_MAX_ROWS, "m2m_score_detokenize: %d rows out of range (1..%d)", R, M2M_SCORE_MAX_ROWS);
-  M2M_REQUIRE(L >= 1 && L <= M2M_SCORE_MAX_TOKENS, "m2m_score_detokenize: L=%d out of range (1..%d)", L, M2M_SCORE_MAX_TOKENS);
-  M2M_REQUIRE(row_stride >= L, "m2m_score_detokenize: row stride %lld below L=%d", (long long)row_stride, L);
-  M2M_REQUIRE(vocab_size >= 1 && vocab_size <= 4096, "m2m_score_detokenize: vocab_size %d out of range (1..4096)", vocab_size);
-  M2M_REQUIRE(pitch_offset >= 5, "m2m_score_detokenize: pitch_offset %d below the 5 special ids", pitch_offset);
-  M2M_REQUIRE(time_offset > pitch_offset && time_offset - pitch_offset <= 128,
-              "m2m_score_detokenize: %d pitch ids out of range (1..128)", time_offset - pitch_offset);
-  M2M_REQUIRE(time_offset <= vocab_size, "m2m_score_detokenize: time_offset %d beyond vocab_size %d", time_offset, vocab_size);
-  M2M_REQUIRE(steps_per_row >= 0 && steps_per_row <= INT32_MAX, "m2m_score_detokenize: steps_per_row %lld out of range",
-              (long long)steps_per_row);
-  M2M_REQUIRE((int64_t)(R - 1) * steps_per_row + (int64_t)(vocab_size - time_offset) <= (int64_t)INT32_MAX,
-              "m2m_score_detokenize: time index of row %d does not fit in int32 (steps_per_row %lld)", R - 1, (long long)steps_per_row);
-  M2M_REQUIRE((int64_t)(R - 1) * row_stride + L <= (int64_t)INT32_MAX, "m2m_score_detokenize: the id tensor does not fit in int32 elements");
+  if (const int st = sc_detok_args("m2m_score_detokenize", R, L, row_stride, steps_per_row, pitch_offset, time_offset, vocab_size)) return st;
   M2M_REQUIRE(ids_dev && notes_out_dev && counts_out_dev, "m2m_score_detokenize: null ids / notes / counts");
-  hipLaunchKernelGGL(sc_detok_kernel, dim3((unsigned)R), dim3(SC_THREADS), 0, (hipStream_t)stream, ids_dev, L, row_stride, steps_per_row,
-                     pitch_offset, time_offset, vocab_size, notes_out_dev, counts_out_dev);
+  hipLaunchKernelGGL(sc_detok_kernel<false>, dim3((unsigned)R), dim3(SC_THREADS), 0, (hipStream_t)stream, ids_dev, L, row_stride,
+                     steps_per_row, pitch_offset, time_offset, vocab_size, (const float*)nullptr, (int64_t)0, 0.0f, notes_out_dev,
+                     counts_out_dev, (float*)nullptr);
+  M2M_CHECK_HIP(hipGetLastError());
+  return M2M_OK;
+}
+
+extern "C" int m2m_score_detokenize_scored(const int64_t* ids_dev, int R, int L, int64_t row_stride, int64_t steps_per_row,
+                                           int pitch_offset, int time_offset, int vocab_size, const float* logprobs_dev,
+                                           int64_t lp_row_stride, float min_logprob, int32_t* notes_dev, int32_t* counts_dev,
+                                           float* note_lp_dev, void* stream) {
+  const char* who = "m2m_score_detokenize_scored";
+  if (const int st = sc_detok_args(who, R, L, row_stride, steps_per_row, pitch_offset, time_offset, vocab_size)) return st;
+  M2M_REQUIRE(lp_row_stride >= L, "%s: log-probability row stride %lld below L=%d", who, (long long)lp_row_stride, L);
+  M2M_REQUIRE((int64_t)(R - 1) * lp_row_stride + L <= (int64_t)INT32_MAX, "%s: the log-probability tensor does not fit in int32 elements",
+              who);
+  M2M_REQUIRE(ids_dev && notes_dev && counts_dev, "%s: null ids / notes / counts", who);
+  M2M_REQUIRE(logprobs_dev && note_lp_dev, "%s: null logprobs / note_lp", who);
+  hipLaunchKernelGGL(sc_detok_kernel<true>, dim3((unsigned)R), dim3(SC_THREADS), 0, (hipStream_t)stream, ids_dev, L, row_stride,
+                     steps_per_row, pitch_offset, time_offset, vocab_size, logprobs_dev, lp_row_stride, min_logprob, notes_dev, counts_dev,
+                     note_lp_dev);
   M2M_CHECK_HIP(hipGetLastError());
   return M2M_OK;
 }

@@ -83,11 +83,16 @@ def evaluate_batch(targets: Iterable, outputs: Iterable) -> float:
     return melody_chroma_accuracy(np.concatenate(ts), np.concatenate(os_))
 
 
-def evaluate_tokens(tokenizer, token_ids, notes_batch, mode: str = "batched", duration_per_batch=None) -> float:
+def evaluate_tokens(tokenizer, token_ids, notes_batch, mode: str = "batched", duration_per_batch=None, token_logprobs=None,
+                    min_confidence: float = 0.0) -> float:
     """``evaluate_batch(numpy_to_midi(labels), numpy_to_midi(tokenizer.decode(token_ids, mode, duration_per_batch)))`` for token ids
     that are on the GPU, computed there (``music2midi_amd.scoring``, csrc/score.hip): the same float, not a close one - for integer
     pitches the 50-cent octave-folded test is "the pitches differ by a multiple of 12", so the score is a ratio of two frame counts.
     ``notes_batch``: one label array per row, or ONE array in ``sequential`` mode.  ``ValueError`` for labels the device path does
-    not take (``scoring.labels_eligible``)."""
+    not take (``scoring.labels_eligible``).  With ``token_logprobs`` (the log-probability of every id, column-aligned) only the
+    decoded notes of at least ``min_confidence`` are scored (``music2midi_amd.confidence``)."""
     from .scoring import chroma_counts
-    return chroma_counts(tokenizer, token_ids, notes_batch, mode, duration_per_batch).score
+    if token_logprobs is None and not min_confidence > 0:
+        return chroma_counts(tokenizer, token_ids, notes_batch, mode, duration_per_batch).score
+    return chroma_counts(tokenizer, token_ids, notes_batch, mode, duration_per_batch, token_logprobs=token_logprobs,
+                         min_confidence=min_confidence).score

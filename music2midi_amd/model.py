@@ -21,6 +21,7 @@ from . import distributed as D
 from .accumulation import check_accumulate_grad_batches, micro_step, windows
 from .audio import load_audio as _load_audio
 from .checkpoint import load_t5_state, read_checkpoint
+from .confidence import confidence_velocities, decode_with_confidence, min_logprob
 from .config import inference_beams, load_config
 from .evaluation import evaluate_batch, evaluate_tokens
 from .input import ModelInputs
@@ -62,6 +63,30 @@ def _score_on_host(tokenizer, token_ids, notes_batch):
     predicted = [numpy_to_midi(n) for n in tokenizer.decode(token_ids, mode="batched")]
     wanted = [numpy_to_midi(n) for n in notes_batch]
     return evaluate_batch(wanted, predicted), predicted, wanted
+
+
+def _scored_decode(model, config, grammar_kwargs: dict, inputs, max_length: int):
+    """(ids [B, n], log-probabilities [B, n]) of one greedy decode with ``output_logprobs=True``: ``generate`` returns the
+    log-probability of ids[:, i + 1] in column i, so one leading 0.0 column (the start token's) aligns column i with ids[:, i]."""
+    if inference_beams(config):
+        raise ValueError("per-note confidence needs the log-probability of every token; with inference.num_beams > 1 the beam search "
+                         "returns sequences_scores only")
+    out = model.generate(inputs, max_length=max_length, return_dict_in_generate=True, output_logprobs=True, **grammar_kwargs)
+    return out.sequences, torch.nn.functional.pad(out.logprobs, (1, 0), value=0.0)
+
+
+def _min_note_confidence(config, min_confidence: Optional[float]) -> float:
+    """The threshold of a call: the argument, else ``config.inference.min_note_confidence`` (absent: 0.0, every note is kept);
+    ``ValueError`` for a value above 1 or NaN."""
+    if min_confidence is None:
+        min_confidence = config.inference.get("min_note_confidence", 0.0)
+    min_logprob(min_confidence)
+    return float(min_confidence)
+
+
+def _single_process(what: str, instead: str) -> None:
+    if D.dist.is_available() and D.dist.is_initialized() and D.dist.get_world_size() > 1:
+        raise NotImplementedError(f"{what} runs on one GPU: with a process group, {instead}")
 
 
 def _on_device_scorable(token_ids, label_arrays) -> bool:
@@ -374,16 +399,30 @@ class Music2MIDI(nn.Module):
     def score_batch(self, inputs: ModelInputs) -> float:
         """``evaluate_batch(inputs)[0]`` without the host: the same decode, then detokenising, melody and counts on the device
         (``evaluation.evaluate_tokens``) - the same float.  Labels the device path does not take, or ids that are not on a GPU,
-        are scored on the host from the same ids."""
+        are scored on the host from the same ids.  With ``config.inference.min_note_confidence`` > 0 the decode also returns the
+        tokens' log-probabilities and only the notes of at least that confidence are scored (``music2midi_amd.confidence``)."""
+        floor = _min_note_confidence(self.config, None)
+        if floor > 0:
+            budget = 4 * max(len(n) for n in inputs.notes_batch)
+            token_ids, lps = _scored_decode(self.model, self.config, self._grammar_kwargs(), inputs, budget)
+            if _on_device_scorable(token_ids, inputs.notes_batch):
+                return evaluate_tokens(self.model.tokenizer, token_ids, inputs.notes_batch, token_logprobs=lps, min_confidence=floor)
+            decoded, _ = decode_with_confidence(self.model.tokenizer, token_ids, lps, mode="batched", min_confidence=floor)
+            return float(evaluate_batch([numpy_to_midi(n) for n in inputs.notes_batch], [numpy_to_midi(n) for n in decoded]))
         token_ids = _labelled_token_ids(self.model, self.config, self._grammar_kwargs(), inputs)
         if _on_device_scorable(token_ids, inputs.notes_batch):
             return evaluate_tokens(self.model.tokenizer, token_ids, inputs.notes_batch)
         return float(_score_on_host(self.model.tokenizer, token_ids, inputs.notes_batch)[0])
 
     def generate(self, audio_path: Optional[Union[str, Path]] = None, audio_y: Optional[np.ndarray] = None,
-                 sr: Optional[int] = None, cond_index: Optional[list] = None):
-        """Specify either audio_path or audio_y as input; returns a MIDI object."""
-        return numpy_to_midi(self.generate_notes(audio_path, audio_y, sr, cond_index))
+                 sr: Optional[int] = None, cond_index: Optional[list] = None, confidence_velocity: bool = False):
+        """Specify either audio_path or audio_y as input; returns a MIDI object.  ``confidence_velocity=True`` writes every note's
+        confidence into its velocity: ``max(1, min(127, int(round(127 * confidence))))``."""
+        if not confidence_velocity:
+            return numpy_to_midi(self.generate_notes(audio_path, audio_y, sr, cond_index))
+        notes, confidence = self.generate_notes(audio_path, audio_y, sr, cond_index, return_confidence=True)
+        notes[:, 3] = confidence_velocities(confidence)
+        return numpy_to_midi(notes)
 
     # The three steps below are what ref model.py:67-140 does inline: validate/load, cut the song into
     # whole segments (zero-padded tail), decode the segments in chunks and stitch the notes together.
@@ -400,10 +439,25 @@ class Music2MIDI(nn.Module):
     def _segment_length(self) -> int:
         return int(self.config.model.sample_rate * self.config.dataset.segment_duration)
 
-    def generate_notes(self, audio_path=None, audio_y=None, sr=None, cond_index=None) -> np.ndarray:
-        """Note array [n, 4] (onset_s, offset_s, pitch, velocity) for a whole recording."""
+    def generate_notes(self, audio_path=None, audio_y=None, sr=None, cond_index=None, return_confidence: bool = False,
+                       min_confidence: Optional[float] = None):
+        """Note array [n, 4] (onset_s, offset_s, pitch, velocity) for a whole recording.  ``return_confidence=True`` returns
+        ``(notes, confidence [n] float64)``: the probability the model gave the six tokens that made each note
+        (``music2midi_amd.confidence``).  ``min_confidence`` (``None``: ``config.inference.min_note_confidence``, absent 0.0) drops
+        the notes below it.  Either one decodes with ``output_logprobs=True`` and detokenises on the device; greedy, one GPU."""
+        floor = _min_note_confidence(self.config, min_confidence)
         padded, seg = self._padded_segments(audio_path, audio_y, sr)
-        return self.sample_tokens(padded, seg, split_duration=self.config.dataset.segment_duration, cond_index=cond_index)
+        if not return_confidence and not floor > 0:
+            return self.sample_tokens(padded, seg, split_duration=self.config.dataset.segment_duration, cond_index=cond_index)
+        token_ids, lps = self.sample_scored_rows(padded, seg, cond_index)
+        duration = self.config.dataset.segment_duration
+        if token_ids.is_cuda:
+            from .scoring import detokenize_scored
+            dn = detokenize_scored(self.model.tokenizer, token_ids, lps, "sequential", duration, floor)
+            notes, confidence = dn.to_numpy(), dn.confidence_numpy()
+        else:
+            notes, confidence = decode_with_confidence(self.model.tokenizer, token_ids, lps, "sequential", duration, floor)
+        return (notes, confidence) if return_confidence else notes
 
     def _device_ingest(self, audio_path, audio_y) -> bool:
         """The device ingest takes the call when ``config.inference.device_ingest`` is set (absent: off), the audio comes as a
@@ -455,31 +509,61 @@ class Music2MIDI(nn.Module):
     @torch.no_grad()
     def sample_token_rows(self, waveform: torch.Tensor, split_size: int, cond_index: Optional[list] = None) -> list:
         """The token row of every segment, in segment order, not detokenised (rows of different chunks may differ in width)."""
-        pieces = torch.split(waveform, split_size)
         decode, decode_kwargs = _decode_entry(self.model, self.config, self._grammar_kwargs())
         per_call = max(1, int(self.config.inference.batch_size) // int(decode_kwargs.get("num_beams", 1)))
         token_rows = []
+        for inputs in self._segment_chunks(waveform, split_size, cond_index, per_call):
+            # with a process group (one process per GPU) the chunk's segments are sharded over the ranks and the ids
+            # all-gathered back in segment order; a single process decodes the chunk itself
+            ids = D.generate_sharded(decode, inputs, max_length=1024, pad_id=self.model.geometry.pad_token_id, **decode_kwargs)
+            token_rows.extend(ids.unbind(0))
+        return token_rows
+
+    def _segment_chunks(self, waveform: torch.Tensor, split_size: int, cond_index: Optional[list], per_call: int):
+        """The segments of a recording as the inputs of one decode call each, ``per_call`` segments at a time."""
+        pieces = torch.split(waveform, split_size)
         for first in range(0, len(pieces), per_call):
             group = pieces[first:first + per_call]
             longest = max(p.shape[0] for p in group)
             wav = waveform.new_zeros((len(group), longest)).to(self.device)
             for row, piece in enumerate(group):                      # right-pad a ragged last piece with zeros
                 wav[row, : piece.shape[0]] = piece
-            # with a process group (one process per GPU) the chunk's segments are sharded over the ranks and the ids
-            # all-gathered back in segment order; a single process decodes the chunk itself
-            ids = D.generate_sharded(decode, ModelInputs(input_waveform=wav, cond_index=self._cond_rows(len(group), cond_index)),
-                                     max_length=1024, pad_id=self.model.geometry.pad_token_id, **decode_kwargs)
-            token_rows.extend(ids.unbind(0))
-        return token_rows
+            yield ModelInputs(input_waveform=wav, cond_index=self._cond_rows(len(group), cond_index))
 
-    def score_recording(self, label_notes: np.ndarray, audio_path=None, audio_y=None, sr=None, cond_index=None) -> float:
+    @torch.no_grad()
+    def sample_scored_rows(self, waveform: torch.Tensor, split_size: int, cond_index: Optional[list] = None):
+        """(ids [segments, W] int64, log-probabilities [segments, W] float32) of every segment, in segment order: the chunks of
+        ``sample_token_rows`` decoded with ``output_logprobs=True`` and padded to one width - PAD for the ids, 0.0 for the
+        log-probabilities; column i of the second belongs to column i of the first.  Greedy decoding on one GPU: beams raise
+        ``ValueError``, a process group of more than one rank ``NotImplementedError``."""
+        _single_process("per-note confidence", "decode on one rank (the log-probabilities are not gathered across ranks)")
+        grammar_kwargs, pad = self._grammar_kwargs(), self.model.geometry.pad_token_id
+        parts = [_scored_decode(self.model, self.config, grammar_kwargs, inputs, 1024)
+                 for inputs in self._segment_chunks(waveform, split_size, cond_index, max(1, int(self.config.inference.batch_size)))]
+        width = max(int(ids.shape[1]) for ids, _ in parts)
+        token_ids = torch.cat([torch.nn.functional.pad(ids, (0, width - int(ids.shape[1])), value=pad) for ids, _ in parts])
+        lps = torch.cat([torch.nn.functional.pad(lp, (0, width - int(lp.shape[1])), value=0.0) for _, lp in parts])
+        return token_ids, lps
+
+    def score_recording(self, label_notes: np.ndarray, audio_path=None, audio_y=None, sr=None, cond_index=None,
+                        min_confidence: Optional[float] = None) -> float:
         """Chroma accuracy of a whole recording against its label notes: ``generate_notes``' segmentation and chunked decode, then
         the sequential detokenising and the scoring on the device.  Equals
         ``evaluate_batch([numpy_to_midi(label_notes)], [self.generate(...)])``; labels the device path does not take, or ids that
-        are not on a GPU, are scored on the host from the same ids.  One GPU only."""
-        if D.dist.is_available() and D.dist.is_initialized() and D.dist.get_world_size() > 1:
-            raise NotImplementedError("score_recording runs on one GPU: with a process group, score generate()'s notes on the host")
+        are not on a GPU, are scored on the host from the same ids.  One GPU only.  ``min_confidence`` (``None``:
+        ``config.inference.min_note_confidence``) scores only the notes of at least that confidence, as ``generate_notes`` drops
+        them; the filter runs on the device, so a sweep over thresholds copies three integers per call to the host."""
+        _single_process("score_recording", "score generate()'s notes on the host")
+        floor = _min_note_confidence(self.config, min_confidence)
         padded, seg = self._padded_segments(audio_path, audio_y, sr)
+        if floor > 0:
+            token_ids, lps = self.sample_scored_rows(padded, seg, cond_index)
+            duration = self.config.dataset.segment_duration
+            if _on_device_scorable(token_ids, [label_notes]):
+                return evaluate_tokens(self.model.tokenizer, token_ids, label_notes, mode="sequential", duration_per_batch=duration,
+                                       token_logprobs=lps, min_confidence=floor)
+            decoded, _ = decode_with_confidence(self.model.tokenizer, token_ids, lps, "sequential", duration, floor)
+            return float(evaluate_batch([numpy_to_midi(label_notes)], [numpy_to_midi(decoded)]))
         rows = self.sample_token_rows(padded, seg, cond_index=cond_index)
         duration = self.config.dataset.segment_duration
         width = max(int(r.shape[0]) for r in rows)

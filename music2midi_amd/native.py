@@ -126,6 +126,8 @@ _SIGNATURES = {
     "m2m_score_frame_count": (C.c_int64, [C.c_double]),
     "m2m_score_detokenize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
+    "m2m_score_detokenize_scored": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m2m_score_chroma_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "m2m_ingest_resampled_length": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),

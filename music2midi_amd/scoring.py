@@ -6,6 +6,8 @@ same pipeline runs as two HIP kernels (csrc/score.hip) on the current stream and
 notes, the same counts, the same float.
 
     detokenize(tokenizer, token_ids [R, L] cuda int64, mode, duration_per_batch)   -> DeviceNotes   (.to_numpy() == tokenizer.decode(...))
+    detokenize_scored(tokenizer, token_ids, token_logprobs [R, L] cuda float32, mode, duration_per_batch, min_confidence)
+                                                                                   -> DeviceNotes   (+ .note_lp, .confidence_numpy())
     chroma_counts(tokenizer, token_ids, notes_batch, mode, duration_per_batch)     -> ChromaCounts  (.correct .voiced .frames .score)
     labels_eligible(notes_batch)                                                   -> bool
 
@@ -53,11 +55,15 @@ def _vocab_size(tokenizer, vocab_size: Optional[int]) -> int:
 
 class DeviceNotes:
     """The notes of every row, on the device: ``notes`` [R, L, 3] int32 (onset index, offset index, pitch), the first
-    ``counts[r]`` of row r in emission order; ``counts`` [R] int32, -1 for a row that held an id outside the vocabulary."""
+    ``counts[r]`` of row r in emission order; ``counts`` [R] int32, -1 for a row that held an id outside the vocabulary.
+    From ``detokenize_scored`` also ``note_lp`` [R, L, 2] float32: the onset and offset parts of the notes' log-probability
+    (``music2midi_amd.confidence``), side by side with ``notes``; ``None`` otherwise."""
 
-    def __init__(self, notes: torch.Tensor, counts: torch.Tensor, mode: str, time_step: float, default_velocity, steps_per_row: int):
+    def __init__(self, notes: torch.Tensor, counts: torch.Tensor, mode: str, time_step: float, default_velocity, steps_per_row: int,
+                 note_lp: Optional[torch.Tensor] = None):
         self.notes, self.counts, self.mode = notes, counts, mode
         self.time_step, self.default_velocity, self.steps_per_row = time_step, default_velocity, steps_per_row
+        self.note_lp = note_lp
 
     def to_numpy(self) -> Union[List[np.ndarray], np.ndarray]:
         """What ``tokenizer.decode(token_ids, mode, duration_per_batch)`` returns: a list of [n, 4] float64 arrays, or their
@@ -74,6 +80,23 @@ class DeviceNotes:
             parts.append(out)
         return parts if self.mode == "batched" else np.concatenate(parts)
 
+    def note_lp_numpy(self) -> Union[List[np.ndarray], np.ndarray]:
+        """The (onset part, offset part) float32 pairs of the notes ``to_numpy()`` returns, [n, 2] per row or concatenated."""
+        if self.note_lp is None:
+            raise ValueError("these notes carry no log-probabilities: they do not come from detokenize_scored")
+        counts = self.counts.cpu().numpy()
+        _raise_for_bad_rows(counts)
+        lp = self.note_lp.cpu().numpy()
+        parts = [lp[r, :c].copy() for r, c in enumerate(counts)]
+        return parts if self.mode == "batched" else np.concatenate(parts)
+
+    def confidence_numpy(self) -> Union[List[np.ndarray], np.ndarray]:
+        """``exp`` in float64 of the notes' float32 total (onset part + offset part), one value per note of ``to_numpy()``, in the
+        list / concatenated shape of the mode: what ``confidence.decode_with_confidence`` returns second."""
+        from .confidence import confidence_of
+        lp = self.note_lp_numpy()
+        return [confidence_of(p) for p in lp] if self.mode == "batched" else confidence_of(lp)
+
 
 def _raise_for_bad_rows(counts: np.ndarray) -> None:
     bad = np.flatnonzero(counts < 0)
@@ -84,6 +107,26 @@ def _raise_for_bad_rows(counts: np.ndarray) -> None:
 def detokenize(tokenizer, token_ids: torch.Tensor, mode: str = "batched", duration_per_batch: Optional[float] = None,
                vocab_size: Optional[int] = None) -> DeviceNotes:
     """``tokenizer.decode`` on the device, one workgroup per row; nothing is copied to the host until ``to_numpy()``."""
+    return _detokenize(tokenizer, token_ids, mode, duration_per_batch, vocab_size, None, 0.0)
+
+
+def detokenize_scored(tokenizer, token_ids: torch.Tensor, token_logprobs: torch.Tensor, mode: str = "batched",
+                      duration_per_batch: Optional[float] = None, min_confidence: float = 0.0,
+                      vocab_size: Optional[int] = None) -> DeviceNotes:
+    """``confidence.decode_with_confidence`` on the device: ``detokenize`` with the log-probability of every id
+    (``token_logprobs`` [R, L] CUDA float32, column-aligned, unit inner stride).  The notes whose float32 total is below
+    ``float32(log(min_confidence))`` are dropped on the device (a NaN total is kept); ``to_numpy()`` and ``confidence_numpy()``
+    give the kept notes and their confidences, ``note_lp`` the two float32 parts."""
+    from .confidence import min_logprob
+    floor = float(min_logprob(min_confidence))
+    if not (isinstance(token_logprobs, torch.Tensor) and token_logprobs.is_cuda and token_logprobs.dim() == 2
+            and token_logprobs.dtype == torch.float32):
+        raise ValueError("detokenize_scored: token_logprobs must be a CUDA float32 tensor [rows, length]")
+    return _detokenize(tokenizer, token_ids, mode, duration_per_batch, vocab_size, token_logprobs, floor)
+
+
+def _detokenize(tokenizer, token_ids, mode, duration_per_batch, vocab_size, token_logprobs, floor: float) -> DeviceNotes:
+    scored = token_logprobs is not None
     steps = _steps_per_row(tokenizer, mode, duration_per_batch)
     velocity = tokenizer.config.default_velocity
     if not velocity > 0:
@@ -92,24 +135,41 @@ def detokenize(tokenizer, token_ids: torch.Tensor, mode: str = "batched", durati
         raise ValueError("detokenize: token_ids must be a CUDA int64 tensor [rows, length]")
     R, L = token_ids.shape
     device = token_ids.device
+    if scored:
+        if tuple(token_logprobs.shape) != (R, L) or token_logprobs.device != device:
+            raise ValueError(f"detokenize_scored: token_logprobs {tuple(token_logprobs.shape)} on {token_logprobs.device} for token_ids "
+                             f"{(R, L)} on {device}")
+        if L > 1 and token_logprobs.stride(1) != 1:
+            raise ValueError("detokenize_scored: token_logprobs must have unit inner stride")
     if R == 0:
         if mode == "sequential":
             raise ValueError("need at least one row to concatenate")
         return DeviceNotes(torch.zeros((0, 1, 3), dtype=torch.int32, device=device), torch.zeros(0, dtype=torch.int32, device=device),
-                           mode, tokenizer.time_step, velocity, steps)
+                           mode, tokenizer.time_step, velocity, steps,
+                           torch.zeros((0, 1, 2), dtype=torch.float32, device=device) if scored else None)
     if L == 0:                                               # PAD is skipped: one column of it decodes as the empty row does
         token_ids, L = token_ids.new_zeros((R, 1)), 1
+        token_logprobs = token_logprobs.new_zeros((R, 1)) if scored else None
     if token_ids.stride(1) != 1:
         token_ids = token_ids.contiguous()
+    if scored and token_logprobs.stride(1) != 1:             # (one column: any stride reads the same element)
+        token_logprobs = token_logprobs.contiguous()
     with torch.cuda.device(device):
         # (sizes the library will refuse are not allocated for: it answers on the arguments alone)
         fits = R <= 65535 and L <= MAX_TOKENS
         notes = torch.empty((R, L, 3) if fits else (1, 1, 3), dtype=torch.int32, device=device)
         counts = torch.empty(R if fits else 1, dtype=torch.int32, device=device)
-        native.check(native.load().m2m_score_detokenize(
+        if not scored:
+            native.check(native.load().m2m_score_detokenize(
+                token_ids.data_ptr(), R, L, token_ids.stride(0), steps, int(tokenizer.pitch_token_offset), int(tokenizer.time_token_offset),
+                _vocab_size(tokenizer, vocab_size), notes.data_ptr(), counts.data_ptr(), native.stream_handle(device)), "m2m_score_detokenize")
+            return DeviceNotes(notes, counts, mode, tokenizer.time_step, velocity, steps)
+        note_lp = torch.empty((R, L, 2) if fits else (1, 1, 2), dtype=torch.float32, device=device)
+        native.check(native.load().m2m_score_detokenize_scored(
             token_ids.data_ptr(), R, L, token_ids.stride(0), steps, int(tokenizer.pitch_token_offset), int(tokenizer.time_token_offset),
-            _vocab_size(tokenizer, vocab_size), notes.data_ptr(), counts.data_ptr(), native.stream_handle(device)), "m2m_score_detokenize")
-    return DeviceNotes(notes, counts, mode, tokenizer.time_step, velocity, steps)
+            _vocab_size(tokenizer, vocab_size), token_logprobs.data_ptr(), token_logprobs.stride(0), floor, notes.data_ptr(),
+            counts.data_ptr(), note_lp.data_ptr(), native.stream_handle(device)), "m2m_score_detokenize_scored")
+    return DeviceNotes(notes, counts, mode, tokenizer.time_step, velocity, steps, note_lp)
 
 
 # ----------------------------------------------------------------------------------------------------------------- labels
@@ -202,11 +262,20 @@ def _enqueue_counts(dn: DeviceNotes, labels_dev: torch.Tensor, offsets_dev: torc
 
 
 def chroma_counts(tokenizer, token_ids: torch.Tensor, notes_batch, mode: str = "batched", duration_per_batch: Optional[float] = None,
-                  vocab_size: Optional[int] = None) -> ChromaCounts:
+                  vocab_size: Optional[int] = None, token_logprobs: Optional[torch.Tensor] = None,
+                  min_confidence: float = 0.0) -> ChromaCounts:
     """The counts of ``evaluation.evaluate_batch(labels, decoded)`` for ids on the device.  ``notes_batch``: one label array per
-    row (``batched``), or ONE array for the whole recording (``sequential``).  One small copy to the host at the end."""
+    row (``batched``), or ONE array for the whole recording (``sequential``).  One small copy to the host at the end.
+    With ``token_logprobs`` the ids are detokenised by ``detokenize_scored`` and only the notes of at least ``min_confidence`` are
+    counted; a threshold without log-probabilities raises ``ValueError``."""
     labels = [notes_batch] if mode == "sequential" else list(notes_batch)
-    dn = detokenize(tokenizer, token_ids, mode, duration_per_batch, vocab_size)
+    if token_logprobs is None:
+        from .confidence import min_logprob
+        if min_logprob(min_confidence) != -np.inf:
+            raise ValueError(f"chroma_counts: min_confidence={min_confidence} needs token_logprobs")
+        dn = detokenize(tokenizer, token_ids, mode, duration_per_batch, vocab_size)
+    else:
+        dn = detokenize_scored(tokenizer, token_ids, token_logprobs, mode, duration_per_batch, min_confidence, vocab_size)
     R = int(dn.counts.shape[0])
     T = 1 if mode == "sequential" else R
     if len(labels) != T:
