@@ -239,6 +239,40 @@ int m2m_score_chroma_counts(const int32_t* notes_dev, const int32_t* counts_dev,
                             const double* labels_dev, const int32_t* label_offsets_dev, int n_labels, int n_timelines, int frame_cap,
                             int32_t* out_dev, void* stream);
 
+#define M2M_SCORE_MAX_THRESHOLDS 64        /* confidence thresholds per m2m_score_note_counts call */
+
+/* The bytes of workspace m2m_score_note_counts needs for these sizes: 36 per label note + 24 per output slot (R * L) +
+ * 8 * n_thresholds * (n_labels + R * L), every array rounded up to 8 bytes.  Host arithmetic; -1 for a size out of range. */
+int64_t m2m_score_note_workspace_bytes(int R, int L, int n_labels, int n_thresholds);
+
+/*
+ * Note-level matching (the definition: music2midi_amd/note_metrics.py, match_counts - the hit rules of
+ * mir_eval.transcription.match_notes and the size of a maximum bipartite matching), per timeline and per confidence threshold.
+ * notes_dev, counts_dev, R, L, sequential, time_step, labels_dev, label_offsets_dev, n_labels and n_timelines are
+ * m2m_score_chroma_counts' (seconds = double(index) * time_step; a note with end <= start does not exist on either side).
+ * A label note r and an output note e hit when their pitches are equal, rint(fabs(r.on - e.on) * 1e6) / 1e6 <= onset_tolerance and,
+ * unless offset_ratio < 0 (onsets only), rint(fabs(r.off - e.off) * 1e6) / 1e6 <= fmax(offset_ratio * (r.off - r.on),
+ * offset_min_tolerance): float64, one rounded operation each, never contracted.
+ * note_lp_dev [R, L, 2] float32 (m2m_score_detokenize_scored's, may be NULL) and min_logprobs_dev [n_thresholds] float32: output
+ * note e counts under threshold k unless float32(on + off) < min_logprobs_dev[k] is true in float32 (a NaN total is kept, -inf
+ * keeps every note).  With note_lp_dev NULL there is one threshold, it keeps every note and min_logprobs_dev is not read (it may
+ * be NULL then, and only then).
+ * workspace_dev: at least m2m_score_note_workspace_bytes(R, L, n_labels, n_thresholds) bytes, 8-byte aligned, the caller's; its
+ * contents are unspecified before and after.  The library allocates nothing.
+ * out_dev [n_timelines, n_thresholds, 3] int32, zeroed on `stream` first: tp = the size of a maximum matching of the hit graph
+ * (exact: augmenting paths per pitch, no cap on the candidates of a note), n_est = the output notes kept under the threshold,
+ * n_ref = the label notes.  A timeline that contains a row whose count is -1 gets tp = -1 (and no counts).  One launch serves all
+ * thresholds.
+ * M2M_ERR_INVALID: R, L, sequential, n_timelines, time_step, n_labels as m2m_score_chroma_counts; n_thresholds outside 1..64;
+ * onset_tolerance or offset_min_tolerance outside [0, 3600] or NaN; offset_ratio NaN or above 1e6; a null notes / counts /
+ * offsets / output pointer; null labels with n_labels > 0; a null note_lp_dev with n_thresholds > 1; a null min_logprobs_dev with
+ * note_lp_dev; a null or misaligned workspace, or workspace_bytes below the need.
+ */
+int m2m_score_note_counts(const int32_t* notes_dev, const int32_t* counts_dev, const float* note_lp_dev, int R, int L, int sequential,
+                          double time_step, const double* labels_dev, const int32_t* label_offsets_dev, int n_labels, int n_timelines,
+                          double onset_tolerance, double offset_ratio, double offset_min_tolerance, const float* min_logprobs_dev,
+                          int n_thresholds, void* workspace_dev, int64_t workspace_bytes, int32_t* out_dev, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Audio ingest: the sample bytes of a WAVE file -> mono fp32 -> another sample rate, zero-padded; replaces, for the files it
  * takes, the host step of ref: music2midi/model.py:83-84 (librosa.load).  The definitions are music2midi_amd/audio.py (read_wav,

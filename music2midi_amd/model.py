@@ -23,7 +23,7 @@ from .audio import load_audio as _load_audio
 from .checkpoint import load_t5_state, read_checkpoint
 from .confidence import confidence_velocities, decode_with_confidence, min_logprob
 from .config import inference_beams, load_config
-from .evaluation import evaluate_batch, evaluate_tokens
+from .evaluation import evaluate_batch, evaluate_tokens, note_scores_host, note_scores_tokens
 from .input import ModelInputs
 from .transformer import T5Transformer
 from .utils import numpy_to_midi
@@ -82,6 +82,13 @@ def _min_note_confidence(config, min_confidence: Optional[float]) -> float:
         min_confidence = config.inference.get("min_note_confidence", 0.0)
     min_logprob(min_confidence)
     return float(min_confidence)
+
+
+def _any_positive(thresholds) -> bool:
+    """True when a sweep needs the tokens' log-probabilities: some threshold keeps less than every note.  ``ValueError`` for a
+    threshold above 1 or NaN, an empty sweep or one longer than the device takes."""
+    from .scoring import threshold_logprobs
+    return bool((threshold_logprobs(thresholds, True, "note_scores") != -np.inf).any())
 
 
 def _single_process(what: str, instead: str) -> None:
@@ -573,3 +580,43 @@ class Music2MIDI(nn.Module):
             return evaluate_tokens(self.model.tokenizer, token_ids, label_notes, mode="sequential", duration_per_batch=duration)
         decoded = self.model.tokenizer.decode(rows, mode="sequential", duration_per_batch=duration)
         return float(evaluate_batch([numpy_to_midi(label_notes)], [numpy_to_midi(decoded)]))
+
+    # -- note-level precision / recall / F1 over confidence thresholds (music2midi_amd.note_metrics) ------------------------
+    @torch.no_grad()
+    def note_scores_batch(self, inputs: ModelInputs, thresholds=None, offset_ratio: Optional[float] = 0.2) -> dict:
+        """Note-level precision, recall and F1 of one labelled batch for every confidence threshold of ``thresholds`` (``None``:
+        ``[0.0]``): ``score_batch``'s decode - with the tokens' log-probabilities when any threshold is positive - then the matching
+        on the device, one launch for all thresholds (``evaluation.note_scores_tokens``).  ``{"precision", "recall", "f1"}`` [K]
+        float64 micro-averaged over the clips, ``{"tp", "n_est", "n_ref"}`` [K] int64.  ``offset_ratio=None`` matches onsets only.
+        Ids that are not on a GPU, or labels the device path does not take, are scored by the definition from the same ids."""
+        _single_process("note_scores_batch", "score the decoded notes on the host")
+        scored = _any_positive(thresholds)
+        tok = self.model.tokenizer
+        if scored:
+            budget = 4 * max(len(n) for n in inputs.notes_batch)
+            token_ids, lps = _scored_decode(self.model, self.config, self._grammar_kwargs(), inputs, budget)
+        else:
+            token_ids, lps = _labelled_token_ids(self.model, self.config, self._grammar_kwargs(), inputs), None
+        score = note_scores_tokens if _on_device_scorable(token_ids, inputs.notes_batch) else note_scores_host
+        return score(tok, token_ids, inputs.notes_batch, "batched", None, token_logprobs=lps, thresholds=thresholds,
+                     offset_ratio=offset_ratio)
+
+    @torch.no_grad()
+    def note_scores_recording(self, label_notes: np.ndarray, audio_path=None, audio_y=None, sr=None, cond_index=None,
+                              thresholds=None, offset_ratio: Optional[float] = 0.2) -> dict:
+        """``note_scores_batch``'s dict for a whole recording against its label notes: ``score_recording``'s segmentation and
+        chunked decode, the sequential detokenising and the matching on the device.  One GPU, greedy when a threshold is positive."""
+        _single_process("note_scores_recording", "score generate()'s notes on the host")
+        scored = _any_positive(thresholds)
+        padded, seg = self._padded_segments(audio_path, audio_y, sr)
+        duration = self.config.dataset.segment_duration
+        if scored:
+            token_ids, lps = self.sample_scored_rows(padded, seg, cond_index)
+        else:
+            rows = self.sample_token_rows(padded, seg, cond_index=cond_index)
+            width = max(int(r.shape[0]) for r in rows)
+            pad = self.model.geometry.pad_token_id
+            token_ids, lps = torch.stack([torch.nn.functional.pad(r, (0, width - int(r.shape[0])), value=pad) for r in rows]), None
+        score = note_scores_tokens if _on_device_scorable(token_ids, [label_notes]) else note_scores_host
+        return score(self.model.tokenizer, token_ids, label_notes, "sequential", duration, token_logprobs=lps, thresholds=thresholds,
+                     offset_ratio=offset_ratio)

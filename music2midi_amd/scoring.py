@@ -9,7 +9,11 @@ notes, the same counts, the same float.
     detokenize_scored(tokenizer, token_ids, token_logprobs [R, L] cuda float32, mode, duration_per_batch, min_confidence)
                                                                                    -> DeviceNotes   (+ .note_lp, .confidence_numpy())
     chroma_counts(tokenizer, token_ids, notes_batch, mode, duration_per_batch)     -> ChromaCounts  (.correct .voiced .frames .score)
+    note_counts(tokenizer, token_ids, notes_batch, ..., token_logprobs, thresholds) -> NoteCounts    (.tp .n_est .n_ref [T, K], .f1 ...)
     labels_eligible(notes_batch)                                                   -> bool
+
+``note_counts`` is the note-level matching of ``music2midi_amd.note_metrics`` (csrc/note_match.hip): one launch for every confidence
+threshold of a sweep, the integers equal to the definition's.
 
 ``batched``: row i is clip i, scored against ``notes_batch[i]``; ``sequential``: the rows are the segments of one recording, scored
 against ONE label array.  ``cutoff_time`` is not supported.  There is no fallback in this module: a missing library or a refused
@@ -301,3 +305,120 @@ def chroma_counts(tokenizer, token_ids: torch.Tensor, notes_batch, mode: str = "
     if (res[:, 2] < 0).any():
         raise native.NativeError(f"m2m_score_chroma_counts: a timeline is longer than its bound of {frame_cap} frames")
     return ChromaCounts(res[:, 0].copy(), res[:, 1].copy(), res[:, 2].copy())
+
+
+# ----------------------------------------------------------------------------------------------------------------- note metrics
+MAX_THRESHOLDS = 64                      # M2M_SCORE_MAX_THRESHOLDS
+
+
+class NoteCounts:
+    """int64 ``tp``, ``n_est``, ``n_ref`` of shape [T, K]: per timeline and per threshold, the size of the maximum matching, the
+    decoded notes kept under the threshold and the label notes (``note_metrics.match_counts``).  ``precision``, ``recall`` and
+    ``f1`` [K] float64 are micro-averaged: the integers are summed over the timelines first; ``per_timeline_f1`` is [T, K]."""
+
+    def __init__(self, tp: np.ndarray, n_est: np.ndarray, n_ref: np.ndarray):
+        self.tp, self.n_est, self.n_ref = tp, n_est, n_ref
+
+    def _micro(self) -> np.ndarray:
+        from .note_metrics import precision_recall_f1
+        sums = zip(self.tp.sum(axis=0).tolist(), self.n_ref.sum(axis=0).tolist(), self.n_est.sum(axis=0).tolist())
+        return np.asarray([precision_recall_f1(*s) for s in sums], dtype=np.float64).reshape(-1, 3)
+
+    @property
+    def precision(self) -> np.ndarray:
+        return self._micro()[:, 0].copy()
+
+    @property
+    def recall(self) -> np.ndarray:
+        return self._micro()[:, 1].copy()
+
+    @property
+    def f1(self) -> np.ndarray:
+        return self._micro()[:, 2].copy()
+
+    @property
+    def per_timeline_f1(self) -> np.ndarray:
+        from .note_metrics import precision_recall_f1
+        out = np.zeros(self.tp.shape, dtype=np.float64)
+        for i in np.ndindex(*self.tp.shape):
+            out[i] = precision_recall_f1(self.tp[i], self.n_ref[i], self.n_est[i])[2]
+        return out
+
+
+def threshold_logprobs(thresholds, scored: bool, who: str = "note_counts") -> np.ndarray:
+    """[K] float32 ``confidence.min_logprob`` of every threshold (``None``: ``[0.0]``); ``ValueError`` for an empty or too long
+    sequence, a threshold that is no probability, or a positive threshold without log-probabilities."""
+    from .confidence import min_logprob
+    values = [0.0] if thresholds is None else [float(c) for c in thresholds]
+    if not 1 <= len(values) <= MAX_THRESHOLDS:
+        raise ValueError(f"{who}: {len(values)} thresholds out of range (1..{MAX_THRESHOLDS})")
+    floors = np.asarray([min_logprob(c) for c in values], dtype=np.float32)
+    if not scored and (floors != -np.inf).any():
+        raise ValueError(f"{who}: thresholds={values} need token_logprobs")
+    return floors
+
+
+def _enqueue_note_counts(dn: DeviceNotes, labels_dev: torch.Tensor, offsets_dev: torch.Tensor, min_logprobs_dev: Optional[torch.Tensor],
+                         onset_tolerance: float, offset_ratio: float, offset_min_tolerance: float) -> torch.Tensor:
+    """The matching kernel on the current stream, for labels and thresholds that are on the device already: [T, K, 3] int32
+    (tp, n_est, n_ref); K = 1 without thresholds.  ``offset_ratio`` < 0: onsets only.  The workspace is torch's."""
+    R, L = int(dn.notes.shape[0]), int(dn.notes.shape[1])
+    T, n_labels = int(offsets_dev.shape[0]) - 1, int(labels_dev.shape[1])
+    K = 1 if min_logprobs_dev is None else int(min_logprobs_dev.shape[0])
+    device = dn.notes.device
+    lib = native.load()
+    need = int(lib.m2m_score_note_workspace_bytes(R, L, n_labels, K))
+    # (sizes the library will refuse are not allocated for: it answers on the arguments alone)
+    workspace = torch.empty(max(need, 8) // 8, dtype=torch.int64, device=device)
+    out = torch.empty((T, K, 3), dtype=torch.int32, device=device)
+    scored = dn.note_lp is not None and min_logprobs_dev is not None
+    native.check(lib.m2m_score_note_counts(
+        dn.notes.data_ptr(), dn.counts.data_ptr(), dn.note_lp.data_ptr() if scored else None, R, L, 1 if dn.mode == "sequential" else 0,
+        float(dn.time_step), labels_dev.data_ptr() if n_labels else None, offsets_dev.data_ptr(), n_labels, T, onset_tolerance,
+        offset_ratio, offset_min_tolerance, min_logprobs_dev.data_ptr() if scored else None, K, workspace.data_ptr(), need,
+        out.data_ptr(), native.stream_handle(device)), "m2m_score_note_counts")
+    return out
+
+
+def note_counts(tokenizer, token_ids: torch.Tensor, notes_batch, mode: str = "batched", duration_per_batch: Optional[float] = None,
+                vocab_size: Optional[int] = None, token_logprobs: Optional[torch.Tensor] = None, thresholds=None,
+                onset_tolerance: float = 0.05, offset_ratio: Optional[float] = 0.2, offset_min_tolerance: float = 0.05) -> NoteCounts:
+    """``note_metrics.match_counts(labels, decoded notes of at least thresholds[k])`` for ids on the device, for every timeline and
+    every threshold: one detokenise, one launch for all thresholds (csrc/note_match.hip), one copy of [T, K, 3] integers to the
+    host.  ``notes_batch`` as in ``chroma_counts``.  ``thresholds``: confidences in [0, 1] (``None``: ``[0.0]``); positive ones need
+    ``token_logprobs``.  ``offset_ratio=None`` is the onset-only metric.  The matching is exact: no cap, no host route."""
+    labels = [notes_batch] if mode == "sequential" else list(notes_batch)
+    floors = threshold_logprobs(thresholds, token_logprobs is not None)
+    K = len(floors)
+    for name, value in (("onset_tolerance", onset_tolerance), ("offset_min_tolerance", offset_min_tolerance)):
+        if not 0.0 <= float(value) <= 3600.0:
+            raise ValueError(f"note_counts: {name}={value} out of range [0, 3600] seconds")
+    ratio = -1.0 if offset_ratio is None else float(offset_ratio)
+    if offset_ratio is not None and not 0.0 <= ratio <= 1e6:
+        raise ValueError(f"note_counts: offset_ratio={offset_ratio} out of range [0, 1e6] (None: onsets only)")
+    if token_logprobs is None:
+        dn = detokenize(tokenizer, token_ids, mode, duration_per_batch, vocab_size)
+    else:
+        dn = detokenize_scored(tokenizer, token_ids, token_logprobs, mode, duration_per_batch, 0.0, vocab_size)
+    R = int(dn.counts.shape[0])
+    T = 1 if mode == "sequential" else R
+    if len(labels) != T:
+        raise ValueError(f"note_counts: {len(labels)} label arrays for {T} timelines")
+    try:
+        packed, offsets, _ = _pack_labels(labels)
+    except ValueError as e:
+        raise ValueError(str(e).replace("chroma_counts", "note_counts", 1)) from None
+    if R == 0:
+        empty = np.zeros((0, K), dtype=np.int64)
+        return NoteCounts(empty, empty.copy(), empty.copy())
+    device = dn.notes.device
+    Kd = K if dn.note_lp is not None else 1                  # without log-probabilities every threshold keeps every note: one column
+    with torch.cuda.device(device):
+        lab = torch.from_numpy(packed).to(device)
+        off = torch.from_numpy(offsets).to(device)
+        thr = torch.from_numpy(floors).to(device) if dn.note_lp is not None else None
+        out = _enqueue_note_counts(dn, lab, off, thr, float(onset_tolerance), ratio, float(offset_min_tolerance))
+        host = torch.cat([out.reshape(-1), dn.counts]).cpu().numpy()
+    _raise_for_bad_rows(host[3 * T * Kd:])
+    res = np.repeat(host[:3 * T * Kd].reshape(T, Kd, 3).astype(np.int64), K // Kd, axis=1)
+    return NoteCounts(res[:, :, 0].copy(), res[:, :, 1].copy(), res[:, :, 2].copy())
