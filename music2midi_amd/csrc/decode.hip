@@ -14,8 +14,13 @@
 //                    (self: q,k,v + cache append; cross: q) fused in front of the attention, which
 //                    streams K then V straight from HBM to registers (16 B per lane per load, no
 //                    LDS staging: each byte is used once), fp32 softmax, shuffle + LDS reduction.
+//   dec_attn_mc_kernel  the same for large chains: one head of C = 2 / 4 consecutive clips per workgroup (one row round trip, the
+//                    head's weights fetched once, the clips' K/V streams back to back).  Per row it repeats dec_attn_kernel's
+//                    pieces (da_project, DaSoftmax, da_merge, da_out_row, da_book_row) by hand: a row's bits do not depend on the form.
 //   dec_ff_kernel    the whole gated feed-forward sub-layer: RMSNorm + MFMA up projection of a 32-column
 //                    slice + gated GELU (LDS) + MFMA down projection, added into the residual stream.
+//   dec_ff_multi_kernel  the same for large chains: several consecutive slices per workgroup, summed as integers before ONE
+//                    atomic per element.  Both are thin wrappers over one body, dec_ff_body.
 //   dec_gemm_kernel  lm_head: RMSNorm + skinny projection, one 16x16 MFMA tile per workgroup, waves split K.
 //   dec_head_kernel  argmax / EOS+pad bookkeeping / next-token embedding / step counter.
 #include "mma.h"
@@ -376,258 +381,102 @@ constexpr int FF_HP = FF_C + 8; // LDS row pitch of the activation slice (elemen
 #ifndef M2M_FF_ABL
 #define M2M_FF_ABL 0
 #endif
-template <typename T, int KS, int FF_R>
-__global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2))) void dec_ff_kernel(DecFfArgs a) {
+// The extra workgroup of each row block carries the residual itself into x_out and zeroes the third buffer (blockDim.x == d_model:
+// one column per thread), so the slice workgroups issue no conditional loads (a branch around a load costs them a full s_waitcnt).
+template <int FF_R>
+__device__ __forceinline__ void dec_ff_carry(const DecFfArgs& a, int b0, int done) {
+  const int tid = threadIdx.x, K = a.d;
+  xq_t v[FF_R];
+#pragma unroll
+  for (int i = 0; i < FF_R; ++i) v[i] = a.x[(int64_t)min(b0 + i, a.B - 1) * K + tid];
+  if (done) return;
+  if (a.check_done && b0 == 0 && tid == 0) {
+    // every row's layer-0 cross workgroup has counted itself in (the kernel before this one): none unfinished = the
+    // batch is complete.  The token fed THIS step (position t) was the last one: t + 1 valid columns.
+    if (a.state->n_unfinished == 0) { a.state->done = 1; a.state->out_len = a.state->t + 1; }
+    a.state->n_unfinished = 0;
+  }
+#pragma unroll
+  for (int i = 0; i < FF_R; ++i) {
+    if (b0 + i < a.B) {
+      const int64_t at = (int64_t)(b0 + i) * K + tid;
+      atomicAdd(reinterpret_cast<unsigned long long*>(a.x_out + at), (unsigned long long)v[i]);
+      a.x_zero[at] = 0;
+    }
+  }
+}
+
+// The whole sub-layer, for both kernels below: a workgroup walks NSL consecutive hidden slices of its FF_R-row block with the SAME
+// normalised rows (read and normalised once).  NSL = 1 is dec_ff_kernel.  NSL > 1 (dec_ff_multi_kernel, large chains, round 6): at
+// 64 clips per chain the one-slice form is bound by its atomics - 36 slice workgroups + the carry add into every residual element
+// (885 K 64-bit atomics per launch; ablation build -DM2M_FF_ABL=1: 11.9 -> 7.6 us of kernel time, tools/r6_ablate.sh) - so each
+// slice's partial output is converted to fixed point as for one slice and the NSL integers are summed in registers: ONE atomic per
+// element and workgroup, atomics and row reads per launch / NSL.  Integer adds are associative and every float operation of a row
+// is the same code whatever NSL and FF_R are, so the residual stream - and every id - is bit-identical in every form
+// (tests/test_t5_gpu.py::test_multi_clip_attention_and_wide_ff_tiles_are_bit_identical).  The next slice's up-projection weights
+// are requested as soon as this slice's MFMAs have consumed theirs, its down-projection weights once this slice's have been used.
+// What depends on the form: the row path, the register sets of slice weights, and the store layout (16-row tiles: NSL = 1 only).
+#ifndef M2M_FF_MULTI_SETS
+#define M2M_FF_MULTI_SETS 1
+#endif
+template <typename T, int KS, int FF_R, int NSL>
+__device__ __forceinline__ void dec_ff_body(const DecFfArgs& a) {
+  static_assert(NSL == 1 || FF_R == 8, "several slices per workgroup: the lane pairing of the 8-row form");
   M2M_STAMP_DECL
   constexpr int CPR = 32 * KS;                         // 16-byte chunks per row
   __shared__ float ss_s[KS][16];
   __shared__ float red[KS][4][16 * 17];
   __shared__ __align__(16) T hs[16 * FF_HP];
-  __shared__ __align__(16) xq2_t xs[FF_R * CPR];       // the block's raw rows (row_stage_at): FF_R x d_model x 8 bytes, 24 KB at 8 x 384
-  M2M_STAMP(4, 0);
+  if constexpr (NSL == 1) M2M_STAMP(4, 0);   // (the stamps are the one-slice form's: kernel id 4)
   const int done = chain_done(a.state);
   const int tid = threadIdx.x, lane = tid & 63, ks = tid >> 6;
   const int r = lane & 15, g = lane >> 4;
-  // XCD-aware order (workgroup id % 8 picks the XCD, each has its own L2): the row blocks that share a weight
-  // slice run on the same XCD, so the slice is fetched into that L2 once instead of once per row block
+  // XCD-aware order (workgroup id % 8 picks the XCD, each has its own L2): the row blocks that share a group of weight
+  // slices run on the same XCD, so the slices are fetched into that L2 once instead of once per row block
   // (PMC: 14.2 MB fetched per launch for 2.75 MB of unique operands with the row-major order)
-  const int nrb = (a.B + FF_R - 1) / FF_R, nsl = a.d_ff / FF_C + 1;      // row blocks; weight slices + the carry
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int c = xcd + 8 * (slot / nrb), b0 = (slot - (slot / nrb) * nrb) * FF_R;
-  const int K = a.d;
-  if (c >= nsl) return;   // padding workgroups (uniform)
-  if (c == nsl - 1) {
-    // the extra workgroup of each row block carries the residual itself into x_out and zeroes the
-    // third buffer (blockDim.x == d_model: one column per thread), so the slice workgroups issue no
-    // conditional loads (a branch around a load costs them a full s_waitcnt)
-    xq_t v[FF_R];
-#pragma unroll
-    for (int i = 0; i < FF_R; ++i) v[i] = a.x[(int64_t)min(b0 + i, a.B - 1) * K + tid];
-    if (done) return;
-    if (a.check_done && b0 == 0 && tid == 0) {
-      // every row's layer-0 cross workgroup has counted itself in (the kernel before this one): none unfinished = the
-      // batch is complete.  The token fed THIS step (position t) was the last one: t + 1 valid columns.
-      if (a.state->n_unfinished == 0) { a.state->done = 1; a.state->out_len = a.state->t + 1; }
-      a.state->n_unfinished = 0;
-    }
-#pragma unroll
-    for (int i = 0; i < FF_R; ++i) {
-      if (b0 + i < a.B) {
-        const int64_t at = (int64_t)(b0 + i) * K + tid;
-        atomicAdd(reinterpret_cast<unsigned long long*>(a.x_out + at), (unsigned long long)v[i]);
-        a.x_zero[at] = 0;
-      }
-    }
-    return;
-  }
-  const int kbeg = ks * 64 + 8 * g;
-  const bool row_ok = r < FF_R && (b0 + r) < a.B;
-  const T* Wi = reinterpret_cast<const T*>(a.Wi);
-  const T* Wo = reinterpret_cast<const T*>(a.Wo);
-
-  // The block's FF_R rows, raw, through LDS.  The block has 64 KS lanes = two rows of chunks per pass: thread tid takes chunk scc of
-  // tile rows srow, srow + 2, ...  Rows past the batch re-read its last row (clamped, never a branch around a load); rs = 0 for them.
-  const int srow = tid >= CPR ? 1 : 0, scc = tid - srow * CPR;
-  xq2_t xst[FF_R / 2];
-#pragma unroll
-  for (int i = 0; i < FF_R / 2; ++i)
-    xst[i] = (M2M_FF_ABL & 2) ? xq2_t{1 << 28, 1 << 27} : *reinterpret_cast<const xq2_t*>(a.x + (int64_t)min(b0 + 2 * i + srow, a.B - 1) * K + 2 * scc);
-  __builtin_amdgcn_sched_barrier(0);               // the latency-critical rows go out FIRST (loads retire in order)
-  float4 g0[2], g1[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    g0[s] = *reinterpret_cast<const float4*>(a.ln_w + kbeg + 32 * s);
-    g1[s] = *reinterpret_cast<const float4*>(a.ln_w + kbeg + 32 * s + 4);
-  }
-  Frag<T> wf[4][2];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) wf[j][s] = load_frag(Wi + (int64_t)(2 * FF_C * c + 16 * j + r) * K + kbeg + 32 * s);
-  // phase-2 operands: this wave's four output n-tiles of wo, columns [32 c, 32 c + 32) of d_ff
-  Frag<T> wo[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) wo[j] = load_frag(Wo + (int64_t)(16 * (4 * ks + j) + r) * a.d_ff + FF_C * c + 8 * g);
-  // every load is in flight; the loop-state flag is forced here (two dependent scalar loads that the
-  // compiler would otherwise sink to the first use, in front of the barrier on the critical path)
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::"s"(done));
-#pragma unroll
-  for (int i = 0; i < FF_R / 2; ++i) xs[row_stage_at(2 * i + srow, scc, CPR)] = xst[i];
-  __syncthreads();
-  // Lane (r, g) takes its operand pieces: elements kbeg + 32 s + 2 q + {0, 1} of row r, converted only here.  With 8-row tiles the
-  // lanes r >= 8 are padding: they re-read the piece of lane (r - 8, g ^ 1), which sits in their own 16-lane LDS read group (the
-  // same address: a broadcast, no bank conflict).
-  const int lr = r & (FF_R - 1), lcc = (kbeg >> 1) ^ (r >= FF_R ? 4 : 0);
-  float4 x0[2], x1[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    xq2_t xraw[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) xraw[q] = xs[row_stage_at(lr, lcc + 16 * s + q, CPR)];
-    x0[s] = make_float4(xq_flt(xraw[0].x), xq_flt(xraw[0].y), xq_flt(xraw[1].x), xq_flt(xraw[1].y));
-    x1[s] = make_float4(xq_flt(xraw[2].x), xq_flt(xraw[2].y), xq_flt(xraw[3].x), xq_flt(xraw[3].y));
-  }
-
-  // ---- phase 1: RMSNorm + up projection of this slice ----
-  float ss = 0.f;
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-    ss += x0[s].x * x0[s].x + x0[s].y * x0[s].y + x0[s].z * x0[s].z + x0[s].w * x0[s].w +
-          x1[s].x * x1[s].x + x1[s].y * x1[s].y + x1[s].z * x1[s].z + x1[s].w * x1[s].w;
-  ss += lane_xor<16>(ss);
-  ss += lane_xor<32>(ss);
-  if (g == 0) ss_s[ks][r] = ss;
-  __syncthreads();
-  M2M_STAMP(4, 3);
-  float tot = 0.f;
-#pragma unroll
-  for (int w = 0; w < KS; ++w) tot += ss_s[w][r];
-  const float rs = row_ok ? rsqrtf(tot / (float)K + a.eps) : 0.f;   // rs = 0 zeroes the padding rows
-  f32x4_t acc[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) acc[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const float xv[8] = {g0[s].x * (x0[s].x * rs), g0[s].y * (x0[s].y * rs), g0[s].z * (x0[s].z * rs),
-                         g0[s].w * (x0[s].w * rs), g1[s].x * (x1[s].x * rs), g1[s].y * (x1[s].y * rs),
-                         g1[s].z * (x1[s].z * rs), g1[s].w * (x1[s].w * rs)};
-    const Frag<T> fa = pack_frag<T>(xv);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) mma32_16(acc[j], fa, wf[j][s]);
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[ks][j][(4 * g + i) * 17 + r] = acc[j][i];
-  M2M_STAMP(4, 1);
-  __syncthreads();
-  if (done) return;   // uniform
-  // gated activation: column cc of the slice lives in tile cc / 8 at columns (cc % 8) [wi_0] and (cc % 8) + 8 [wi_1];
-  // k-slices are summed in a fixed order
-  for (int idx = tid; idx < FF_R * FF_C; idx += 64 * KS) {   // rows FF_R..15 of the tile are padding and stay unread
-    const int row = idx / FF_C, cc = idx % FF_C;
-    const int t = cc >> 3, q = row * 17 + (cc & 7);
-    float v0 = red[0][t][q], v1 = red[0][t][q + 8];
-#pragma unroll
-    for (int w = 1; w < KS; ++w) { v0 += red[w][t][q]; v1 += red[w][t][q + 8]; }
-    hs[row * FF_HP + cc] = from_f32<T>(gelu_new_t<T>(v0) * v1);
-  }
-  __syncthreads();
-  M2M_STAMP(4, 5);
-
-  // ---- phase 2: [16 x 32] activations x [32 x d_model] slice of wo, added into the residual rows ----
-  const Frag<T> fh = load_frag(hs + r * FF_HP + 8 * g);
-  f32x4_t o[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    o[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    mma32_16(o[j], fh, wo[j]);
-  }
-  if (M2M_FF_ABL & 1) return;
-  if constexpr (FF_R <= 8) {
-    // Rows 8..15 of the MFMA tile are padding, i.e. lanes g >= 2 hold nothing to store.  They take over half
-    // of their partner's rows (lane ^ 32 <-> g ^ 2) so that every lane issues 2 adds per tile instead of
-    // half the lanes issuing 4: lane (r, g) stores tile rows 4 (g & 1) + 2 (g >> 1) + {0, 1}.
-    const int rl = 4 * (g & 1) + 2 * (g >> 1);
-    xq_t* const p0 = a.x_out + (int64_t)(b0 + rl) * K + 64 * ks + r;
-    const bool ok0 = rl < FF_R && b0 + rl < a.B, ok1 = rl + 1 < FF_R && b0 + rl + 1 < a.B;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x2 = lane_xor<32>(o[j][2]), x3 = lane_xor<32>(o[j][3]);
-      const float v0 = g < 2 ? o[j][0] : x2, v1 = g < 2 ? o[j][1] : x3;
-      if (ok0) atomicAdd(reinterpret_cast<unsigned long long*>(p0 + 16 * j), (unsigned long long)xq_fix_guarded(v0, a.state));
-      if (ok1) atomicAdd(reinterpret_cast<unsigned long long*>(p0 + 16 * j + K), (unsigned long long)xq_fix_guarded(v1, a.state));
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int col = 16 * (4 * ks + j) + r;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = b0 + 4 * g + i;
-        if (4 * g + i < FF_R && row < a.B)
-          atomicAdd(reinterpret_cast<unsigned long long*>(a.x_out + (int64_t)row * K + col), (unsigned long long)xq_fix_guarded(o[j][i], a.state));
-      }
-    }
-  }
-  M2M_STAMP(4, 2);
-}
-
-template <typename T, int FF_R>
-static int launch_dec_ff_t(const DecFfArgs& a, hipStream_t st) {
-  const int nsl = a.d_ff / FF_C + 1;                                          // + 1: the residual-carry workgroup
-  dim3 grid((unsigned)(ceil_div(nsl, 8) * 8 * ceil_div(a.B, FF_R)));
-  switch (a.d / 64) {
-    case 2: hipLaunchKernelGGL((dec_ff_kernel<T, 2, FF_R>), grid, dim3(128), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((dec_ff_kernel<T, 4, FF_R>), grid, dim3(256), 0, st, a); break;
-    case 6: hipLaunchKernelGGL((dec_ff_kernel<T, 6, FF_R>), grid, dim3(384), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((dec_ff_kernel<T, 8, FF_R>), grid, dim3(512), 0, st, a); break;
-    default: set_error("dec_ff: d_model=%d not supported (128/256/384/512)", a.d); return M2M_ERR_INVALID;
-  }
-  M2M_CHECK_HIP(hipGetLastError());
-  return M2M_OK;
-}
-
-// ---- the same sub-layer for LARGE chains: NSL consecutive hidden slices per workgroup (round 6) ----
-// At 64 clips per chain the kernel above is bound by its atomics: 36 slice workgroups + the carry add into every residual element
-// (885 K 64-bit atomics per launch; ablation build -DM2M_FF_ABL=1: 11.9 -> 7.6 us of kernel time, tools/r6_ablate.sh).  Here a
-// workgroup walks NSL consecutive slices of its row block with the SAME normalised rows (read and normalised once), converts each
-// slice's partial output to fixed point exactly as the first kernel does and sums the NSL integers in registers: ONE atomic per
-// element and workgroup.  Integer adds are associative, so the residual stream - and every id - is bit-identical to the first form
-// (tests/test_t5_gpu.py::test_multi_clip_attention_and_wide_ff_tiles_are_bit_identical); atomics and row reads per launch / NSL.
-// The next slice's up-projection weights are requested as soon as this slice's MFMAs have consumed theirs, its down-projection
-// weights once this slice's have been used.  FF_R <= 8 only (the lane pairing of the 8-row form).
-template <typename T, int KS, int NSL>
-__global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2))) void dec_ff_multi_kernel(DecFfArgs a) {
-  constexpr int FF_R = 8;
-  __shared__ float ss_s[KS][16];
-  __shared__ float red[KS][4][16 * 17];
-  __shared__ __align__(16) T hs[16 * FF_HP];
-  const int done = chain_done(a.state);
-  const int tid = threadIdx.x, lane = tid & 63, ks = tid >> 6;
-  const int r = lane & 15, g = lane >> 4;
-  // XCD-aware order as in the first kernel: the row blocks that share a group of slices run on the same XCD
   const int nrb = (a.B + FF_R - 1) / FF_R, ngr = a.d_ff / (FF_C * NSL) + 1;   // row blocks; slice groups + the carry
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
   const int c = xcd + 8 * (slot / nrb), b0 = (slot - (slot / nrb) * nrb) * FF_R;
   const int K = a.d;
   if (c >= ngr) return;   // padding workgroups (uniform)
-  if (c == ngr - 1) {     // the carry workgroup of the row block: as in the first kernel
-    xq_t v[FF_R];
-#pragma unroll
-    for (int i = 0; i < FF_R; ++i) v[i] = a.x[(int64_t)min(b0 + i, a.B - 1) * K + tid];
-    if (done) return;
-    if (a.check_done && b0 == 0 && tid == 0) {
-      if (a.state->n_unfinished == 0) { a.state->done = 1; a.state->out_len = a.state->t + 1; }
-      a.state->n_unfinished = 0;
-    }
-#pragma unroll
-    for (int i = 0; i < FF_R; ++i) {
-      if (b0 + i < a.B) {
-        const int64_t at = (int64_t)(b0 + i) * K + tid;
-        atomicAdd(reinterpret_cast<unsigned long long*>(a.x_out + at), (unsigned long long)v[i]);
-        a.x_zero[at] = 0;
-      }
-    }
+  if (c == ngr - 1) {
+    dec_ff_carry<FF_R>(a, b0, done);
     return;
   }
   const int kbeg = ks * 64 + 8 * g;
   const bool row_ok = r < FF_R && (b0 + r) < a.B;
-  const int arow = b0 + (row_ok ? r : 0);
   const T* Wi = reinterpret_cast<const T*>(a.Wi);
   const T* Wo = reinterpret_cast<const T*>(a.Wo);
   const int s0 = c * NSL;                                   // first slice of this workgroup
 
-  // (rows read from memory in the operand pattern: staging them through LDS as the first kernel does gave 12.28 -> 12.09 us per
-  // launch at 64 clips, inside the run-to-run spread - DESIGN 4.3)
-  const xq_t* xr = a.x + (int64_t)arow * K + kbeg;
-  longlong2 xraw[2][4];
+  // Lane (r, g)'s operand pieces of the rows: xraw[s][q] = elements kbeg + 32 s + 2 q + {0, 1} of row r, raw, converted only below.
+  xq2_t xraw[2][4];
+  // NSL = 1: the block's FF_R rows go through LDS (row_stage_at).  The block has 64 KS lanes = two rows of chunks per pass: thread tid
+  // takes chunk scc of tile rows srow, srow + 2, ...  Rows past the batch re-read its last row (clamped, never a branch around a load);
+  // rs = 0 for them.  srow, scc, xst and xs belong to this path alone; they stand here because the path has two halves, the requests
+  // in front of the weight requests and the LDS image behind them.
+  const int srow = tid >= CPR ? 1 : 0, scc = tid - srow * CPR;
+  xq2_t xst[FF_R / 2];
+  xq2_t* xs = nullptr;
+  if constexpr (NSL == 1) {
+    __shared__ __align__(16) xq2_t xs_lds[FF_R * CPR];   // the block's raw rows: FF_R x d_model x 8 bytes, 24 KB at 8 x 384
+    xs = xs_lds;
+#pragma unroll
+    for (int i = 0; i < FF_R / 2; ++i)
+      xst[i] = (M2M_FF_ABL & 2) ? xq2_t{1 << 28, 1 << 27} : *reinterpret_cast<const xq2_t*>(a.x + (int64_t)min(b0 + 2 * i + srow, a.B - 1) * K + 2 * scc);
+    __builtin_amdgcn_sched_barrier(0);               // the latency-critical rows go out FIRST (loads retire in order)
+  } else {
+    // NSL > 1: rows read from memory in the operand pattern (staging them through LDS gave 12.28 -> 12.09 us per launch at 64 clips,
+    // inside the run-to-run spread - DESIGN 4.3)
+    const xq_t* xr = a.x + (int64_t)(b0 + (row_ok ? r : 0)) * K + kbeg;
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) xraw[s][q] = (M2M_FF_ABL & 2) ? xq2_t{1 << 28, 1 << 27} : *reinterpret_cast<const xq2_t*>(xr + 32 * s + 2 * q);
+  }
   float4 g0[2], g1[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) xraw[s][q] = (M2M_FF_ABL & 2) ? make_longlong2(1 << 28, 1 << 27) : *reinterpret_cast<const longlong2*>(xr + 32 * s + 2 * q);
     g0[s] = *reinterpret_cast<const float4*>(a.ln_w + kbeg + 32 * s);
     g1[s] = *reinterpret_cast<const float4*>(a.ln_w + kbeg + 32 * s + 4);
   }
@@ -636,10 +485,8 @@ __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2)))
   // first slice's weights), but TWO sets in flight measured SLOWER on the same box (tools/native_mc_sweep.py, us per step): 2 x 64
   // clips 351.7 / 352.7 against 344-348, with 2 slices 365.7 against 349-353, 2 x 32 clips 301.1 against 291.9 - as with the K/V
   // prefetch, bytes requested earlier delay everybody's latency-critical rows.  NB = 1.
-#ifndef M2M_FF_MULTI_SETS
-#define M2M_FF_MULTI_SETS 1
-#endif
   constexpr int NB = (NSL > 1 && sizeof(T) == 2) ? M2M_FF_MULTI_SETS : 1;
+  // wf: the four n-tiles of the slice's wi rows; wo (phase 2): this wave's four output n-tiles of wo, columns [32 s, 32 s + 32) of d_ff
   Frag<T> wf[NB][4][2];
   Frag<T> wo[NB][4];
 #pragma unroll
@@ -651,14 +498,29 @@ __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2)))
 #pragma unroll
     for (int j = 0; j < 4; ++j) wo[b][j] = load_frag(Wo + (int64_t)(16 * (4 * ks + j) + r) * a.d_ff + FF_C * (s0 + b) + 8 * g);
   }
+  // every load is in flight; the loop-state flag is forced here (two dependent scalar loads that the
+  // compiler would otherwise sink to the first use, in front of the barrier on the critical path)
   __builtin_amdgcn_sched_barrier(0);
   asm volatile("" ::"s"(done));
+  if constexpr (NSL == 1) {
+#pragma unroll
+    for (int i = 0; i < FF_R / 2; ++i) xs[row_stage_at(2 * i + srow, scc, CPR)] = xst[i];
+    __syncthreads();
+    // With 8-row tiles the lanes r >= 8 are padding: they re-read the piece of lane (r - 8, g ^ 1), which sits in their own 16-lane
+    // LDS read group (the same address: a broadcast, no bank conflict).
+    const int lr = r & (FF_R - 1), lcc = (kbeg >> 1) ^ (r >= FF_R ? 4 : 0);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) xraw[s][q] = xs[row_stage_at(lr, lcc + 16 * s + q, CPR)];
+  }
   float4 x0[2], x1[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     x0[s] = make_float4(xq_flt(xraw[s][0].x), xq_flt(xraw[s][0].y), xq_flt(xraw[s][1].x), xq_flt(xraw[s][1].y));
     x1[s] = make_float4(xq_flt(xraw[s][2].x), xq_flt(xraw[s][2].y), xq_flt(xraw[s][3].x), xq_flt(xraw[s][3].y));
   }
+
   // ---- RMSNorm once: the normalised fragments serve every slice ----
   float ss = 0.f;
 #pragma unroll
@@ -669,10 +531,11 @@ __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2)))
   ss += lane_xor<32>(ss);
   if (g == 0) ss_s[ks][r] = ss;
   __syncthreads();
+  if constexpr (NSL == 1) M2M_STAMP(4, 3);
   float tot = 0.f;
 #pragma unroll
   for (int w = 0; w < KS; ++w) tot += ss_s[w][r];
-  const float rs = row_ok ? rsqrtf(tot / (float)K + a.eps) : 0.f;
+  const float rs = row_ok ? rsqrtf(tot / (float)K + a.eps) : 0.f;   // rs = 0 zeroes the padding rows
   Frag<T> fa[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -681,9 +544,14 @@ __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2)))
                          g1[s].z * (x1[s].z * rs), g1[s].w * (x1[s].w * rs)};
     fa[s] = pack_frag<T>(xv);
   }
-  // lane (r, g) stores tile rows 4 (g & 1) + 2 (g >> 1) + {0, 1} (the 8-row form's lane pairing)
+  // 8-row tiles: rows 8..15 of the MFMA tile are padding, i.e. lanes g >= 2 hold nothing to store.  They take over half
+  // of their partner's rows (lane ^ 32 <-> g ^ 2) so that every lane issues 2 adds per tile instead of
+  // half the lanes issuing 4: lane (r, g) stores tile rows 4 (g & 1) + 2 (g >> 1) + {0, 1}.  (rl .. sum1 serve the 8-row forms only,
+  // in the slice loop and behind it; with 16-row tiles nothing reads them.)
   const int rl = 4 * (g & 1) + 2 * (g >> 1);
-  xq_t sum0[4], sum1[4];
+  xq_t* const p0 = a.x_out + (int64_t)(b0 + rl) * K + 64 * ks + r;
+  const bool ok0 = rl < FF_R && b0 + rl < a.B, ok1 = rl + 1 < FF_R && b0 + rl + 1 < a.B;
+  xq_t sum0[4], sum1[4];       // NSL > 1: the slices' partial outputs, summed as integers
 #pragma unroll
   for (int j = 0; j < 4; ++j) { sum0[j] = 0; sum1[j] = 0; }
 
@@ -707,9 +575,12 @@ __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2)))
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int q = 0; q < 4; ++q) red[ks][j][(4 * g + q) * 17 + r] = acc[j][q];
+    if constexpr (NSL == 1) M2M_STAMP(4, 1);
     __syncthreads();
     if (done) return;   // uniform
-    for (int idx = tid; idx < FF_R * FF_C; idx += 64 * KS) {
+    // gated activation: column cc of the slice lives in tile cc / 8 at columns (cc % 8) [wi_0] and (cc % 8) + 8 [wi_1];
+    // k-slices are summed in a fixed order
+    for (int idx = tid; idx < FF_R * FF_C; idx += 64 * KS) {   // rows FF_R..15 of the tile are padding and stay unread
       const int row = idx / FF_C, cc = idx % FF_C;
       const int t = cc >> 3, q = row * 17 + (cc & 7);
       float v0 = red[0][t][q], v1 = red[0][t][q + 8];
@@ -718,7 +589,9 @@ __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2)))
       hs[row * FF_HP + cc] = from_f32<T>(gelu_new_t<T>(v0) * v1);
     }
     __syncthreads();
-    // ---- phase 2: down projection of the slice, converted to fixed point per slice, summed as integers ----
+    if constexpr (NSL == 1) M2M_STAMP(4, 5);
+
+    // ---- phase 2: [16 x 32] activations x [32 x d_model] slice of wo, converted to fixed point per slice ----
     const Frag<T> fh = load_frag(hs + r * FF_HP + 8 * g);
     f32x4_t o[4];
 #pragma unroll
@@ -730,33 +603,71 @@ __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2)))
 #pragma unroll
       for (int j = 0; j < 4; ++j) wo[i % NB][j] = load_frag(Wo + (int64_t)(16 * (4 * ks + j) + r) * a.d_ff + FF_C * (s0 + i + NB) + 8 * g);
     }
+    if (NSL == 1 && (M2M_FF_ABL & 1)) return;
+    if constexpr (FF_R <= 8) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float x2 = lane_xor<32>(o[j][2]), x3 = lane_xor<32>(o[j][3]);
-      const float v0 = g < 2 ? o[j][0] : x2, v1 = g < 2 ? o[j][1] : x3;
-      sum0[j] += xq_fix_guarded(v0, a.state);
-      sum1[j] += xq_fix_guarded(v1, a.state);
+      for (int j = 0; j < 4; ++j) {
+        const float x2 = lane_xor<32>(o[j][2]), x3 = lane_xor<32>(o[j][3]);
+        const float v0 = g < 2 ? o[j][0] : x2, v1 = g < 2 ? o[j][1] : x3;
+        if constexpr (NSL == 1) {
+          // one slice: every element is added as soon as it is converted (all eight converted first, then added - the order of the
+          // several-slice form - measured 6.59 -> 6.78 us per launch at 2 x 16 clips: DESIGN 9.5)
+          if (ok0) atomicAdd(reinterpret_cast<unsigned long long*>(p0 + 16 * j), (unsigned long long)xq_fix_guarded(v0, a.state));
+          if (ok1) atomicAdd(reinterpret_cast<unsigned long long*>(p0 + 16 * j + K), (unsigned long long)xq_fix_guarded(v1, a.state));
+        } else {
+          sum0[j] += xq_fix_guarded(v0, a.state);
+          sum1[j] += xq_fix_guarded(v1, a.state);
+        }
+      }
+    } else {   // 16-row tiles (one slice only): every lane adds its four rows of each tile
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int col = 16 * (4 * ks + j) + r;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int row = b0 + 4 * g + q;
+          if (4 * g + q < FF_R && row < a.B)
+            atomicAdd(reinterpret_cast<unsigned long long*>(a.x_out + (int64_t)row * K + col), (unsigned long long)xq_fix_guarded(o[j][q], a.state));
+        }
+      }
     }
   }
-  if (M2M_FF_ABL & 1) return;
-  xq_t* const p0 = a.x_out + (int64_t)(b0 + rl) * K + 64 * ks + r;
-  const bool ok0 = rl < FF_R && b0 + rl < a.B, ok1 = rl + 1 < FF_R && b0 + rl + 1 < a.B;
+  if constexpr (NSL > 1) {   // ONE atomic per element and workgroup
+    if (M2M_FF_ABL & 1) return;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (ok0) atomicAdd(reinterpret_cast<unsigned long long*>(p0 + 16 * j), (unsigned long long)sum0[j]);
-    if (ok1) atomicAdd(reinterpret_cast<unsigned long long*>(p0 + 16 * j + K), (unsigned long long)sum1[j]);
+    for (int j = 0; j < 4; ++j) {
+      if (ok0) atomicAdd(reinterpret_cast<unsigned long long*>(p0 + 16 * j), (unsigned long long)sum0[j]);
+      if (ok1) atomicAdd(reinterpret_cast<unsigned long long*>(p0 + 16 * j + K), (unsigned long long)sum1[j]);
+    }
   }
+  if constexpr (NSL == 1) M2M_STAMP(4, 2);
 }
 
-template <typename T, int NSL>
-static int launch_dec_ff_multi_t(const DecFfArgs& a, hipStream_t st) {
-  const int ngr = a.d_ff / (FF_C * NSL) + 1;
-  dim3 grid((unsigned)(ceil_div(ngr, 8) * 8 * ceil_div(a.B, 8)));
+// FF_R rows, one hidden slice per workgroup: the form of small chains
+template <typename T, int KS, int FF_R>
+__global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2))) void dec_ff_kernel(DecFfArgs a) {
+  dec_ff_body<T, KS, FF_R, 1>(a);
+}
+// 8 rows, NSL consecutive hidden slices per workgroup: the form of large chains
+template <typename T, int KS, int NSL>
+__global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(1, 2))) void dec_ff_multi_kernel(DecFfArgs a) {
+  dec_ff_body<T, KS, 8, NSL>(a);
+}
+
+template <typename T, int KS, int FF_R, int NSL>
+static void launch_dec_ff_ks(const DecFfArgs& a, dim3 grid, hipStream_t st) {
+  if constexpr (NSL == 1) hipLaunchKernelGGL((dec_ff_kernel<T, KS, FF_R>), grid, dim3(64 * KS), 0, st, a);
+  else hipLaunchKernelGGL((dec_ff_multi_kernel<T, KS, NSL>), grid, dim3(64 * KS), 0, st, a);
+}
+template <typename T, int FF_R, int NSL>
+static int launch_dec_ff_t(const DecFfArgs& a, hipStream_t st) {
+  const int ngr = a.d_ff / (FF_C * NSL) + 1;                                  // + 1: the residual-carry workgroup
+  dim3 grid((unsigned)(ceil_div(ngr, 8) * 8 * ceil_div(a.B, FF_R)));
   switch (a.d / 64) {
-    case 2: hipLaunchKernelGGL((dec_ff_multi_kernel<T, 2, NSL>), grid, dim3(128), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((dec_ff_multi_kernel<T, 4, NSL>), grid, dim3(256), 0, st, a); break;
-    case 6: hipLaunchKernelGGL((dec_ff_multi_kernel<T, 6, NSL>), grid, dim3(384), 0, st, a); break;
-    case 8: hipLaunchKernelGGL((dec_ff_multi_kernel<T, 8, NSL>), grid, dim3(512), 0, st, a); break;
+    case 2: launch_dec_ff_ks<T, 2, FF_R, NSL>(a, grid, st); break;
+    case 4: launch_dec_ff_ks<T, 4, FF_R, NSL>(a, grid, st); break;
+    case 6: launch_dec_ff_ks<T, 6, FF_R, NSL>(a, grid, st); break;
+    case 8: launch_dec_ff_ks<T, 8, FF_R, NSL>(a, grid, st); break;
     default: set_error("dec_ff: d_model=%d not supported (128/256/384/512)", a.d); return M2M_ERR_INVALID;
   }
   M2M_CHECK_HIP(hipGetLastError());
@@ -770,11 +681,11 @@ static int launch_dec_ff(int precision, const DecFfArgs& a, int rows, int slices
   }
   const bool bf = precision == M2M_PREC_BF16;
   if (slices > 1 && (a.d_ff / FF_C) % slices == 0) {        // several hidden slices per workgroup (large chains)
-    if (slices == 2) return bf ? launch_dec_ff_multi_t<bf16_t, 2>(a, st) : launch_dec_ff_multi_t<float, 2>(a, st);
-    if (slices == 4) return bf ? launch_dec_ff_multi_t<bf16_t, 4>(a, st) : launch_dec_ff_multi_t<float, 4>(a, st);
+    if (slices == 2) return bf ? launch_dec_ff_t<bf16_t, 8, 2>(a, st) : launch_dec_ff_t<float, 8, 2>(a, st);
+    if (slices == 4) return bf ? launch_dec_ff_t<bf16_t, 8, 4>(a, st) : launch_dec_ff_t<float, 8, 4>(a, st);
   }
-  if (rows == 16) return bf ? launch_dec_ff_t<bf16_t, 16>(a, st) : launch_dec_ff_t<float, 16>(a, st);
-  return bf ? launch_dec_ff_t<bf16_t, 8>(a, st) : launch_dec_ff_t<float, 8>(a, st);
+  if (rows == 16) return bf ? launch_dec_ff_t<bf16_t, 16, 1>(a, st) : launch_dec_ff_t<float, 16, 1>(a, st);
+  return bf ? launch_dec_ff_t<bf16_t, 8, 1>(a, st) : launch_dec_ff_t<float, 8, 1>(a, st);
 }
 
 // ======================================================= decode attention ====
@@ -875,6 +786,179 @@ template <typename T> __device__ inline void put_in(float* in_lds, int i, float 
   else in_lds[i] = v;
 }
 
+// ---- the per-row pieces of the decode attention (dec_attn_kernel: one clip per workgroup; C = 1 below) ----
+// A row's ids and logits are bit-identical whichever kernel decodes it (tests/test_t5_gpu.py::
+// test_multi_clip_attention_and_wide_ff_tiles_are_bit_identical): every float operation of a row is one of these functions - same
+// lane -> element maps, same reduction trees, same key -> lane-group partition, same rounding points.  They are written over the
+// clip count so that dec_attn_mc_kernel (C clips per workgroup) can call them too, and it did: ids, logits and resources held, but
+// its cross-attention instantiations measured 0.03-0.07 us per launch over the parent's at 2 x 64 clips and the piece responsible
+// was not found.  So dec_attn_mc_kernel still carries its own copy of each piece, kept equal by hand and by the tests:
+// a change here has to be made there as well.
+
+// The online softmax of one lane group: running (max, sum, weighted-V) over the keys the group visits.
+template <typename T> struct DaSoftmax {
+  static constexpr int E = 16 / sizeof(T);
+  float m_run = -1e30f, l_run = 0.f;
+  float acc[E];
+  __device__ __forceinline__ DaSoftmax() {
+#pragma unroll
+    for (int e = 0; e < E; ++e) acc[e] = 0.f;
+  }
+  // one exponential per key: of (alpha, p) = (exp(m_run - m_new), exp(s - m_new)) one is always exp(0) = 1
+  __device__ __forceinline__ void visit(float s, const float (&vrow)[E]) {
+    const bool up = s > m_run;
+    const float m_new = up ? s : m_run;
+    const float ex = m2m_exp<T>(up ? m_run - s : s - m_run);
+    const float alpha = up ? ex : 1.f;
+    const float p = up ? 1.f : ex;
+    l_run = fmaf(l_run, alpha, p);
+#pragma unroll
+    for (int e = 0; e < E; ++e) acc[e] = fmaf(acc[e], alpha, p * vrow[e]);
+    m_run = m_new;
+  }
+  // the key/value appended this step (relative position 0), from the LDS rows kn / vn: for the lanes of group 0
+  __device__ __forceinline__ void visit_own(const float (&qv)[E], const float* kn, const float* vn, const float* biasl, int sub) {
+    float s = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) s = fmaf(qv[e], kn[sub * E + e], s);
+    s = group_sum<DK / E>(s);
+    s += biasl[0];
+    float vrow[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) vrow[e] = vn[sub * E + e];
+    visit(s, vrow);
+  }
+};
+
+// LDS of the merge below: w[16], l[16], lf[16], o[16][DK], g[groups][DK] (per-group partial outputs, 32 KB bf16 / 16 KB fp32).  Each
+// kernel declares them as arrays of its own - as members of ONE struct their offsets turned the ORs of the merge's address arithmetic
+// into multiplies and adds: dec_attn_kernel 10.66 -> 10.70 us per launch.
+struct DaMergeLds { float *w, *l, *lf; float (*o)[DK]; float (*g)[DK]; };
+// Merge of the 128 key groups (16 waves x 64 / LPR groups) of one row into oh, the head's output rounded to T.
+// Each group's partial output goes to LDS scaled to its WAVE's maximum (one LDS write per lane
+// instead of 3 cross-lane exchanges per accumulator register: the exchanges were the bulk of the
+// tail's VALU time with 16 waves on 4 SIMDs); waves are then summed group by group, and the 16 wave
+// results are brought to the global maximum by the 64 threads that finish the row.  `mid` runs behind the first barrier.
+template <typename T, typename Mid>
+__device__ __forceinline__ void da_merge(const DaSoftmax<T>& sm, const DaMergeLds& red, float* oh, Mid mid) {
+  constexpr int E = 16 / sizeof(T), LPR = DK / E;
+  constexpr int GPW = 64 / LPR;                    // groups per wave: 8 (bf16) / 4 (fp32)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, sub = lane % LPR;
+  const float mw = wave_max(sm.m_run);
+  const float scale = m2m_exp<T>(sm.m_run - mw);       // groups that saw no key have m_run = -1e30 -> 0 (or 1 if the whole wave saw none: l = acc = 0)
+  float lsum = (sub == 0) ? sm.l_run * scale : 0.f;   // l is replicated over a group's lanes: count it once
+  lsum = wave_sum(lsum);
+  float* gp = &red.g[wave * GPW + lane / LPR][sub * E];
+#pragma unroll
+  for (int e = 0; e < E; e += 4)
+    *reinterpret_cast<float4*>(gp + e) = make_float4(sm.acc[e] * scale, sm.acc[e + 1] * scale, sm.acc[e + 2] * scale, sm.acc[e + 3] * scale);
+  if (lane == 0) { red.w[wave] = mw; red.l[wave] = lsum; }
+  __syncthreads();
+  mid();
+  {
+    // every wave brings ITS partial sums to the global maximum here (one exponential per wave, in parallel),
+    // so the single wave that finishes the row below only adds: the 16 exponentials it used to evaluate were
+    // ~0.4 us of serial VALU time per launch
+    float M = red.w[lane & 15];
+    M = fmaxf(M, lane_xor<8>(M)); M = fmaxf(M, lane_xor<4>(M)); M = fmaxf(M, lane_xor<2>(M)); M = fmaxf(M, lane_xor<1>(M));
+    const float fw = m2m_exp<T>(red.w[wave] - M);
+    float sw = red.g[wave * GPW][lane];             // thread (wave, lane = dim): this wave's groups, fixed order
+#pragma unroll
+    for (int j = 1; j < GPW; ++j) sw += red.g[wave * GPW + j][lane];
+    red.o[wave][lane] = sw * fw;
+    if (lane == 0) red.lf[wave] = red.l[wave] * fw;
+  }
+  __syncthreads();
+  if (tid < DK) {
+    float s = 0.f, L = 0.f;
+#pragma unroll
+    for (int wv = 0; wv < 16; ++wv) {
+      s += red.o[wv][tid];
+      L += red.lf[wv];
+    }
+    // the projection input is rounded to T, as every GEMM input (L = 0: a finished row's empty cross softmax).  !(L <= 0) keeps a NaN
+    // softmax (NaN encoder states, e.g. from a NaN sample) NaN, so the residual's range guard sees it instead of a zero head output.
+    put_in<T>(oh, tid, !(L <= 0.f) ? s / L : 0.f);
+  }
+  __syncthreads();
+}
+
+// One projection output of this head for C rows: acc[c] = <weight row, hn row c>, the weight row's 16-byte chunks strided over the
+// LPO lanes of the output (`part`: this lane's), the first WREG of them in registers, the rest (d_model / dtype combinations
+// beyond the register budget: fp32) fetched here; every lane of the output gets the sums.  hn: [C][d], normalised, rounded to T.
+template <typename T, int C, int LPO, int WREG>
+__device__ __forceinline__ void da_project(float (&acc)[C], const Vec16<T> (&w)[WREG], const T* wrow, int cnt, int part, const float* hn, int d) {
+  constexpr int E = 16 / sizeof(T);
+  using V16 = decltype(Vec16<T>().v);
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = 0.f;
+#pragma unroll
+  for (int u = 0; u < WREG; ++u) {
+    if (u < cnt) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) acc[c] = chunk_dot<T>(w[u], hn + c * d, u * LPO + part, acc[c]);
+    }
+  }
+  for (int i = WREG; i < cnt; i += 4) {
+    Vec16<T> w2[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) w2[u].v = *reinterpret_cast<const V16*>(wrow + (min(i + u, cnt - 1) * LPO + part) * E);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (i + u < cnt) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = chunk_dot<T>(w2[u], hn + c * d, (i + u) * LPO + part, acc[c]);
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = group_sum<LPO>(acc[c]);
+}
+
+// The k / v element (k: which2 == 1) dd2 of this step for row c: rounded to T, appended to the row's cache block at position t
+// (Kb / Vb: the block of row 0, rows kv_clip elements apart; `store`: the row exists and its chain is live) and published in kn / vn.
+template <typename T>
+__device__ __forceinline__ void da_append_kv(float s2, int c, int which2, int dd2, int t, int64_t kv_clip, T* Kb, T* Vb, float* kn, float* vn, bool store) {
+  const T r = from_f32<T>(s2);                       // k, v are stored (and used) rounded to T
+  const int64_t slot = (int64_t)c * kv_clip + (int64_t)t * DK + dd2;
+  if (which2 == 1) { kn[c * DK + dd2] = to_f32(r); if (store) Kb[slot] = r; }
+  else             { vn[c * DK + dd2] = to_f32(r); if (store) Vb[slot] = r; }
+}
+
+// Output projection of this head (wo: this lane's half of output column on_) from oh, ADDED into residual row b of x_out.  Head 0 also
+// carries the residual itself (`carry()`: its fixed-point value, evaluated by head 0 only), the last head zeroes the third buffer.
+template <typename T, int OCH, typename Carry>
+__device__ __forceinline__ void da_out_row(const DecAttnArgs& a, const Vec16<T> (&wo)[OCH], const float* oh, int b, bool live, bool add_heads, Carry carry) {
+  const int tid = threadIdx.x, hh = blockIdx.x, on_ = min(tid >> 1, a.d - 1), opart = tid & 1;
+  float accp = 0.f;
+#pragma unroll
+  for (int u = 0; u < OCH; ++u) accp = chunk_dot<T>(wo[u], oh, opart * OCH + u, accp);
+  accp += lane_xor<1>(accp);
+  if (opart == 0 && tid < 2 * a.d && live) {
+    xq_t add = xq_fix_guarded(accp, a.state);
+    if (hh == 0) add += carry();
+    if (add_heads || hh == 0)
+      atomicAdd(reinterpret_cast<unsigned long long*>(a.x_out + (int64_t)b * a.d + on_), (unsigned long long)add);
+    if (hh == a.H - 1) a.x_zero[(int64_t)b * a.d + on_] = 0;
+  }
+}
+
+// Headless bookkeeping of row b (one thread), after the layer-0 self-attention kernel (all head workgroups of the row) has consumed
+// the key: the token fed at this step goes into the token matrix, EOS finishes the row, the key is cleared for this
+// step's lm_head.  (hf generation/utils.py:2925-2937.)
+__device__ __forceinline__ void da_book_row(const DecAttnArgs& a, int b, int st_t, int st_done) {
+  if (!st_done) {
+    const int fin = a.finished[b];
+    const int next = amax_key_token(a.keys[b], fin, a.V, a.pad_id);
+    if (st_t < a.max_len) a.tokens[(int64_t)a.tok_row[b] * a.max_len + st_t] = next;
+    const int nf = fin | (next == a.eos_id);
+    a.finished[b] = nf;
+    if (!nf) atomicAdd(&a.state->n_unfinished, 1);
+    a.keys[b] = 0ull;
+  }
+  if (b == 0) a.state->t_copy = st_t;      // ALWAYS (also in the no-op steps after the end): the lm_head kernel's "live" test reads it
+}
+
 template <typename T, bool SELF, bool NT, bool FETCH = false, bool BEAM = false>
 __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   static_assert(!FETCH || SELF, "only the layer-0 self-attention fetches its input row from the embedding table");
@@ -916,9 +1000,10 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   constexpr int WMAX = 3;                // q weight chunks per lane held in registers (d_model 384, bf16)
   using V16 = decltype(Vec16<T>().v);
   extern __shared__ __align__(16) float hn[];   // [d] normalised input row (already rounded to T)
-  __shared__ float redw[16], redl[16], redlf[16];
+  __shared__ float redw[16], redl[16], redlf[16];   // (redw: also the norm's cross-wave slots, before the merge needs it)
   __shared__ float redo[16][DK];
-  __shared__ __align__(16) float redg[16 * (64 / LPR)][DK];   // per-group partial outputs (32 KB bf16 / 16 KB fp32)
+  __shared__ __align__(16) float redg[16 * (64 / LPR)][DK];
+  const DaMergeLds red{redw, redl, redlf, redo, redg};
   __shared__ __align__(16) float qs[DK];
   __shared__ __align__(16) float kn[DK];
   __shared__ __align__(16) float vn[DK];
@@ -1062,29 +1147,12 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
 
   // ---- 2. this head's projection: NOUT outputs, LPO lanes each, 16-byte chunks strided over lanes ----
   {
-    float acc = 0.f;
-#pragma unroll
-    for (int u = 0; u < WMAX; ++u) {
-      if (u < cnt) {
-        acc = chunk_dot<T>(w[u], hn, u * LPO + part, acc);
-      }
-    }
-    for (int i = WMAX; i < cnt; i += 4) {   // d_model / dtype combinations beyond the register budget (fp32)
-      Vec16<T> w2[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) w2[u].v = *reinterpret_cast<const V16*>(wrow + (min(i + u, cnt - 1) * LPO + part) * E);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (i + u < cnt) {
-          acc = chunk_dot<T>(w2[u], hn, (i + u) * LPO + part, acc);
-        }
-      }
-    }
-    acc = group_sum<LPO>(acc);
+    float q[1];
+    da_project<T, 1, LPO>(q, w, wrow, cnt, part, hn, a.d);
 #ifndef M2M_STAMPS_MERGE
     M2M_STAMP(6 + (SELF ? 1 : 0), 6);
 #endif
-    if (part == 0 && tid < NOUT * LPO) qs[dd] = acc;      // q stays fp32
+    if (part == 0 && tid < NOUT * LPO) qs[dd] = q[0];      // q stays fp32
   }
   if (SELF) {
 #pragma unroll
@@ -1122,22 +1190,7 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   float qv[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) qv[e] = qs[sub * E + e];
-  float m_run = -1e30f, l_run = 0.f;
-  float acc[E];
-#pragma unroll
-  for (int e = 0; e < E; ++e) acc[e] = 0.f;
-  // one exponential per key: of (alpha, p) = (exp(m_run - m_new), exp(s - m_new)) one is always exp(0) = 1
-  auto visit = [&](float s, const float (&vrow)[E]) {
-    const bool up = s > m_run;
-    const float m_new = up ? s : m_run;
-    const float ex = m2m_exp<T>(up ? m_run - s : s - m_run);
-    const float alpha = up ? ex : 1.f;
-    const float p = up ? 1.f : ex;
-    l_run = fmaf(l_run, alpha, p);
-#pragma unroll
-    for (int e = 0; e < E; ++e) acc[e] = fmaf(acc[e], alpha, p * vrow[e]);
-    m_run = m_new;
-  };
+  DaSoftmax<T> sm;
   // One round: consume slot u (scores, online-softmax update), optionally re-request the round PF ahead
   // into the same slot.  REISSUE is a compile-time choice per loop: in the main loop every re-request
   // exists, so the loads are unconditional and the compiler can count them (s_waitcnt vmcnt(N) keeps the
@@ -1160,7 +1213,7 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
     }
     if (key < n_live) {   // VALU-only predicate
       if (SELF) s += biasl[t - key];
-      visit(s, vrow);
+      sm.visit(s, vrow);
     }
 #else
     // The slot is re-requested AFTER it has been consumed (round 6).  With the request in front of the visit the compiler sinks V's
@@ -1172,7 +1225,7 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
 #pragma unroll
       for (int e = 0; e < E; ++e) vrow[e] = vs.get(e);
       if (SELF) s += biasl[t - key];
-      visit(s, vrow);
+      sm.visit(s, vrow);
     }
     if (reissue == 1 || (reissue == 2 && k0 + (u + PF) * KPB < n_live)) {   // workgroup-uniform, no lane is predicated
       const int64_t off = kvoff(min(key + PF * KPB, last));
@@ -1195,124 +1248,24 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   }
   if (SELF) {
     // project, round to T, append to the cache and publish through LDS the k,v rows of this step
-    float acc2 = 0.f;
-#pragma unroll
-    for (int u = 0; u < WMAX2; ++u) {
-      if (u < cnt2) {
-        acc2 = chunk_dot<T>(wkv[u], hn, u * LPO2 + part2, acc2);
-      }
-    }
-    for (int i = WMAX2; i < cnt2; i += 4) {   // d_model / dtype combinations beyond the register budget (fp32)
-      Vec16<T> w2[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) w2[u].v = *reinterpret_cast<const V16*>(wrow2 + (min(i + u, cnt2 - 1) * LPO2 + part2) * E);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (i + u < cnt2) {
-          acc2 = chunk_dot<T>(w2[u], hn, (i + u) * LPO2 + part2, acc2);
-        }
-      }
-    }
-    acc2 = group_sum<LPO2>(acc2);
-    if (part2 == 0) {
-      const T r = from_f32<T>(acc2);                       // k, v are stored (and used) rounded to T
-      const int64_t slot = (int64_t)t * DK + dd2;
-      if (which2 == 1) { kn[dd2] = to_f32(r); if (!st_done) Kb[slot] = r; }
-      else             { vn[dd2] = to_f32(r); if (!st_done) Vb[slot] = r; }
-    }
+    float kvn[1];
+    da_project<T, 1, LPO2>(kvn, wkv, wrow2, cnt2, part2, hn, a.d);
+    if (part2 == 0) da_append_kv<T>(kvn[0], 0, which2, dd2, t, 0, Kb, Vb, kn, vn, !st_done);
     __syncthreads();
   }
-  if (SELF && wave == 0 && lane < LPR) {   // the key/value appended this step (relative position 0): group 0
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < E; ++e) s = fmaf(qv[e], kn[sub * E + e], s);
-    s = group_sum<LPR>(s);
-    s += biasl[0];
-    float vrow[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) vrow[e] = vn[sub * E + e];
-    visit(s, vrow);
-  }
+  if (SELF && wave == 0 && lane < LPR) sm.visit_own(qv, kn, vn, biasl, sub);   // group 0
   M2M_STAMP(6 + (SELF ? 1 : 0), 2);
 
   // ---- 4. merge the 128 key groups (16 waves x 64 / LPR groups) ----
-  // Each group's partial output goes to LDS scaled to its WAVE's maximum (one LDS write per lane
-  // instead of 3 cross-lane exchanges per accumulator register: the exchanges were the bulk of the
-  // tail's VALU time with 16 waves on 4 SIMDs); waves are then summed group by group, and the 16 wave
-  // results are brought to the global maximum by the 64 threads that finish the row.
-  {
-    constexpr int GPW = 64 / LPR;                    // groups per wave: 8 (bf16) / 4 (fp32)
-    const float mw = wave_max(m_run);
-    const float scale = m2m_exp<T>(m_run - mw);          // groups that saw no key have m_run = -1e30 -> 0 (or 1 if the whole wave saw none: l = acc = 0)
-    float lsum = (sub == 0) ? l_run * scale : 0.f;   // l is replicated over a group's lanes: count it once
-    lsum = wave_sum(lsum);
-    float* gp = &redg[wave * GPW + lane / LPR][sub * E];
-#pragma unroll
-    for (int e = 0; e < E; e += 4)
-      *reinterpret_cast<float4*>(gp + e) = make_float4(acc[e] * scale, acc[e + 1] * scale, acc[e + 2] * scale, acc[e + 3] * scale);
-    if (lane == 0) { redw[wave] = mw; redl[wave] = lsum; }
-    __syncthreads();
+  da_merge<T>(sm, red, oh, [&] {
 #ifdef M2M_STAMPS_MERGE
     M2M_STAMP(6 + (SELF ? 1 : 0), 6);
 #endif
-    {
-      // every wave brings ITS partial sums to the global maximum here (one exponential per wave, in parallel),
-      // so the single wave that finishes the row below only adds: the 16 exponentials it used to evaluate were
-      // ~0.4 us of serial VALU time per launch
-      float M = redw[lane & 15];
-      M = fmaxf(M, lane_xor<8>(M)); M = fmaxf(M, lane_xor<4>(M)); M = fmaxf(M, lane_xor<2>(M)); M = fmaxf(M, lane_xor<1>(M));
-      const float fw = m2m_exp<T>(redw[wave] - M);
-      float sw = redg[wave * GPW][lane];             // thread (wave, lane = dim): this wave's groups, fixed order
-#pragma unroll
-      for (int j = 1; j < GPW; ++j) sw += redg[wave * GPW + j][lane];
-      redo[wave][lane] = sw * fw;
-      if (lane == 0) redlf[wave] = redl[wave] * fw;
-    }
-    __syncthreads();
-    if (tid < DK) {
-      float s = 0.f, L = 0.f;
-#pragma unroll
-      for (int wv = 0; wv < 16; ++wv) {
-        s += redo[wv][tid];
-        L += redlf[wv];
-      }
-      // the projection input is rounded to T, as every GEMM input (L = 0: a finished row's empty cross softmax).  !(L <= 0) keeps a NaN
-      // softmax (NaN encoder states, e.g. from a NaN sample) NaN, so the residual's range guard sees it instead of a zero head output.
-      put_in<T>(oh, tid, !(L <= 0.f) ? s / L : 0.f);
-    }
-    __syncthreads();
-    M2M_STAMP(6 + (SELF ? 1 : 0), 7);
-  }
+  });
+  M2M_STAMP(6 + (SELF ? 1 : 0), 7);
   // ---- 5. output projection of this head, accumulated into the residual row ----
-  {
-    float accp = 0.f;
-#pragma unroll
-    for (int u = 0; u < OCH; ++u) {
-      accp = chunk_dot<T>(wo[u], oh, opart * OCH + u, accp);
-    }
-    accp += lane_xor<1>(accp);
-    if (opart == 0 && tid < 2 * a.d && !st_done) {
-      xq_t add = xq_fix_guarded(accp, a.state);
-      if (hh == 0) add += FETCH ? xq_fix_guarded(eres, a.state) : xres;   // head 0 also carries the residual itself
-      atomicAdd(reinterpret_cast<unsigned long long*>(a.x_out + (int64_t)b * a.d + on_), (unsigned long long)add);
-      if (hh == a.H - 1) a.x_zero[(int64_t)b * a.d + on_] = 0;
-    }
-  }
-  if (!SELF && a.book && hh == 0 && tid == 0) {
-    // headless bookkeeping of row b, after the layer-0 self-attention kernel (all 8 head workgroups of the row) has consumed
-    // the key: the token fed at this step goes into the token matrix, EOS finishes the row, the key is cleared for this
-    // step's lm_head.  (hf generation/utils.py:2925-2937.)
-    if (!st_done) {
-      const int fin = a.finished[b];
-      const int next = amax_key_token(a.keys[b], fin, a.V, a.pad_id);
-      if (st_t < a.max_len) a.tokens[(int64_t)a.tok_row[b] * a.max_len + st_t] = next;
-      const int nf = fin | (next == a.eos_id);
-      a.finished[b] = nf;
-      if (!nf) atomicAdd(&a.state->n_unfinished, 1);
-      a.keys[b] = 0ull;
-    }
-    if (b == 0) a.state->t_copy = st_t;      // ALWAYS (also in the no-op steps after the end): the lm_head kernel's "live" test reads it
-  }
+  da_out_row<T>(a, wo, oh, b, !st_done, true, [&] { return FETCH ? xq_fix_guarded(eres, a.state) : xres; });
+  if (!SELF && a.book && hh == 0 && tid == 0) da_book_row(a, b, st_t, st_done);
   M2M_STAMP(6 + (SELF ? 1 : 0), 3);
 }
 
@@ -1328,8 +1281,9 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
 // after the other by all 16 waves as ONE continuous stream: a clip's rounds are padded to a multiple of the prefetch depth, and
 // its last rounds re-request into the NEXT live clip, so MC_PF rounds are in flight through every merge - and the C output
 // projections at the end.
-// Per row the arithmetic is the first kernel's, operation for operation (same lane -> element maps, same reduction trees, same
-// key -> lane-group partition, same rounding points): ids and logits are bit-identical whichever form a chain takes
+// Per row the arithmetic is the first kernel's (dec_attn_kernel and its da_* pieces above), repeated here operation for operation
+// (same lane -> element maps, same reduction trees, same key -> lane-group partition, same rounding points; why it is repeated and not
+// called: the note above the pieces): ids and logits are bit-identical whichever form a chain takes
 // (tests/test_t5_gpu.py::test_multi_clip_attention_and_wide_ff_tiles_are_bit_identical).  Chosen per chain by its clip count.
 // Prefetch depth (rounds in flight per workgroup).  Same-box A/B at 128 x S = 190, two chains of 64 clips, C = 2 (tools/r6_mc_ab.sh,
 // us per decode step): 2 rounds 370.0, 3 rounds 379.5, 4 rounds 394.0, 6 rounds 457.5 - as in the small-chain regime (the first
