@@ -364,6 +364,61 @@ int m2m_dataset_crop_f32(const m2m_dataset_clip* clips_host, int n_clips, void* 
                          int64_t T, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Rendering notes to audio: the packed notes of a batch of clips -> fp32 samples by ONE launch, a wavetable voice.  Stands in for
+ * ref: webui.py:66 (PrettyMIDI.fluidsynth) and PrettyMIDI.synthesize, with a built-in timbre instead of a SoundFont.  The definition
+ * is music2midi_amd/render.py (render_host); every sample is EQUAL to its: integer phase and decay arithmetic, then single rounded
+ * fp32 operations in its order, nothing contracted, the notes of a sample added in packed order.
+ * No handle, no workspace, no environment switch; the call copies nothing, enqueues one kernel on `stream` and returns nothing to
+ * the host.  Every M2M_ERR_INVALID below is answered on the arguments alone, before the first HIP call.
+ * ------------------------------------------------------------------------- */
+#define M2M_RENDER_MAX_SAMPLES (1 << 28)
+#define M2M_RENDER_MAX_NOTES (1 << 20)     /* packed notes of one call, all clips together */
+#define M2M_RENDER_MAX_CLIPS 65535
+#define M2M_RENDER_MAX_RAMP (1 << 24)      /* attack, release and decay steps: fp32 holds every integer up to it */
+
+typedef struct {
+  int32_t on;                              /* first sample, may be negative (>= -2^30): k = n - on */
+  int32_t off;                             /* release begins here; min(off, n_samples) */
+  uint32_t inc;                            /* phase step per sample, 2^32 = one period */
+  uint32_t dec;                            /* decay steps per sample in units of 2^-16 */
+  int32_t table;                           /* row of wave_dev, 0..n_tables - 1 */
+  float gain;
+} m2m_render_note;
+
+typedef struct {
+  const float* wave_dev;                   /* [n_tables][table_size + 1], entry table_size of a row equal to its entry 0 */
+  const float* decay_dev;                  /* [decay_steps + 1] */
+  int32_t table_size;                      /* a power of two, 256..65536 */
+  int32_t n_tables;                        /* 1..64 */
+  int32_t decay_steps;                     /* J, 1..2^24 */
+  int32_t attack, release;                 /* A, R in samples, 1..2^24 */
+  int32_t reserved;                        /* 0 */
+} m2m_render_voice;
+
+/* Output samples per workgroup: the tile of the lists below.  Host arithmetic. */
+int m2m_render_tile(void);
+
+/*
+ * out_dev[c * row_stride + n], c < n_clips, n < n_samples: the sum, from +0 and in list order, over the notes of tile
+ * (c, n / tile) with on <= n < min(off + release, n_samples) of (((w e) att) rel) gain, k = n - on:
+ *   phase = (uint32)(k inc), s = 32 - log2 table_size, i = phase >> s, fr = (float)(phase & (2^s - 1)) 2^-s, W = row `table`,
+ *   w = W[i] + fr (W[i + 1] - W[i]);  u = (uint64)k dec, j = u >> 16, ef = (float)(u & 0xFFFF) 2^-16,
+ *   e = E[j] + ef (E[j + 1] - E[j]) for j < decay_steps, else E[decay_steps];
+ *   att = (float)min(k + 1, attack) (1.0f / attack);  rel = 1 for n < off, else (float)(release - (n - off)) (1.0f / release).
+ * Every sample of the n_clips rows is written (a tile without notes: zeros), nothing outside them.
+ * notes_dev [n_notes]; tile_start_dev int32 [n_clips * tiles + 1], tiles = ceil(n_samples / tile), ascending from 0 to n_entries:
+ * the notes of tile t of clip c are tile_notes_dev[tile_start_dev[c * tiles + t] .. tile_start_dev[c * tiles + t + 1]), int32
+ * indices into notes_dev (an index outside it is clamped, a table outside the voice likewise).  With n_notes = 0, notes_dev and
+ * tile_notes_dev may be null.
+ * M2M_ERR_INVALID: n_samples outside 1..2^28, n_clips outside 1..65535, n_notes outside 0..2^20, n_entries outside 0..2^31 - 1 or
+ * positive without notes, row_stride < n_samples, attack or release outside 1..2^24, a table_size that is not a power of two in
+ * 256..65536, n_tables outside 1..64, decay_steps outside 1..2^24, reserved != 0, a null pointer, a pointer that is not 4-byte aligned.
+ */
+int m2m_render_notes_f32(const m2m_render_note* notes_dev, int n_notes, const int32_t* tile_start_dev, const int32_t* tile_notes_dev,
+                         int64_t n_entries, const m2m_render_voice* voice, float* out_dev, int64_t n_samples, int64_t row_stride,
+                         int n_clips, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Tokenising of note labels: the note arrays of a batch -> token ids, replaces for the batches it takes
  * ref: music2midi/tokenizer.py:86-141 (MidiTokenizer.__call__, _tokenize).  The definition is music2midi_amd/tokenizer.py
  * (_quantize, _tokenize); the ids are EQUAL to its (integer placement; the quantisation repeats the host's float64 operations).

@@ -106,6 +106,18 @@ def read_wav(path) -> Tuple[np.ndarray, int]:
     return y.reshape(-1, n_ch), int(lay.rate)
 
 
+def write_wav(path, y, sr: int) -> None:
+    """Mono 16-bit PCM RIFF/WAVE: ``clip(round(y * 32767), -32768, 32767)``.  ``read_wav`` of the file gives ``y`` back to within
+    that quantisation: half a step of the rounding plus ``|y| / 32768``, because ``read_wav`` divides by 32768 where this
+    multiplies by 32767 - within 1 / 32767 up to half of full scale, up to 1.5 / 32767 at full scale.  What ``soundfile.write``
+    does for the reference's preview (ref: webui.py:67)."""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    body = np.clip(np.round(y * 32767.0), -32768, 32767).astype("<i2").tobytes()
+    fmt = struct.pack("<HHIIHH", _WAVE_FORMAT_PCM, 1, int(sr), int(sr) * 2, 2, 16)
+    chunks = b"fmt " + struct.pack("<I", 16) + fmt + b"data" + struct.pack("<I", len(body)) + body
+    Path(path).write_bytes(b"RIFF" + struct.pack("<I", 4 + len(chunks)) + b"WAVE" + chunks)
+
+
 def resample(y: np.ndarray, orig_sr: float, target_sr: float) -> np.ndarray:
     """Polyphase resampling along the last axis (rational approximation of the rate ratio)."""
     if orig_sr == target_sr:

@@ -466,6 +466,15 @@ class Music2MIDI(nn.Module):
             notes, confidence = decode_with_confidence(self.model.tokenizer, token_ids, lps, "sequential", duration, floor)
         return (notes, confidence) if return_confidence else notes
 
+    def generate_audio(self, audio_path=None, audio_y=None, sr=None, cond_index=None, fs=None, normalize: bool = True):
+        """``(notes, audio)``: ``generate_notes``, then the notes rendered on the model's device by ``music2midi_amd.render.render``
+        at ``fs`` (``None``: the model's sample rate) - a fp32 tensor of ``last offset + release`` samples, peak-normalised unless
+        ``normalize=False``.  The timbre is the renderer's built-in voice."""
+        from .render import render
+        notes = self.generate_notes(audio_path, audio_y, sr, cond_index)
+        fs = self.config.model.sample_rate if fs is None else fs
+        return notes, render(notes, fs, normalize=normalize, device=self.device)
+
     def _device_ingest(self, audio_path, audio_y) -> bool:
         """The device ingest takes the call when ``config.inference.device_ingest`` is set (absent: off), the audio comes as a
         path, the model is on a GPU and ``ingest.eligible`` accepts the file; everything else is the host's ``load_audio``."""

@@ -55,6 +55,17 @@ class DatasetClip(C.Structure):
                 ("format", C.c_int32), ("up", C.c_int32), ("down", C.c_int32), ("half", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RenderNote(C.Structure):
+    """m2m_render_note: one packed note of m2m_render_notes_f32 (six 32-bit words)."""
+    _fields_ = [("on", C.c_int32), ("off", C.c_int32), ("inc", C.c_uint32), ("dec", C.c_uint32), ("table", C.c_int32), ("gain", C.c_float)]
+
+
+class RenderVoice(C.Structure):
+    """m2m_render_voice: the device tables and integer constants of a render.Voice."""
+    _fields_ = [("wave_dev", C.c_void_p), ("decay_dev", C.c_void_p), ("table_size", C.c_int32), ("n_tables", C.c_int32),
+                ("decay_steps", C.c_int32), ("attack", C.c_int32), ("release", C.c_int32), ("reserved", C.c_int32)]
+
+
 class T5GeometryC(C.Structure):
     _fields_ = [(n, C.c_int) for n in
                 ("d_model", "d_ff", "num_layers", "num_decoder_layers", "num_heads", "d_kv", "vocab_size",
@@ -141,6 +152,9 @@ _SIGNATURES = {
                                           C.c_void_p]),
     "m2m_dataset_crop_window": (C.c_int, [C.c_int, C.c_int]),
     "m2m_dataset_crop_f32": (C.c_int, [C.POINTER(DatasetClip), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "m2m_render_tile": (C.c_int, []),
+    "m2m_render_notes_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RenderVoice), C.c_void_p, C.c_int64,
+                                       C.c_int64, C.c_int, C.c_void_p]),
     "m2m_tokenize_quantize": (C.c_int, [C.c_double, C.c_double, C.c_int]),
     "m2m_tokenize_row_bound": (C.c_int64, [C.c_int, C.c_int]),
     "m2m_tokenize_notes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -4,8 +4,9 @@ With ``pretty_midi`` installed this returns a real ``PrettyMIDI`` exactly as the
 reference does (resolution 384, 120 bpm, one piano instrument, invalid notes
 removed).  The image used for the MI355X build has no pretty_midi, so a small
 stand-in with the members the reference's callers touch (``instruments[0].notes``,
-``get_end_time``, ``write``) is returned instead; ``fluidsynth`` needs the real
-package and says so.
+``get_end_time``, ``write``, ``synthesize``, ``fluidsynth``) is returned instead; its two
+audio methods go through ``music2midi_amd.render``: the built-in wavetable voice, not a
+SoundFont.
 """
 from __future__ import annotations
 
@@ -82,8 +83,23 @@ class SimpleMIDI:
             f.write(b"MThd" + struct.pack(">IHHH", 6, 0, 1, self.resolution))
             f.write(b"MTrk" + struct.pack(">I", len(track)) + track)
 
-    def fluidsynth(self, *a, **k):
-        raise ImportError("audio rendering needs the real pretty_midi + fluidsynth packages")
+    def synthesize(self, fs=44100) -> np.ndarray:
+        """The notes as audio at ``fs``, float64 like ``PrettyMIDI.synthesize``: the wavetable voice of ``music2midi_amd.render``,
+        rendered on the GPU when one is present and by the host definition otherwise (the same samples bit for bit)."""
+        return self._render(fs, normalize=False)
+
+    def fluidsynth(self, fs=44100, sf2_path=None) -> np.ndarray:
+        """``synthesize(fs)`` divided by its peak, as ``PrettyMIDI.fluidsynth`` normalises.  The timbre is the built-in voice of
+        ``music2midi_amd.render`` and NOT a SoundFont: a given ``sf2_path`` needs the real pretty_midi + fluidsynth packages."""
+        if sf2_path is not None:
+            raise ImportError("rendering through a SoundFont needs the real pretty_midi + fluidsynth packages")
+        return self._render(fs, normalize=True)
+
+    def _render(self, fs, normalize: bool) -> np.ndarray:
+        import torch
+        from . import render
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+        return render.render(self.note_array(), fs, normalize=normalize, device=device).cpu().numpy().astype(np.float64)
 
 
 def numpy_to_midi(notes: np.ndarray):
