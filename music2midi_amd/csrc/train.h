@@ -1,4 +1,4 @@
-// Internal structures of the training path (train.hip); not part of the C ABI.
+// Internal structures of the training path (train.hip and the files of kernels it drives); not part of the C ABI.
 #pragma once
 
 #include "common.h"
@@ -79,6 +79,50 @@ struct BGemmArgs {
 
 
 int launch_bgemm(int precision, int epi, const BGemmArgs& g, hipStream_t st, const TrainSwitches& sw);
+constexpr int TG_BM = 64, TG_BN = 64;      // launch_bgemm's output tile
+constexpr int TG_BK_MAX = 128;             // ... and a bound of the k it stages per step: a split-K kchunk is a multiple of it
+
+// Weight gradient (train_gemm.hip): C[N1, N2] (fp32) = A[K, N1]^T . B[K, N2], the reduction index as the row of both operands
+struct DwGemmArgs {
+  const void *A, *B;
+  float* C;
+  float* Cpart;
+  int N1, N2, K;
+  int64_t lda, ldb, ldc;
+  int ksplit, kchunk;
+  int accum;             // 1: C += A^T . B (gradient accumulation; never set on a k-slice's partial tile)
+};
+int launch_dw_gemm(int precision, const void* A, int64_t lda, int N1, const void* B, int64_t ldb, int N2, int K, float* C, int64_t ldc,
+                   float* kpart, int64_t kpart_floats, hipStream_t st, int accumulate, const TrainSwitches& sw);
+// ... and every weight gradient of a step as ONE launch over a device table of them, 128 x 128 tiles numbered through the table
+struct DwProb {
+  DwGemmArgs g;
+  int tile0, tn2;          // first tile of this problem in the launch; tiles along N2
+};
+int launch_dw_group(int precision, const DwProb* probs_dev, int n_probs, int tiles, hipStream_t st, const TrainSwitches& sw);
+// dY [M][Ny] -> tA [Ny][Mp], X [M][Kx] -> tB [Kx][Mp] (columns [M, Mp) zeroed): the operands of a weight gradient on the split-K bgemm route
+int launch_transpose_pair(int precision, const void* dY, int64_t ldy, int Ny, const void* X, int64_t ldx, int Kx, void* tA, void* tB, int M, int Mp,
+                          hipStream_t st);
+// all weight matrices of the model in one launch (weights_transpose_kernel, train_gemm.hip), from a table of 64 x 64 tiles
+struct WtBlock { int64_t off; int N, K, tn, tk; int il_half; };     // il_half > 0: a gate pair [wi_0 | wi_1], il_half = d_ff rows each
+int launch_weights_transpose(int precision, const WtBlock* blocks_dev, int n_blocks, const float* P, void* WT, void* Wc, void* Wil, hipStream_t st);
+
+__device__ inline uint32_t u4_get(const uint4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+// Column j of an E x E block held as E 16-byte rows (E = 8 bf16 / 4 fp32), as one 16-byte row of the transposed block.
+// bf16: halves (2d, 2d+1) of dword j/2 through v_perm_b32; fp32: register renaming.  (The k-major staging of train_gemm.hip and
+// kv_transpose_kernel of train.hip.)
+template <typename T, int E>
+__device__ inline uint4 tr_col(const uint4 (&rg)[E], int j) {
+  if constexpr (sizeof(T) == 2) {
+    const uint32_t sel = (j & 1) ? 0x07060302u : 0x05040100u;
+    return make_uint4(__builtin_amdgcn_perm(u4_get(rg[1], j >> 1), u4_get(rg[0], j >> 1), sel),
+                      __builtin_amdgcn_perm(u4_get(rg[3], j >> 1), u4_get(rg[2], j >> 1), sel),
+                      __builtin_amdgcn_perm(u4_get(rg[5], j >> 1), u4_get(rg[4], j >> 1), sel),
+                      __builtin_amdgcn_perm(u4_get(rg[7], j >> 1), u4_get(rg[6], j >> 1), sel));
+  } else {
+    return make_uint4(u4_get(rg[0], j), u4_get(rg[1], j), u4_get(rg[2], j), u4_get(rg[3], j));
+  }
+}
 
 // MXFP8 product (mx8.hip): C[M,N] (epi)= A[M,K] . B[N,K]^T, block-scaled fp8 operands (32 elements along K per E8M0 scale)
 struct MxGemmArgs {
@@ -109,7 +153,7 @@ int launch_mxq_cols(int src_kind, const void* src, int64_t ld_s, uint8_t* qt, ui
 
 // fp8 mode: the MXFP8 images of one projection matrix W [N][K] (fp32 master at parameter offset `off`), as byte offsets into the
 // trainer's w8 buffer: q [N][K] + qs [N][K/32] with blocks along K (the forward's B operand), qt [K][Np] + qts [K][Np/32] with
-// blocks along N (the B operand of dX = dY . W); Np = align_up(N, 128).  mxq_weights_kernel (train.hip) writes all four from a
+// blocks along N (the B operand of dX = dY . W); Np = align_up(N, 128).  mxq_weights_kernel (train_gemm.hip) writes all four from a
 // table of 32 x 64 tiles.  w8_add_matrix is the per-matrix part of the table builder: it places the four images behind
 // `w8_bytes` (advancing it, 256-byte aligned) and appends the matrix's tiles.
 struct W8Lin { int64_t off; int N, K, Np; int64_t q, qs, qt, qts; };

@@ -1,7 +1,8 @@
 // Training-step kernels: what `loss.backward()` + `Adafactor.step()` run for
 // ref: music2midi/model.py:27-43 (training_step -> T5Transformer.forward with labels, ref transformer.py:28-39;
 // optimizer = transformers Adafactor(warmup_init=True) + AdafactorSchedule), written for gfx950.
-// (The Adafactor kernels and their launcher are in adafactor.hip; the plan they run on is built here, build_optimizer.)
+// (The Adafactor kernels and their launcher are in adafactor.hip; the plan they run on is built here, build_optimizer.  The strided
+// and the weight-gradient GEMMs, the transposes and the per-step weight copies are in train_gemm.hip, behind the launchers of train.h.)
 //
 // Layout rules of the training path (train_api.hip drives these kernels):
 //   * every activation is a plain row-major [rows, features] matrix — fp32 for the residual stream, its
@@ -23,664 +24,12 @@
 #include <string.h>
 #include <algorithm>
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
 
 namespace m2m {
-
-// ============================================================ strided batched GEMM ====
-// C[z][M,N] (op)= alpha * A[z][M,K] . B[z][N,K]^T,  z = (b1, b2) with independent strides per operand.
-// 64x64 output tile per 256-thread workgroup (2x2 waves, one 32x32 MFMA tile each), BK = 32.
-// Operand storage: a_kmajor == 0: element (m, k) at A[m*lda + k]; a_kmajor == 1: at A[k*lda + m]
-// (the transposed product reads the buffer as it is: the tile is transposed on its way into LDS).
-constexpr int TG_BM = 64, TG_BN = 64;
-// k extent staged per step: 96 (bf16) / 64 (fp32).  The attention products reduce over <= ~360 keys / queries, so the dependent
-// load -> LDS -> MFMA chain of a workgroup is 3 steps instead of the 9 of BK = 32 (16 -> us per launch).  96 rather than 128 for
-// bf16 (round 3): 26.6 KB of LDS instead of 34.8 — five workgroups per CU (97 registers allow them) instead of four, so the
-// 1 280 workgroups of the paired dV | dK launch of a 16-clip step are ONE round of the chip, and 261 keys are three steps either way
-// (18 launches per step, 17.8 -> 16.3 us each; M2M_TG_BK at build time for measurements).
-constexpr int TG_BK_MAX = 128;
-
-template <typename T> struct TgCfg;
-#ifndef M2M_TG_BK
-#define M2M_TG_BK 96
-#endif
-template <> struct TgCfg<bf16_t> { static constexpr int E = 8, BK = M2M_TG_BK, PITCH = BK + 8; };
-template <> struct TgCfg<float> { static constexpr int E = 4, BK = 64, PITCH = BK + 4; };
-
-__device__ inline uint32_t u4_get(const uint4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
-// Column j of an E x E block held as E 16-byte rows (E = 8 bf16 / 4 fp32), as one 16-byte row of the transposed block.
-// bf16: halves (2d, 2d+1) of dword j/2 through v_perm_b32; fp32: register renaming.
-template <typename T, int E>
-__device__ inline uint4 tr_col(const uint4 (&rg)[E], int j) {
-  if constexpr (sizeof(T) == 2) {
-    const uint32_t sel = (j & 1) ? 0x07060302u : 0x05040100u;
-    return make_uint4(__builtin_amdgcn_perm(u4_get(rg[1], j >> 1), u4_get(rg[0], j >> 1), sel),
-                      __builtin_amdgcn_perm(u4_get(rg[3], j >> 1), u4_get(rg[2], j >> 1), sel),
-                      __builtin_amdgcn_perm(u4_get(rg[5], j >> 1), u4_get(rg[4], j >> 1), sel),
-                      __builtin_amdgcn_perm(u4_get(rg[7], j >> 1), u4_get(rg[6], j >> 1), sel));
-  } else {
-    return make_uint4(u4_get(rg[0], j), u4_get(rg[1], j), u4_get(rg[2], j), u4_get(rg[3], j));
-  }
-}
-
-// one operand tile [64 rows][32 k] -> LDS (row-major, k contiguous), zero-filled outside (rows_valid, k_valid).
-// k-major operands: E x E blocks transposed in registers (16-byte LDS rows instead of 2-byte scatters), threads
-// [tshift, tshift + blocks) do the work so that the A and the B tile of a step are staged by different waves; the row
-// (non-reduction) index may run past `rows` inside the 16-byte chunk: those tile rows only feed outputs that are never stored
-// (launch_bgemm checks that the padded row still lies inside the operand's row stride).
-template <typename T>
-__device__ inline void tg_stage(T* __restrict__ S, const T* __restrict__ G, int64_t ld, int kmajor, int row0, int k0,
-                                int rows, int K, int tid, int tshift) {
-  using Cfg = TgCfg<T>;
-  constexpr int E = Cfg::E;
-  if (!kmajor) {
-    constexpr int TG_BK = Cfg::BK;
-    constexpr int CPR = TG_BK / E;                      // chunks per row
-    for (int c = tid; c < TG_BM * CPR; c += 256) {
-      const int rl = c / CPR, kc = (c % CPR) * E;
-      const int row = row0 + rl, k = k0 + kc;
-      T* dst = S + rl * Cfg::PITCH + kc;
-      if (row < rows && k + E <= K) {
-        *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(G + (int64_t)row * ld + k);
-      } else {
-#pragma unroll
-        for (int e = 0; e < E; ++e) dst[e] = (row < rows && k + e < K) ? G[(int64_t)row * ld + k + e] : from_f32<T>(0.f);
-      }
-    }
-  } else {
-    constexpr int KBn = Cfg::BK / E, RBn = TG_BM / E;   // blocks along k / along the tile rows
-    const int c0 = tid - tshift;                                             // 128 threads per operand
-    for (int c = c0; c0 >= 0 && c0 < 128 && c < KBn * RBn; c += 128) {
-      const int kb = c % KBn, rb = c / KBn;
-      const int row = row0 + rb * E;
-      uint4 rg[E];
-#pragma unroll
-      for (int kk = 0; kk < E; ++kk) {
-        const int k = k0 + kb * E + kk;
-        rg[kk] = (k < K && row < rows) ? *reinterpret_cast<const uint4*>(G + (int64_t)k * ld + row) : make_uint4(0, 0, 0, 0);
-      }
-#pragma unroll
-      for (int j = 0; j < E; ++j) *reinterpret_cast<uint4*>(S + (rb * E + j) * Cfg::PITCH + kb * E) = tr_col<T, E>(rg, j);
-    }
-  }
-}
-
-template <typename T, int EPI>
-__global__ __launch_bounds__(256) void bgemm_kernel(BGemmArgs g) {
-  using Cfg = TgCfg<T>;
-  __shared__ __align__(16) T As[TG_BM * Cfg::PITCH];
-  __shared__ __align__(16) T Bs[TG_BN * Cfg::PITCH];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int r = lane & 31, h = lane >> 5;
-  const bool split = g.ksplit > 1;
-  const int nz = g.nb1 * g.nb2;
-  // XCD-contiguous workgroup order (g.xcd_total > 0: 1-D launch; workgroup id % 8 picks the XCD): an XCD walks one eighth of the
-  // (x, y, z) list front to back, so the row tiles of one (clip, head) product — which all read the same k-major operand — run
-  // side by side on ONE XCD and meet in its L2 (dV / dK: 124 MB fetched per launch for 33 MB of operands with the launch order)
-  int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  if (g.xcd_total > 0) {
-    const int per = (g.xcd_total + 7) >> 3, l = (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-    if (l >= g.xcd_total || (int)(blockIdx.x >> 3) >= per) return;        // padding workgroups (uniform)
-    bx = l % g.xcd_nx; by = (l / g.xcd_nx) % g.xcd_ny; bz = l / (g.xcd_nx * g.xcd_ny);
-  }
-  const bool second = !split && g.A2 && bz >= nz;            // pair mode: the second product of the launch
-  const int zz = second ? bz - nz : bz;
-  const int z1 = split ? 0 : zz / g.nb2, z2 = split ? 0 : zz - z1 * g.nb2;
-  const T* A = reinterpret_cast<const T*>(second ? g.A2 : g.A) + z1 * g.sA1 + z2 * g.sA2;
-  const T* B = second ? reinterpret_cast<const T*>(g.B2) + z1 * g.sB1_2 + z2 * g.sB2_2 : reinterpret_cast<const T*>(g.B) + z1 * g.sB1 + z2 * g.sB2;
-  const int64_t ldb = second ? g.ldb2 : g.ldb;
-  void* const Cout = second ? g.C2 : g.C;
-  const int64_t coff = z1 * g.sC1 + z2 * g.sC2;
-  const int m0 = by * TG_BM, n0 = bx * TG_BN;
-  const int kbeg = split ? bz * g.kchunk : 0, kend = split ? min(g.K, kbeg + g.kchunk) : g.K;
-
-  f32x16 acc = zero_acc();
-  constexpr int TG_BK = Cfg::BK;
-  for (int k0 = kbeg; k0 < kend; k0 += TG_BK) {
-    __syncthreads();
-    tg_stage<T>(As, A, g.lda, g.a_kmajor, m0, k0, g.M, kend, tid, 0);
-    tg_stage<T>(Bs, B, ldb, g.b_kmajor, n0, k0, g.N, kend, tid, 128);
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < TG_BK / 16; ++s) {
-      const Frag<T> fa = load_frag(As + (wm * 32 + r) * Cfg::PITCH + s * 16 + 8 * h);
-      const Frag<T> fb = load_frag(Bs + (wn * 32 + r) * Cfg::PITCH + s * 16 + 8 * h);
-      mma16(acc, fa, fb);
-    }
-  }
-  const int col = n0 + wn * 32 + r;
-  if (col >= g.N) return;
-  const uint64_t dkey = (EPI == TG_RESID_F32 && g.drop_thresh) ? splitmix64(*g.drop_step + g.drop_key) : 0ull;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int row = m0 + wm * 32 + acc_row(i, lane);
-    if (row >= g.M) continue;
-    if (split) {                                   // partial tile of this k-slice
-      g.Cpart[((int64_t)bz * g.M + row) * g.N + col] = acc[i];
-      continue;
-    }
-    const int64_t at = coff + (int64_t)row * g.ldc + col;
-    const float v = g.alpha * acc[i];
-    if constexpr (EPI == TG_STORE_T) reinterpret_cast<T*>(Cout)[at] = from_f32<T>(v);
-    else if constexpr (EPI == TG_STORE_F32) reinterpret_cast<float*>(Cout)[at] = v;
-    else if constexpr (EPI == TG_ACC_F32) reinterpret_cast<float*>(Cout)[at] += v;
-    else {                                                                       // TG_RESID_F32: C = R + dropout(acc)
-      float u = v;
-      if (g.drop_thresh) u = drop_keep(dkey, at, g.drop_thresh) ? v * g.drop_scale : 0.f;
-      reinterpret_cast<float*>(Cout)[at] = g.R[at] + u;
-    }
-  }
-}
-
-template <typename T>
-static int launch_bgemm_t(int epi, const BGemmArgs& g_in, hipStream_t st, bool xcd) {
-  BGemmArgs g = g_in;
-  dim3 grid((unsigned)ceil_div(g.N, TG_BN), (unsigned)ceil_div(g.M, TG_BM), (unsigned)(g.ksplit > 1 ? g.ksplit : g.nb1 * g.nb2 * (g.A2 ? 2 : 1)));
-  if (xcd && (int64_t)grid.x * grid.y * grid.z >= 64 && (int64_t)grid.x * grid.y * grid.z < (1 << 30)) {
-    g.xcd_nx = (int)grid.x; g.xcd_ny = (int)grid.y; g.xcd_total = (int)(grid.x * grid.y * grid.z);
-    grid = dim3((unsigned)(8 * ceil_div(g.xcd_total, 8)));
-  }
-  switch (epi) {
-    case TG_STORE_T: hipLaunchKernelGGL((bgemm_kernel<T, TG_STORE_T>), grid, dim3(256), 0, st, g); break;
-    case TG_STORE_F32: hipLaunchKernelGGL((bgemm_kernel<T, TG_STORE_F32>), grid, dim3(256), 0, st, g); break;
-    case TG_ACC_F32: hipLaunchKernelGGL((bgemm_kernel<T, TG_ACC_F32>), grid, dim3(256), 0, st, g); break;
-    case TG_RESID_F32: hipLaunchKernelGGL((bgemm_kernel<T, TG_RESID_F32>), grid, dim3(256), 0, st, g); break;
-    default: set_error("bgemm: bad epilogue %d", epi); return M2M_ERR_INVALID;
-  }
-  M2M_CHECK_HIP(hipGetLastError());
-  return M2M_OK;
-}
-
-// C[row][col] = alpha * sum_z part[z][row][col]   (z ascending: fixed order)
-// (accumulate != 0: C[row][col] += alpha * sum — the accumulate mode of a weight gradient, m2m_train_forward_backward_acc)
-__global__ void splitk_reduce_kernel(const float* __restrict__ part, float* __restrict__ C, int M, int N, int64_t ldc, int ksplit, float alpha,
-                                     int accumulate) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t n = (int64_t)M * N, stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    float acc = 0.f;
-    for (int z = 0; z < ksplit; ++z) acc += part[(int64_t)z * n + i];
-    const int64_t row = i / N;
-    float* c = C + row * ldc + (i - row * N);
-    *c = accumulate ? *c + alpha * acc : alpha * acc;
-  }
-}
-
-// ============================================================ weight-gradient GEMM ====
-// C[N1, N2] (fp32) = A[K, N1]^T . B[K, N2]: both operands row-major with the REDUCTION index as the row (a weight
-// gradient dW = dY^T . X reads dY [rows, N1] and X [rows, N2] exactly as the forward / backward passes left them).
-// The MFMA wants 8 consecutive k per lane, memory has 8 consecutive n: every thread loads an E x E block (E rows of k,
-// 16 bytes = E elements of n each; a wave's request is eight full 128-byte lines), transposes it IN REGISTERS (bf16:
-// 32 v_perm_b32 per 8x8 block; fp32: pure renaming) and writes E 16-byte rows of the usual [n][k] LDS tile — the same
-// number of LDS writes as a k-contiguous operand, where the generic kernel above scatters 2-byte elements.
-// Tiles 128x128 (TF = 2) or 64x64 (TF = 1), BK = 64 / 32, next k-step prefetched into registers, split over k on
-// blockIdx.z with fp32 partial tiles summed in z order by splitk_reduce_kernel (deterministic).
-struct DwGemmArgs {
-  const void *A, *B;
-  float* C;
-  float* Cpart;
-  int N1, N2, K;
-  int64_t lda, ldb, ldc;
-  int ksplit, kchunk;
-  int accum;             // 1: C += A^T . B (gradient accumulation; never set on a k-slice's partial tile)
-};
-
-template <typename T> struct DwCfg;
-template <> struct DwCfg<bf16_t> { static constexpr int BK = 64, E = 8; };
-template <> struct DwCfg<float> { static constexpr int BK = 32, E = 4; };
-
-// the epilogue's store: overwrite, or (accum, workgroup-uniform) add to what the buffer holds — one extra read per element
-__device__ inline void dw_put(float* p, float v, int accum) { *p = accum ? *p + v : v; }
-
-// one output tile [n1_0, +BT) x [n2_0, +BT) over k in [kbeg, kend), written to (accum: added to) out (row stride ldo)
-template <typename T, int TF>
-__device__ inline void dw_tile(const DwGemmArgs& g, T* __restrict__ AB, int n1_0, int n2_0, int kbeg, int kend, float* __restrict__ out, int64_t ldo,
-                               int accum) {
-  using Cfg = DwCfg<T>;
-  constexpr int BK = Cfg::BK, E = Cfg::E, PITCH = BK + E;
-  constexpr int BT = 64 * TF, WT = 32 * TF;
-  constexpr int KB = BK / E, NB = BT / E, BPO = KB * NB, TB = 2 * BPO, NBT = (TB + 255) / 256;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int r = lane & 31, h = lane >> 5;
-
-  // this thread's blocks: (operand, n block, k block); kb runs fastest over the lanes, so one store instruction of a wave
-  // covers whole 128-byte LDS rows and one load instruction whole 128-byte lines of 8 k-rows
-  const T* src[NBT];
-  int64_t ld[NBT];
-  int kofs[NBT], lds_off[NBT];
-  bool ok[NBT];
-#pragma unroll
-  for (int u = 0; u < NBT; ++u) {
-    const int bi = tid + 256 * u;
-    const int op = bi / BPO, id = bi - op * BPO;
-    const int kb = id % KB, nb = id / KB;
-    const int n0 = op ? n2_0 : n1_0, nlim = op ? g.N2 : g.N1;
-    ok[u] = bi < TB && n0 + nb * E + E <= nlim;
-    src[u] = reinterpret_cast<const T*>(op ? g.B : g.A) + (ok[u] ? n0 + nb * E : 0);
-    ld[u] = op ? g.ldb : g.lda;
-    kofs[u] = kb * E;
-    lds_off[u] = (min(op, 1) * BT + nb * E) * PITCH + kb * E;
-  }
-  uint4 rg[NBT][E];
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int u = 0; u < NBT; ++u)
-#pragma unroll
-      for (int kk = 0; kk < E; ++kk) {
-        const int k = k0 + kofs[u] + kk;
-        const uint4 v = *reinterpret_cast<const uint4*>(src[u] + (int64_t)min(k, kend - 1) * ld[u]);   // clamped, never predicated
-        rg[u][kk] = (ok[u] && k < kend) ? v : make_uint4(0, 0, 0, 0);
-      }
-  };
-  auto sstore = [&]() {
-#pragma unroll
-    for (int u = 0; u < NBT; ++u) {
-      if (TB < 256 && tid >= TB) continue;
-#pragma unroll
-      for (int j = 0; j < E; ++j) *reinterpret_cast<uint4*>(AB + lds_off[u] + j * PITCH) = tr_col<T, E>(rg[u], j);
-    }
-  };
-
-  f32x16 acc[TF][TF];
-#pragma unroll
-  for (int i = 0; i < TF; ++i)
-#pragma unroll
-    for (int j = 0; j < TF; ++j) acc[i][j] = zero_acc();
-  const T* As = AB;
-  const T* Bs = AB + BT * PITCH;
-  gload(kbeg);
-  for (int k0 = kbeg; k0 < kend; k0 += BK) {
-    __syncthreads();
-    sstore();
-    __syncthreads();
-    if (k0 + BK < kend) gload(k0 + BK);
-#pragma unroll
-    for (int s = 0; s < BK / 16; ++s) {
-      Frag<T> fa[TF], fb[TF];
-#pragma unroll
-      for (int i = 0; i < TF; ++i) {
-        fa[i] = load_frag(As + (wm * WT + i * 32 + r) * PITCH + s * 16 + 8 * h);
-        fb[i] = load_frag(Bs + (wn * WT + i * 32 + r) * PITCH + s * 16 + 8 * h);
-      }
-#pragma unroll
-      for (int i = 0; i < TF; ++i)
-#pragma unroll
-        for (int j = 0; j < TF; ++j) mma16(acc[i][j], fa[i], fb[j]);
-    }
-  }
-#pragma unroll
-  for (int mi = 0; mi < TF; ++mi)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int row = n1_0 + wm * WT + mi * 32 + acc_row(e, lane);
-      if (row >= g.N1) continue;
-#pragma unroll
-      for (int ni = 0; ni < TF; ++ni) {
-        const int col = n2_0 + wn * WT + ni * 32 + r;
-        if (col < g.N2) dw_put(out + (int64_t)row * ldo + col, acc[mi][ni][e], accum);
-      }
-    }
-}
-
-// The same 128 x 128 tile for bf16 WITHOUT the register transposes: the operands' k-major rows are copied to LDS as they lie in
-// memory ([k][n], 320-byte rows: four consecutive k-rows fall into four different 16-bank groups), and an MFMA fragment — 8
-// consecutive k of one column — is two `ds_read_b64_tr_b16` (gfx950's transposing LDS read: per 16 lanes a 4 x 16 block comes back
-// column-major; lane map checked by tools/trprobe.hip).  What this buys is on the LOAD side: with an 8 x 8 register block per
-// thread, neighbouring lanes had to sit in different k-rows (so that the transposed block lands in one LDS row), and every
-// 16-byte request was a cache access of its own — PMC: 2.5e8 L1 accesses per launch for 3.9 GB, 77 % of the kernel's cycles per
-// CU; here 16 neighbouring lanes read one 256-byte row segment.  ~140 VALU instructions per k-step and wave disappear with it.
-constexpr int DWT_PITCH = 160;                       // bf16 elements per staged k-row: 128 + 32 of padding
-typedef short dw_v4s __attribute__((ext_vector_type(4)));
-__device__ inline Frag<bf16_t> dw_tr_frag(const bf16_t* p) {            // p: this lane's address of the first 4 k-rows (see dw_tile_tr)
-  typedef dw_v4s __attribute__((address_space(3))) * lds_v4s;
-  const dw_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s)(p));
-  const dw_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s)(p + 4 * DWT_PITCH));
-  Frag<bf16_t> f;
-  f.v = make_uint4(__builtin_bit_cast(uint2, lo).x, __builtin_bit_cast(uint2, lo).y, __builtin_bit_cast(uint2, hi).x, __builtin_bit_cast(uint2, hi).y);
-  return f;
-}
-// FULL: the tile lies inside the matrix on both sides (every tile of the projection weights; not the last tiles of lm_head):
-// no column predicate anywhere.  The k loop runs whole 64-row steps from pointers that advance by a constant — no clamp, no
-// select, no 64-bit multiply per load — and one guarded step takes the ragged end (M = 4 176 rows = 65 steps + 16 rows).
-template <bool FULL>
-__device__ inline void dw_tile_tr(const DwGemmArgs& g, bf16_t* __restrict__ AB, int n1_0, int n2_0, int kbeg, int kend, float* __restrict__ out,
-                                  int64_t ldo, int accum) {
-  constexpr int BK = 64, P = DWT_PITCH;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  // staging: threads 0..127 copy operand A (dY), 128..255 operand B (X); a thread owns 16-byte chunk `ch` of the k-rows
-  // rw, rw + 8, ... rw + 56: 16 neighbouring lanes cover one 256-byte row segment
-  const int op = tid >> 7, c = tid & 127, ch = c & 15, rw = c >> 4;
-  const int n0 = op ? n2_0 : n1_0, nlim = op ? g.N2 : g.N1;
-  const bool ok = FULL || n0 + ch * 8 + 8 <= nlim;
-  const int64_t ld = op ? g.ldb : g.lda;
-  const bf16_t* pk = reinterpret_cast<const bf16_t*>(op ? g.B : g.A) + (ok ? n0 + ch * 8 : 0) + (int64_t)(kbeg + rw) * ld;   // row rw of the current step
-  const int64_t step = (int64_t)BK * ld, ld8 = 8 * ld;
-  bf16_t* dst = AB + op * (BK * P) + rw * P + ch * 8;
-  uint4 r0, r1, r2, r3, r4, r5, r6, r7;               // named: arrays across the k loop end up in scratch (hipcc 7.2)
-#define M2M_DW_LD(u) { const uint4 v = *reinterpret_cast<const uint4*>(pk + (u) * ld8); r##u = ok ? v : make_uint4(0, 0, 0, 0); }
-#define M2M_DW_LD_TAIL(u, k0) { const int k = (k0) + rw + 8 * (u); const uint4 v = *reinterpret_cast<const uint4*>(pk + (int64_t)(min(k, kend - 1) - ((k0) + rw)) * ld); \
-                                r##u = (ok && k < kend) ? v : make_uint4(0, 0, 0, 0); }
-#define M2M_DW_GLOAD() { M2M_DW_LD(0) M2M_DW_LD(1) M2M_DW_LD(2) M2M_DW_LD(3) M2M_DW_LD(4) M2M_DW_LD(5) M2M_DW_LD(6) M2M_DW_LD(7) }
-#define M2M_DW_GLOAD_TAIL(k0) { M2M_DW_LD_TAIL(0, k0) M2M_DW_LD_TAIL(1, k0) M2M_DW_LD_TAIL(2, k0) M2M_DW_LD_TAIL(3, k0) M2M_DW_LD_TAIL(4, k0) \
-                                M2M_DW_LD_TAIL(5, k0) M2M_DW_LD_TAIL(6, k0) M2M_DW_LD_TAIL(7, k0) }
-#define M2M_DW_ST(u) *reinterpret_cast<uint4*>(dst + 8 * (u) * P) = r##u;
-#define M2M_DW_SSTORE() { M2M_DW_ST(0) M2M_DW_ST(1) M2M_DW_ST(2) M2M_DW_ST(3) M2M_DW_ST(4) M2M_DW_ST(5) M2M_DW_ST(6) M2M_DW_ST(7) }
-  // fragment addresses: lane = 16 g + 4 q + p supplies row q of its group's 4 x 16 block, columns 4p .. 4p+3; groups 0 / 1 are the
-  // column halves of k 0..7, groups 2 / 3 those of k 8..15 (h = g >> 1) of a 16-deep substep
-  const int li = lane & 15, q = li >> 2, pp = li & 3, gq = lane >> 4, h = lane >> 5;
-  const bf16_t* fa = AB + (8 * h + q) * P + wm * 64 + 16 * (gq & 1) + 4 * pp;
-  const bf16_t* fb = AB + BK * P + (8 * h + q) * P + wn * 64 + 16 * (gq & 1) + 4 * pp;
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = zero_acc();
-  const int nfull = (kend - kbeg) / BK;               // whole steps; a ragged one may follow
-  const bool ragged = kbeg + nfull * BK < kend;
-  const int nsteps = nfull + (ragged ? 1 : 0);
-  if (nfull > 0) M2M_DW_GLOAD() else M2M_DW_GLOAD_TAIL(kbeg)
-  for (int it = 0; it < nsteps; ++it) {
-    __syncthreads();
-    M2M_DW_SSTORE()
-    __syncthreads();
-    pk += step;
-    if (it + 1 < nfull) M2M_DW_GLOAD()
-    else if (it + 1 < nsteps) M2M_DW_GLOAD_TAIL(kbeg + (it + 1) * BK)
-#pragma unroll
-    for (int s = 0; s < BK / 16; ++s) {
-      Frag<bf16_t> a[2], b[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        a[i] = dw_tr_frag(fa + 16 * s * P + 32 * i);
-        b[i] = dw_tr_frag(fb + 16 * s * P + 32 * i);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) mma16(acc[i][j], a[i], b[j]);
-    }
-  }
-#undef M2M_DW_LD
-#undef M2M_DW_LD_TAIL
-#undef M2M_DW_GLOAD
-#undef M2M_DW_GLOAD_TAIL
-#undef M2M_DW_ST
-#undef M2M_DW_SSTORE
-  const int r = lane & 31;
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int row = n1_0 + wm * 64 + mi * 32 + acc_row(e, lane);
-      if (!FULL && row >= g.N1) continue;
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        const int col = n2_0 + wn * 64 + ni * 32 + r;
-        if (FULL || col < g.N2) dw_put(out + (int64_t)row * ldo + col, acc[mi][ni][e], accum);
-      }
-    }
-}
-
-template <typename T, int TF>
-__global__ __launch_bounds__(256) void dw_gemm_kernel(DwGemmArgs g) {
-  constexpr int BT = 64 * TF, PITCH = DwCfg<T>::BK + DwCfg<T>::E;
-  __shared__ __align__(16) T AB[2 * BT * PITCH];
-  const bool split = g.ksplit > 1;
-  const int kbeg = split ? blockIdx.z * g.kchunk : 0, kend = split ? min(g.K, kbeg + g.kchunk) : g.K;
-  dw_tile<T, TF>(g, AB, blockIdx.y * BT, blockIdx.x * BT, kbeg, kend, split ? g.Cpart + (int64_t)blockIdx.z * g.N1 * g.N2 : g.C,
-                 split ? (int64_t)g.N2 : g.ldc, split ? 0 : g.accum);
-}
-
-// Every weight gradient of a step in ONE launch: the backward pass only records (dY, X, dW) triples — each sub-layer
-// keeps its dY operands in buffers of its own, 0.55 GB at 16 clips, nothing for a 288 GB part — and this kernel walks
-// the table: workgroup -> (problem, 128x128 tile), full reduction length per tile.  ~1 850 tiles fill the 256 CUs
-// seven times over, so no product is split over k: the split-K partial images (3.8 GB written and re-read per step
-// for the 67 products, 134 launches) are gone.
-struct DwProb {
-  DwGemmArgs g;
-  int tile0, tn2;          // first tile of this problem in the launch; tiles along N2
-};
-template <typename T, bool TR>
-__global__ __launch_bounds__(256) void dw_group_kernel(const DwProb* __restrict__ probs, int n_probs, int n_tiles, int xcd_order) {
-  constexpr int PITCH = DwCfg<T>::BK + DwCfg<T>::E;
-  constexpr int LDS_ELEMS = TR ? 2 * 64 * DWT_PITCH : 2 * 128 * PITCH;
-  __shared__ __align__(16) T AB[LDS_ELEMS];
-  // XCD-contiguous tile order (workgroup id % 8 picks the XCD): each XCD walks one eighth of the tile list front to back, so the
-  // tiles that run side by side on an XCD are neighbours in the list — the same product, the same dY column block (tiles of a
-  // product are numbered along X fastest), a handful of X column blocks — and their operand slices meet in that XCD's L2
-  const int per = (n_tiles + 7) >> 3;
-  const int tile = xcd_order ? (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-  if (tile >= n_tiles || (xcd_order && (int)(blockIdx.x >> 3) >= per)) return;       // padding workgroups (uniform)
-  int p = 0;
-  while (p + 1 < n_probs && tile >= probs[p + 1].tile0) ++p;                          // uniform scan of <= ~70 entries
-  const DwProb pr = probs[p];
-  const int tl = tile - pr.tile0;
-  if constexpr (TR) {
-    const int n1_0 = (tl / pr.tn2) * 128, n2_0 = (tl % pr.tn2) * 128;
-    if (n1_0 + 128 <= pr.g.N1 && n2_0 + 128 <= pr.g.N2) dw_tile_tr<true>(pr.g, AB, n1_0, n2_0, 0, pr.g.K, pr.g.C, pr.g.ldc, pr.g.accum);      // (workgroup-uniform)
-    else dw_tile_tr<false>(pr.g, AB, n1_0, n2_0, 0, pr.g.K, pr.g.C, pr.g.ldc, pr.g.accum);
-  } else dw_tile<T, 2>(pr.g, AB, (tl / pr.tn2) * 128, (tl % pr.tn2) * 128, 0, pr.g.K, pr.g.C, pr.g.ldc, pr.g.accum);
-}
-
-// C = A^T . B with the split chosen here: enough workgroups to fill the chip, as few k-slices as that allows (every slice
-// writes and re-reads an fp32 image of C).
-int launch_dw_gemm(int precision, const void* A, int64_t lda, int N1, const void* B, int64_t ldb, int N2, int K, float* C, int64_t ldc,
-                   float* kpart, int64_t kpart_floats, hipStream_t st, int accumulate, const TrainSwitches& sw) {
-  const int E = precision == M2M_PREC_BF16 ? 8 : 4, BK = precision == M2M_PREC_BF16 ? 64 : 32;
-  M2M_REQUIRE(N1 % E == 0 && N2 % E == 0 && lda % E == 0 && ldb % E == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(B) & 15) == 0,
-              "dw_gemm: operands must be 16-byte aligned with row lengths that are multiples of %d", E);
-  const int t128 = ceil_div(N1, 128) * ceil_div(N2, 128);
-  const int tf = sw.dw_tile == 64 ? 1 : 2;   // 128x128 measured faster for every weight shape of the model (16 clips: 8.80 vs 9.90 ms per step)
-  (void)t128;
-  const int bt = 64 * tf;
-  const int tiles = ceil_div(N1, bt) * ceil_div(N2, bt);
-  int ks = ceil_div(sw.dw_wgs, tiles);
-  if (ks > 32) ks = 32;
-  while (ks > 1 && ((int64_t)ks * N1 * N2 > kpart_floats || K / ks < 2 * BK)) --ks;
-  DwGemmArgs g{};
-  g.A = A; g.B = B; g.C = C; g.Cpart = kpart; g.N1 = N1; g.N2 = N2; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.ksplit = 1; g.kchunk = K;
-  if (ks > 1) { g.kchunk = (int)align_up(ceil_div(K, ks), BK); g.ksplit = ceil_div(K, g.kchunk); }
-  g.accum = accumulate;                   // (a split product adds in splitk_reduce_kernel; its partial tiles are stored)
-  dim3 grid((unsigned)ceil_div(N2, bt), (unsigned)ceil_div(N1, bt), (unsigned)g.ksplit);
-  if (precision == M2M_PREC_BF16) {
-    if (tf == 2) hipLaunchKernelGGL((dw_gemm_kernel<bf16_t, 2>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((dw_gemm_kernel<bf16_t, 1>), grid, dim3(256), 0, st, g);
-  } else {
-    if (tf == 2) hipLaunchKernelGGL((dw_gemm_kernel<float, 2>), grid, dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((dw_gemm_kernel<float, 1>), grid, dim3(256), 0, st, g);
-  }
-  M2M_CHECK_HIP(hipGetLastError());
-  if (g.ksplit > 1) {
-    const int64_t n = (int64_t)N1 * N2;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), dim3(256), 0, st, kpart, C, N1, N2,
-                       ldc, g.ksplit, 1.0f, accumulate);
-    M2M_CHECK_HIP(hipGetLastError());
-  }
-  return M2M_OK;
-}
-
-// dst[c][r] = src[r][c]: src [R][C] (row stride ld_s) -> dst [C][ld_d]; the columns [R, Rpad) of dst are zeroed
-template <typename TS, typename TD>
-__global__ __launch_bounds__(256) void transpose_kernel(const TS* __restrict__ src, int64_t ld_s, TD* __restrict__ dst, int64_t ld_d, int R, int C,
-                                                        int Rpad) {
-  __shared__ float tile[64][65];
-  const int c0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
-  for (int i = threadIdx.x; i < 64 * 64; i += 256) {
-    const int rl = i >> 6, cl = i & 63;
-    tile[rl][cl] = (r0 + rl < R && c0 + cl < C) ? to_f32(src[(int64_t)(r0 + rl) * ld_s + c0 + cl]) : 0.f;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 64 * 64; i += 256) {
-    const int cl = i >> 6, rl = i & 63;
-    if (c0 + cl < C && r0 + rl < Rpad) dst[(int64_t)(c0 + cl) * ld_d + r0 + rl] = from_f32<TD>(tile[rl][cl]);
-  }
-}
-
-// all weight matrices of the model in one launch: WT[off .. ] = W[off ..]^T in the storage type (block -> (matrix, tile) table)
-struct WtBlock { int64_t off; int N, K, tn, tk; int il_half; };     // il_half > 0: a gate pair [wi_0 | wi_1], il_half = d_ff rows each
-// ... and, in the same pass over the fp32 master (Wc != null: bf16 mode), the plain copy in the storage type the forward products
-// read: every matrix a product reads is in the table, so the separate conversion of the whole parameter buffer (30 us, 121 MB read
-// a second time) is gone.  WT == null (a forward-only pass): the copy only.
-// Wil (bf16 mode): the gate-pair matrices once more with their rows interleaved in 32-row chunks (wi_0 rows [32c, 32c + 32), then the
-// matching wi_1 rows), the B operand of the fused gated-GELU product (EPI_GATED_TRAIN): a wave's 64 output columns are then a | b of
-// the same 32 hidden units.
-template <typename TD>
-__global__ __launch_bounds__(256) void weights_transpose_kernel(const WtBlock* __restrict__ blocks, const float* __restrict__ P, TD* __restrict__ WT,
-                                                                TD* __restrict__ Wc, TD* __restrict__ Wil) {
-  __shared__ float tile[64][65];
-  const WtBlock b = blocks[blockIdx.x];
-  const int n0 = b.tn * 64, k0 = b.tk * 64;
-  const float* src = P + b.off;
-  TD* dst = WT + b.off;
-  // four elements per thread and access (16-byte loads, 8-byte bf16 stores; the element-wise form moved 2 bytes per store: 62 us for the
-  // step's 265 MB); tiles at a ragged edge (K or N not a multiple of 4 there) take the element-wise loop
-  const bool vec = sizeof(TD) == 2 && (b.K & 3) == 0 && (b.N & 3) == 0 && ((b.off & 3) == 0);
-  if (vec) {
-    for (int i = threadIdx.x; i < 64 * 16; i += 256) {
-      const int nl = i >> 4, kl = (i & 15) * 4;
-      const bool in = n0 + nl < b.N && k0 + kl < b.K;          // (K % 4 == 0: the whole piece is inside or outside)
-      const int64_t at = (int64_t)(n0 + nl) * b.K + k0 + kl;
-      const float4 v = in ? *reinterpret_cast<const float4*>(src + at) : make_float4(0.f, 0.f, 0.f, 0.f);
-      tile[nl][kl] = v.x; tile[nl][kl + 1] = v.y; tile[nl][kl + 2] = v.z; tile[nl][kl + 3] = v.w;
-      if (in && (Wc || (Wil && b.il_half))) {
-        const uint2 pk = make_uint2(pack2_bf16(v.x, v.y), pack2_bf16(v.z, v.w));
-        if (Wc) *reinterpret_cast<uint2*>(Wc + b.off + at) = pk;
-        if (Wil && b.il_half) {
-          const int n = n0 + nl, m = n < b.il_half ? n : n - b.il_half;
-          *reinterpret_cast<uint2*>(Wil + b.off + (int64_t)((m >> 5) * 64 + (n < b.il_half ? 0 : 32) + (m & 31)) * b.K + k0 + kl) = pk;
-        }
-      }
-    }
-    if (!WT) return;
-    __syncthreads();
-    for (int i = threadIdx.x; i < 64 * 16; i += 256) {
-      const int kl = i >> 4, nl = (i & 15) * 4;
-      if (k0 + kl < b.K && n0 + nl < b.N)
-        *reinterpret_cast<uint2*>(dst + (int64_t)(k0 + kl) * b.N + n0 + nl) =
-            make_uint2(pack2_bf16(tile[nl][kl], tile[nl + 1][kl]), pack2_bf16(tile[nl + 2][kl], tile[nl + 3][kl]));
-    }
-    return;
-  }
-  for (int i = threadIdx.x; i < 64 * 64; i += 256) {
-    const int nl = i >> 6, kl = i & 63;
-    const bool in = n0 + nl < b.N && k0 + kl < b.K;
-    const float v = in ? src[(int64_t)(n0 + nl) * b.K + k0 + kl] : 0.f;
-    tile[nl][kl] = v;
-    if (Wc && in) Wc[b.off + (int64_t)(n0 + nl) * b.K + k0 + kl] = from_f32<TD>(v);
-    if (Wil && in && b.il_half) {
-      const int n = n0 + nl, m = n < b.il_half ? n : n - b.il_half;
-      Wil[b.off + (int64_t)((m >> 5) * 64 + (n < b.il_half ? 0 : 32) + (m & 31)) * b.K + k0 + kl] = from_f32<TD>(v);
-    }
-  }
-  if (!WT) return;
-  __syncthreads();
-  for (int i = threadIdx.x; i < 64 * 64; i += 256) {
-    const int kl = i >> 6, nl = i & 63;
-    if (k0 + kl < b.K && n0 + nl < b.N) dst[(int64_t)(k0 + kl) * b.N + n0 + nl] = from_f32<TD>(tile[nl][kl]);
-  }
-}
-
-// fp8 mode: every projection matrix W [N][K] (fp32 master) -> MXFP8 in BOTH layouts in one launch: row-major with blocks
-// along K (the forward's B operand) and transposed [K][Np] with blocks along N (the B operand of dX = dY . W).
-// One 64-thread workgroup per 32 x 64 tile (table entry, W8Tile of train.h); e4m3.
-__device__ inline float w8_scale_exp(float amax) {
-  if (!(amax > 0.f)) return -127.f;
-  int e;
-  (void)frexpf(amax, &e);
-  int se = e - 1 - 8;
-  return (float)(se < -127 ? -127 : (se > 127 ? 127 : se));
-}
-__device__ inline uint32_t w8_pack4(float a, float b, float c, float d) {
-  a = fminf(fmaxf(a, -448.f), 448.f); b = fminf(fmaxf(b, -448.f), 448.f); c = fminf(fmaxf(c, -448.f), 448.f); d = fminf(fmaxf(d, -448.f), 448.f);
-  int w = 0;
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (uint32_t)w;
-}
-__global__ __launch_bounds__(64) void mxq_weights_kernel(const W8Tile* __restrict__ tiles, const float* __restrict__ P, uint8_t* __restrict__ w8) {
-  __shared__ float tile[32][65];
-  const W8Tile tl = tiles[blockIdx.x];
-  const int n0 = tl.tn * 32, k0 = tl.tk * 64;
-  const float* src = P + tl.off;
-  for (int i = threadIdx.x; i < 32 * 64; i += 64) {
-    const int nl = i >> 6, kl = i & 63;
-    tile[nl][kl] = (n0 + nl < tl.N && k0 + kl < tl.K) ? src[(int64_t)(n0 + nl) * tl.K + k0 + kl] : 0.f;
-  }
-  __syncthreads();
-  {  // rows: thread -> (row, k-block)
-    const int nl = threadIdx.x >> 1, kb = threadIdx.x & 1;
-    if (n0 + nl < tl.N && k0 + 32 * kb < tl.K) {
-      float v[32], amax = 0.f;
-#pragma unroll
-      for (int j = 0; j < 32; ++j) { v[j] = tile[nl][32 * kb + j]; amax = fmaxf(amax, fabsf(v[j])); }
-      const float se = w8_scale_exp(amax), inv = exp2f(-se);
-      uint32_t* dst = reinterpret_cast<uint32_t*>(w8 + tl.q + (int64_t)(n0 + nl) * tl.K + k0 + 32 * kb);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) dst[j] = w8_pack4(v[4 * j] * inv, v[4 * j + 1] * inv, v[4 * j + 2] * inv, v[4 * j + 3] * inv);
-      w8[tl.qs + (int64_t)(n0 + nl) * (tl.K / 32) + (k0 + 32 * kb) / 32] = (uint8_t)((int)se + 127);
-    }
-  }
-  {  // columns: thread -> column k, block of 32 rows n0 .. n0 + 31
-    const int kl = threadIdx.x;
-    if (k0 + kl < tl.K) {
-      float v[32], amax = 0.f;
-#pragma unroll
-      for (int j = 0; j < 32; ++j) { v[j] = tile[j][kl]; amax = fmaxf(amax, fabsf(v[j])); }
-      const float se = w8_scale_exp(amax), inv = exp2f(-se);
-      uint32_t* dst = reinterpret_cast<uint32_t*>(w8 + tl.qt + (int64_t)(k0 + kl) * tl.Np + n0);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) dst[j] = w8_pack4(v[4 * j] * inv, v[4 * j + 1] * inv, v[4 * j + 2] * inv, v[4 * j + 3] * inv);
-      w8[tl.qts + (int64_t)(k0 + kl) * (tl.Np / 32) + n0 / 32] = (uint8_t)((int)se + 127);
-    }
-  }
-}
-W8Lin w8_add_matrix(int64_t off, int N, int K, int64_t& w8_bytes, std::vector<W8Tile>& tiles) {
-  W8Lin w{off, N, K, (int)align_up(N, 128), 0, 0, 0, 0};
-  w.q = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)N * K, 256);
-  w.qs = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)N * (K / 32), 256);
-  w.qt = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)K * w.Np, 256);
-  w.qts = w8_bytes; w8_bytes = align_up(w8_bytes + (int64_t)K * (w.Np / 32), 256);
-  for (int tn = 0; tn < ceil_div(N, 32); ++tn)
-    for (int tk = 0; tk < ceil_div(K, 64); ++tk) tiles.push_back({off, N, K, w.Np, w.q, w.qs, w.qt, w.qts, tn, tk});
-  return w;
-}
-int launch_mxq_weights(const W8Tile* tiles_dev, int n_tiles, const float* P, uint8_t* w8, hipStream_t st) {
-  hipLaunchKernelGGL(mxq_weights_kernel, dim3(n_tiles), dim3(64), 0, st, tiles_dev, P, w8);
-  M2M_CHECK_HIP(hipGetLastError());
-  return M2M_OK;
-}
-
-int launch_bgemm(int precision, int epi, const BGemmArgs& g, hipStream_t st, const TrainSwitches& sw) {
-  const int E = precision == M2M_PREC_BF16 ? 8 : 4;
-  M2M_REQUIRE(g.M >= 1 && g.N >= 1 && g.K >= 1 && g.nb1 >= 1 && g.nb2 >= 1, "bgemm: empty problem");
-  M2M_REQUIRE(g.lda % E == 0 && g.ldb % E == 0, "bgemm: operand row strides (%lld, %lld) must be multiples of %d elements (16-byte rows)",
-              (long long)g.lda, (long long)g.ldb, E);
-  M2M_REQUIRE(g.sA1 % E == 0 && g.sA2 % E == 0 && g.sB1 % E == 0 && g.sB2 % E == 0, "bgemm: batch strides must keep 16-byte alignment");
-  M2M_REQUIRE((int64_t)g.nb1 * g.nb2 * (g.A2 ? 2 : 1) <= 65535, "bgemm: too many batch entries");
-  M2M_REQUIRE(!g.A2 || (g.B2 && g.C2 && g.ksplit <= 1 && g.ldb2 % E == 0 && g.sB1_2 % E == 0 && g.sB2_2 % E == 0 && (!g.b_kmajor || g.ldb2 >= align_up(g.N, E))),
-              "bgemm: bad second product");
-  M2M_REQUIRE((!g.a_kmajor || g.lda >= align_up(g.M, E)) && (!g.b_kmajor || g.ldb >= align_up(g.N, E)),
-              "bgemm: a k-major operand's row stride must cover its rows padded to %d", E);
-  if (g.ksplit > 1) {
-    M2M_REQUIRE(g.nb1 == 1 && g.nb2 == 1 && (epi == TG_STORE_F32 || epi == TG_ACC_F32) && g.Cpart && g.kchunk % TG_BK_MAX == 0,
-                "bgemm: split-K is for plain fp32-store / fp32-accumulate products");
-    int rc = precision == M2M_PREC_BF16 ? launch_bgemm_t<bf16_t>(epi, g, st, sw.xcd_order) : launch_bgemm_t<float>(epi, g, st, sw.xcd_order);
-    if (rc != M2M_OK) return rc;
-    const int64_t n = (int64_t)g.M * g.N;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256)), dim3(256), 0, st, g.Cpart,
-                       reinterpret_cast<float*>(g.C), g.M, g.N, g.ldc, g.ksplit, g.alpha, epi == TG_ACC_F32 ? 1 : 0);
-    M2M_CHECK_HIP(hipGetLastError());
-    return M2M_OK;
-  }
-  return precision == M2M_PREC_BF16 ? launch_bgemm_t<bf16_t>(epi, g, st, sw.xcd_order) : launch_bgemm_t<float>(epi, g, st, sw.xcd_order);
-}
 
 // ============================================================ element / row kernels ====
 template <typename T>
@@ -1815,8 +1164,16 @@ struct TensorDesc {
   int rows, cols;          // 1-D tensors: rows = length, cols = 0
 };
 
-struct EncOff { int64_t ln0, qkv, o, ln1, wi, wo; };
-struct DecOff { int64_t ln0, qkv, o, ln1, cq, ckv, co, ln2, wi, wo; };
+// A sub-layer: the offsets of its weights (floats into the flat buffers, build_layout) next to what its forward pass keeps for the
+// backward pass (pointers into the arena, build_arena): h = the normed input, then the projections' outputs, P = the probabilities
+// (whole-head kernels: their dropout keep words), ao = the attention output rows, kt = K and V transposed, [2][B*H][64][Sp]
+// (kv_transpose_kernel, for the fused stripe products), lse = the row log-sum-exp [B*H][queries] of the whole-head kernels.
+struct SelfAttn { int64_t ln, qkv, o; void *h, *qkv_out, *P, *ao, *kt; float* lse; };
+struct CrossAttn { int64_t ln, q, kv, o; void *h, *q_out, *kv_out, *P, *ao, *kt; float* lse; };
+struct FeedFwd { int64_t ln, wi, wo; void *h, *ab, *mid; };
+struct EncLayer { SelfAttn self; FeedFwd ff; };
+struct DecLayer { SelfAttn self; CrossAttn cross; FeedFwd ff; };
+struct ProjMat { int64_t off; int N, K; };      // a fused projection group as one matrix [N][K] at parameter offset `off`
 
 // build the relative-position tables for one (Sq, Sk) geometry: bucket of every (key - query) offset
 std::vector<int> bucket_table(const m2m_t5_geometry& g, int Sq, int Sk, bool bidirectional) {
@@ -1837,8 +1194,9 @@ struct m2m_trainer {
   int64_t n_floats = 0;
   // offsets
   int64_t o_shared, o_lm, o_erb, o_drb, o_eln, o_dln;
-  std::vector<EncOff> enc;
-  std::vector<DecOff> dec;
+  std::vector<EncLayer> enc;             // per layer: weight offsets and activation buffers (sized by build_layout, never resized after)
+  std::vector<DecLayer> dec;
+  std::vector<ProjMat> proj;             // every projection matrix (fused groups), encoder layers then decoder layers, without lm_head
   std::vector<int64_t> o_cond;
   // device memory owned by the trainer
   unsigned char* arena = nullptr;
@@ -1852,18 +1210,14 @@ struct m2m_trainer {
   void* wt_blocks = nullptr;             // WtBlock table on the device
   int n_wt_blocks = 0;
   // activations (pointers into the arena)
-  std::vector<float*> xe, xd;            // residual streams: 2*Le + 1 and 3*Ld + 1 buffers
-  std::vector<void*> h0e, h1e, qkve, Pe, aoe, abe, mide;
-  std::vector<void*> h0d, h1d, h2d, qkvd, Pd, aod, cqd, ckvd, Pcd, aocd, abd, midd;
-  std::vector<float*> lse_e, lse_d, lse_c;   // per attention layer: row log-sum-exp [B*H][queries] of the whole-head attention kernels (attn_train.hip)
-  std::vector<void*> kte, ktd, ktc;      // per layer: K and V transposed, [2][B*H][64][Sp] (kv_transpose_kernel), for the fused stripe products
+  std::vector<float*> xe, xd;            // residual streams: 2*Le + 1 and 3*Ld + 1 buffers (a sub-layer's buffers: enc / dec above)
   void *hE = nullptr, *hD = nullptr;
   float *logits = nullptr, *sc = nullptr, *dxa = nullptr, *dxb = nullptr, *dh = nullptr, *dhE = nullptr, *dw_part = nullptr,
         *row_loss = nullptr, *inv_n = nullptr, *drel = nullptr, *etab = nullptr, *dtab = nullptr;
   void *dlog = nullptr, *dxT = nullptr, *dmid = nullptr, *dab = nullptr, *dO = nullptr, *dqkv = nullptr, *dS = nullptr, *dcq = nullptr,
        *dckv = nullptr;
   int64_t* dec_in = nullptr;
-  int *ebucket = nullptr, *dbucket = nullptr, *counter = nullptr;
+  int *ebucket = nullptr, *dbucket = nullptr;
   int64_t* cond_off_dev = nullptr;
   int* cond_rows_dev = nullptr;
   int64_t* pads_dev = nullptr;           // (offset, count) of the alignment gaps of the flat layout
@@ -1883,7 +1237,7 @@ struct m2m_trainer {
   int n_w8_tiles = 0;
   uint8_t *q8a = nullptr, *s8a = nullptr, *q8ta = nullptr, *s8ta = nullptr, *q8tb = nullptr, *s8tb = nullptr;
   // dropout (hf T5Config.dropout_rate; the reference trains in model.train() mode, ref train.py:33): off unless set
-  float drop_p = 0.f, drop_scale = 1.f;
+  float drop_scale = 1.f;
   uint32_t drop_thresh = 0;
   uint64_t drop_seed = 0;
   uint64_t *step_key_dev = nullptr, *step_ctr_dev = nullptr;   // key of the current pass / passes since set_dropout (device words:
@@ -1901,7 +1255,6 @@ struct m2m_trainer {
   enum { K_DXT = 0, K_DAB, K_DQKV, K_DCQ, K_DCKV, K_KINDS };
   std::vector<void*> ring[K_KINDS];
   void* dw_probs_dev = nullptr;          // DwProb tables on the device: [N_SLOTS + 1 table slots][2 phases][128 entries] (see GraphSlot)
-  int dw_tiles = 0;
   int64_t drel_slot_floats = 0;          // one self-attention layer's per-stripe diagonal sums (t->drel holds Le + Ld of them, then the scratch)
   int64_t* norm_offs_dev = nullptr;      // parameter offsets of the RMSNorm weights, in the order the backward pass meets them: [N_SLOTS + 1][2][32]
   // data-parallel overlap (m2m_trainer_set_sync_stream): the backward pass is issued in two parts — decoder side, then encoder side —
@@ -1969,46 +1322,45 @@ void build_layout(m2m_trainer* t) {
   t->o_drb = add_tensor(t, T5 + "decoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight", g.num_buckets, H, off);
   t->o_eln = add_tensor(t, T5 + "encoder.final_layer_norm.weight", d, 0, off);
   t->o_dln = add_tensor(t, T5 + "decoder.final_layer_norm.weight", d, 0, off);
-  auto attn3 = [&](const std::string& p, int64_t& first) {   // q, k, v back to back WITHOUT padding: one fused [3*inner, d] matrix
-    first = off;
-    for (const char* n : {"q", "k", "v"}) {
-      t->tensors.push_back({p + "." + n + ".weight", off, inner, d});
-      off += (int64_t)inner * d;
+  // a projection group: the matrices `names` back to back WITHOUT padding, one fused [n * rows, cols] matrix to the products
+  // (q|k|v, wi_0|wi_1, cross k|v; a single name: the matrix alone).  Recorded in t->proj: the one list of projection matrices.
+  auto group = [&](const std::string& p, std::initializer_list<const char*> names, int rows, int cols) {
+    const int64_t first = off;
+    for (const char* n : names) {
+      t->tensors.push_back({p + n + ".weight", off, rows, cols});
+      off += (int64_t)rows * cols;
     }
     off = align_up(off, 64);
+    t->proj.push_back({first, (int)names.size() * rows, cols});
+    return first;
+  };
+  auto self_attn = [&](const std::string& p, SelfAttn& a) {
+    a.ln = add_tensor(t, p + "layer_norm.weight", d, 0, off);
+    a.qkv = group(p + "SelfAttention.", {"q", "k", "v"}, inner, d);
+    a.o = group(p + "SelfAttention.", {"o"}, d, inner);
+  };
+  auto feed_fwd = [&](const std::string& p, FeedFwd& f) {
+    f.ln = add_tensor(t, p + "layer_norm.weight", d, 0, off);
+    f.wi = group(p + "DenseReluDense.", {"wi_0", "wi_1"}, dff, d);
+    f.wo = group(p + "DenseReluDense.", {"wo"}, d, dff);
   };
   t->enc.resize(g.num_layers);
   for (int l = 0; l < g.num_layers; ++l) {
     const std::string p = T5 + "encoder.block." + std::to_string(l) + ".layer.";
-    EncOff& e = t->enc[l];
-    e.ln0 = add_tensor(t, p + "0.layer_norm.weight", d, 0, off);
-    attn3(p + "0.SelfAttention", e.qkv);
-    e.o = add_tensor(t, p + "0.SelfAttention.o.weight", d, inner, off);
-    e.ln1 = add_tensor(t, p + "1.layer_norm.weight", d, 0, off);
-    e.wi = off;
-    t->tensors.push_back({p + "1.DenseReluDense.wi_0.weight", off, dff, d}); off += (int64_t)dff * d;
-    t->tensors.push_back({p + "1.DenseReluDense.wi_1.weight", off, dff, d}); off = align_up(off + (int64_t)dff * d, 64);
-    e.wo = add_tensor(t, p + "1.DenseReluDense.wo.weight", d, dff, off);
+    self_attn(p + "0.", t->enc[l].self);
+    feed_fwd(p + "1.", t->enc[l].ff);
   }
   t->dec.resize(g.num_decoder_layers);
   t->dec_begin = off;
   for (int l = 0; l < g.num_decoder_layers; ++l) {
     const std::string p = T5 + "decoder.block." + std::to_string(l) + ".layer.";
-    DecOff& e = t->dec[l];
-    e.ln0 = add_tensor(t, p + "0.layer_norm.weight", d, 0, off);
-    attn3(p + "0.SelfAttention", e.qkv);
-    e.o = add_tensor(t, p + "0.SelfAttention.o.weight", d, inner, off);
-    e.ln1 = add_tensor(t, p + "1.layer_norm.weight", d, 0, off);
-    e.cq = add_tensor(t, p + "1.EncDecAttention.q.weight", inner, d, off);
-    e.ckv = off;
-    t->tensors.push_back({p + "1.EncDecAttention.k.weight", off, inner, d}); off += (int64_t)inner * d;
-    t->tensors.push_back({p + "1.EncDecAttention.v.weight", off, inner, d}); off = align_up(off + (int64_t)inner * d, 64);
-    e.co = add_tensor(t, p + "1.EncDecAttention.o.weight", d, inner, off);
-    e.ln2 = add_tensor(t, p + "2.layer_norm.weight", d, 0, off);
-    e.wi = off;
-    t->tensors.push_back({p + "2.DenseReluDense.wi_0.weight", off, dff, d}); off += (int64_t)dff * d;
-    t->tensors.push_back({p + "2.DenseReluDense.wi_1.weight", off, dff, d}); off = align_up(off + (int64_t)dff * d, 64);
-    e.wo = add_tensor(t, p + "2.DenseReluDense.wo.weight", d, dff, off);
+    self_attn(p + "0.", t->dec[l].self);
+    CrossAttn& c = t->dec[l].cross;
+    c.ln = add_tensor(t, p + "1.layer_norm.weight", d, 0, off);
+    c.q = group(p + "1.EncDecAttention.", {"q"}, inner, d);
+    c.kv = group(p + "1.EncDecAttention.", {"k", "v"}, inner, d);
+    c.o = group(p + "1.EncDecAttention.", {"o"}, d, inner);
+    feed_fwd(p + "2.", t->dec[l].ff);
   }
   t->dec_end = off;
   t->o_cond.resize(t->n_cond);
@@ -2018,9 +1370,20 @@ void build_layout(m2m_trainer* t) {
 }
 
 // -------------------------------------------------------------- arena
+// Sizes one device allocation and points the members at their parts of it.  A buffer is declared ONCE, as take(member, bytes): it
+// gets the next 256-byte aligned offset, and the carver notes (member, offset); bind(base), after the allocation, sets every noted
+// member to base + offset.  The order of the declarations is the layout.  The carver keeps REFERENCES to the members: a container of
+// them (the per-layer structs, the residual streams, the rings) is resized before the first declaration into it and never grows after.
 struct Carver {
   int64_t off = 0;
-  int64_t take(int64_t bytes) { const int64_t o = off; off = align_up(off + bytes, 256); return o; }
+  std::vector<std::function<void(unsigned char*)>> binds;
+  int64_t take(int64_t bytes) { const int64_t o = off; off = align_up(off + bytes, 256); return o; }      // unnamed: a reservation
+  template <typename P>
+  void take(P*& member, int64_t bytes) {
+    const int64_t o = take(bytes);
+    binds.push_back([&member, o](unsigned char* base) { member = reinterpret_cast<P*>(base + o); });
+  }
+  void bind(unsigned char* base) const { for (const auto& b : binds) b(base); }
 };
 
 int build_optimizer(m2m_trainer* t) {
@@ -2044,16 +1407,19 @@ int build_optimizer(m2m_trainer* t) {
   AfPlan& p = t->af;
   p.n_tensors = (int)at.size(); p.n_blocks = (int)ab.size(); p.state_floats = state_off;
   Carver c;
-  const int64_t o_t = c.take((int64_t)at.size() * sizeof(AfTensor)), o_b = c.take((int64_t)ab.size() * sizeof(AfBlock));
-  const int64_t o_rs = c.take((int64_t)row_off * 4), o_cp = c.take(col_off * 4), o_ba = c.take((int64_t)ab.size() * 4),
-                o_bb = c.take((int64_t)ab.size() * 4), o_st = c.take(state_off * 4), o_rf = c.take((int64_t)row_off * 4),
-                o_cf = c.take((int64_t)cfac_off * 4), o_ts = c.take((int64_t)at.size() * 2 * 4);
+  c.take(p.tensors, (int64_t)at.size() * sizeof(AfTensor));
+  c.take(p.blocks, (int64_t)ab.size() * sizeof(AfBlock));
+  c.take(p.rowsum, (int64_t)row_off * 4);
+  c.take(p.colpart, col_off * 4);
+  c.take(p.blk_a, (int64_t)ab.size() * 4);
+  c.take(p.blk_b, (int64_t)ab.size() * 4);
+  c.take(p.state, state_off * 4);
+  c.take(p.rfac, (int64_t)row_off * 4);
+  c.take(p.cfac, (int64_t)cfac_off * 4);
+  c.take(p.tstat, (int64_t)at.size() * 2 * 4);
   M2M_CHECK_HIP(hipMalloc((void**)&t->af_mem, (size_t)c.off));
   M2M_CHECK_HIP(hipMemset(t->af_mem, 0, (size_t)c.off));
-  unsigned char* b = t->af_mem;
-  p.tensors = (AfTensor*)(b + o_t); p.blocks = (AfBlock*)(b + o_b); p.rowsum = (float*)(b + o_rs); p.colpart = (float*)(b + o_cp);
-  p.blk_a = (float*)(b + o_ba); p.blk_b = (float*)(b + o_bb); p.state = (float*)(b + o_st); p.rfac = (float*)(b + o_rf);
-  p.cfac = (float*)(b + o_cf); p.tstat = (float*)(b + o_ts);
+  c.bind(t->af_mem);
   M2M_CHECK_HIP(hipMemcpy(p.tensors, at.data(), at.size() * sizeof(AfTensor), hipMemcpyHostToDevice));
   M2M_CHECK_HIP(hipMemcpy(p.blocks, ab.data(), ab.size() * sizeof(AfBlock), hipMemcpyHostToDevice));
   return M2M_OK;
@@ -2066,56 +1432,76 @@ int build_arena(m2m_trainer* t) {
   const int64_t Me = B * S, Md = B * L, Mx = Me > Md ? Me : Md;
   const int64_t lps = align_up(S, 8), lpl = align_up(L, 8), lpm = lps > lpl ? lps : lpl, Sm = S > L ? S : L;
   const int Le = g.num_layers, Ld = g.num_decoder_layers;
+  using Tr = m2m_trainer;
   Carver c;
-  std::vector<int64_t> o;
-  auto T = [&](int64_t elems) { return c.take(elems * es); };
-  auto F = [&](int64_t elems) { return c.take(elems * 4); };
+  auto T = [&](auto*& member, int64_t elems) { c.take(member, elems * es); };
+  auto F = [&](float*& member, int64_t elems) { c.take(member, elems * 4); };
   // a layer's probability buffer [B*H][Sq][ldp]; the whole-head attention path keeps only its dropout keep words there ([B*H][ceil(Sk/32)][round_up_32(Sq)] x 4 bytes)
   auto PB = [&](int64_t Sq, int64_t Sk, int64_t ldp) { return std::max<int64_t>(B * H * Sq * ldp, B * H * ((Sk + 31) / 32) * align_up(Sq, 32) * 2); };
-  // order of `o` must match the assignment below
-  for (int i = 0; i < 2 * Le + 1; ++i) o.push_back(F(Me * d));
-  for (int i = 0; i < 3 * Ld + 1; ++i) o.push_back(F(Md * d));
-  for (int l = 0; l < Le; ++l) { o.push_back(T(Me * d)); o.push_back(T(Me * d)); o.push_back(T(Me * 3 * inner)); o.push_back(T(PB(S, S, lps)));
-                                  o.push_back(T(Me * inner)); o.push_back(T(Me * 2 * dff)); o.push_back(T(Me * dff)); }
-  for (int l = 0; l < Ld; ++l) { o.push_back(T(Md * d)); o.push_back(T(Md * d)); o.push_back(T(Md * d)); o.push_back(T(Md * 3 * inner));
-                                  o.push_back(T(PB(L, L, lpl))); o.push_back(T(Md * inner)); o.push_back(T(Md * inner)); o.push_back(T(Me * 2 * inner));
-                                  o.push_back(T(PB(L, S, lps))); o.push_back(T(Md * inner)); o.push_back(T(Md * 2 * dff)); o.push_back(T(Md * dff)); }
-  const int64_t Sp32 = align_up(S, 32), Lp32 = align_up(L, 32);
-  std::vector<int64_t> o_kte, o_ktd, o_ktc;
-  std::vector<int64_t> o_lse;
-  for (int l = 0; l < Le + 2 * Ld; ++l) o_lse.push_back(F(B * H * Sm));
-  for (int l = 0; l < Le; ++l) o_kte.push_back(T(2 * B * H * 64 * Sp32));
-  for (int l = 0; l < Ld; ++l) { o_ktd.push_back(T(2 * B * H * 64 * Lp32)); o_ktc.push_back(T(2 * B * H * 64 * Sp32)); }
-  const int64_t o_hE = T(Me * d), o_hD = T(Md * d), o_logits = F(Md * V), o_sc = F(B * H * Sm * lpm), o_dxa = F(Mx * d), o_dxb = F(Mx * d),
-                o_dh = F(Mx * d), o_dhE = F(Me * d), o_dwp = F((int64_t)RN_BLOCKS * d * (2 * Le + 3 * Ld + 2)), o_nofs = c.take((int64_t)(m2m_trainer::N_SLOTS + 1) * 64 * 8), o_rl = F(Md), o_inv = F(64), o_drel = F((int64_t)(Le + Ld) * B * H * std::max<int64_t>(2 * Sm, ((Sm + 31) / 32) * (Sm + 32)) + (int64_t)std::max(Le, Ld) * H * 2 * Sm + B * H * 2 * Sm),
-                o_etab = F(H * (2 * S)), o_dtab = F(H * (2 * L)), o_dlog = T(Md * align_up(V, 8)), o_dxT = T(Mx * d), o_dmid = T(Mx * dff),
-                o_dab = T(Mx * 2 * dff), o_dO = T(Mx * inner), o_dqkv = T(Mx * 3 * inner), o_dS = T(B * H * Sm * lpm), o_dcq = T(Md * inner),
-                o_dckv = T(Me * 2 * inner), o_lab = c.take(Md * 8), o_cnd = c.take(B * 8 * 8), o_skey = c.take(256), o_decin = c.take(Md * 8), o_eb = c.take(2 * S * 4), o_db = c.take(2 * L * 4),
-                o_co = c.take(64 * 8), o_cr = c.take(64 * 4), o_cnt = c.take(256), o_wc = (t->precision == M2M_PREC_BF16) ? T(t->n_floats) : 0, o_wil = (t->precision == M2M_PREC_BF16) ? T(t->n_floats) : 0,
-                o_wt = T(t->n_floats);
-  std::vector<int64_t> o_ring[m2m_trainer::K_KINDS];
-  for (int i = 1; i < 2 * Le + 3 * Ld; ++i) o_ring[m2m_trainer::K_DXT].push_back(T(Mx * d));
-  for (int i = 1; i < Le + Ld; ++i) { o_ring[m2m_trainer::K_DAB].push_back(T(Mx * 2 * dff)); o_ring[m2m_trainer::K_DQKV].push_back(T(Mx * 3 * inner)); }
-  for (int i = 1; i < Ld; ++i) { o_ring[m2m_trainer::K_DCQ].push_back(T(Md * inner)); o_ring[m2m_trainer::K_DCKV].push_back(T(Me * 2 * inner)); }
-  const int64_t o_dwp_tab = c.take((int64_t)(m2m_trainer::N_SLOTS + 1) * 256 * (int64_t)sizeof(DwProb));
-  const int64_t Mxp = align_up(Mx, 8), fmax = std::max<int64_t>(std::max<int64_t>(3 * inner, 2 * dff), align_up(V, 8));
-  const int64_t o_tA = T(fmax * Mxp), o_tB = T(std::max<int64_t>(std::max<int64_t>(dff, inner), d) * Mxp);
-  t->kpart_floats = std::max<int64_t>((int64_t)8 << 20, fmax * std::max<int64_t>(dff, d) + 64);
-  const int64_t o_kp = F(t->kpart_floats);
-  // weight-transpose table: every 2-D weight group as one matrix [N][K] (q|k|v, wi_0|wi_1, cross k|v are fused groups)
-  std::vector<WtBlock> wtb;
-  {
-    auto add = [&](int64_t off, int N, int K) {
-      const int il = (N == 2 * (int)dff && K == (int)d && dff % 32 == 0) ? (int)dff : 0;      // the gate pairs
-      for (int tn = 0; tn < ceil_div(N, 64); ++tn)
-        for (int tk = 0; tk < ceil_div(K, 64); ++tk) wtb.push_back({off, N, K, tn, tk, il});
-    };
-    add(t->o_lm, (int)V, (int)d);
-    for (const EncOff& e : t->enc) { add(e.qkv, 3 * (int)inner, (int)d); add(e.o, (int)d, (int)inner); add(e.wi, 2 * (int)dff, (int)d); add(e.wo, (int)d, (int)dff); }
-    for (const DecOff& e : t->dec) { add(e.qkv, 3 * (int)inner, (int)d); add(e.o, (int)d, (int)inner); add(e.cq, (int)inner, (int)d);
-                                     add(e.ckv, 2 * (int)inner, (int)d); add(e.co, (int)d, (int)inner); add(e.wi, 2 * (int)dff, (int)d); add(e.wo, (int)d, (int)dff); }
+  // the containers the carver points into get their final size first (t->enc / t->dec have theirs from build_layout)
+  t->xe.resize(2 * Le + 1);
+  t->xd.resize(3 * Ld + 1);
+  const int ring_len[Tr::K_KINDS] = {2 * Le + 3 * Ld, Le + Ld, Le + Ld, Ld, Ld};      // one entry per use in a pass
+  for (int k = 0; k < Tr::K_KINDS; ++k) t->ring[k].resize(std::max(ring_len[k], 1));
+  // ---- the layout: every declaration below is one buffer, in arena order
+  for (float*& x : t->xe) F(x, Me * d);
+  for (float*& x : t->xd) F(x, Md * d);
+  for (EncLayer& e : t->enc) {
+    T(e.self.h, Me * d); T(e.ff.h, Me * d); T(e.self.qkv_out, Me * 3 * inner); T(e.self.P, PB(S, S, lps)); T(e.self.ao, Me * inner);
+    T(e.ff.ab, Me * 2 * dff); T(e.ff.mid, Me * dff);
   }
-  const int64_t o_wtb = c.take((int64_t)wtb.size() * sizeof(WtBlock));
+  for (DecLayer& e : t->dec) {
+    T(e.self.h, Md * d); T(e.cross.h, Md * d); T(e.ff.h, Md * d); T(e.self.qkv_out, Md * 3 * inner); T(e.self.P, PB(L, L, lpl));
+    T(e.self.ao, Md * inner); T(e.cross.q_out, Md * inner); T(e.cross.kv_out, Me * 2 * inner); T(e.cross.P, PB(L, S, lps));
+    T(e.cross.ao, Md * inner); T(e.ff.ab, Md * 2 * dff); T(e.ff.mid, Md * dff);
+  }
+  for (EncLayer& e : t->enc) F(e.self.lse, B * H * Sm);
+  for (DecLayer& e : t->dec) { F(e.self.lse, B * H * Sm); F(e.cross.lse, B * H * Sm); }
+  const int64_t Sp32 = align_up(S, 32), Lp32 = align_up(L, 32);
+  for (EncLayer& e : t->enc) T(e.self.kt, 2 * B * H * 64 * Sp32);
+  for (DecLayer& e : t->dec) { T(e.self.kt, 2 * B * H * 64 * Lp32); T(e.cross.kt, 2 * B * H * 64 * Sp32); }
+  T(t->hE, Me * d); T(t->hD, Md * d);
+  F(t->logits, Md * V); F(t->sc, B * H * Sm * lpm);
+  F(t->dxa, Mx * d); F(t->dxb, Mx * d); F(t->dh, Mx * d); F(t->dhE, Me * d);
+  F(t->dw_part, (int64_t)RN_BLOCKS * d * (2 * Le + 3 * Ld + 2));
+  c.take(t->norm_offs_dev, (int64_t)(Tr::N_SLOTS + 1) * 64 * 8);
+  F(t->row_loss, Md); F(t->inv_n, 64);
+  // per self-attention layer a slot of per-stripe diagonal sums, then the stacks' reduction scratch, then bias_grad's own
+  t->drel_slot_floats = B * H * std::max<int64_t>(2 * Sm, ((Sm + 31) / 32) * (Sm + 32));
+  F(t->drel, (int64_t)(Le + Ld) * t->drel_slot_floats + (int64_t)std::max(Le, Ld) * H * 2 * Sm + B * H * 2 * Sm);
+  F(t->etab, H * (2 * S)); F(t->dtab, H * (2 * L));
+  T(t->dlog, Md * align_up(V, 8));
+  T(t->dxT, Mx * d); T(t->dmid, Mx * dff); T(t->dab, Mx * 2 * dff); T(t->dO, Mx * inner); T(t->dqkv, Mx * 3 * inner);
+  T(t->dS, B * H * Sm * lpm); T(t->dcq, Md * inner); T(t->dckv, Me * 2 * inner);
+  c.take(t->labels_buf, Md * 8); c.take(t->cond_buf, B * 8 * 8);
+  c.take(t->step_key_dev, 256);          // its words: [0] the key, [1] step_ctr_dev, [4] loss_dev (set behind the bind)
+  c.take(t->dec_in, Md * 8);
+  c.take(t->ebucket, 2 * S * 4); c.take(t->dbucket, 2 * L * 4);
+  c.take(t->cond_off_dev, 64 * 8); c.take(t->cond_rows_dev, 64 * 4);
+  c.take(256);                           // reserved (a counter that is gone): keeps every offset behind it where it was
+  if (t->precision == M2M_PREC_BF16) { T(t->Wc, t->n_floats); T(t->Wil, t->n_floats); }
+  T(t->WT, t->n_floats);
+  // ring entry 0 of a kind is the buffer declared above (set behind the bind), the others follow here
+  for (int i = 1; i < ring_len[Tr::K_DXT]; ++i) T(t->ring[Tr::K_DXT][i], Mx * d);
+  for (int i = 1; i < ring_len[Tr::K_DAB]; ++i) { T(t->ring[Tr::K_DAB][i], Mx * 2 * dff); T(t->ring[Tr::K_DQKV][i], Mx * 3 * inner); }
+  for (int i = 1; i < ring_len[Tr::K_DCQ]; ++i) { T(t->ring[Tr::K_DCQ][i], Md * inner); T(t->ring[Tr::K_DCKV][i], Me * 2 * inner); }
+  c.take(t->dw_probs_dev, (int64_t)(Tr::N_SLOTS + 1) * 256 * (int64_t)sizeof(DwProb));
+  const int64_t Mxp = align_up(Mx, 8), fmax = std::max<int64_t>(std::max<int64_t>(3 * inner, 2 * dff), align_up(V, 8));
+  const int64_t fmin = std::max<int64_t>(std::max<int64_t>(dff, inner), d);
+  T(t->tA, fmax * Mxp); T(t->tB, fmin * Mxp);
+  t->kpart_floats = std::max<int64_t>((int64_t)8 << 20, fmax * std::max<int64_t>(dff, d) + 64);
+  F(t->kpart, t->kpart_floats);
+  // weight-transpose table: lm_head, then every projection group as one matrix [N][K], in 64 x 64 tiles
+  std::vector<WtBlock> wtb;
+  auto wt_add = [&](const ProjMat& m) {
+    const int il = (m.N == 2 * (int)dff && m.K == (int)d && dff % 32 == 0) ? (int)dff : 0;      // the gate pairs
+    for (int tn = 0; tn < ceil_div(m.N, 64); ++tn)
+      for (int tk = 0; tk < ceil_div(m.K, 64); ++tk) wtb.push_back({m.off, m.N, m.K, tn, tk, il});
+  };
+  wt_add({t->o_lm, (int)V, (int)d});
+  for (const ProjMat& m : t->proj) wt_add(m);
+  t->n_wt_blocks = (int)wtb.size();
+  c.take(t->wt_blocks, (int64_t)wtb.size() * sizeof(WtBlock));
   std::vector<int64_t> pads;             // gaps between consecutive tensors of the flat layout (and behind the last one)
   {
     std::vector<std::pair<int64_t, int64_t>> spans;
@@ -2128,69 +1514,31 @@ int build_arena(m2m_trainer* t) {
     }
     if (t->n_floats > pos) { pads.push_back(pos); pads.push_back(t->n_floats - pos); }
   }
-  const int64_t o_pads = c.take((int64_t)std::max<size_t>(pads.size(), 2) * 8);
+  t->n_pads = (int)(pads.size() / 2);
+  c.take(t->pads_dev, (int64_t)std::max<size_t>(pads.size(), 2) * 8);
   // fp8 mode: MXFP8 copies of every projection matrix (lm_head stays bf16) + quantised-activation scratch
   std::vector<W8Tile> w8t;
-  int64_t w8_bytes = 0, o_w8 = 0, o_w8t = 0, o_q8a = 0, o_s8a = 0, o_q8ta = 0, o_s8ta = 0, o_q8tb = 0, o_s8tb = 0;
   if (t->fp8) {
-    auto addl = [&](int64_t off, int N, int K) { t->lin.push_back(w8_add_matrix(off, N, K, w8_bytes, w8t)); };
-    for (const EncOff& e : t->enc) { addl(e.qkv, 3 * (int)inner, (int)d); addl(e.o, (int)d, (int)inner); addl(e.wi, 2 * (int)dff, (int)d); addl(e.wo, (int)d, (int)dff); }
-    for (const DecOff& e : t->dec) { addl(e.qkv, 3 * (int)inner, (int)d); addl(e.o, (int)d, (int)inner); addl(e.cq, (int)inner, (int)d);
-                                     addl(e.ckv, 2 * (int)inner, (int)d); addl(e.co, (int)d, (int)inner); addl(e.wi, 2 * (int)dff, (int)d); addl(e.wo, (int)d, (int)dff); }
-    const int64_t Mp128 = align_up(Mx, 128), f8 = align_up(fmax, 128);
-    o_w8 = c.take(w8_bytes); o_w8t = c.take((int64_t)w8t.size() * sizeof(W8Tile));
-    o_q8a = c.take(Mx * f8); o_s8a = c.take(Mx * (f8 / 32));
-    o_q8ta = c.take(f8 * Mp128); o_s8ta = c.take(f8 * (Mp128 / 32));
-    o_q8tb = c.take(align_up(std::max<int64_t>(std::max<int64_t>(dff, inner), d), 128) * Mp128);
-    o_s8tb = c.take(align_up(std::max<int64_t>(std::max<int64_t>(dff, inner), d), 128) * (Mp128 / 32));
+    int64_t w8_bytes = 0;
+    for (const ProjMat& m : t->proj) t->lin.push_back(w8_add_matrix(m.off, m.N, m.K, w8_bytes, w8t));
+    t->n_w8_tiles = (int)w8t.size();
+    const int64_t Mp128 = align_up(Mx, 128), f8 = align_up(fmax, 128), f8b = align_up(fmin, 128);
+    c.take(t->w8, w8_bytes); c.take(t->w8_tiles, (int64_t)w8t.size() * sizeof(W8Tile));
+    c.take(t->q8a, Mx * f8); c.take(t->s8a, Mx * (f8 / 32));
+    c.take(t->q8ta, f8 * Mp128); c.take(t->s8ta, f8 * (Mp128 / 32));
+    c.take(t->q8tb, f8b * Mp128); c.take(t->s8tb, f8b * (Mp128 / 32));
   }
   t->arena_bytes = c.off;
   hipError_t e = hipMalloc((void**)&t->arena, (size_t)c.off);
   if (e != hipSuccess) { set_error("m2m_trainer_create: hipMalloc(%lld) failed: %s", (long long)c.off, hipGetErrorString(e)); return M2M_ERR_NOMEM; }
   M2M_CHECK_HIP(hipMemset(t->arena, 0, (size_t)c.off));
-  unsigned char* b = t->arena;
-  size_t k = 0;
-  auto nextF = [&]() { return (float*)(b + o[k++]); };
-  auto nextT = [&]() { return (void*)(b + o[k++]); };
-  for (int i = 0; i < 2 * Le + 1; ++i) t->xe.push_back(nextF());
-  for (int i = 0; i < 3 * Ld + 1; ++i) t->xd.push_back(nextF());
-  for (int l = 0; l < Le; ++l) { t->h0e.push_back(nextT()); t->h1e.push_back(nextT()); t->qkve.push_back(nextT()); t->Pe.push_back(nextT());
-                                  t->aoe.push_back(nextT()); t->abe.push_back(nextT()); t->mide.push_back(nextT()); }
-  for (int l = 0; l < Ld; ++l) { t->h0d.push_back(nextT()); t->h1d.push_back(nextT()); t->h2d.push_back(nextT()); t->qkvd.push_back(nextT());
-                                  t->Pd.push_back(nextT()); t->aod.push_back(nextT()); t->cqd.push_back(nextT()); t->ckvd.push_back(nextT());
-                                  t->Pcd.push_back(nextT()); t->aocd.push_back(nextT()); t->abd.push_back(nextT()); t->midd.push_back(nextT()); }
-  for (int l = 0; l < Le; ++l) t->lse_e.push_back((float*)(b + o_lse[l]));
-  for (int l = 0; l < Ld; ++l) { t->lse_d.push_back((float*)(b + o_lse[Le + 2 * l])); t->lse_c.push_back((float*)(b + o_lse[Le + 2 * l + 1])); }
-  for (int64_t off : o_kte) t->kte.push_back(b + off);
-  for (int64_t off : o_ktd) t->ktd.push_back(b + off);
-  for (int64_t off : o_ktc) t->ktc.push_back(b + off);
-  t->hE = b + o_hE; t->hD = b + o_hD; t->logits = (float*)(b + o_logits); t->sc = (float*)(b + o_sc); t->dxa = (float*)(b + o_dxa);
-  t->dxb = (float*)(b + o_dxb); t->dh = (float*)(b + o_dh); t->dhE = (float*)(b + o_dhE); t->dw_part = (float*)(b + o_dwp); t->norm_offs_dev = (int64_t*)(b + o_nofs);
-  t->row_loss = (float*)(b + o_rl); t->inv_n = (float*)(b + o_inv); t->drel = (float*)(b + o_drel); t->drel_slot_floats = B * H * std::max<int64_t>(2 * Sm, ((Sm + 31) / 32) * (Sm + 32)); t->etab = (float*)(b + o_etab);
-  t->dtab = (float*)(b + o_dtab); t->dlog = b + o_dlog; t->dxT = b + o_dxT; t->dmid = b + o_dmid; t->dab = b + o_dab; t->dO = b + o_dO;
-  t->dqkv = b + o_dqkv; t->dS = b + o_dS; t->dcq = b + o_dcq; t->dckv = b + o_dckv; t->dec_in = (int64_t*)(b + o_decin);
-  {
-    void* first[m2m_trainer::K_KINDS] = {t->dxT, t->dab, t->dqkv, t->dcq, t->dckv};
-    for (int k = 0; k < m2m_trainer::K_KINDS; ++k) {
-      t->ring[k].push_back(first[k]);
-      for (int64_t off : o_ring[k]) t->ring[k].push_back(b + off);
-    }
-    t->dw_probs_dev = b + o_dwp_tab;
-  }
-  t->labels_buf = (int64_t*)(b + o_lab); t->cond_buf = (int64_t*)(b + o_cnd);
-  t->step_key_dev = (uint64_t*)(b + o_skey); t->step_ctr_dev = t->step_key_dev + 1; t->loss_dev = (float*)(t->step_key_dev + 4);
-  t->ebucket = (int*)(b + o_eb); t->dbucket = (int*)(b + o_db); t->counter = (int*)(b + o_cnt); t->cond_off_dev = (int64_t*)(b + o_co); t->cond_rows_dev = (int*)(b + o_cr);
-  t->Wc = (t->precision == M2M_PREC_BF16) ? (void*)(b + o_wc) : nullptr;
-  t->Wil = (t->precision == M2M_PREC_BF16) ? (void*)(b + o_wil) : nullptr;
-  t->WT = b + o_wt; t->tA = b + o_tA; t->tB = b + o_tB; t->kpart = (float*)(b + o_kp); t->wt_blocks = b + o_wtb; t->n_wt_blocks = (int)wtb.size();
+  c.bind(t->arena);
+  t->step_ctr_dev = t->step_key_dev + 1; t->loss_dev = (float*)(t->step_key_dev + 4);
+  void* const first[Tr::K_KINDS] = {t->dxT, t->dab, t->dqkv, t->dcq, t->dckv};
+  for (int k = 0; k < Tr::K_KINDS; ++k) t->ring[k][0] = first[k];
   M2M_CHECK_HIP(hipMemcpy(t->wt_blocks, wtb.data(), wtb.size() * sizeof(WtBlock), hipMemcpyHostToDevice));
-  t->pads_dev = (int64_t*)(b + o_pads); t->n_pads = (int)(pads.size() / 2);
   if (!pads.empty()) M2M_CHECK_HIP(hipMemcpy(t->pads_dev, pads.data(), pads.size() * 8, hipMemcpyHostToDevice));
-  if (t->fp8) {
-    t->w8 = b + o_w8; t->w8_tiles = b + o_w8t; t->n_w8_tiles = (int)w8t.size();
-    t->q8a = b + o_q8a; t->s8a = b + o_s8a; t->q8ta = b + o_q8ta; t->s8ta = b + o_s8ta; t->q8tb = b + o_q8tb; t->s8tb = b + o_s8tb;
-    M2M_CHECK_HIP(hipMemcpy(t->w8_tiles, w8t.data(), w8t.size() * sizeof(W8Tile), hipMemcpyHostToDevice));
-  }
+  if (t->fp8) M2M_CHECK_HIP(hipMemcpy(t->w8_tiles, w8t.data(), w8t.size() * sizeof(W8Tile), hipMemcpyHostToDevice));
   M2M_CHECK_HIP(hipMemcpy(t->cond_off_dev, t->o_cond.data(), t->o_cond.size() * 8, hipMemcpyHostToDevice));
   M2M_CHECK_HIP(hipMemcpy(t->cond_rows_dev, t->cond_rows.data(), t->cond_rows.size() * 4, hipMemcpyHostToDevice));
   return M2M_OK;
@@ -2244,6 +1592,15 @@ struct Ops {
   // dropout sites: one key per (layer, place); site < 0 or p == 0: no dropout
   bool dropping(int site) const { return site >= 0 && t->drop_thresh != 0; }
   DropKey key(int site) const { return DropKey{t->step_key_dev, (uint64_t)site * 0x9E3779B97F4A7C15ull}; }
+  // what a kernel with dropout in it takes for a site: (key, thresh, scale), the key null and thresh 0 where the site does not drop
+  struct Drop { DropKey key; uint32_t thresh; float scale; };
+  Drop drop(int site) const { return dropping(site) ? Drop{key(site), t->drop_thresh, t->drop_scale} : Drop{DropKey{nullptr, 0}, 0u, t->drop_scale}; }
+  // ... and the same as the dropout fields of a product's arguments (BGemmArgs, GemmArgs), left zero where the site does not drop
+  template <typename Args>
+  void drop_fields(Args& a, int site) const {
+    if (!dropping(site)) return;
+    a.drop_thresh = t->drop_thresh; a.drop_scale = t->drop_scale; a.drop_key = key(site).salt; a.drop_step = t->step_key_dev;
+  }
 
   // ---- weight-gradient products.  A backward sub-layer brackets itself with begin_sub(kinds) / end_sub(): begin_sub
   // points t->dxT ... at fresh ring entries, dW() calls in between are queued.  Grouped mode: the queue becomes ONE launch
@@ -2340,25 +1697,16 @@ struct Ops {
       M2M_CHECK_HIP(hipMemcpy(tab_dev, probs.data(), bytes, hipMemcpyHostToDevice));
       tab_host.assign(reinterpret_cast<const unsigned char*>(probs.data()), reinterpret_cast<const unsigned char*>(probs.data()) + bytes);
     }
-    const bool tr_reads = t->sw.dw_tr;
-    const int xcd_order = t->sw.dw_xcd;
-    const int grid = xcd_order ? 8 * ceil_div(tiles, 8) : tiles;
-    if (t->precision == M2M_PREC_BF16 && tr_reads)
-      hipLaunchKernelGGL((dw_group_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, st, (const DwProb*)tab_dev, (int)probs.size(), tiles, xcd_order);
-    else if (t->precision == M2M_PREC_BF16)
-      hipLaunchKernelGGL((dw_group_kernel<bf16_t, false>), dim3(grid), dim3(256), 0, st, (const DwProb*)tab_dev, (int)probs.size(), tiles, xcd_order);
-    else
-      hipLaunchKernelGGL((dw_group_kernel<float, false>), dim3(grid), dim3(256), 0, st, (const DwProb*)tab_dev, (int)probs.size(), tiles, xcd_order);
-    M2M_CHECK_HIP(hipGetLastError());
+    const int rc = launch_dw_group(t->precision, (const DwProb*)tab_dev, (int)probs.size(), tiles, st, t->sw);
     probs.clear();
-    return M2M_OK;
+    return rc;
   }
   int mm(int epi, const void* A, int64_t lda, int akm, const void* B, int64_t ldb, int bkm, void* C, int64_t ldc, int M, int N, int K,
          const float* R = nullptr, int drop_site = -1) const {
     BGemmArgs g{};
     g.A = A; g.B = B; g.C = C; g.R = R; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.a_kmajor = akm; g.b_kmajor = bkm;
     g.nb1 = 1; g.nb2 = 1; g.alpha = 1.0f;
-    if (dropping(drop_site)) { g.drop_thresh = t->drop_thresh; g.drop_scale = t->drop_scale; g.drop_key = key(drop_site).salt; g.drop_step = t->step_key_dev; }
+    drop_fields(g, drop_site);
     if (!akm && !bkm && t->fp8 && t->sw.fp8.fwd) {          // a forward projection Y = X . W^T on MXFP8 operands
       const int64_t off = reinterpret_cast<const T*>(B) - W(0);
       if (const m2m_trainer::LinW* w = lin8(off))
@@ -2373,7 +1721,8 @@ struct Ops {
       if (epi == TG_STORE_T) return launch_gemm(t->precision, EPI_STORE, a, st);
       if (epi == TG_STORE_F32) return launch_gemm(t->precision, EPI_STORE_F32, a, st);
       if (epi == TG_ACC_F32) return launch_gemm(t->precision, EPI_RESID, a, st);
-      a.resid = R; a.drop_thresh = g.drop_thresh; a.drop_scale = g.drop_scale; a.drop_key = g.drop_key; a.drop_step = g.drop_step;
+      a.resid = R;
+      drop_fields(a, drop_site);
       return launch_gemm(t->precision, EPI_RESID, a, st);
     }
     return launch_bgemm(t->precision, epi, g, st, t->sw);
@@ -2443,9 +1792,8 @@ struct Ops {
     if (t->sw.dw_kmajor == 1 || (t->sw.dw_kmajor < 0 && M < 8192)) {
       g.A = dY; g.B = X; g.lda = ldy; g.ldb = ldx; g.a_kmajor = 1; g.b_kmajor = 1;
     } else {
-      hipLaunchKernelGGL((transpose_kernel<T, T>), dim3(ceil_div(Ny, 64), ceil_div(Mp, 64)), dim3(256), 0, st, (const T*)dY, ldy, (T*)t->tA, (int64_t)Mp, M, Ny, Mp);
-      hipLaunchKernelGGL((transpose_kernel<T, T>), dim3(ceil_div(Kx, 64), ceil_div(Mp, 64)), dim3(256), 0, st, (const T*)X, ldx, (T*)t->tB, (int64_t)Mp, M, Kx, Mp);
-      M2M_CHECK_HIP(hipGetLastError());
+      const int rc = launch_transpose_pair(t->precision, dY, ldy, Ny, X, ldx, Kx, t->tA, t->tB, M, Mp, st);
+      if (rc != M2M_OK) return rc;
       g.A = t->tA; g.B = t->tB; g.lda = Mp; g.ldb = Mp;
     }
     const int tiles = ceil_div(Ny, TG_BM) * ceil_div(Kx, TG_BN);
@@ -2481,16 +1829,14 @@ struct Ops {
     const int slot = group ? norm_slot_base + (int)norm_offs.size() : 0;
     float* part = t->dw_part + (int64_t)slot * RN_BLOCKS * d;
     T* out_t = nullptr;
-    DropKey dk{nullptr, 0};
-    uint32_t thr = 0;
-    if (group && after_site != -2) {
+    const bool emits = group && after_site != -2;
+    if (emits) {
       out_t = (T*)t->ring[m2m_trainer::K_DXT][pos[m2m_trainer::K_DXT] % t->ring[m2m_trainer::K_DXT].size()];      // what the next begin_sub() selects
-      if (dropping(after_site)) { dk = key(after_site); thr = t->drop_thresh; }
       pre.src = dx_out; pre.dst = out_t; pre.site = after_site;
     }
-    const bool din = dropping(dy_site);
+    const Drop after = drop(emits ? after_site : -1), din = drop(dy_site);
     hipLaunchKernelGGL(rmsnorm_bwd_kernel<T>, dim3(RN_BLOCKS), dim3(256), (size_t)4 * d * sizeof(float), st, x, P + w_off, dy, dx_res, dx_out,
-                       part, M, d, t->g.layer_norm_eps, out_t, dk, thr, t->drop_scale, din ? key(dy_site) : DropKey{nullptr, 0}, din ? t->drop_thresh : 0u);
+                       part, M, d, t->g.layer_norm_eps, out_t, after.key, after.thresh, after.scale, din.key, din.thresh);
     if (group) norm_offs.push_back(w_off);
     else hipLaunchKernelGGL(colsum_kernel, dim3(ceil_div(d, 32)), dim3(256), 0, st, part, G + w_off, RN_BLOCKS, d, gacc);
     M2M_CHECK_HIP(hipGetLastError());
@@ -2506,8 +1852,8 @@ struct Ops {
     a.O = (bf16_t*)d.ao; a.ldo = t->inner; a.sOb = (int64_t)Sq * t->inner; a.lse = d.lse;
     a.bias_tab = d.tab; a.tab_stride = Sq + Sk - 1; a.tab_center = Sq - 1;
     a.H = t->g.num_heads; a.Sq = Sq; a.Sk = Sk; a.causal = d.causal; a.ldp = (int)align_up(Sk, 8);
-    const bool dr = dropping(d.site);
-    a.dk = dr ? key(d.site) : DropKey{nullptr, 0}; a.thresh = dr ? t->drop_thresh : 0u; a.scale = t->drop_scale;
+    const Drop dr = drop(d.site);
+    a.dk = dr.key; a.thresh = dr.thresh; a.scale = dr.scale;
     a.keep_bits = (uint32_t*)d.Pm;           // (the layer's probability buffer, unused on this path: B*H*Sq*Sk/8 bytes of its B*H*Sq*ldp*2)
     if (bwd) {
       a.dO = (const bf16_t*)d.dO; a.dQ = (bf16_t*)d.dq.p; a.dK = (bf16_t*)d.dk.p; a.dV = (bf16_t*)d.dv.p;
@@ -2530,11 +1876,11 @@ struct Ops {
   // what the two stripe launches of a layer share: X = (key, d) operand, Y = (query, d) operand, the probabilities, the dropout key, and the
   // fused product of the rows a workgroup has just formed: Xt its transposed second operand, `out` its result
   StripeArgs stripe_args(const AttnDesc& d, const Mat& X, const Mat& Y, const T* Xt, const Mat& out) const {
-    const bool dr = dropping(d.site);
+    const Drop dr = drop(d.site);
     StripeArgs a{};
     a.X = X.p; a.ldx = X.ld; a.sX1 = X.sb; a.sX2 = X.sh; a.Y = Y.p; a.ldy = Y.ld; a.sY1 = Y.sb; a.sY2 = Y.sh;
     a.P = d.Pm; a.H = t->g.num_heads; a.Sq = d.Sq; a.Sk = d.Sk; a.ldp = (int)align_up(d.Sk, 8); a.causal = d.causal;
-    a.dk = dr ? key(d.site) : DropKey{nullptr, 0}; a.thresh = dr ? t->drop_thresh : 0u; a.scale = t->drop_scale;
+    a.dk = dr.key; a.thresh = dr.thresh; a.scale = dr.scale;
     a.Xt = Xt; a.xt_ld = align_up(d.Sk, 32); a.O = const_cast<void*>(out.p); a.ldo = out.ld; a.sO1 = out.sb; a.sO2 = out.sh;
     return a;
   }
@@ -2557,11 +1903,12 @@ struct Ops {
   // P (kept for the backward) and, with dropout, the dropped copy the P.V product reads (scratch: t->dS); returns it through *Puse
   int softmax(const AttnDesc& d, int nB, const T** Puse) const {
     const int H = t->g.num_heads, Sq = d.Sq, Sk = d.Sk, rows = nB * H * Sq;
-    const bool dr = dropping(d.site);
+    const Drop dr = drop(d.site);
+    T* const Pd = dr.thresh ? (T*)t->dS : (T*)nullptr;
     hipLaunchKernelGGL(softmax_fwd_kernel<T>, dim3(ceil_div(rows, 4)), dim3(256), 0, st, t->sc, (T*)d.Pm, rows, H, Sq, Sk, (int)align_up(Sk, 8), d.tab, Sq + Sk - 1,
-                       Sq - 1, d.causal, dr ? (T*)t->dS : (T*)nullptr, dr ? key(d.site) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u, t->drop_scale);
+                       Sq - 1, d.causal, Pd, dr.key, dr.thresh, dr.scale);
     M2M_CHECK_HIP(hipGetLastError());
-    *Puse = dr ? (const T*)t->dS : (const T*)d.Pm;
+    *Puse = Pd ? Pd : (const T*)d.Pm;
     return M2M_OK;
   }
   // backward: the dropped probabilities again (into t->dS, consumed by the dV product before dS overwrites it)
@@ -2573,23 +1920,22 @@ struct Ops {
     return M2M_OK;
   }
   int softmax_bwd(const AttnDesc& d, int nB) const {      // dS (t->dS) from P and dPd (t->sc)
-    const bool dr = dropping(d.site);
+    const Drop dr = drop(d.site);
     hipLaunchKernelGGL(softmax_bwd_kernel<T>, dim3(ceil_div(nB * t->g.num_heads * d.Sq, 4)), dim3(256), 0, st, (const T*)d.Pm, t->sc, (T*)t->dS,
-                       nB * t->g.num_heads * d.Sq, d.Sk, (int)align_up(d.Sk, 8), dr ? key(d.site) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u, t->drop_scale);
+                       nB * t->g.num_heads * d.Sq, d.Sk, (int)align_up(d.Sk, 8), dr.key, dr.thresh, dr.scale);
     M2M_CHECK_HIP(hipGetLastError());
     return M2M_OK;
   }
   int gated(const void* ab, void* mid, int64_t M, int site) const {
-    const bool dr = dropping(site);
-    hipLaunchKernelGGL(gated_fwd_kernel<T>, dim3(grid_1d(M * t->g.d_ff / 4)), dim3(256), 0, st, (const T*)ab, (T*)mid, M, t->g.d_ff,
-                       dr ? key(site) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u, t->drop_scale);
+    const Drop dr = drop(site);
+    hipLaunchKernelGGL(gated_fwd_kernel<T>, dim3(grid_1d(M * t->g.d_ff / 4)), dim3(256), 0, st, (const T*)ab, (T*)mid, M, t->g.d_ff, dr.key, dr.thresh, dr.scale);
     M2M_CHECK_HIP(hipGetLastError());
     return M2M_OK;
   }
   int gated_bwd(const void* ab, const void* dmid, void* dab, int64_t M, int site) const {
-    const bool dr = dropping(site);
+    const Drop dr = drop(site);
     hipLaunchKernelGGL(gated_bwd_kernel<T>, dim3(grid_1d(M * t->g.d_ff / 4)), dim3(256), 0, st, (const T*)ab, (const T*)dmid, (T*)dab, M, t->g.d_ff,
-                       dr ? key(site) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u, t->drop_scale);
+                       dr.key, dr.thresh, dr.scale);
     M2M_CHECK_HIP(hipGetLastError());
     return M2M_OK;
   }
@@ -2693,147 +2039,155 @@ int attn_core_bwd(const Ops<T>& o, const AttnDesc& a, int nB) {
   return M2M_OK;
 }
 
+// What the layers of one stack share in a pass (forward_backward_t builds one per stack).  The backward pass walks a stack from its
+// LAST layer down: that layer starts the sums the layers of a stack share (the bias table's gradient, dhE), the others add to them.
+struct Stack {
+  int S, Sx;               // rows per clip; Sx: of the encoder output the decoder's cross-attention reads
+  int layers;
+  const float* tab;        // self-attention: the relative-position bias table [H][2 S - 1], ...
+  const int* buckets;      // ... its bucket table, and where the bias weights sit in the flat buffers
+  int64_t bias_off;
+  int causal;
+  int site0;               // SITE_ENC / SITE_DEC
+  int site(int l) const { return site0 + 16 * l; }
+  bool last(int l) const { return l == layers - 1; }
+};
+
 // the descriptor of a self-attention layer: q | k | v from the layer's one projection, dq | dk | dv into its gradient (t->dqkv)
 template <typename T>
-AttnDesc self_desc(const Ops<T>& o, const void* qkv, int S, const float* tab, int causal, int site0, const void* Pm, const void* kt, float* lse, const void* ao) {
+AttnDesc self_desc(const Ops<T>& o, const SelfAttn& w, const Stack& s, int l) {
   AttnDesc a{};
-  a.q = o.part(qkv, 3, 0, S); a.k = o.part(qkv, 3, 1, S); a.v = o.part(qkv, 3, 2, S);
-  a.dq = o.part(o.t->dqkv, 3, 0, S); a.dk = o.part(o.t->dqkv, 3, 1, S); a.dv = o.part(o.t->dqkv, 3, 2, S);
-  a.Sq = a.Sk = S; a.tab = tab; a.causal = causal; a.site = site0 + PL_PROBS_SELF;
-  a.Pm = const_cast<void*>(Pm); a.kt = const_cast<void*>(kt); a.lse = lse; a.ao = const_cast<void*>(ao);
+  a.q = o.part(w.qkv_out, 3, 0, s.S); a.k = o.part(w.qkv_out, 3, 1, s.S); a.v = o.part(w.qkv_out, 3, 2, s.S);
+  a.dq = o.part(o.t->dqkv, 3, 0, s.S); a.dk = o.part(o.t->dqkv, 3, 1, s.S); a.dv = o.part(o.t->dqkv, 3, 2, s.S);
+  a.Sq = a.Sk = s.S; a.tab = s.tab; a.causal = s.causal; a.site = s.site(l) + PL_PROBS_SELF;
+  a.Pm = w.P; a.kt = w.kt; a.lse = w.lse; a.ao = w.ao;
   return a;
 }
 
-// self-attention block, forward: x_in -> x_out = x_in + Attn(norm(x_in)).  Buffers of this layer are passed in.
+// self-attention block of layer l, forward: x_in -> x_out = x_in + Attn(norm(x_in))
 template <typename T>
-int attn_self_fwd(const Ops<T>& o, const float* x_in, float* x_out, int64_t ln, int64_t wqkv, int64_t wo, void* h, void* qkv, void* Pm, void* ao,
-                  int nB, int S, const float* tab, int causal, int site0, void* kt, float* lse) {
+int attn_self_fwd(const Ops<T>& o, const SelfAttn& w, const Stack& s, int l, int nB, const float* x_in, float* x_out) {
   m2m_trainer* t = o.t;
-  const int d = t->g.d_model, inner = t->inner, M = nB * S;
+  const int d = t->g.d_model, inner = t->inner, M = nB * s.S;
   int rc;
-  RC(o.norm(x_in, ln, h, M));
-  RC(o.mm(TG_STORE_T, h, d, 0, o.W(wqkv), d, 0, qkv, 3 * inner, M, 3 * inner, d));
-  RC(attn_core_fwd<T>(o, self_desc<T>(o, qkv, S, tab, causal, site0, Pm, kt, lse, ao), nB));
-  RC(o.mm_resid(ao, wo, x_out, M, d, inner, x_in, site0 + PL_SELF_OUT));
+  RC(o.norm(x_in, w.ln, w.h, M));
+  RC(o.mm(TG_STORE_T, w.h, d, 0, o.W(w.qkv), d, 0, w.qkv_out, 3 * inner, M, 3 * inner, d));
+  RC(attn_core_fwd<T>(o, self_desc<T>(o, w, s, l), nB));
+  RC(o.mm_resid(w.ao, w.o, x_out, M, d, inner, x_in, s.site(l) + PL_SELF_OUT));
   return M2M_OK;
 }
 
 // ... and backward: dx_out (fp32, gradient wrt x_out) -> dx_in; weight gradients into G
 template <typename T>
-int attn_self_bwd(const Ops<T>& o, const float* x_in, const float* dx_out, float* dx_in, float* G, int64_t ln, int64_t wqkv, int64_t wo,
-                  const void* h, const void* qkv, const void* Pm, const void* ao, int nB, int S, const int* buckets, int64_t bias_off,
-                  int bias_accumulate, int site0, const void* kt, float* lse, const float* tab) {
+int attn_self_bwd(const Ops<T>& o, const SelfAttn& w, const Stack& s, int l, int nB, const float* x_in, const float* dx_out, float* dx_in, float* G) {
   m2m_trainer* t = o.t;
-  const int d = t->g.d_model, inner = t->inner, M = nB * S;
+  const int d = t->g.d_model, inner = t->inner, M = nB * s.S;
   int rc;
   RC(o.begin_sub(1u << m2m_trainer::K_DXT | 1u << m2m_trainer::K_DQKV));
-  RC(o.cvt_branch(dx_out, t->dxT, (int64_t)M * d, site0 + PL_SELF_OUT));
-  RC(o.dW(t->dxT, d, d, ao, inner, inner, G + wo, M));                                            // dWo = dx^T . ao
-  RC(o.dX(TG_STORE_T, t->dxT, d, wo, d, inner, t->dO, inner, M));                                 // dO = dx . Wo
-  AttnDesc a = self_desc<T>(o, qkv, S, tab, buckets == t->dbucket ? 1 : 0, site0, Pm, kt, lse, ao);
-  a.dO = t->dO; a.buckets = buckets; a.Gbias = G + bias_off; a.bias_accumulate = bias_accumulate;
+  RC(o.cvt_branch(dx_out, t->dxT, (int64_t)M * d, s.site(l) + PL_SELF_OUT));
+  RC(o.dW(t->dxT, d, d, w.ao, inner, inner, G + w.o, M));                                         // dWo = dx^T . ao
+  RC(o.dX(TG_STORE_T, t->dxT, d, w.o, d, inner, t->dO, inner, M));                                // dO = dx . Wo
+  AttnDesc a = self_desc<T>(o, w, s, l);
+  a.dO = t->dO; a.buckets = s.buckets; a.Gbias = G + s.bias_off; a.bias_accumulate = s.last(l) ? 0 : 1;
   RC(attn_core_bwd<T>(o, a, nB));
-  RC(o.dW(t->dqkv, 3 * inner, 3 * inner, h, d, d, G + wqkv, M));                                  // dWqkv = dqkv^T . h
-  RC(o.dX(TG_STORE_F32, t->dqkv, 3 * inner, wqkv, 3 * inner, d, t->dh, d, M));                    // dh = dqkv . Wqkv
-  RC(o.norm_bwd(x_in, ln, t->dh, dx_out, dx_in, G, M));
+  RC(o.dW(t->dqkv, 3 * inner, 3 * inner, w.h, d, d, G + w.qkv, M));                               // dWqkv = dqkv^T . h
+  RC(o.dX(TG_STORE_F32, t->dqkv, 3 * inner, w.qkv, 3 * inner, d, t->dh, d, M));                   // dh = dqkv . Wqkv
+  RC(o.norm_bwd(x_in, w.ln, t->dh, dx_out, dx_in, G, M));
   RC(o.end_sub());
   return M2M_OK;
 }
 
 // the descriptor of decoder layer l's cross-attention (hf: modeling_t5.py:319-342: K/V from the encoder output, zero bias, no mask)
 template <typename T>
-AttnDesc cross_desc(const Ops<T>& o, int l, int L, int S) {
+AttnDesc cross_desc(const Ops<T>& o, const CrossAttn& w, const Stack& s, int l) {
   m2m_trainer* t = o.t;
   AttnDesc a{};
-  a.q = o.part(t->cqd[l], 1, 0, L); a.k = o.part(t->ckvd[l], 2, 0, S); a.v = o.part(t->ckvd[l], 2, 1, S);
-  a.dq = o.part(t->dcq, 1, 0, L); a.dk = o.part(t->dckv, 2, 0, S); a.dv = o.part(t->dckv, 2, 1, S);
-  a.Sq = L; a.Sk = S; a.site = SITE_DEC + 16 * l + PL_PROBS_CROSS;
-  a.Pm = t->Pcd[l]; a.kt = t->ktc[l]; a.lse = t->lse_c[l]; a.ao = t->aocd[l];
+  a.q = o.part(w.q_out, 1, 0, s.S); a.k = o.part(w.kv_out, 2, 0, s.Sx); a.v = o.part(w.kv_out, 2, 1, s.Sx);
+  a.dq = o.part(t->dcq, 1, 0, s.S); a.dk = o.part(t->dckv, 2, 0, s.Sx); a.dv = o.part(t->dckv, 2, 1, s.Sx);
+  a.Sq = s.S; a.Sk = s.Sx; a.site = s.site(l) + PL_PROBS_CROSS;
+  a.Pm = w.P; a.kt = w.kt; a.lse = w.lse; a.ao = w.ao;
   return a;
 }
 
 // cross-attention block of decoder layer l, forward: x_in -> x_out = x_in + Attn(norm(x_in), hE)
 template <typename T>
-int attn_cross_fwd(const Ops<T>& o, const float* x_in, float* x_out, int l, int nB, int L, int S) {
+int attn_cross_fwd(const Ops<T>& o, const CrossAttn& w, const Stack& s, int l, int nB, const float* x_in, float* x_out) {
   m2m_trainer* t = o.t;
-  const DecOff& e = t->dec[l];
-  const int d = t->g.d_model, inner = t->inner, Md = nB * L, Me = nB * S;
+  const int d = t->g.d_model, inner = t->inner, Md = nB * s.S, Me = nB * s.Sx;
   int rc;
-  RC(o.norm(x_in, e.ln1, t->h1d[l], Md));
-  RC(o.mm(TG_STORE_T, t->h1d[l], d, 0, o.W(e.cq), d, 0, t->cqd[l], inner, Md, inner, d));
-  RC(o.mm(TG_STORE_T, t->hE, d, 0, o.W(e.ckv), d, 0, t->ckvd[l], 2 * inner, Me, 2 * inner, d));
-  RC(attn_core_fwd<T>(o, cross_desc<T>(o, l, L, S), nB));
-  RC(o.mm_resid(t->aocd[l], e.co, x_out, Md, d, inner, x_in, SITE_DEC + 16 * l + PL_CROSS_OUT));
+  RC(o.norm(x_in, w.ln, w.h, Md));
+  RC(o.mm(TG_STORE_T, w.h, d, 0, o.W(w.q), d, 0, w.q_out, inner, Md, inner, d));
+  RC(o.mm(TG_STORE_T, t->hE, d, 0, o.W(w.kv), d, 0, w.kv_out, 2 * inner, Me, 2 * inner, d));
+  RC(attn_core_fwd<T>(o, cross_desc<T>(o, w, s, l), nB));
+  RC(o.mm_resid(w.ao, w.o, x_out, Md, d, inner, x_in, s.site(l) + PL_CROSS_OUT));
   return M2M_OK;
 }
 
-// ... and backward: dx_out -> dx_in, and the layer's share of the encoder output's gradient into t->dhE (acc_dhE: added to what it holds)
+// ... and backward: dx_out -> dx_in, and the layer's share of the encoder output's gradient into t->dhE
 template <typename T>
-int attn_cross_bwd(const Ops<T>& o, const float* x_in, const float* dx_out, float* dx_in, float* G, int l, int nB, int L, int S, bool acc_dhE) {
+int attn_cross_bwd(const Ops<T>& o, const CrossAttn& w, const Stack& s, int l, int nB, const float* x_in, const float* dx_out, float* dx_in, float* G) {
   m2m_trainer* t = o.t;
-  const DecOff& e = t->dec[l];
-  const int d = t->g.d_model, inner = t->inner, Md = nB * L, Me = nB * S;
+  const int d = t->g.d_model, inner = t->inner, Md = nB * s.S, Me = nB * s.Sx;
   int rc;
   RC(o.begin_sub(1u << m2m_trainer::K_DXT | 1u << m2m_trainer::K_DCQ | 1u << m2m_trainer::K_DCKV));
-  RC(o.cvt_branch(dx_out, t->dxT, (int64_t)Md * d, SITE_DEC + 16 * l + PL_CROSS_OUT));
-  RC(o.dW(t->dxT, d, d, t->aocd[l], inner, inner, G + e.co, Md));
-  RC(o.dX(TG_STORE_T, t->dxT, d, e.co, d, inner, t->dO, inner, Md));
-  AttnDesc a = cross_desc<T>(o, l, L, S);
+  RC(o.cvt_branch(dx_out, t->dxT, (int64_t)Md * d, s.site(l) + PL_CROSS_OUT));
+  RC(o.dW(t->dxT, d, d, w.ao, inner, inner, G + w.o, Md));
+  RC(o.dX(TG_STORE_T, t->dxT, d, w.o, d, inner, t->dO, inner, Md));
+  AttnDesc a = cross_desc<T>(o, w, s, l);
   a.dO = t->dO;
   RC(attn_core_bwd<T>(o, a, nB));
-  RC(o.dW(t->dcq, inner, inner, t->h1d[l], d, d, G + e.cq, Md));
-  RC(o.dX(TG_STORE_F32, t->dcq, inner, e.cq, inner, d, t->dh, d, Md));
-  RC(o.norm_bwd(x_in, e.ln1, t->dh, dx_out, dx_in, G, Md));
-  RC(o.dW(t->dckv, 2 * inner, 2 * inner, t->hE, d, d, G + e.ckv, Me));                            // dWckv = dckv^T . hE
-  RC(o.dX(acc_dhE ? TG_ACC_F32 : TG_STORE_F32, t->dckv, 2 * inner, e.ckv, 2 * inner, d, t->dhE, d, Me));      // dhE (+)= dckv . Wckv
+  RC(o.dW(t->dcq, inner, inner, w.h, d, d, G + w.q, Md));
+  RC(o.dX(TG_STORE_F32, t->dcq, inner, w.q, inner, d, t->dh, d, Md));
+  RC(o.norm_bwd(x_in, w.ln, t->dh, dx_out, dx_in, G, Md));
+  RC(o.dW(t->dckv, 2 * inner, 2 * inner, t->hE, d, d, G + w.kv, Me));                             // dWckv = dckv^T . hE
+  RC(o.dX(s.last(l) ? TG_STORE_F32 : TG_ACC_F32, t->dckv, 2 * inner, w.kv, 2 * inner, d, t->dhE, d, Me));      // dhE (+)= dckv . Wckv
   RC(o.end_sub());
   return M2M_OK;
 }
 
 template <typename T>
-int ff_fwd(const Ops<T>& o, const float* x_in, float* x_out, int64_t ln, int64_t wi, int64_t wo, void* h, void* ab, void* mid, int M, int site0) {
+int ff_fwd(const Ops<T>& o, const FeedFwd& w, const Stack& s, int l, int nB, const float* x_in, float* x_out) {
   m2m_trainer* t = o.t;
-  const int d = t->g.d_model, dff = t->g.d_ff;
+  const int d = t->g.d_model, dff = t->g.d_ff, M = nB * s.S;
   int rc;
-  RC(o.norm(x_in, ln, h, M));
+  RC(o.norm(x_in, w.ln, w.h, M));
   // the gate product with the activation in its epilogue (bf16, grids the 128x128 tile takes anyway): a | b and
   // mid = dropout(gelu_new(a) * b) leave the product together — the gated_fwd_kernel launch and its read of the pair are gone
   if (t->sw.gate_epi && !t->fp8 && t->sw.tuned_gemm && t->Wil && gemm_takes_gated_train(t->precision, M, 2 * dff, d)) {
     GemmArgs a{};
-    a.A = h; a.W = reinterpret_cast<const T*>(t->Wil) + wi; a.M = M; a.N = 2 * dff; a.K = d; a.out = mid; a.ldo = dff; a.ab_out = ab; a.vt_which = -1;
-    if (o.dropping(site0 + PL_MID)) { a.drop_thresh = t->drop_thresh; a.drop_scale = t->drop_scale; a.drop_key = o.key(site0 + PL_MID).salt; a.drop_step = t->step_key_dev; }
+    a.A = w.h; a.W = reinterpret_cast<const T*>(t->Wil) + w.wi; a.M = M; a.N = 2 * dff; a.K = d; a.out = w.mid; a.ldo = dff; a.ab_out = w.ab; a.vt_which = -1;
+    o.drop_fields(a, s.site(l) + PL_MID);
     RC(launch_gemm(t->precision, EPI_GATED_TRAIN, a, o.st));
   } else {
-    RC(o.mm(TG_STORE_T, h, d, 0, o.W(wi), d, 0, ab, 2 * dff, M, 2 * dff, d));
-    RC(o.gated(ab, mid, M, site0 + PL_MID));
+    RC(o.mm(TG_STORE_T, w.h, d, 0, o.W(w.wi), d, 0, w.ab, 2 * dff, M, 2 * dff, d));
+    RC(o.gated(w.ab, w.mid, M, s.site(l) + PL_MID));
   }
-  RC(o.mm_resid(mid, wo, x_out, M, d, dff, x_in, site0 + PL_FF_OUT));
+  RC(o.mm_resid(w.mid, w.wo, x_out, M, d, dff, x_in, s.site(l) + PL_FF_OUT));
   return M2M_OK;
 }
 template <typename T>
-int ff_bwd(const Ops<T>& o, const float* x_in, const float* dx_out, float* dx_in, float* G, int64_t ln, int64_t wi, int64_t wo, const void* h,
-           const void* ab, const void* mid, int M, int site0) {
+int ff_bwd(const Ops<T>& o, const FeedFwd& w, const Stack& s, int l, int nB, const float* x_in, const float* dx_out, float* dx_in, float* G) {
   m2m_trainer* t = o.t;
-  const int d = t->g.d_model, dff = t->g.d_ff;
+  const int d = t->g.d_model, dff = t->g.d_ff, M = nB * s.S;
   int rc;
   RC(o.begin_sub(1u << m2m_trainer::K_DXT | 1u << m2m_trainer::K_DAB));
-  RC(o.cvt_branch(dx_out, t->dxT, (int64_t)M * d, site0 + PL_FF_OUT));
-  RC(o.dW(t->dxT, d, d, mid, dff, dff, G + wo, M));                                               // dWo = dx^T . mid
+  RC(o.cvt_branch(dx_out, t->dxT, (int64_t)M * d, s.site(l) + PL_FF_OUT));
+  RC(o.dW(t->dxT, d, d, w.mid, dff, dff, G + w.wo, M));                                           // dWo = dx^T . mid
   // dmid = dx . Wo, turned into the gate pair's gradient by the product's own epilogue where it can (bf16): dmid is never stored,
   // the gated_bwd_kernel launch and its reads are gone
   if (t->sw.gate_epi && !t->fp8 && t->sw.tuned_gemm && gemm_takes_gated_bwd(t->precision, M, dff, d)) {
     GemmArgs a{};
-    a.A = t->dxT; a.W = reinterpret_cast<const T*>(t->WT) + wo; a.M = M; a.N = dff; a.K = d; a.out = t->dab; a.ldo = 2 * dff; a.ab_out = const_cast<void*>(ab);
+    a.A = t->dxT; a.W = reinterpret_cast<const T*>(t->WT) + w.wo; a.M = M; a.N = dff; a.K = d; a.out = t->dab; a.ldo = 2 * dff; a.ab_out = w.ab;
     a.vt_which = -1;
-    if (o.dropping(site0 + PL_MID)) { a.drop_thresh = t->drop_thresh; a.drop_scale = t->drop_scale; a.drop_key = o.key(site0 + PL_MID).salt; a.drop_step = t->step_key_dev; }
+    o.drop_fields(a, s.site(l) + PL_MID);
     RC(launch_gemm(t->precision, EPI_GATED_BWD, a, o.st));
   } else {
-    RC(o.dX(TG_STORE_T, t->dxT, d, wo, d, dff, t->dmid, dff, M));                                 // dmid = dx . Wo
-    RC(o.gated_bwd(ab, t->dmid, t->dab, M, site0 + PL_MID));
+    RC(o.dX(TG_STORE_T, t->dxT, d, w.wo, d, dff, t->dmid, dff, M));                               // dmid = dx . Wo
+    RC(o.gated_bwd(w.ab, t->dmid, t->dab, M, s.site(l) + PL_MID));
   }
-  RC(o.dW(t->dab, 2 * dff, 2 * dff, h, d, d, G + wi, M));                                         // dWi = dab^T . h
-  RC(o.dX(TG_STORE_F32, t->dab, 2 * dff, wi, 2 * dff, d, t->dh, d, M));                           // dh = dab . Wi
-  RC(o.norm_bwd(x_in, ln, t->dh, dx_out, dx_in, G, M));
+  RC(o.dW(t->dab, 2 * dff, 2 * dff, w.h, d, d, G + w.wi, M));                                     // dWi = dab^T . h
+  RC(o.dX(TG_STORE_F32, t->dab, 2 * dff, w.wi, 2 * dff, d, t->dh, d, M));                         // dh = dab . Wi
+  RC(o.norm_bwd(x_in, w.ln, t->dh, dx_out, dx_in, G, M));
   RC(o.end_sub());
   return M2M_OK;
 }
@@ -2932,6 +2286,7 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
   const bool scaled = G && (t->gmode & m2m_trainer::GM_SCALED);
   o.group = G && t->sw.dw_group && !(t->fp8 && t->sw.fp8.dw);
   o.st2 = (G && !o.group) ? st_side : nullptr;
+  const Stack enc{S, 0, Le, t->etab, t->ebucket, t->o_erb, 0, SITE_ENC}, dec{L, S, Ld, t->dtab, t->dbucket, t->o_drb, 1, SITE_DEC};
   int rc;
   // (the bucket tables of this geometry are on the device already: ensure_tables())
   {
@@ -2947,9 +2302,9 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
     M2M_CHECK_HIP(hipGetLastError());
   }
   if (G || t->precision == M2M_PREC_BF16) {      // W^T for the dX products (with gradients) and the bf16 copy the forward products read, one pass over P
-    hipLaunchKernelGGL(weights_transpose_kernel<T>, dim3(t->n_wt_blocks), dim3(256), 0, st, (const WtBlock*)t->wt_blocks, P, G ? (T*)t->WT : (T*)nullptr,
-                       t->precision == M2M_PREC_BF16 ? (T*)t->Wc : (T*)nullptr, (t->precision == M2M_PREC_BF16 && !t->fp8) ? (T*)t->Wil : (T*)nullptr);
-    M2M_CHECK_HIP(hipGetLastError());
+    const bool bf16 = t->precision == M2M_PREC_BF16;
+    RC(launch_weights_transpose(t->precision, (const WtBlock*)t->wt_blocks, t->n_wt_blocks, P, G ? t->WT : nullptr, bf16 ? t->Wc : nullptr,
+                                bf16 && !t->fp8 ? t->Wil : nullptr, st));
   }
   if (t->fp8) {
     const int rc = launch_mxq_weights((const W8Tile*)t->w8_tiles, t->n_w8_tiles, P, t->w8, st);
@@ -2966,10 +2321,8 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
                        t->xe[0], S, d);
   }
   for (int l = 0; l < Le; ++l) {
-    const EncOff& e = t->enc[l];
-    RC(attn_self_fwd<T>(o, t->xe[2 * l], t->xe[2 * l + 1], e.ln0, e.qkv, e.o, t->h0e[l], t->qkve[l], t->Pe[l], t->aoe[l], B, S, t->etab, 0,
-                        SITE_ENC + 16 * l, t->kte[l], t->lse_e[l]));
-    RC(ff_fwd<T>(o, t->xe[2 * l + 1], t->xe[2 * l + 2], e.ln1, e.wi, e.wo, t->h1e[l], t->abe[l], t->mide[l], Me, SITE_ENC + 16 * l));
+    RC(attn_self_fwd<T>(o, t->enc[l].self, enc, l, B, t->xe[2 * l], t->xe[2 * l + 1]));
+    RC(ff_fwd<T>(o, t->enc[l].ff, enc, l, B, t->xe[2 * l + 1], t->xe[2 * l + 2]));
   }
   RC(o.norm_drop(t->xe[2 * Le], t->o_eln, t->hE, Me, SITE_ENC + SITE_FIN));
   // decoder
@@ -2981,11 +2334,9 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
     RC(launch_embed_rows(t->dec_in, P + t->o_shared, t->xd[0], Md, d, V, g.pad_token_id, st));
   }
   for (int l = 0; l < Ld; ++l) {
-    const DecOff& e = t->dec[l];
-    RC(attn_self_fwd<T>(o, t->xd[3 * l], t->xd[3 * l + 1], e.ln0, e.qkv, e.o, t->h0d[l], t->qkvd[l], t->Pd[l], t->aod[l], B, L, t->dtab, 1,
-                        SITE_DEC + 16 * l, t->ktd[l], t->lse_d[l]));
-    RC(attn_cross_fwd<T>(o, t->xd[3 * l + 1], t->xd[3 * l + 2], l, B, L, S));
-    RC(ff_fwd<T>(o, t->xd[3 * l + 2], t->xd[3 * l + 3], e.ln2, e.wi, e.wo, t->h2d[l], t->abd[l], t->midd[l], Md, SITE_DEC + 16 * l));
+    RC(attn_self_fwd<T>(o, t->dec[l].self, dec, l, B, t->xd[3 * l], t->xd[3 * l + 1]));
+    RC(attn_cross_fwd<T>(o, t->dec[l].cross, dec, l, B, t->xd[3 * l + 1], t->xd[3 * l + 2]));
+    RC(ff_fwd<T>(o, t->dec[l].ff, dec, l, B, t->xd[3 * l + 2], t->xd[3 * l + 3]));
   }
   RC(o.norm_drop(t->xd[3 * Ld], t->o_dln, t->hD, Md, SITE_DEC + SITE_FIN));
   RC(o.mm(TG_STORE_F32, t->hD, d, 0, o.W(t->o_lm), d, 0, t->logits, V, Md, V, d));
@@ -3011,26 +2362,24 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
   o.after_site = SITE_DEC + 16 * (Ld - 1) + PL_FF_OUT;
   RC(o.norm_bwd(t->xd[3 * Ld], t->o_dln, t->dh, nullptr, dcur, G, Md, SITE_DEC + SITE_FIN));
   for (int l = Ld - 1; l >= 0; --l) {
-    const DecOff& e = t->dec[l];
     o.after_site = SITE_DEC + 16 * l + PL_CROSS_OUT;
-    RC(ff_bwd<T>(o, t->xd[3 * l + 2], dcur, dnext, G, e.ln2, e.wi, e.wo, t->h2d[l], t->abd[l], t->midd[l], Md, SITE_DEC + 16 * l));
+    RC(ff_bwd<T>(o, t->dec[l].ff, dec, l, B, t->xd[3 * l + 2], dcur, dnext, G));
     std::swap(dcur, dnext);
     // ---- cross-attention backward: dcur = d x[3l+2] ----
     o.after_site = SITE_DEC + 16 * l + PL_SELF_OUT;
-    RC(attn_cross_bwd<T>(o, t->xd[3 * l + 1], dcur, dnext, G, l, B, L, S, l != Ld - 1));
+    RC(attn_cross_bwd<T>(o, t->dec[l].cross, dec, l, B, t->xd[3 * l + 1], dcur, dnext, G));
     std::swap(dcur, dnext);
     // ---- causal self-attention backward ----
     o.after_site = l > 0 ? SITE_DEC + 16 * (l - 1) + PL_FF_OUT : -2;
-    RC(attn_self_bwd<T>(o, t->xd[3 * l], dcur, dnext, G, e.ln0, e.qkv, e.o, t->h0d[l], t->qkvd[l], t->Pd[l], t->aod[l], B, L, t->dbucket, t->o_drb,
-                        l == Ld - 1 ? 0 : 1, SITE_DEC + 16 * l, t->ktd[l], t->lse_d[l], t->dtab));
+    RC(attn_self_bwd<T>(o, t->dec[l].self, dec, l, B, t->xd[3 * l], dcur, dnext, G));
     std::swap(dcur, dnext);
   }
   // token embedding (decoder inputs; the encoder is fed inputs_embeds) — hf: modeling_t5.py embed_tokens = shared
   {
-    const bool dr = o.dropping(SITE_DEC + SITE_EMB);
+    const auto dr = o.drop(SITE_DEC + SITE_EMB);
     M2M_OPT_IN_LDS(embed_bwd_kernel<EMB_NW_SHARED>, 158 * 1024);
     hipLaunchKernelGGL(embed_bwd_kernel<EMB_NW_SHARED>, dim3(V), dim3(64 * EMB_NW_SHARED), embed_bwd_smem(Md), st, t->dec_in, Md, 1, 0, dcur, (int64_t)1, (int64_t)0, G + t->o_shared, d,
-                       g.pad_token_id, V, dr ? o.key(SITE_DEC + SITE_EMB) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u, t->drop_scale, o.gacc);
+                       g.pad_token_id, V, dr.key, dr.thresh, dr.scale, o.gacc);
   }
   // Split pass (data-parallel overlap): everything the decoder side deferred is issued now, so the gradients of the shared embedding,
   // lm_head and every decoder block are FINAL here — the caller's hook releases whoever waits for them — and the encoder side
@@ -3051,13 +2400,11 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
   o.after_site = SITE_ENC + 16 * (Le - 1) + PL_FF_OUT;
   RC(o.norm_bwd(t->xe[2 * Le], t->o_eln, t->dhE, nullptr, dcur, G, Me, SITE_ENC + SITE_FIN));
   for (int l = Le - 1; l >= 0; --l) {
-    const EncOff& e = t->enc[l];
     o.after_site = SITE_ENC + 16 * l + PL_SELF_OUT;
-    RC(ff_bwd<T>(o, t->xe[2 * l + 1], dcur, dnext, G, e.ln1, e.wi, e.wo, t->h1e[l], t->abe[l], t->mide[l], Me, SITE_ENC + 16 * l));
+    RC(ff_bwd<T>(o, t->enc[l].ff, enc, l, B, t->xe[2 * l + 1], dcur, dnext, G));
     std::swap(dcur, dnext);
     o.after_site = l > 0 ? SITE_ENC + 16 * (l - 1) + PL_FF_OUT : -2;
-    RC(attn_self_bwd<T>(o, t->xe[2 * l], dcur, dnext, G, e.ln0, e.qkv, e.o, t->h0e[l], t->qkve[l], t->Pe[l], t->aoe[l], B, S, t->ebucket, t->o_erb,
-                        l == Le - 1 ? 0 : 1, SITE_ENC + 16 * l, t->kte[l], t->lse_e[l], t->etab));
+    RC(attn_self_bwd<T>(o, t->enc[l].self, enc, l, B, t->xe[2 * l], dcur, dnext, G));
     std::swap(dcur, dnext);
   }
   // The tail of the pass is a set of reductions that do not depend on one another: the grouped weight-gradient launch (0.35 ms,
@@ -3071,10 +2418,9 @@ int forward_backward_t(m2m_trainer* t, const float* P, const float* enc_inputs, 
   }
   // conditioning embeddings: rows 0 .. n_cond-1 of every clip's encoder input (ref: music2midi/input.py:57-59)
   for (int i = 0; i < t->n_cond; ++i) {
-    const bool dr = o.dropping(SITE_ENC + SITE_EMB);
+    const auto dr = o.drop(SITE_ENC + SITE_EMB);
     hipLaunchKernelGGL(embed_bwd_kernel<4>, dim3(t->cond_rows[i]), dim3(256), embed_bwd_smem(B, 4), small, cond_idx, B, t->n_cond, i, dcur, (int64_t)S, (int64_t)i,
-                       G + t->o_cond[i], d, 0, t->cond_rows[i], dr ? o.key(SITE_ENC + SITE_EMB) : DropKey{nullptr, 0}, dr ? t->drop_thresh : 0u,
-                       t->drop_scale, o.gacc);
+                       G + t->o_cond[i], d, 0, t->cond_rows[i], dr.key, dr.thresh, dr.scale, o.gacc);
   }
   M2M_CHECK_HIP(hipGetLastError());
   RC(o.join_side());
@@ -3380,7 +2726,6 @@ extern "C" int m2m_train_forward_backward_acc(m2m_trainer* t, const float* param
 
 extern "C" int m2m_trainer_set_dropout(m2m_trainer* t, float p, uint64_t seed) {
   M2M_REQUIRE(t && p >= 0.f && p < 1.f, "m2m_trainer_set_dropout: p must be in [0, 1)");
-  t->drop_p = p;
   t->drop_thresh = p > 0.f ? (uint32_t)((double)p * 4294967296.0) : 0u;
   t->drop_scale = 1.0f / (1.0f - p);
   t->drop_seed = seed;

@@ -1,4 +1,4 @@
-"""GPU: every MXFP8 kernel route of the fp8 training step on single products (csrc/mx8.hip, mxq_weights_kernel of csrc/train.hip).
+"""GPU: every MXFP8 kernel route of the fp8 training step on single products (csrc/mx8.hip, mxq_weights_kernel of csrc/train_gemm.hip).
 
 tests/test_mx8_gpu.py reaches the row quantiser and the two forward-style product kernels with the fp32-store epilogue only.  The
 step runs more: the weight quantiser (both images of every projection matrix), the transposing quantiser and the split-K product

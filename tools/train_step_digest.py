@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""SHA-256 over loss, logits and the flat gradient buffer of one forward_backward call, per kernel family of the training attention,
-and the launches of the captured graph.  For host-side changes of the training pass: run once per build and compare the lines.
+"""SHA-256 over loss, logits and the flat gradient buffer of the forward_backward calls of a case, per kernel family of the training
+attention and per host path of the pass (grouped, per-product, accumulating, split), with the launches of the captured graph and
+the bytes of the trainer's arena.  For host-side changes of the training pass: run once per build and compare the lines.
 
     M2M_LIBRARY=<the other build> python tools/train_step_digest.py > a.txt;  python tools/train_step_digest.py > b.txt;  diff a.txt b.txt
 
@@ -16,19 +17,24 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from music2midi_amd import synth  # noqa: E402
+from music2midi_amd import native, synth  # noqa: E402
 from music2midi_amd.checkpoint import load_t5_state  # noqa: E402
 from music2midi_amd.config import T5Geometry, load_config  # noqa: E402
 from music2midi_amd.training import NativeTrainer  # noqa: E402
 from music2midi_amd.transformer import T5Transformer  # noqa: E402
 from test_t5_gpu import tiny_config  # noqa: E402
 
-SWITCHES = ("M2M_TRAIN_GRAPH", "M2M_TRAIN_ATTN")
-# (precision, B, F, Ld, dropout, environment): stripes; unfused past 512 keys; whole-head; the same on stripes; mixed (402 > AH_MAX_S); fp8
-SHAPES = [("fp32", 3, 21, 14, 0.0, {}), ("fp32", 3, 21, 14, 0.1, {}), ("fp32", 1, 530, 5, 0.0, {}), ("fp32", 1, 530, 5, 0.1, {}),
-          ("bf16", 2, 70, 33, 0.1, {}), ("bf16", 2, 70, 33, 0.1, {"M2M_TRAIN_ATTN": "stripes"}), ("bf16", 2, 400, 37, 0.1, {}),
-          ("fp8", 3, 21, 14, 0.0, {})]
-CASES = SHAPES + [(*c[:5], {**c[5], "M2M_TRAIN_GRAPH": "0"}) for c in SHAPES]
+SWITCHES = ("M2M_TRAIN_GRAPH", "M2M_TRAIN_ATTN", "M2M_TRAIN_DW_GROUP", "M2M_TRAIN_SIDE")
+# (precision, B, F, Ld, dropout, environment, mode): stripes; unfused past 512 keys; whole-head; the same on stripes; mixed (402 > AH_MAX_S); fp8
+SHAPES = [("fp32", 3, 21, 14, 0.0, {}, ""), ("fp32", 3, 21, 14, 0.1, {}, ""), ("fp32", 1, 530, 5, 0.0, {}, ""), ("fp32", 1, 530, 5, 0.1, {}, ""),
+          ("bf16", 2, 70, 33, 0.1, {}, ""), ("bf16", 2, 70, 33, 0.1, {"M2M_TRAIN_ATTN": "stripes"}, ""), ("bf16", 2, 400, 37, 0.1, {}, ""),
+          ("fp8", 3, 21, 14, 0.0, {}, ""),
+          # the host paths beside the grouped single pass: a launch per weight gradient on the side stream (the two alternating ring
+          # sets) and on one stream; accumulation (mode "accum": a scaled overwriting call, then a scaled adding one); the split pass of
+          # the data-parallel overlap (mode "split": a sync stream set, the second half of the tables, the second graph)
+          ("bf16", 3, 21, 14, 0.1, {"M2M_TRAIN_DW_GROUP": "0"}, ""), ("bf16", 3, 21, 14, 0.1, {"M2M_TRAIN_DW_GROUP": "0", "M2M_TRAIN_SIDE": "0"}, ""),
+          ("bf16", 3, 21, 14, 0.1, {}, "accum"), ("fp32", 3, 21, 14, 0.1, {}, "accum"), ("bf16", 3, 21, 14, 0.1, {}, "split")]
+CASES = SHAPES + [(*c[:5], {**c[5], "M2M_TRAIN_GRAPH": "0"}, c[6]) for c in SHAPES]
 
 
 def main():
@@ -39,7 +45,7 @@ def main():
     model = T5Transformer(cfg, precision="fp32")
     load_t5_state(model, sd, strict=False)
     model = model.cuda()
-    for prec, B, F, Ld, p, env in CASES:
+    for prec, B, F, Ld, p, env, mode in CASES:
         for k in SWITCHES:
             os.environ.pop(k, None)
         os.environ.update(env)
@@ -52,13 +58,19 @@ def main():
         h = hashlib.sha256()
         if p:
             tr.set_dropout(p, seed=1234)
-        for call in range(3):                                    # a graph build replays the captured graph from its second call on
-            loss, logits = tr.forward_backward(x, cond, labels, want_logits=True)
-            torch.cuda.synchronize()
-            for a in (loss, logits, tr.grads):
-                h.update(a.cpu().numpy().tobytes())
-        what = " ".join(f"{k}={v}" for k, v in env.items()) or "-"
-        print(f"{prec} B={B} F={F} Ld={Ld} p={p} {what}: graph nodes {tr.graph_nodes()} sha256 {h.hexdigest()}", flush=True)
+        if mode == "split":
+            tr.set_sync_stream(torch.cuda.Stream())
+        # the calls of one round; a graph build replays the captured graph of a key from that key's second call on: three rounds
+        calls = [dict(grad_scale=0.5, accumulate=False), dict(grad_scale=0.5, accumulate=True)] if mode == "accum" else [{}]
+        for _ in range(3):
+            for kw in calls:
+                loss, logits = tr.forward_backward(x, cond, labels, want_logits=True, **kw)
+                torch.cuda.synchronize()
+                for a in (loss, logits, tr.grads):
+                    h.update(a.cpu().numpy().tobytes())
+        what = " ".join([f"{k}={v}" for k, v in env.items()] + ([mode] if mode else [])) or "-"
+        ws = int(native.load().m2m_trainer_workspace_bytes(tr.handle))
+        print(f"{prec} B={B} F={F} Ld={Ld} p={p} {what}: graph nodes {tr.graph_nodes()} workspace {ws} sha256 {h.hexdigest()}", flush=True)
         tr.close()
 
 
