@@ -15,8 +15,9 @@
 //                    streams K then V straight from HBM to registers (16 B per lane per load, no
 //                    LDS staging: each byte is used once), fp32 softmax, shuffle + LDS reduction.
 //   dec_attn_mc_kernel  the same for large chains: one head of C = 2 / 4 consecutive clips per workgroup (one row round trip, the
-//                    head's weights fetched once, the clips' K/V streams back to back).  Per row it repeats dec_attn_kernel's
-//                    pieces (da_project, DaSoftmax, da_merge, da_out_row, da_book_row) by hand: a row's bits do not depend on the form.
+//                    head's weights fetched once, the clips' K/V streams back to back).  This step's k / v rows go through dec_attn_kernel's
+//                    da_project + da_append_kv; the other pieces (q, DaSoftmax, da_merge, da_out_row, da_book_row) it repeats by hand
+//                    (DESIGN 9.7): a row's bits do not depend on the form.
 //   dec_ff_kernel    the whole gated feed-forward sub-layer: RMSNorm + MFMA up projection of a 32-column
 //                    slice + gated GELU (LDS) + MFMA down projection, added into the residual stream.
 //   dec_ff_multi_kernel  the same for large chains: several consecutive slices per workgroup, summed as integers before ONE
@@ -790,10 +791,11 @@ template <typename T> __device__ inline void put_in(float* in_lds, int i, float 
 // A row's ids and logits are bit-identical whichever kernel decodes it (tests/test_t5_gpu.py::
 // test_multi_clip_attention_and_wide_ff_tiles_are_bit_identical): every float operation of a row is one of these functions - same
 // lane -> element maps, same reduction trees, same key -> lane-group partition, same rounding points.  They are written over the
-// clip count so that dec_attn_mc_kernel (C clips per workgroup) can call them too, and it did: ids, logits and resources held, but
-// its cross-attention instantiations measured 0.03-0.07 us per launch over the parent's at 2 x 64 clips and the piece responsible
-// was not found.  So dec_attn_mc_kernel still carries its own copy of each piece, kept equal by hand and by the tests:
-// a change here has to be made there as well.
+// clip count so that dec_attn_mc_kernel (C clips per workgroup) can call them too.  It calls da_project<T, C, LPO2> + da_append_kv
+// for this step's k / v rows.  The other five were each put into it alone and timed against the parent, runs alternating in one
+// job (tools/mc_piece_map.py, tools/ab_kernel_time.py): every one held ids, logits and resources, none held the time bar
+// at every geometry, so dec_attn_mc_kernel still carries its own copy of da_project for q, DaSoftmax, da_merge, da_out_row and
+// da_book_row, kept equal by hand and by the tests: a change to one of THOSE has to be made there as well.
 
 // The online softmax of one lane group: running (max, sum, weighted-V) over the keys the group visits.
 template <typename T> struct DaSoftmax {
@@ -917,12 +919,14 @@ __device__ __forceinline__ void da_project(float (&acc)[C], const Vec16<T> (&w)[
 
 // The k / v element (k: which2 == 1) dd2 of this step for row c: rounded to T, appended to the row's cache block at position t
 // (Kb / Vb: the block of row 0, rows kv_clip elements apart; `store`: the row exists and its chain is live) and published in kn / vn.
+// k or v is a SELECT of the two targets, not a branch: which2 comes from threadIdx, so a branch is two exec-masked store sequences per
+// row - in dec_attn_mc_kernel's four rows 18.32 against 18.17 us per launch where the select reads 18.00.
 template <typename T>
 __device__ __forceinline__ void da_append_kv(float s2, int c, int which2, int dd2, int t, int64_t kv_clip, T* Kb, T* Vb, float* kn, float* vn, bool store) {
   const T r = from_f32<T>(s2);                       // k, v are stored (and used) rounded to T
   const int64_t slot = (int64_t)c * kv_clip + (int64_t)t * DK + dd2;
-  if (which2 == 1) { kn[c * DK + dd2] = to_f32(r); if (store) Kb[slot] = r; }
-  else             { vn[c * DK + dd2] = to_f32(r); if (store) Vb[slot] = r; }
+  (which2 == 1 ? kn : vn)[c * DK + dd2] = to_f32(r);
+  if (store) (which2 == 1 ? Kb : Vb)[slot] = r;
 }
 
 // Output projection of this head (wo: this lane's half of output column on_) from oh, ADDED into residual row b of x_out.  Head 0 also
@@ -1281,9 +1285,10 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
 // after the other by all 16 waves as ONE continuous stream: a clip's rounds are padded to a multiple of the prefetch depth, and
 // its last rounds re-request into the NEXT live clip, so MC_PF rounds are in flight through every merge - and the C output
 // projections at the end.
-// Per row the arithmetic is the first kernel's (dec_attn_kernel and its da_* pieces above), repeated here operation for operation
-// (same lane -> element maps, same reduction trees, same key -> lane-group partition, same rounding points; why it is repeated and not
-// called: the note above the pieces): ids and logits are bit-identical whichever form a chain takes
+// Per row the arithmetic is the first kernel's (dec_attn_kernel and its da_* pieces above): this step's k / v rows are its
+// da_project + da_append_kv, called; the rest is repeated here operation for operation (same lane -> element maps, same reduction
+// trees, same key -> lane-group partition, same rounding points; why it is repeated and not called: the note above the pieces and, per
+// piece, the one-line notes below): ids and logits are bit-identical whichever form a chain takes
 // (tests/test_t5_gpu.py::test_multi_clip_attention_and_wide_ff_tiles_are_bit_identical).  Chosen per chain by its clip count.
 // Prefetch depth (rounds in flight per workgroup).  Same-box A/B at 128 x S = 190, two chains of 64 clips, C = 2 (tools/r6_mc_ab.sh,
 // us per decode step): 2 rounds 370.0, 3 rounds 379.5, 4 rounds 394.0, 6 rounds 457.5 - as in the small-chain regime (the first
@@ -1514,7 +1519,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
   __syncthreads();
 
   // ---- 2. this head's projections of the C rows: the weights are in registers once ----
-  {
+  {   // (da_project<T, C, LPO>, by hand: called, the cross form at S = 864 read 31.28 us per launch against the parent's 31.13-31.25)
     float acc[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) acc[c] = 0.f;
@@ -1551,38 +1556,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
     Vec16<T> wkv[WMAX2];
 #pragma unroll
     for (int u = 0; u < WMAX2; ++u) wkv[u].v = *reinterpret_cast<const V16*>(wrow2 + (min(u, cnt2 - 1) * LPO2 + part2) * E);
-    float acc2[C];
+    float kvn[C];
+    da_project<T, C, LPO2>(kvn, wkv, wrow2, cnt2, part2, hn, a.d);
+    if (part2 == 0) {
 #pragma unroll
-    for (int c = 0; c < C; ++c) acc2[c] = 0.f;
-#pragma unroll
-    for (int u = 0; u < WMAX2; ++u) {
-      if (u < cnt2) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc2[c] = chunk_dot<T>(wkv[u], hn + c * a.d, u * LPO2 + part2, acc2[c]);
-      }
-    }
-    for (int i = WMAX2; i < cnt2; i += 4) {
-      Vec16<T> w2[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) w2[u].v = *reinterpret_cast<const V16*>(wrow2 + (min(i + u, cnt2 - 1) * LPO2 + part2) * E);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (i + u < cnt2) {
-#pragma unroll
-          for (int c = 0; c < C; ++c) acc2[c] = chunk_dot<T>(w2[u], hn + c * a.d, (i + u) * LPO2 + part2, acc2[c]);
-        }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const float s2 = group_sum<LPO2>(acc2[c]);
-      if (part2 == 0) {
-        const T r = from_f32<T>(s2);                       // k, v are stored (and used) rounded to T
-        const int64_t slot = (int64_t)c * kv_clip + (int64_t)t * DK + dd2;
-        const bool st_ok = !st_done && b0 + c < nb;
-        if (which2 == 1) { kn[c][dd2] = to_f32(r); if (st_ok) Kb0[slot] = r; }
-        else             { vn[c][dd2] = to_f32(r); if (st_ok) Vb0[slot] = r; }
-      }
+      for (int c = 0; c < C; ++c) da_append_kv<T>(kvn[c], c, which2, dd2, t, kv_clip, Kb0, Vb0, &kn[0][0], &vn[0][0], !st_done && b0 + c < nb);
     }
 #pragma unroll
     for (int u = 0; u < BPT; ++u)
@@ -1608,6 +1586,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
     float qv[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) qv[e] = qs[c][sub * E + e];
+    // (DaSoftmax, by hand: as the struct, the fp32 cross form read 20.37 us per launch against the parent's 20.24-20.34)
     float m_run = -1e30f, l_run = 0.f;
     float acc[E];
 #pragma unroll
@@ -1697,7 +1676,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
       for (int e = 0; e < E; ++e) vrow[e] = vn[c][sub * E + e];
       visit(s, vrow);
     }
-    // ---- merge of the 128 key groups (as in the first kernel) ----
+    // ---- merge of the 128 key groups (da_merge, by hand: called, the bf16 self form read 18.30 us per launch against the parent's
+    //      18.15-18.22) ----
     {
       const float mw = wave_max(m_run);
       const float scale = m2m_exp<T>(m_run - mw);
@@ -1735,7 +1715,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
   }
 
   // ---- 4. output projections of this head, accumulated into the C residual rows (the slice of wo is requested only here: 16 / 32
-  //         registers that would otherwise be held through every stream) ----
+  //         registers that would otherwise be held through every stream).  da_out_row, by hand: called, the bf16 self form read
+  //         18.23 us per launch against the parent's 18.15-18.22 ----
   constexpr int OCH = 32 / E;
   const T* worow = reinterpret_cast<const T*>(a.Wo) + (int64_t)on_ * a.inner + hh * DK + opart * 32;
   Vec16<T> wo[OCH];
@@ -1757,7 +1738,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
     }
   }
   if (!SELF && a.book && hh == 0 && tid == 0) {
-    // headless bookkeeping of the C rows (see the first kernel)
+    // headless bookkeeping of the C rows (da_book_row, by hand: called, the fp32 cross form read 21.83 us per launch against the
+    // parent's 21.66-21.71 - eight bytes of code, another schedule of the q projection)
     for (int c = 0; c < C && b0 + c < nb; ++c) {
       const int b = b0 + c;
       if (!st_done) {
@@ -1774,23 +1756,32 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
   }
 }
 
+// The (beam, headless, self, nt) decision tree of both attention kernels: launch(SELF, NT, FETCH, BEAM), each a std::bool_constant.
+template <typename F>
+static void launch_dec_attn_form(bool self, bool nt, const DecAttnArgs& a, F launch) {
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  auto by_nt = [&](auto s, auto fetch, auto beam) {
+    if (nt) launch(s, yes, fetch, beam);
+    else launch(s, no, fetch, beam);
+  };
+  if (a.beam_nb > 0) {          // beam search: ancestry reads (self) / a clip's K/V shared by its beams (cross)
+    if (self) by_nt(yes, no, yes);
+    else by_nt(no, no, yes);
+  } else if (self && a.emb) {   // headless layer 0
+    by_nt(yes, yes, no);
+  } else if (self) {
+    by_nt(yes, no, no);
+  } else {
+    by_nt(no, no, no);
+  }
+}
+
 template <typename T>
 static void launch_dec_attn_t(bool self, bool nt, const DecAttnArgs& a, dim3 grid, size_t smem, hipStream_t st) {
-  if (a.beam_nb > 0) {          // beam search: ancestry reads (self) / a clip's K/V shared by its beams (cross)
-    if (self && nt) hipLaunchKernelGGL((dec_attn_kernel<T, true, true, false, true>), grid, dim3(1024), smem, st, a);
-    else if (self) hipLaunchKernelGGL((dec_attn_kernel<T, true, false, false, true>), grid, dim3(1024), smem, st, a);
-    else if (nt) hipLaunchKernelGGL((dec_attn_kernel<T, false, true, false, true>), grid, dim3(1024), smem, st, a);
-    else hipLaunchKernelGGL((dec_attn_kernel<T, false, false, false, true>), grid, dim3(1024), smem, st, a);
-  } else if (self && a.emb) {
-    if (nt) hipLaunchKernelGGL((dec_attn_kernel<T, true, true, true>), grid, dim3(1024), smem, st, a);
-    else hipLaunchKernelGGL((dec_attn_kernel<T, true, false, true>), grid, dim3(1024), smem, st, a);
-  } else if (self) {
-    if (nt) hipLaunchKernelGGL((dec_attn_kernel<T, true, true>), grid, dim3(1024), smem, st, a);
-    else hipLaunchKernelGGL((dec_attn_kernel<T, true, false>), grid, dim3(1024), smem, st, a);
-  } else {
-    if (nt) hipLaunchKernelGGL((dec_attn_kernel<T, false, true>), grid, dim3(1024), smem, st, a);
-    else hipLaunchKernelGGL((dec_attn_kernel<T, false, false>), grid, dim3(1024), smem, st, a);
-  }
+  launch_dec_attn_form(self, nt, a, [&](auto s, auto n, auto f, auto bm) {
+    hipLaunchKernelGGL((dec_attn_kernel<T, s.value, n.value, f.value, bm.value>), grid, dim3(1024), smem, st, a);
+  });
 }
 
 // several clips per workgroup (dec_attn_mc_kernel): C = 2 or 4
@@ -1801,26 +1792,16 @@ static void launch_dec_attn_mc_t(bool self, bool nt, const DecAttnArgs& a, int n
   // one round trip, so the kernel is C dependent round trips long and two register-slot sets overlap them - on paper 14 -> ~10.5 us
   // per launch; measured on one box (tools/native_mc_sweep.py, us per step, one / two in flight): 2 x 64 clips bf16 340.6 / 338.9
   // against 351.4 / 350.9, fp32 577.2 against 591.9, 2 x 32 clips 220.4 against 226.6, 2 x 64 at S = 864 480.9 against 485.0.  One
-  // in flight.
-  const bool two_in_flight = !self && cif == 2;
-  if (a.beam_nb > 0) {          // beam search (one clip in flight whatever M2M_MC_CIF says)
-    if (self && nt) hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, true, false, C, 1, true>), grid, dim3(1024), smem, st, a, nb);
-    else if (self) hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, false, false, C, 1, true>), grid, dim3(1024), smem, st, a, nb);
-    else if (nt) hipLaunchKernelGGL((dec_attn_mc_kernel<T, false, true, false, C, 1, true>), grid, dim3(1024), smem, st, a, nb);
-    else hipLaunchKernelGGL((dec_attn_mc_kernel<T, false, false, false, C, 1, true>), grid, dim3(1024), smem, st, a, nb);
-  } else if (self && a.emb) {
-    if (nt) hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, true, true, C>), grid, dim3(1024), smem, st, a, nb);
-    else hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, false, true, C>), grid, dim3(1024), smem, st, a, nb);
-  } else if (self) {
-    if (nt) hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, true, false, C>), grid, dim3(1024), smem, st, a, nb);
-    else hipLaunchKernelGGL((dec_attn_mc_kernel<T, true, false, false, C>), grid, dim3(1024), smem, st, a, nb);
-  } else if (two_in_flight) {     // short cross streams (a clip's keys fit the prefetch window): two clips in flight
-    if (nt) hipLaunchKernelGGL((dec_attn_mc_kernel<T, false, true, false, C, 2>), grid, dim3(1024), smem, st, a, nb);
-    else hipLaunchKernelGGL((dec_attn_mc_kernel<T, false, false, false, C, 2>), grid, dim3(1024), smem, st, a, nb);
-  } else {
-    if (nt) hipLaunchKernelGGL((dec_attn_mc_kernel<T, false, true, false, C>), grid, dim3(1024), smem, st, a, nb);
-    else hipLaunchKernelGGL((dec_attn_mc_kernel<T, false, false, false, C>), grid, dim3(1024), smem, st, a, nb);
-  }
+  // in flight.  (Beam search: one clip in flight whatever M2M_MC_CIF says.)
+  launch_dec_attn_form(self, nt, a, [&](auto s, auto n, auto f, auto bm) {
+    if constexpr (!s.value && !bm.value) {     // short cross streams (a clip's keys fit the prefetch window): two clips in flight
+      if (cif == 2) {
+        hipLaunchKernelGGL((dec_attn_mc_kernel<T, false, n.value, false, C, 2>), grid, dim3(1024), smem, st, a, nb);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((dec_attn_mc_kernel<T, s.value, n.value, f.value, C, 1, bm.value>), grid, dim3(1024), smem, st, a, nb);
+  });
 }
 
 static int launch_dec_attn(int precision, bool self, bool nt, DecAttnArgs a, int B, int clips, int cif, hipStream_t st) {

@@ -17,4 +17,4 @@ q = (f"select s.kernel_name, count(*), avg(d.end-d.start), sum(d.end-d.start) fr
      f"join {ks} s on d.kernel_id=s.id group by 1 order by 4 desc limit {int(sys.argv[2]) if len(sys.argv) > 2 else 14}")
 tot = c.execute(f"select sum(end-start) from {kd}").fetchone()[0]
 for name, n, avg, s in c.execute(q):
-    print(f"{name[:78]:78s} n={n:6d} avg {avg / 1e3:8.2f} us  total {s / 1e6:8.2f} ms  {100 * s / tot:5.1f}%")
+    print(f"{name[:78]:78s} n={n:6d} avg {avg / 1e3:9.3f} us  total {s / 1e6:8.2f} ms  {100 * s / tot:5.1f}%")
