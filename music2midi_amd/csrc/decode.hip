@@ -2850,7 +2850,7 @@ int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int 
 // ============================================================ step driver ====
 static xq_t* xbuf(m2m_session* s, const DecView& v, int which);
 // the headless fold is a greedy-only form: the sampling and processed heads keep their own kernel (the step of M2M_HEADLESS=0)
-static bool headless_for(const m2m_session* s, bool forced) { return !forced && s->head_mode == HEAD_GREEDY && s->headless; }
+static bool headless_for(const m2m_session* s, bool forced) { return !forced && s->head_mode == HEAD_GREEDY && s->sw.headless; }
 // All per-clip buffers are [B][...] with the clip index outermost, so a view is a pointer offset.
 static DecHeadArgs head_args(m2m_session* s, const DecView& v, bool forced, float* logits_out, int Ld) {
   const m2m_model* m = s->m;
@@ -2918,9 +2918,9 @@ static xq_t* xbuf(m2m_session* s, const DecView& v, int which) {
 
 // Clips of one head per attention workgroup for a chain of nb clips: the multi-clip form (dec_attn_mc_kernel) from the chain sizes at
 // which the launches stop being single latency chains and become rounds of workgroups (measured: tools/native_chain_sweep.py, DESIGN
-// 4.3); s->attn_clips > 0 forces a value (M2M_DA_CLIPS, latched when the session is created; tests and A/B runs).
+// 4.3); s->sw.attn_clips > 0 forces a value (M2M_DA_CLIPS, latched when the session is created; tests and A/B runs).
 int decode_attn_clips(const m2m_session* s, int nb) {
-  if (s->attn_clips > 0) return s->attn_clips;
+  if (s->sw.attn_clips > 0) return s->sw.attn_clips;
   // same-box sweeps (tools/native_mc_sweep.py, us per step, C = 1 / 2 / 4): 2 x 16 clips, S = 864: 195 / 238 / -; 2 x 24: 264 / 266 / 363;
   // 2 x 32: 329 / 300 / 386; 2 x 64, S = 864: 595 / 522 / 512; 2 x 64, S = 190 (the reference's chunk): 446 / 383 / 362;
   // S = 190: 2 x 32: 256 / 226 / 289; 2 x 40: - / 276 / 299; 2 x 48: - / 316 / 313
@@ -2931,11 +2931,11 @@ int decode_attn_clips(const m2m_session* s, int nb) {
 // measured no different from 8 at 2 x 64 clips (365.5 / 366.3 us per step): 8 everywhere.
 int decode_ff_rows(const m2m_session* s, int nb) {
   (void)nb;
-  return s->ff_rows > 0 ? s->ff_rows : 8;
+  return s->sw.ff_rows > 0 ? s->sw.ff_rows : 8;
 }
 // hidden slices per feed-forward workgroup (dec_ff_multi_kernel from 2; M2M_DEC_FF_SLICES forces 1, 2 or 4, latched per session)
 int decode_ff_slices(const m2m_session* s, int nb) {
-  if (s->ff_slices > 0) return s->ff_slices;
+  if (s->sw.ff_slices > 0) return s->sw.ff_slices;
   // same-box sweeps (tools/native_mc_sweep.py, us per step, 1 / 2 / 4 slices): 2 x 16 clips 196 / 204 / -; 2 x 32: 301 / 292 / 312;
   // 2 x 48, S = 190: - / 313 / 326; 2 x 64 (the reference's chunk): 362 / 349-353 / 345-347
   return nb >= 56 ? 4 : (nb >= 32 ? 2 : 1);
@@ -2956,16 +2956,16 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
     // cache-resident from step to step (they are re-read every step; the rest streams past them
     // non-temporally).  B = 32: 3 of 6 layers, 271.0 -> 266.6 ms per batch.
     const double per_layer = 2.0 * s->B * m->inner * (double)s->S * (double)es;
-    const int resident = s->kv_resident_layers >= 0 ? s->kv_resident_layers : (int)(180e6 / per_layer);
+    const int resident = s->sw.kv_resident_layers >= 0 ? s->sw.kv_resident_layers : (int)(180e6 / per_layer);
     if (layer < resident) nt = false;
   }
   int clips = decode_attn_clips(s, v.nb);
-  if (self && s->attn_clips_self > 0) clips = s->attn_clips_self;      // diagnostic: another width for the self-attention launches
+  if (self && s->sw.attn_clips_self > 0) clips = s->sw.attn_clips_self;      // diagnostic: another width for the self-attention launches
   // self: A -> B (zero C); cross: B -> C (zero A)
   a.x = xbuf(s, v, self ? 0 : 1); a.x_out = xbuf(s, v, self ? 1 : 2); a.x_zero = xbuf(s, v, self ? 2 : 0);
   a.eps = g.layer_norm_eps; a.d = g.d_model;
   a.H = H; a.inner = m->inner; a.state = v.state;
-  if (skip_finished && s->finished_skip) { a.fin_skip = s->finished + v.b0; a.fin_stride = 1; }
+  if (skip_finished && s->sw.finished_skip) { a.fin_skip = s->finished + v.b0; a.fin_stride = 1; }
   else { a.fin_skip = &v.state->zero; a.fin_stride = 0; }
   // beam search: the view's rows are clips x beam_nb beams (the view starts at a clip boundary)
   const bool beam = (s->head_mode & HEAD_BEAM) && s->beam_nb > 0;
@@ -2985,7 +2985,7 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
     a.Vc = (unsigned char*)s->self_v + off;
     a.kv_stride = s->max_dec; a.n_keys = 0; a.self_len_override = self_len;
     a.bias = s->dec_bias_tab; a.bias_stride = s->max_dec;
-    return launch_dec_attn(m->precision, true, nt, a, v.nb, clips, s->mc_cif, st);
+    return launch_dec_attn(m->precision, true, nt, a, v.nb, clips, s->sw.mc_cif, st);
   }
   // cross K/V: [L][2][B][H][S][64] with B, S = the encoded problem
   const size_t per = (size_t)s->B * H * s->S * DK;
@@ -2994,7 +2994,7 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
   a.Kc = (unsigned char*)s->cross_kv + (((size_t)layer * 2 + 0) * per + voff) * es;
   a.Vc = (unsigned char*)s->cross_kv + (((size_t)layer * 2 + 1) * per + voff) * es;
   a.kv_stride = s->S; a.n_keys = s->S; a.self_len_override = 0; a.bias = nullptr; a.bias_stride = 0;
-  return launch_dec_attn(m->precision, false, nt, a, v.nb, clips, s->mc_cif, st);
+  return launch_dec_attn(m->precision, false, nt, a, v.nb, clips, s->sw.mc_cif, st);
 }
 
 int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* logits_out, int Ld, hipStream_t st) {

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.h"
+#include "env.h"
 
 #include <vector>
 
@@ -164,6 +165,16 @@ struct BeamRow {            // row c * nb + h: running beam h of clip c, and hyp
   int pad_;
 };
 
+// The host side of the five parameter blocks: one pinned allocation of the session.  An export fills the blocks its head reads,
+// decode_call copies each of those to its device block in the workspace (sample_dev, proc_dev, ...).
+struct CallParams {
+  SampleParams sample;
+  ProcessParams proc;
+  ScoreParams score;
+  GrammarParams gram;       // written by decode_call from the call's block
+  BeamParams beam;
+};
+
 }  // namespace m2m
 
 namespace m2m {
@@ -190,6 +201,23 @@ struct EncSwitchScope {
   ~EncSwitchScope() { tl_enc_switches = prev; }
 };
 inline const EncSwitches& enc_switches_now() { return tl_enc_switches ? *tl_enc_switches : process_enc_switches(); }
+
+// Environment switches of a session.  CONSTRUCTING one reads the environment - every member's initialiser is the one read of its
+// switch - and m2m_session holds one (sw): a session latches them when it is created and keeps the kernel forms it started with
+// (its graphs bake them in); m2m_session_create refuses the values outside a switch's range.
+struct SessionSwitches {
+  static int one_of_124(int c) { return (c == 1 || c == 2 || c == 4) ? c : 0; }
+  static int zero_is_1(int c) { return c == 0 ? 1 : c; }
+  EncSwitches enc = read_enc_switches();                            // the encoder-side kernel families (above)
+  int attn_clips = env_int("M2M_DA_CLIPS", 0);                      // decode attention: clips per workgroup (0: by chain size)
+  int attn_clips_self = one_of_124(env_int("M2M_DA_CLIPS_SELF", 0));    // (diagnostic) clips per self-attention workgroup when it should differ from the cross kernels
+  int ff_rows = env_int("M2M_DEC_FF_ROWS", 0);                      // decode feed-forward: residual rows per workgroup (0: by chain size)
+  int ff_slices = env_int("M2M_DEC_FF_SLICES", 0);                  // decode feed-forward: hidden slices per workgroup (0: by chain size)
+  int mc_cif = zero_is_1(env_int("M2M_MC_CIF", 0));                 // multi-clip cross-attention: clips in flight (diagnostic: 2; 0 or unset: 1, the product)
+  bool headless = env_on("M2M_HEADLESS");                           // 0 keeps dec_head_kernel in the greedy loop (the round-1 step: 20 kernels); default: folded away (19 kernels)
+  bool finished_skip = env_on("M2M_FINISHED_SKIP");                 // 0: finished rows keep streaming their K/V (the behaviour before round 4; bench.py's ragged_eos "before" leg)
+  int kv_resident_layers = env_int("M2M_KV_RESIDENT_LAYERS", -1);   // layers of cross K/V kept cache-resident when the rest streams non-temporally (-1: by a 180 MB budget)
+};
 
 constexpr int MAX_GROUPS = 8;
 
@@ -244,31 +272,19 @@ struct m2m_session {
   int64_t* forced_ids;     // [B, max_dec]
   // current problem
   int B = 0, S = 0;
-  m2m::EncSwitches enc_sw;  // encoder-side kernel switches, latched at creation
-  int attn_clips = 0;      // decode attention: clips per workgroup forced by M2M_DA_CLIPS when the session was created (0: by chain size)
-  int attn_clips_self = 0; // M2M_DA_CLIPS_SELF (diagnostic): clips per self-attention workgroup when it should differ from the cross kernels
-  int ff_rows = 0;         // decode feed-forward: residual rows per workgroup forced by M2M_DEC_FF_ROWS (0: by chain size)
-  int ff_slices = 0;       // decode feed-forward: hidden slices per workgroup forced by M2M_DEC_FF_SLICES (0: by chain size)
-  int mc_cif = 1;          // multi-clip cross-attention: clips in flight, M2M_MC_CIF (diagnostic: 2; 0 or unset: 1, the product)
-  bool headless = true;    // M2M_HEADLESS=0 keeps dec_head_kernel in the greedy loop (the round-1 step: 20 kernels); default: folded away (19 kernels)
-  bool finished_skip = true;   // M2M_FINISHED_SKIP=0: finished rows keep streaming their K/V (the behaviour before round 4; bench.py's ragged_eos "before" leg)
-  int kv_resident_layers = -1; // M2M_KV_RESIDENT_LAYERS: layers of cross K/V kept cache-resident when the rest streams non-temporally (-1: by a 180 MB budget)
+  m2m::SessionSwitches sw;  // every switch of the session, latched at creation
   int repacks = 0, rows_moved = 0;   // live-row re-packings / rows moved by them in the last m2m_generate_greedy / _sample
   int head_mode = 0;       // head form of the free-running decode step: 0 greedy (arg-max), 1 sampling, 2 beam, | 4 processed, | 8 scored
                            // (set for the length of a call)
-  m2m::SampleParams* sample_dev = nullptr;    // [1] in the workspace
-  m2m::SampleParams* sample_host = nullptr;   // pinned staging copy
-  m2m::ProcessParams* proc_dev = nullptr;     // [1] in the workspace
-  m2m::ProcessParams* proc_host = nullptr;    // pinned staging copy
-  m2m::ScoreParams* score_dev = nullptr;      // [1] in the workspace
-  m2m::ScoreParams* score_host = nullptr;     // pinned staging copy
-  m2m::GrammarParams* gram_dev = nullptr;     // [1] in the workspace
-  m2m::GrammarParams* gram_host = nullptr;    // pinned staging copy, written by decode_call from the call's block
+  m2m::CallParams* call_host = nullptr;       // pinned staging copy of the five parameter blocks; their device blocks, [1] each in the workspace:
+  m2m::SampleParams* sample_dev = nullptr;
+  m2m::ProcessParams* proc_dev = nullptr;
+  m2m::ScoreParams* score_dev = nullptr;
+  m2m::GrammarParams* gram_dev = nullptr;
   m2m::GrammarState* gram_state = nullptr;    // [max_batch] in the workspace, by clip (by row in a processed beam call)
   // beam search (m2m_generate_beam): rows = encoded clips x beam_nb; every buffer below is in the workspace
   int beam_nb = 0;                            // beams per clip during a beam call, 0 otherwise
   m2m::BeamParams* beam_dev = nullptr;        // [1]
-  m2m::BeamParams* beam_host = nullptr;       // pinned staging copy
   m2m::BeamClip* beam_clip = nullptr;         // [max_batch]
   m2m::BeamRow* beam_row = nullptr;           // [max_batch]
   unsigned char* anc = nullptr;               // [2][max_batch][max_dec] ancestries (slot within the clip of every cached position)

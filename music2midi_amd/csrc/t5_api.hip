@@ -1,5 +1,6 @@
 // C ABI of the T5 encoder/decoder path: model (repacked weights), session (workspace +
 // captured decode-step graph), encode, greedy generate, teacher-forced decode, bench hooks.
+#include "carver.h"
 #include "env.h"
 #include "t5.h"
 
@@ -7,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 using namespace m2m;
@@ -64,85 +66,76 @@ extern "C" int m2m_model_create(const m2m_t5_geometry* geom, const m2m_t5_weight
   const size_t es = precision == M2M_PREC_BF16 ? 2 : 4;
   const int vocab_pad = ceil_div(V, 16) * 16;
 
-  // ---- carve one blob ----
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { int64_t o = off; off = align_up(off + bytes, 256); return o; };
-  struct EncOff { int64_t ln0, wqkv, wo, ln1, wi, wo_ff; };
-  struct DecOff { int64_t ln0, wqkv, wo, ln1, wcq, wco, ln2, wi, wo_ff; };
-  std::vector<EncOff> eo(Le);
-  std::vector<DecOff> dof(Ld);
-  for (int l = 0; l < Le; ++l) {
-    eo[l].ln0 = take(d * 4); eo[l].wqkv = take((int64_t)3 * inner * d * es); eo[l].wo = take((int64_t)d * inner * es);
-    eo[l].ln1 = take(d * 4); eo[l].wi = take((int64_t)2 * dff * d * es); eo[l].wo_ff = take((int64_t)d * dff * es);
-  }
-  for (int l = 0; l < Ld; ++l) {
-    dof[l].ln0 = take(d * 4); dof[l].wqkv = take((int64_t)3 * inner * d * es); dof[l].wo = take((int64_t)d * inner * es);
-    dof[l].ln1 = take(d * 4); dof[l].wcq = take((int64_t)inner * d * es); dof[l].wco = take((int64_t)d * inner * es);
-    dof[l].ln2 = take(d * 4); dof[l].wi = take((int64_t)2 * dff * d * es); dof[l].wo_ff = take((int64_t)d * dff * es);
-  }
-  const int64_t o_eln = take(d * 4), o_dln = take(d * 4);
-  const int64_t o_shared = take((int64_t)V * d * 4);
-  const int64_t o_head = take((int64_t)vocab_pad * d * es);
-  const int64_t o_ckv = take((int64_t)Ld * 2 * inner * d * es);
-
+  // ---- one blob: every packed tensor is declared once, in layout order ----
   m2m_model* m = new m2m_model();
-  m->g = g; m->precision = precision; m->inner = inner; m->vocab_pad = vocab_pad; m->esize = es; m->blob_bytes = off;
-  hipError_t e = hipMalloc(&m->blob, (size_t)off);
+  m->g = g; m->precision = precision; m->inner = inner; m->vocab_pad = vocab_pad; m->esize = es;
+  m->enc.resize(Le); m->dec.resize(Ld);
+  Carver c;
+  auto F = [&](const float*& member, int64_t elems) { c.take(member, elems * 4); };
+  auto T = [&](const void*& member, int64_t elems) { c.take(member, elems * es); };
+  for (EncLayerPacked& L : m->enc) {
+    F(L.ln0, d); T(L.wqkv, (int64_t)3 * inner * d); T(L.wo, (int64_t)d * inner);
+    F(L.ln1, d); T(L.wi, (int64_t)2 * dff * d); T(L.wo_ff, (int64_t)d * dff);
+  }
+  for (DecLayerPacked& L : m->dec) {
+    F(L.ln0, d); T(L.wqkv, (int64_t)3 * inner * d); T(L.wo, (int64_t)d * inner);
+    F(L.ln1, d); T(L.wcq, (int64_t)inner * d); T(L.wco, (int64_t)d * inner);
+    F(L.ln2, d); T(L.wi, (int64_t)2 * dff * d); T(L.wo_ff, (int64_t)d * dff);
+  }
+  F(m->enc_final_ln, d); F(m->dec_final_ln, d);
+  F(m->shared, (int64_t)V * d);
+  T(m->lm_head, (int64_t)vocab_pad * d);
+  T(m->wckv, (int64_t)Ld * 2 * inner * d);
+  m->blob_bytes = c.off;
+  hipError_t e = hipMalloc(&m->blob, (size_t)c.off);
   if (e != hipSuccess) {
-    set_error("m2m_model_create: hipMalloc(%lld) failed: %s", (long long)off, hipGetErrorString(e));
+    set_error("m2m_model_create: hipMalloc(%lld) failed: %s", (long long)c.off, hipGetErrorString(e));
     delete m;
     return M2M_ERR_NOMEM;
   }
-  unsigned char* base = (unsigned char*)m->blob;
+  c.bind((unsigned char*)m->blob);
   int rc = M2M_OK;
   // the alignment gaps between the packed tensors are part of what m2m_model_checksum covers: they must not be allocator garbage
-  if (hipMemsetAsync(m->blob, 0, (size_t)off, st) != hipSuccess) { set_error("m2m_model_create: hipMemsetAsync failed"); rc = M2M_ERR_HIP; }
-  auto conv = [&](const float* src, int64_t o, int64_t n) {
+  if (hipMemsetAsync(m->blob, 0, (size_t)c.off, st) != hipSuccess) { set_error("m2m_model_create: hipMemsetAsync failed"); rc = M2M_ERR_HIP; }
+  // the blob is written through the members: `part` is the matrix's place in a declaration that packs several (q | k | v, ck | cv)
+  auto at = [&](const void* member, int64_t part = 0) { return (unsigned char*)const_cast<void*>(member) + part * inner * d * (int64_t)es; };
+  auto conv = [&](const float* src, void* dst, int64_t n) {
     if (rc == M2M_OK && !src) { set_error("m2m_model_create: null layer weight pointer"); rc = M2M_ERR_INVALID; }
-    if (rc == M2M_OK) rc = launch_convert(precision, src, base + o, n, st);
+    if (rc == M2M_OK) rc = launch_convert(precision, src, dst, n, st);
   };
-  auto copyf = [&](const float* src, int64_t o, int64_t n) {
+  auto copyf = [&](const float* src, const float* dst, int64_t n) {
     if (rc == M2M_OK && !src) { set_error("m2m_model_create: null layer weight pointer"); rc = M2M_ERR_INVALID; }
-    if (rc == M2M_OK) rc = launch_copy_f32(src, (float*)(base + o), n, st);
+    if (rc == M2M_OK) rc = launch_copy_f32(src, const_cast<float*>(dst), n, st);
   };
-  m->enc.resize(Le); m->dec.resize(Ld);
+  auto interleave = [&](const float* wi0, const float* wi1, const void* dst, int half) {
+    if (rc == M2M_OK && !(wi0 && wi1)) { set_error("m2m_model_create: null wi pointer"); rc = M2M_ERR_INVALID; }
+    if (rc == M2M_OK) rc = launch_interleave(precision, wi0, wi1, at(dst), dff, d, half, st);
+  };
   for (int l = 0; l < Le && rc == M2M_OK; ++l) {
     const m2m_enc_layer_weights& s = w->enc[l];
-    copyf(s.ln0, eo[l].ln0, d); copyf(s.ln1, eo[l].ln1, d);
-    conv(s.q, eo[l].wqkv, (int64_t)inner * d);
-    conv(s.k, eo[l].wqkv + (int64_t)inner * d * es, (int64_t)inner * d);
-    conv(s.v, eo[l].wqkv + (int64_t)2 * inner * d * es, (int64_t)inner * d);
-    conv(s.o, eo[l].wo, (int64_t)d * inner);
-    if (rc == M2M_OK && !(s.wi0 && s.wi1)) { set_error("m2m_model_create: null wi pointer"); rc = M2M_ERR_INVALID; }
-    if (rc == M2M_OK) rc = launch_interleave(precision, s.wi0, s.wi1, base + eo[l].wi, dff, d, 32, st);
-    conv(s.wo, eo[l].wo_ff, (int64_t)d * dff);
-    m->enc[l] = {(const float*)(base + eo[l].ln0), base + eo[l].wqkv, base + eo[l].wo, (const float*)(base + eo[l].ln1),
-                 base + eo[l].wi, base + eo[l].wo_ff};
+    const EncLayerPacked& L = m->enc[l];
+    copyf(s.ln0, L.ln0, d); copyf(s.ln1, L.ln1, d);
+    conv(s.q, at(L.wqkv, 0), (int64_t)inner * d); conv(s.k, at(L.wqkv, 1), (int64_t)inner * d); conv(s.v, at(L.wqkv, 2), (int64_t)inner * d);
+    conv(s.o, at(L.wo), (int64_t)d * inner);
+    interleave(s.wi0, s.wi1, L.wi, 32);
+    conv(s.wo, at(L.wo_ff), (int64_t)d * dff);
   }
   for (int l = 0; l < Ld && rc == M2M_OK; ++l) {
     const m2m_dec_layer_weights& s = w->dec[l];
-    copyf(s.ln0, dof[l].ln0, d); copyf(s.ln1, dof[l].ln1, d); copyf(s.ln2, dof[l].ln2, d);
-    conv(s.q, dof[l].wqkv, (int64_t)inner * d);
-    conv(s.k, dof[l].wqkv + (int64_t)inner * d * es, (int64_t)inner * d);
-    conv(s.v, dof[l].wqkv + (int64_t)2 * inner * d * es, (int64_t)inner * d);
-    conv(s.o, dof[l].wo, (int64_t)d * inner);
-    conv(s.cq, dof[l].wcq, (int64_t)inner * d);
-    conv(s.co, dof[l].wco, (int64_t)d * inner);
-    if (rc == M2M_OK && !(s.wi0 && s.wi1)) { set_error("m2m_model_create: null wi pointer"); rc = M2M_ERR_INVALID; }
-    if (rc == M2M_OK) rc = launch_interleave(precision, s.wi0, s.wi1, base + dof[l].wi, dff, d, 8, st);
-    conv(s.wo, dof[l].wo_ff, (int64_t)d * dff);
-    conv(s.ck, o_ckv + (int64_t)(l * 2 + 0) * inner * d * es, (int64_t)inner * d);
-    conv(s.cv, o_ckv + (int64_t)(l * 2 + 1) * inner * d * es, (int64_t)inner * d);
-    m->dec[l] = {(const float*)(base + dof[l].ln0), base + dof[l].wqkv, base + dof[l].wo,
-                 (const float*)(base + dof[l].ln1), base + dof[l].wcq, base + dof[l].wco,
-                 (const float*)(base + dof[l].ln2), base + dof[l].wi, base + dof[l].wo_ff};
+    const DecLayerPacked& L = m->dec[l];
+    copyf(s.ln0, L.ln0, d); copyf(s.ln1, L.ln1, d); copyf(s.ln2, L.ln2, d);
+    conv(s.q, at(L.wqkv, 0), (int64_t)inner * d); conv(s.k, at(L.wqkv, 1), (int64_t)inner * d); conv(s.v, at(L.wqkv, 2), (int64_t)inner * d);
+    conv(s.o, at(L.wo), (int64_t)d * inner);
+    conv(s.cq, at(L.wcq), (int64_t)inner * d);
+    conv(s.co, at(L.wco), (int64_t)d * inner);
+    interleave(s.wi0, s.wi1, L.wi, 8);
+    conv(s.wo, at(L.wo_ff), (int64_t)d * dff);
+    conv(s.ck, at(m->wckv, l * 2 + 0), (int64_t)inner * d); conv(s.cv, at(m->wckv, l * 2 + 1), (int64_t)inner * d);
   }
-  copyf(w->enc_final_ln, o_eln, d); copyf(w->dec_final_ln, o_dln, d);
-  copyf(w->shared, o_shared, (int64_t)V * d);
-  if (rc == M2M_OK) rc = launch_fill_zero(base + o_head, (int64_t)vocab_pad * d * es, st);
-  conv(w->lm_head, o_head, (int64_t)V * d);
-  m->enc_final_ln = (const float*)(base + o_eln); m->dec_final_ln = (const float*)(base + o_dln);
-  m->shared = (const float*)(base + o_shared); m->lm_head = base + o_head; m->wckv = base + o_ckv;
+  copyf(w->enc_final_ln, m->enc_final_ln, d); copyf(w->dec_final_ln, m->dec_final_ln, d);
+  copyf(w->shared, m->shared, (int64_t)V * d);
+  if (rc == M2M_OK) rc = launch_fill_zero(at(m->lm_head), (int64_t)vocab_pad * d * es, st);
+  conv(w->lm_head, at(m->lm_head), (int64_t)V * d);
   m->enc_rel_bias_host.resize((size_t)g.num_buckets * g.num_heads);
   m->dec_rel_bias_host.resize((size_t)g.num_buckets * g.num_heads);
   hipError_t he = hipSuccess;
@@ -187,116 +180,65 @@ extern "C" int m2m_model_checksum(const m2m_model* m, uint64_t* out_host, void* 
 
 // ---------------------------------------------------------------- session ---
 namespace {
-struct WsLayout {
-  int64_t x_enc, h_enc, qkv_enc, vt_enc, attn_enc, mid_enc, enc_bias, dec_bias, dec_bias_full, cross_vt, cross_kv, self_k, self_v;
-  int64_t x_dec, logits, tokens, finished, tok_row, keys, state, forced, sample, proc, beam, beam_clip, beam_row, anc, hyp_tok, score, gram, gram_state, total;
-};
-
-WsLayout ws_layout(const m2m_model* m, int B, int S, int L) {
+// The session's workspace: every buffer declared once, on its member, in layout order (sizes from s->m and the session's maxima).
+void carve_workspace(m2m_session* s, Carver& c) {
+  const m2m_model* m = s->m;
   const m2m_t5_geometry& g = m->g;
+  const int B = s->max_batch, S = s->max_enc, L = s->max_dec;
   // the activation buffers serve the encoder (S rows per clip) and the batched teacher-forced decoder pass (L rows)
   const int64_t es = (int64_t)m->esize, M = (int64_t)B * S, Ma = (int64_t)B * (S > L ? S : L), Bp = (int64_t)ceil_div(B, 32) * 32;
   const int64_t Spa = (int64_t)ceil_div(S > L ? S : L, 64) * 64;
-  WsLayout w{};
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { int64_t o = off; off = align_up(off + bytes, 256); return o; };
-  w.x_enc = take(Ma * g.d_model * 4);
-  w.h_enc = take(Ma * g.d_model * es);
-  w.qkv_enc = take(3 * Ma * m->inner * es);
-  w.vt_enc = take((int64_t)B * m->inner * Spa * es);
-  w.attn_enc = take(Ma * m->inner * es);
-  w.mid_enc = take(Ma * g.d_ff * es);
-  w.enc_bias = take((int64_t)g.num_heads * (2 * S - 1) * 4);
-  w.dec_bias = take((int64_t)g.num_heads * L * 4);
-  w.dec_bias_full = take((int64_t)g.num_heads * (2 * L - 1) * 4);
-  w.cross_vt = take((int64_t)B * m->inner * (ceil_div(S, 64) * 64) * es);
-  w.cross_kv = take((int64_t)g.num_decoder_layers * 2 * M * m->inner * es);
-  w.self_k = take((int64_t)g.num_decoder_layers * B * m->inner * L * es);
-  w.self_v = take((int64_t)g.num_decoder_layers * B * m->inner * L * es);
-  w.x_dec = take(3 * Bp * g.d_model * 8);   // int64 fixed-point residual stream, 3 rotating buffers
-  w.logits = take(Bp * m->vocab_pad * 4);
-  w.tokens = take((int64_t)B * L * 8);
-  w.finished = take((int64_t)B * 4);
-  w.tok_row = take((int64_t)B * 4);
-  w.keys = take((int64_t)B * 8);
-  w.state = take(sizeof(DecState) * MAX_GROUPS);
-  w.forced = take((int64_t)B * L * 8);
-  w.sample = take(sizeof(SampleParams));
-  w.proc = take(sizeof(ProcessParams));
-  w.beam = take(sizeof(BeamParams));
-  w.beam_clip = take((int64_t)B * sizeof(BeamClip));
-  w.beam_row = take((int64_t)B * sizeof(BeamRow));
-  w.anc = take(2 * (int64_t)B * L);
-  w.hyp_tok = take((int64_t)B * L * 8);
-  w.score = take(sizeof(ScoreParams));
-  w.gram = take(sizeof(GrammarParams));
-  w.gram_state = take((int64_t)B * sizeof(GrammarState));
-  w.total = off;
-  return w;
-}
-}  // namespace
-
-extern "C" int64_t m2m_session_workspace_bytes(const m2m_model* m, int max_batch, int max_enc_len, int max_dec_len) {
-  if (!m || max_batch < 1 || max_enc_len < 1 || max_dec_len < 1) {
-    set_error("m2m_session_workspace_bytes: bad argument");
-    return M2M_ERR_INVALID;
-  }
-  return ws_layout(m, max_batch, max_enc_len, max_dec_len).total;
+  c.take(s->x_enc, Ma * g.d_model * 4);
+  c.take(s->h_enc, Ma * g.d_model * es);
+  c.take(s->qkv_enc, 3 * Ma * m->inner * es);
+  c.take(s->vt_enc, (int64_t)B * m->inner * Spa * es);
+  c.take(s->attn_enc, Ma * m->inner * es);
+  c.take(s->mid_enc, Ma * g.d_ff * es);
+  c.take(s->enc_bias_tab, (int64_t)g.num_heads * (2 * S - 1) * 4);
+  c.take(s->dec_bias_tab, (int64_t)g.num_heads * L * 4);
+  c.take(s->dec_bias_full_tab, (int64_t)g.num_heads * (2 * L - 1) * 4);
+  c.take(s->cross_vt, (int64_t)B * m->inner * (ceil_div(S, 64) * 64) * es);
+  c.take(s->cross_kv, (int64_t)g.num_decoder_layers * 2 * M * m->inner * es);
+  c.take(s->self_k, (int64_t)g.num_decoder_layers * B * m->inner * L * es);
+  c.take(s->self_v, (int64_t)g.num_decoder_layers * B * m->inner * L * es);
+  c.take(s->x_dec, 3 * Bp * g.d_model * 8);   // int64 fixed-point residual stream, 3 rotating buffers
+  c.take(s->logits, Bp * m->vocab_pad * 4);
+  c.take(s->tokens, (int64_t)B * L * 8);
+  c.take(s->finished, (int64_t)B * 4);
+  c.take(s->tok_row, (int64_t)B * 4);
+  c.take(s->keys, (int64_t)B * 8);
+  c.take(s->states, sizeof(DecState) * MAX_GROUPS);
+  c.take(s->forced_ids, (int64_t)B * L * 8);
+  c.take(s->sample_dev, sizeof(SampleParams));
+  c.take(s->proc_dev, sizeof(ProcessParams));
+  c.take(s->beam_dev, sizeof(BeamParams));
+  c.take(s->beam_clip, (int64_t)B * sizeof(BeamClip));
+  c.take(s->beam_row, (int64_t)B * sizeof(BeamRow));
+  c.take(s->anc, 2 * (int64_t)B * L);
+  c.take(s->hyp_tok, (int64_t)B * L * 8);
+  c.take(s->score_dev, sizeof(ScoreParams));
+  c.take(s->gram_dev, sizeof(GrammarParams));
+  c.take(s->gram_state, (int64_t)B * sizeof(GrammarState));
 }
 
-extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc_len, int max_dec_len,
-                                  void* workspace_dev, int64_t workspace_bytes, m2m_session** out) {
-  M2M_REQUIRE(m && workspace_dev && out, "m2m_session_create: null argument");
-  M2M_REQUIRE(max_batch >= 1 && max_enc_len >= 1 && max_dec_len >= 1, "m2m_session_create: bad geometry");
-  M2M_REQUIRE(((uintptr_t)workspace_dev & 255) == 0, "m2m_session_create: workspace must be 256-byte aligned");
-  const WsLayout w = ws_layout(m, max_batch, max_enc_len, max_dec_len);
-  if (workspace_bytes < w.total) {
-    set_error("m2m_session_create: workspace %lld bytes < required %lld", (long long)workspace_bytes, (long long)w.total);
-    return M2M_ERR_NOMEM;
-  }
-  M2M_REQUIRE((size_t)(2 * max_enc_len - 1) * 4 + 40 * 1024 <= 150 * 1024,
-              "m2m_session_create: max_enc_len=%d too long (attention bias table must fit LDS)", max_enc_len);
-  M2M_REQUIRE((size_t)max_enc_len * 4 <= 60 * 1024 && (size_t)max_dec_len * 4 <= 60 * 1024,
-              "m2m_session_create: sequence too long for the decode attention score buffer");
-  // switches of the decode path are read ONCE per session (graphs bake them in; the environment is not safe against a concurrent setenv)
-  const int da_clips = env_int("M2M_DA_CLIPS", 0);
-  M2M_REQUIRE(da_clips == 0 || da_clips == 1 || da_clips == 2 || da_clips == 4,
-              "M2M_DA_CLIPS=%d: clips per decode-attention workgroup must be 0 (by chain size), 1, 2 or 4", da_clips);
-  const int ff_rows = env_int("M2M_DEC_FF_ROWS", 0);
-  M2M_REQUIRE(ff_rows == 0 || ff_rows == 8 || ff_rows == 16, "M2M_DEC_FF_ROWS=%d: rows per decode feed-forward workgroup must be 0 (by chain size), 8 or 16", ff_rows);
-  const int ff_slices = env_int("M2M_DEC_FF_SLICES", 0);
-  M2M_REQUIRE(ff_slices == 0 || ff_slices == 1 || ff_slices == 2 || ff_slices == 4,
-              "M2M_DEC_FF_SLICES=%d: hidden slices per decode feed-forward workgroup must be 0 (by chain size), 1, 2 or 4", ff_slices);
-  const int mc_cif = env_int("M2M_MC_CIF", 0);
-  M2M_REQUIRE(mc_cif == 0 || mc_cif == 1 || mc_cif == 2,
-              "M2M_MC_CIF=%d: clips in flight in the multi-clip cross-attention must be 0 (default: 1), 1 or 2", mc_cif);
-  m2m_session* s = new m2m_session();
-  s->m = m; s->max_batch = max_batch; s->max_enc = max_enc_len; s->max_dec = max_dec_len;
-  s->ws = (unsigned char*)workspace_dev; s->ws_bytes = workspace_bytes;
-  s->attn_clips = da_clips; s->ff_rows = ff_rows; s->ff_slices = ff_slices; s->mc_cif = mc_cif == 2 ? 2 : 1;
-  s->enc_sw = read_enc_switches();
-  { const int c = env_int("M2M_DA_CLIPS_SELF", 0); s->attn_clips_self = (c == 1 || c == 2 || c == 4) ? c : 0; }
-  s->headless = env_on("M2M_HEADLESS");
-  s->finished_skip = env_on("M2M_FINISHED_SKIP");
-  s->kv_resident_layers = env_int("M2M_KV_RESIDENT_LAYERS", -1);
-  unsigned char* b = s->ws;
-  s->x_enc = (float*)(b + w.x_enc); s->h_enc = b + w.h_enc; s->qkv_enc = b + w.qkv_enc; s->vt_enc = b + w.vt_enc; s->attn_enc = b + w.attn_enc;
-  s->mid_enc = b + w.mid_enc; s->enc_bias_tab = (float*)(b + w.enc_bias); s->dec_bias_tab = (float*)(b + w.dec_bias);
-  s->cross_kv = b + w.cross_kv; s->self_k = b + w.self_k; s->self_v = b + w.self_v;
-  s->dec_bias_full_tab = (float*)(b + w.dec_bias_full); s->cross_vt = b + w.cross_vt;
-  s->x_dec = (b + w.x_dec);
-  s->logits = (float*)(b + w.logits); s->tokens = (int64_t*)(b + w.tokens);
-  s->finished = (int*)(b + w.finished); s->tok_row = (int*)(b + w.tok_row); s->keys = (unsigned long long*)(b + w.keys); s->states = (DecState*)(b + w.state); s->forced_ids = (int64_t*)(b + w.forced);
-  s->sample_dev = (SampleParams*)(b + w.sample);
-  s->proc_dev = (ProcessParams*)(b + w.proc);
-  s->beam_dev = (BeamParams*)(b + w.beam); s->beam_clip = (BeamClip*)(b + w.beam_clip); s->beam_row = (BeamRow*)(b + w.beam_row);
-  s->anc = b + w.anc; s->hyp_tok = (int64_t*)(b + w.hyp_tok);
-  s->score_dev = (ScoreParams*)(b + w.score);
-  s->gram_dev = (GrammarParams*)(b + w.gram); s->gram_state = (GrammarState*)(b + w.gram_state);
+// a switch outside its range refuses the session
+int check_switches(const SessionSwitches& sw) {
+  M2M_REQUIRE(sw.attn_clips == 0 || sw.attn_clips == 1 || sw.attn_clips == 2 || sw.attn_clips == 4,
+              "M2M_DA_CLIPS=%d: clips per decode-attention workgroup must be 0 (by chain size), 1, 2 or 4", sw.attn_clips);
+  M2M_REQUIRE(sw.ff_rows == 0 || sw.ff_rows == 8 || sw.ff_rows == 16,
+              "M2M_DEC_FF_ROWS=%d: rows per decode feed-forward workgroup must be 0 (by chain size), 8 or 16", sw.ff_rows);
+  M2M_REQUIRE(sw.ff_slices == 0 || sw.ff_slices == 1 || sw.ff_slices == 2 || sw.ff_slices == 4,
+              "M2M_DEC_FF_SLICES=%d: hidden slices per decode feed-forward workgroup must be 0 (by chain size), 1, 2 or 4", sw.ff_slices);
+  M2M_REQUIRE(sw.mc_cif == 1 || sw.mc_cif == 2,
+              "M2M_MC_CIF=%d: clips in flight in the multi-clip cross-attention must be 0 (default: 1), 1 or 2", sw.mc_cif);
+  return M2M_OK;
+}
 
-  // relative-position bias tables (fp32), built on the host from the bucket function
+// relative-position bias tables (fp32), built on the host from the bucket function, and how far out each becomes constant
+hipError_t upload_bias_tables(m2m_session* s) {
+  const m2m_model* m = s->m;
   const m2m_t5_geometry& g = m->g;
-  const int H = g.num_heads, S = max_enc_len, L = max_dec_len;
+  const int H = g.num_heads, S = s->max_enc, L = s->max_dec;
   std::vector<float> et((size_t)H * (2 * S - 1)), dt((size_t)H * L);
   for (int rel = -(S - 1); rel <= S - 1; ++rel) {
     const int bk = m2m_rel_bucket(rel, 1, g.num_buckets, g.max_distance);
@@ -324,14 +266,50 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   hipError_t e = hipMemcpy(s->enc_bias_tab, et.data(), et.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(s->dec_bias_tab, dt.data(), dt.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(s->dec_bias_full_tab, df.data(), df.size() * 4, hipMemcpyHostToDevice);
+  return e;
+}
+}  // namespace
+
+extern "C" int64_t m2m_session_workspace_bytes(const m2m_model* m, int max_batch, int max_enc_len, int max_dec_len) {
+  if (!m || max_batch < 1 || max_enc_len < 1 || max_dec_len < 1) {
+    set_error("m2m_session_workspace_bytes: bad argument");
+    return M2M_ERR_INVALID;
+  }
+  m2m_session scratch;                     // sized, never bound (no size depends on a switch)
+  scratch.m = m; scratch.max_batch = max_batch; scratch.max_enc = max_enc_len; scratch.max_dec = max_dec_len;
+  Carver c;
+  carve_workspace(&scratch, c);
+  return c.off;
+}
+
+// check, latch, carve, bias tables, streams
+extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc_len, int max_dec_len,
+                                  void* workspace_dev, int64_t workspace_bytes, m2m_session** out) {
+  M2M_REQUIRE(m && workspace_dev && out, "m2m_session_create: null argument");
+  M2M_REQUIRE(max_batch >= 1 && max_enc_len >= 1 && max_dec_len >= 1, "m2m_session_create: bad geometry");
+  M2M_REQUIRE(((uintptr_t)workspace_dev & 255) == 0, "m2m_session_create: workspace must be 256-byte aligned");
+  // the switches are read ONCE per session, here, by the construction of its SessionSwitches; a refusal below frees the session
+  std::unique_ptr<m2m_session, void (*)(m2m_session*)> s(new m2m_session(), m2m_session_destroy);
+  s->m = m; s->max_batch = max_batch; s->max_enc = max_enc_len; s->max_dec = max_dec_len;
+  s->ws = (unsigned char*)workspace_dev; s->ws_bytes = workspace_bytes;
+  Carver c;
+  carve_workspace(s.get(), c);
+  if (workspace_bytes < c.off) {
+    set_error("m2m_session_create: workspace %lld bytes < required %lld", (long long)workspace_bytes, (long long)c.off);
+    return M2M_ERR_NOMEM;
+  }
+  M2M_REQUIRE((size_t)(2 * max_enc_len - 1) * 4 + 40 * 1024 <= 150 * 1024,
+              "m2m_session_create: max_enc_len=%d too long (attention bias table must fit LDS)", max_enc_len);
+  M2M_REQUIRE((size_t)max_enc_len * 4 <= 60 * 1024 && (size_t)max_dec_len * 4 <= 60 * 1024,
+              "m2m_session_create: sequence too long for the decode attention score buffer");
+  if (const int rc = check_switches(s->sw)) return rc;
+  c.bind(s->ws);
+
+  hipError_t e = upload_bias_tables(s.get());
   if (e == hipSuccess) e = hipMemset(s->states, 0, sizeof(DecState) * MAX_GROUPS);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s->sample_host, sizeof(SampleParams), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s->proc_host, sizeof(ProcessParams), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s->beam_host, sizeof(BeamParams), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s->score_host, sizeof(ScoreParams), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s->gram_host, sizeof(GrammarParams), hipHostMallocDefault);
-  if (e == hipSuccess) *s->gram_host = GrammarParams{};
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s->call_host, sizeof(CallParams), hipHostMallocDefault);
+  if (e == hipSuccess) s->call_host->gram = GrammarParams{};
   for (int i = 0; i < MAX_GROUPS && e == hipSuccess; ++i) {
     DecGroup& gr = s->groups[i];
     gr.view.state = s->states + i;
@@ -341,10 +319,9 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   }
   if (e != hipSuccess) {
     set_error("m2m_session_create: %s", hipGetErrorString(e));
-    m2m_session_destroy(s);
     return M2M_ERR_HIP;
   }
-  *out = s;
+  *out = s.release();
   return M2M_OK;
 }
 
@@ -362,13 +339,87 @@ extern "C" void m2m_session_destroy(m2m_session* s) {
     if (gr.state_host) (void)hipHostFree(gr.state_host);
   }
   if (s->ev_in) (void)hipEventDestroy(s->ev_in);
-  if (s->sample_host) (void)hipHostFree(s->sample_host);
-  if (s->proc_host) (void)hipHostFree(s->proc_host);
-  if (s->beam_host) (void)hipHostFree(s->beam_host);
-  if (s->score_host) (void)hipHostFree(s->score_host);
-  if (s->gram_host) (void)hipHostFree(s->gram_host);
+  if (s->call_host) (void)hipHostFree(s->call_host);
   delete s;
 }
+
+// --------------------------------------------------------- batched layers ---
+// One batched pass over the session's activation buffers: the encoder (S rows per clip) or the teacher-forced decoder pass (Ld rows).
+// The sub-layers below are what the two passes share; each reads and updates the fp32 residual stream x_enc in place.
+namespace {
+struct BatchedPass {
+  m2m_session* s;
+  int P;            // precision
+  int B, rows;      // clips, rows per clip
+  int Sp;           // rows rounded up to the 64-key tile (row pitch of the transposed V)
+  hipStream_t st;
+  int M() const { return B * rows; }
+};
+
+// x_enc += A . W^T, A [M, K]
+int resid_proj(const BatchedPass& p, const void* A, const void* W, int K) {
+  const int d = p.s->m->g.d_model;
+  GemmArgs a{}; a.vt_which = -1;
+  a.A = A; a.W = W; a.M = p.M(); a.N = d; a.K = K; a.out = p.s->x_enc; a.ldo = d;
+  return launch_gemm(p.P, EPI_RESID, a, p.st);
+}
+
+// RMSNorm + QKV projection into heads (V transposed), flash attention under the pass's bias table, output projection into the residual
+int self_attn_sublayer(const BatchedPass& p, const float* ln, const void* wqkv, const void* wo, const float* bias_tab, int tab_len,
+                       int bias_far, bool causal) {
+  m2m_session* s = p.s;
+  const m2m_model* m = s->m;
+  const m2m_t5_geometry& g = m->g;
+  int rc;
+  // RMSNorm + QKV projection: one kernel in the bf16 mode (launch_norm_gemm), norm into h_enc + GEMM otherwise
+  GemmArgs a{};
+  a.A = s->h_enc; a.W = wqkv; a.M = p.M(); a.N = 3 * m->inner; a.K = g.d_model; a.out = s->qkv_enc;
+  a.Bsz = p.B; a.S = p.rows; a.H = g.num_heads; a.inner = m->inner;
+  a.vt_which = 2; a.vt_out = s->vt_enc; a.Sp = p.Sp;
+  a.nx = s->x_enc; a.nw = ln; a.neps = g.layer_norm_eps;
+  if ((rc = launch_norm_gemm(p.P, EPI_HEADS, a, p.st))) return rc;
+  AttnArgs at{};
+  at.Q = s->qkv_enc; at.K = (const unsigned char*)s->qkv_enc + (size_t)p.M() * m->inner * m->esize; at.Vt = s->vt_enc; at.Sp = p.Sp;
+  at.bias_tab = bias_tab; at.tab_stride = 2 * tab_len - 1; at.tab_center = tab_len - 1; at.bias_far = bias_far;
+  at.out = s->attn_enc; at.B = p.B; at.H = g.num_heads; at.Sq = p.rows; at.Sk = p.rows;
+  if ((rc = launch_attn(p.P, at, causal, p.st))) return rc;
+  return resid_proj(p, s->attn_enc, wo, m->inner);
+}
+
+// RMSNorm + gated wi (epi: EPI_GATED for the encoder's 64-row interleave of wi, EPI_GATED16 for the decoder's 16-row one), wo_ff into the residual
+int feed_fwd_sublayer(const BatchedPass& p, const float* ln, const void* wi, const void* wo_ff, int epi) {
+  m2m_session* s = p.s;
+  const m2m_t5_geometry& g = s->m->g;
+  GemmArgs a{}; a.vt_which = -1;
+  a.A = s->h_enc; a.W = wi; a.M = p.M(); a.N = 2 * g.d_ff; a.K = g.d_model; a.out = s->mid_enc; a.ldo = g.d_ff;
+  a.nx = s->x_enc; a.nw = ln; a.neps = g.layer_norm_eps;
+  if (const int rc = launch_norm_gemm(p.P, epi, a, p.st)) return rc;
+  return resid_proj(p, s->mid_enc, wo_ff, g.d_ff);
+}
+
+// decoder pass: cross-attention of layer l over the cached encoder K/V (V transposed here, once per layer)
+int cross_attn_sublayer(const BatchedPass& p, const DecLayerPacked& L, int l) {
+  m2m_session* s = p.s;
+  const m2m_model* m = s->m;
+  const m2m_t5_geometry& g = m->g;
+  const int H = g.num_heads, S = s->S, Sp = ceil_div(S, 64) * 64;
+  const size_t per_enc = (size_t)s->B * H * S * DK;                       // elements of one cross K (or V) block
+  int rc;
+  GemmArgs a{};
+  a.A = s->h_enc; a.W = L.wcq; a.M = p.M(); a.N = m->inner; a.K = g.d_model; a.out = s->qkv_enc;
+  a.Bsz = p.B; a.S = p.rows; a.H = H; a.inner = m->inner; a.vt_which = -1;
+  a.nx = s->x_enc; a.nw = L.ln1; a.neps = g.layer_norm_eps;
+  if ((rc = launch_norm_gemm(p.P, EPI_HEADS, a, p.st))) return rc;
+  const unsigned char* ck = (const unsigned char*)s->cross_kv + ((size_t)l * 2 + 0) * per_enc * m->esize;
+  const unsigned char* cv = (const unsigned char*)s->cross_kv + ((size_t)l * 2 + 1) * per_enc * m->esize;
+  if ((rc = launch_transpose_v(p.P, cv, s->cross_vt, p.B * H, S, Sp, p.st))) return rc;
+  AttnArgs at{};
+  at.Q = s->qkv_enc; at.K = ck; at.Vt = s->cross_vt; at.Sp = Sp; at.bias_tab = nullptr;
+  at.out = s->attn_enc; at.B = p.B; at.H = H; at.Sq = p.rows; at.Sk = S;
+  if ((rc = launch_attn(p.P, at, false, p.st))) return rc;
+  return resid_proj(p, s->attn_enc, L.wco, m->inner);
+}
+}  // namespace
 
 // ----------------------------------------------------------------- encode ---
 extern "C" int m2m_encode(m2m_session* s, const float* inputs_embeds_dev, int B, int S, float* enc_out_dev, void* stream) {
@@ -380,35 +431,14 @@ extern "C" int m2m_encode(m2m_session* s, const float* inputs_embeds_dev, int B,
   const int P = m->precision;
   hipStream_t st = (hipStream_t)stream;
   const int M = B * S, d = g.d_model;
-  const EncSwitchScope sw_scope(&s->enc_sw);
+  const EncSwitchScope sw_scope(&s->sw.enc);
   s->encoded = false;
   M2M_CHECK_HIP(hipMemcpyAsync(s->x_enc, inputs_embeds_dev, (size_t)M * d * 4, hipMemcpyDeviceToDevice, st));
   int rc;
-  for (int l = 0; l < g.num_layers; ++l) {
-    const EncLayerPacked& L = m->enc[l];
-    // RMSNorm + QKV projection: one kernel in the bf16 mode (launch_norm_gemm), norm into h_enc + GEMM otherwise
-    GemmArgs a{};
-    const int Sp = ceil_div(S, 64) * 64;
-    a.A = s->h_enc; a.W = L.wqkv; a.M = M; a.N = 3 * m->inner; a.K = d; a.out = s->qkv_enc;
-    a.Bsz = B; a.S = S; a.H = g.num_heads; a.inner = m->inner;
-    a.vt_which = 2; a.vt_out = s->vt_enc; a.Sp = Sp;
-    a.nx = s->x_enc; a.nw = L.ln0; a.neps = g.layer_norm_eps;
-    if ((rc = launch_norm_gemm(P, EPI_HEADS, a, st))) return rc;
-    AttnArgs at{};
-    at.Q = s->qkv_enc; at.K = (const unsigned char*)s->qkv_enc + (size_t)M * m->inner * m->esize; at.Vt = s->vt_enc; at.Sp = Sp;
-    at.bias_tab = s->enc_bias_tab; at.tab_stride = 2 * s->max_enc - 1; at.tab_center = s->max_enc - 1; at.bias_far = s->enc_bias_far;
-    at.out = s->attn_enc; at.B = B; at.H = g.num_heads; at.Sq = S; at.Sk = S;
-    if ((rc = launch_attn(P, at, false, st))) return rc;
-    a = GemmArgs{}; a.vt_which = -1;
-    a.A = s->attn_enc; a.W = L.wo; a.M = M; a.N = d; a.K = m->inner; a.out = s->x_enc; a.ldo = d;
-    if ((rc = launch_gemm(P, EPI_RESID, a, st))) return rc;
-    a = GemmArgs{}; a.vt_which = -1;
-    a.A = s->h_enc; a.W = L.wi; a.M = M; a.N = 2 * g.d_ff; a.K = d; a.out = s->mid_enc; a.ldo = g.d_ff;
-    a.nx = s->x_enc; a.nw = L.ln1; a.neps = g.layer_norm_eps;
-    if ((rc = launch_norm_gemm(P, EPI_GATED, a, st))) return rc;
-    a = GemmArgs{}; a.vt_which = -1;
-    a.A = s->mid_enc; a.W = L.wo_ff; a.M = M; a.N = d; a.K = g.d_ff; a.out = s->x_enc; a.ldo = d;
-    if ((rc = launch_gemm(P, EPI_RESID, a, st))) return rc;
+  const BatchedPass p{s, P, B, S, ceil_div(S, 64) * 64, st};
+  for (const EncLayerPacked& L : m->enc) {
+    if ((rc = self_attn_sublayer(p, L.ln0, L.wqkv, L.wo, s->enc_bias_tab, s->max_enc, s->enc_bias_far, false))) return rc;
+    if ((rc = feed_fwd_sublayer(p, L.ln1, L.wi, L.wo_ff, EPI_GATED))) return rc;
   }
   // final norm -> GEMM input (T) and, if asked, the fp32 encoder states
   // cross-attention K/V of every decoder layer in one GEMM, written in decode layout
@@ -464,7 +494,7 @@ static int plan_groups(m2m_session* s, int rows_env, int rows = -1) {       // r
 // One graph = `steps` consecutive decode steps of one chain (kernels read the step index from
 // device memory, so the same graph replays for every position; steps past the end are no-ops).
 static int ensure_graph(m2m_session* s, DecGroup& gr, int steps) {
-  const int key[8] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, s->finished_skip ? 1 : 0, s->head_mode, s->beam_nb};
+  const int key[8] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, s->sw.finished_skip ? 1 : 0, s->head_mode, s->beam_nb};
   ++gr.graph_clock;
   for (auto& ge : gr.graphs)
     if (memcmp(key, ge.key, sizeof(key)) == 0) { ge.used = gr.graph_clock; gr.graph_exec = ge.exec; return M2M_OK; }
@@ -551,7 +581,7 @@ extern "C" int m2m_generate_sample(m2m_session* s, int max_length, const m2m_sam
   const char* fn = "m2m_generate_sample";
   M2M_REQUIRE(s && p && tokens_out_dev && out_len_host, "m2m_generate_sample: null argument");
   int rc;
-  if ((rc = fill_sample_params(p, *s->sample_host, fn))) return rc;
+  if ((rc = fill_sample_params(p, s->call_host->sample, fn))) return rc;
   M2M_REQUIRE(s->m->g.vocab_size <= SAMPLE_MAX_VOCAB, "m2m_generate_sample: vocab_size %d > %d (the sampling head keeps a row in one "
               "wavefront's registers)", s->m->g.vocab_size, SAMPLE_MAX_VOCAB);
   if ((rc = require_encoded(s, fn))) return rc;
@@ -621,9 +651,9 @@ static int generate_processed(m2m_session* s, int max_length, const m2m_process_
                               int64_t* tokens_out_dev, int* out_len_host, void* stream, const GrammarParams* gram, const char* fn) {
   M2M_REQUIRE(s && proc && tokens_out_dev && out_len_host, "%s: null argument", fn);
   int rc;
-  if (sample && (rc = fill_sample_params(sample, *s->sample_host, fn))) return rc;
+  if (sample && (rc = fill_sample_params(sample, s->call_host->sample, fn))) return rc;
   M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "%s: max_length %d outside [1, %d]", fn, max_length, s->max_dec);
-  if ((rc = fill_process_params(s, max_length, proc, *s->proc_host, fn))) return rc;
+  if ((rc = fill_process_params(s, max_length, proc, s->call_host->proc, fn))) return rc;
   if ((rc = require_encoded(s, fn))) return rc;
   return decode_call(s, {fn, HEAD_PROCESSED | (sample ? HEAD_SAMPLE : HEAD_GREEDY), 0, tokens_out_dev, nullptr, gram}, max_length,
                      out_len_host, (hipStream_t)stream);
@@ -646,20 +676,20 @@ static int generate_scored(m2m_session* s, int max_length, const m2m_process_par
     return m2m_generate_greedy(s, max_length, tokens_out_dev, out_len_host, stream);
   }
   int rc;
-  if (sample && (rc = fill_sample_params(sample, *s->sample_host, fn))) return rc;
+  if (sample && (rc = fill_sample_params(sample, s->call_host->sample, fn))) return rc;
   const int V = s->m->g.vocab_size;
   M2M_REQUIRE(V <= PROC_MAX_VOCAB, "%s: vocab_size %d > %d (the scored head keeps a row in one wavefront's registers)", fn, V,
               PROC_MAX_VOCAB);
   M2M_REQUIRE(max_length >= 1 && max_length <= s->max_dec, "%s: max_length %d outside [1, %d]", fn, max_length, s->max_dec);
   if (proc) {
-    if ((rc = fill_process_params(s, max_length, proc, *s->proc_host, fn))) return rc;
+    if ((rc = fill_process_params(s, max_length, proc, s->call_host->proc, fn))) return rc;
   } else {                                   // no processor: the neutral block (nothing banned, nothing forced)
-    ProcessParams& h = *s->proc_host;
+    ProcessParams& h = s->call_host->proc;
     h = ProcessParams{};
     h.penalty = 1.0f; h.forced_bos = -1; h.forced_eos = -1; h.begin_index = 1; h.max_length = max_length;
   }
   if ((rc = require_encoded(s, fn))) return rc;
-  ScoreParams& sc = *s->score_host;
+  ScoreParams& sc = s->call_host->score;
   sc = ScoreParams{};
   sc.scores = scores_out_dev; sc.logprobs = logprobs_out_dev; sc.rows = s->B; sc.steps = max_length - 1;
   sc.vec4 = (V % 4 == 0 && ((uintptr_t)scores_out_dev & 15) == 0) ? 1 : 0;
@@ -831,13 +861,13 @@ static int decode_loop(m2m_session* s, const DecodeCall& c, int max_length, int*
   // the output, on the caller's stream (all chains are idle now)
   if (beam) {   // finalize (a clip that is not done stopped at max_length, t = steps); valid length = the longest hypothesis
     if ((rc = decode_beam_finalize(s, rows, steps, c.tokens_out, c.scores_out, max_length, caller))) return rc;
-    M2M_CHECK_HIP(hipMemcpyAsync(s->beam_host, s->beam_dev, sizeof(BeamParams), hipMemcpyDeviceToHost, caller));
+    M2M_CHECK_HIP(hipMemcpyAsync(&s->call_host->beam, s->beam_dev, sizeof(BeamParams), hipMemcpyDeviceToHost, caller));
   } else {      // pack [B, max_dec] -> caller's [B, max_length]
     M2M_CHECK_HIP(hipMemcpy2DAsync(c.tokens_out, (size_t)max_length * 8, s->tokens, (size_t)s->max_dec * 8,
                                    (size_t)max_length * 8, (size_t)s->B, hipMemcpyDeviceToDevice, caller));
   }
   M2M_CHECK_HIP(hipStreamSynchronize(caller));
-  if (beam) { const int w = s->beam_host->max_hyp_len + 1; out_len = w < max_length ? w : max_length; }
+  if (beam) { const int w = s->call_host->beam.max_hyp_len + 1; out_len = w < max_length ? w : max_length; }
   *out_len_host = out_len;
   if (range_error) {
     set_error("%s: a decoder activation left the fixed-point residual range (|x| >= 2^21) or was not finite; "
@@ -858,29 +888,29 @@ static int upload(void* dev, const void* host, size_t bytes, hipStream_t caller,
 // The session's head mode holds for this call only, and nothing of a failed call is left running.
 static int decode_call(m2m_session* s, const DecodeCall& c, int max_length, int* out_len_host, hipStream_t caller) {
   int rc = M2M_OK;
-  if (c.head_mode & HEAD_SAMPLE) rc = upload(s->sample_dev, s->sample_host, sizeof(SampleParams), caller, c.fn);
-  if (rc == M2M_OK && (c.head_mode & HEAD_PROCESSED)) rc = upload(s->proc_dev, s->proc_host, sizeof(ProcessParams), caller, c.fn);
+  if (c.head_mode & HEAD_SAMPLE) rc = upload(s->sample_dev, &s->call_host->sample, sizeof(SampleParams), caller, c.fn);
+  if (rc == M2M_OK && (c.head_mode & HEAD_PROCESSED)) rc = upload(s->proc_dev, &s->call_host->proc, sizeof(ProcessParams), caller, c.fn);
   if (rc == M2M_OK && (c.head_mode & HEAD_PROCESSED)) {
     // the grammar block travels with every processed call (enable = 0 without a grammar); with one, the states of the call's rows
     // restart (one per clip; one per beam row in a processed beam call)
-    *s->gram_host = c.gram ? *c.gram : GrammarParams{};
-    rc = upload(s->gram_dev, s->gram_host, sizeof(GrammarParams), caller, c.fn);
+    s->call_host->gram = c.gram ? *c.gram : GrammarParams{};
+    rc = upload(s->gram_dev, &s->call_host->gram, sizeof(GrammarParams), caller, c.fn);
     const size_t gram_rows = (size_t)s->B * (size_t)((c.head_mode & HEAD_BEAM) ? c.beam_nb : 1);
     if (rc == M2M_OK && c.gram && hipMemsetAsync(s->gram_state, 0, gram_rows * sizeof(GrammarState), caller) != hipSuccess) {
       set_error("%s: hipMemsetAsync: %s", c.fn, hipGetErrorString(hipGetLastError()));
       rc = M2M_ERR_HIP;
     }
   }
-  if (rc == M2M_OK && (c.head_mode & HEAD_BEAM)) rc = upload(s->beam_dev, s->beam_host, sizeof(BeamParams), caller, c.fn);
+  if (rc == M2M_OK && (c.head_mode & HEAD_BEAM)) rc = upload(s->beam_dev, &s->call_host->beam, sizeof(BeamParams), caller, c.fn);
   if (rc == M2M_OK && (c.head_mode & HEAD_SCORED)) {
     // finished rows write nothing: the caller's buffers are zeroed on its stream, before the chains start
-    const ScoreParams& sc = *s->score_host;
+    const ScoreParams& sc = s->call_host->score;
     const size_t cells = (size_t)sc.rows * (size_t)sc.steps;
     hipError_t e = hipSuccess;
     if (sc.scores && cells) e = hipMemsetAsync(sc.scores, 0, cells * (size_t)s->m->g.vocab_size * sizeof(float), caller);
     if (e == hipSuccess && sc.logprobs && cells) e = hipMemsetAsync(sc.logprobs, 0, cells * sizeof(float), caller);
     if (e != hipSuccess) { set_error("%s: hipMemsetAsync: %s", c.fn, hipGetErrorString(e)); rc = M2M_ERR_HIP; }
-    if (rc == M2M_OK) rc = upload(s->score_dev, s->score_host, sizeof(ScoreParams), caller, c.fn);
+    if (rc == M2M_OK) rc = upload(s->score_dev, &s->call_host->score, sizeof(ScoreParams), caller, c.fn);
   }
   if (rc == M2M_OK) {
     s->head_mode = c.head_mode; s->beam_nb = c.beam_nb;
@@ -924,7 +954,7 @@ extern "C" int m2m_generate_beam(m2m_session* s, int max_length, const m2m_beam_
   int rc;
   BeamParams bp{};
   if ((rc = fill_beam_params(s, max_length, p, bp, fn))) return rc;
-  *s->beam_host = bp;
+  s->call_host->beam = bp;
   return decode_call(s, {fn, HEAD_BEAM, p->num_beams, tokens_out_dev, scores_out_dev}, max_length, out_len_host, (hipStream_t)stream);
 }
 
@@ -950,8 +980,8 @@ extern "C" int m2m_generate_beam_processed(m2m_session* s, int max_length, const
   if ((rc = fill_process_params(s, max_length, proc ? proc : &neutral, h, fn))) return rc;   // (max_length <= 2048 too)
   M2M_REQUIRE(h.penalty == 1.0f && h.ngram == 0 && h.n_bad == 0, "%s: repetition_penalty, no_repeat_ngram_size and bad_words sequences of "
               "two or more ids read a row's history and are not applied under beam search", fn);
-  *s->beam_host = bp;
-  *s->proc_host = h;
+  s->call_host->beam = bp;
+  s->call_host->proc = h;
   return decode_call(s, {fn, HEAD_BEAM | HEAD_PROCESSED, p->num_beams, tokens_out_dev, scores_out_dev, grammar ? &gp : nullptr}, max_length,
                      out_len_host, (hipStream_t)stream);
 }
@@ -963,57 +993,19 @@ extern "C" int m2m_generate_beam_processed(m2m_session* s, int max_length, const
 static int forward_batched(m2m_session* s, const int64_t* ids, int Ld, float* logits_out, hipStream_t st) {
   const m2m_model* m = s->m;
   const m2m_t5_geometry& g = m->g;
-  const int P = m->precision, B = s->B, S = s->S, H = g.num_heads, d = g.d_model;
-  const size_t es = m->esize;
-  const int M = B * Ld, Lp = ceil_div(Ld, 64) * 64, Sp = ceil_div(S, 64) * 64;
+  const int P = m->precision, d = g.d_model;
+  const BatchedPass p{s, P, s->B, Ld, ceil_div(Ld, 64) * 64, st};
   int rc;
-  if ((rc = launch_embed_rows(ids, m->shared, s->x_enc, M, d, g.vocab_size, g.pad_token_id, st))) return rc;
-  unsigned char* qkv = (unsigned char*)s->qkv_enc;
-  const size_t per_enc = (size_t)s->B * H * S * DK;                       // elements of one cross K (or V) block
+  if ((rc = launch_embed_rows(ids, m->shared, s->x_enc, p.M(), d, g.vocab_size, g.pad_token_id, st))) return rc;
   for (int l = 0; l < g.num_decoder_layers; ++l) {
     const DecLayerPacked& L = m->dec[l];
-    // --- causal self-attention
-    GemmArgs a{};
-    a.A = s->h_enc; a.W = L.wqkv; a.M = M; a.N = 3 * m->inner; a.K = d; a.out = qkv;
-    a.Bsz = B; a.S = Ld; a.H = H; a.inner = m->inner; a.vt_which = 2; a.vt_out = s->vt_enc; a.Sp = Lp;
-    a.nx = s->x_enc; a.nw = L.ln0; a.neps = g.layer_norm_eps;
-    if ((rc = launch_norm_gemm(P, EPI_HEADS, a, st))) return rc;
-    AttnArgs at{};
-    at.Q = qkv; at.K = qkv + (size_t)M * m->inner * es; at.Vt = s->vt_enc; at.Sp = Lp;
-    at.bias_tab = s->dec_bias_full_tab; at.tab_stride = 2 * s->max_dec - 1; at.tab_center = s->max_dec - 1; at.bias_far = s->dec_bias_far;
-    at.out = s->attn_enc; at.B = B; at.H = H; at.Sq = Ld; at.Sk = Ld;
-    if ((rc = launch_attn(P, at, true, st))) return rc;
-    a = GemmArgs{}; a.vt_which = -1;
-    a.A = s->attn_enc; a.W = L.wo; a.M = M; a.N = d; a.K = m->inner; a.out = s->x_enc; a.ldo = d;
-    if ((rc = launch_gemm(P, EPI_RESID, a, st))) return rc;
-    // --- cross-attention over the cached encoder K/V
-    a = GemmArgs{};
-    a.A = s->h_enc; a.W = L.wcq; a.M = M; a.N = m->inner; a.K = d; a.out = qkv;
-    a.Bsz = B; a.S = Ld; a.H = H; a.inner = m->inner; a.vt_which = -1;
-    a.nx = s->x_enc; a.nw = L.ln1; a.neps = g.layer_norm_eps;
-    if ((rc = launch_norm_gemm(P, EPI_HEADS, a, st))) return rc;
-    const unsigned char* ck = (const unsigned char*)s->cross_kv + ((size_t)l * 2 + 0) * per_enc * es;
-    const unsigned char* cv = (const unsigned char*)s->cross_kv + ((size_t)l * 2 + 1) * per_enc * es;
-    if ((rc = launch_transpose_v(P, cv, s->cross_vt, B * H, S, Sp, st))) return rc;
-    at = AttnArgs{};
-    at.Q = qkv; at.K = ck; at.Vt = s->cross_vt; at.Sp = Sp; at.bias_tab = nullptr;
-    at.out = s->attn_enc; at.B = B; at.H = H; at.Sq = Ld; at.Sk = S;
-    if ((rc = launch_attn(P, at, false, st))) return rc;
-    a = GemmArgs{}; a.vt_which = -1;
-    a.A = s->attn_enc; a.W = L.wco; a.M = M; a.N = d; a.K = m->inner; a.out = s->x_enc; a.ldo = d;
-    if ((rc = launch_gemm(P, EPI_RESID, a, st))) return rc;
-    // --- gated feed-forward (the decoder's 16-row interleave of wi)
-    a = GemmArgs{}; a.vt_which = -1;
-    a.A = s->h_enc; a.W = L.wi; a.M = M; a.N = 2 * g.d_ff; a.K = d; a.out = s->mid_enc; a.ldo = g.d_ff;
-    a.nx = s->x_enc; a.nw = L.ln2; a.neps = g.layer_norm_eps;
-    if ((rc = launch_norm_gemm(P, EPI_GATED16, a, st))) return rc;
-    a = GemmArgs{}; a.vt_which = -1;
-    a.A = s->mid_enc; a.W = L.wo_ff; a.M = M; a.N = d; a.K = g.d_ff; a.out = s->x_enc; a.ldo = d;
-    if ((rc = launch_gemm(P, EPI_RESID, a, st))) return rc;
+    if ((rc = self_attn_sublayer(p, L.ln0, L.wqkv, L.wo, s->dec_bias_full_tab, s->max_dec, s->dec_bias_far, true))) return rc;
+    if ((rc = cross_attn_sublayer(p, L, l))) return rc;
+    if ((rc = feed_fwd_sublayer(p, L.ln2, L.wi, L.wo_ff, EPI_GATED16))) return rc;
   }
   GemmArgs a{};
   a.vt_which = -1;
-  a.A = s->h_enc; a.W = m->lm_head; a.M = M; a.N = g.vocab_size; a.K = d; a.out = logits_out; a.ldo = g.vocab_size;
+  a.A = s->h_enc; a.W = m->lm_head; a.M = p.M(); a.N = g.vocab_size; a.K = d; a.out = logits_out; a.ldo = g.vocab_size;
   a.nx = s->x_enc; a.nw = m->dec_final_ln; a.neps = g.layer_norm_eps;
   return launch_norm_gemm(P, EPI_STORE_F32, a, st);
 }
@@ -1029,7 +1021,7 @@ extern "C" int m2m_decode_forced(m2m_session* s, const int64_t* dec_input_ids_de
   if (const int rc = require_encoded(s, "m2m_decode_forced")) return rc;
   M2M_REQUIRE(Ld >= 1 && Ld <= s->max_dec, "m2m_decode_forced: Ld %d outside [1, %d]", Ld, s->max_dec);
   hipStream_t st = (hipStream_t)stream;
-  const EncSwitchScope sw_scope(&s->enc_sw);
+  const EncSwitchScope sw_scope(&s->sw.enc);
   M2M_CHECK_HIP(hipMemcpyAsync(s->forced_ids, dec_input_ids_dev, (size_t)s->B * Ld * 8, hipMemcpyDeviceToDevice, st));
   const char* fwd = env_str("M2M_FORWARD");         // "step": Ld KV-cached decode steps instead (read per call, here only: tests toggle it on one session)
   const bool stepwise = fwd && strcmp(fwd, "step") == 0;
@@ -1092,8 +1084,8 @@ extern "C" int m2m_bench_kernel(m2m_session* s, int which, int self_len, int ite
       const int layer = same_layer ? 0 : i % Ld;
       for (int c = 0; c < G; ++c) {
         const DecGroup& gr = s->groups[c];
-        if (which == M2M_KERNEL_DEC_CROSS_ATTN) { if ((rc = decode_launch_attn(s, gr.view, false, layer, 0, gr.stream, s->headless))) return rc; }
-        else if (which == M2M_KERNEL_DEC_SELF_ATTN) { if ((rc = decode_launch_attn(s, gr.view, true, layer, self_len, gr.stream, s->headless))) return rc; }
+        if (which == M2M_KERNEL_DEC_CROSS_ATTN) { if ((rc = decode_launch_attn(s, gr.view, false, layer, 0, gr.stream, s->sw.headless))) return rc; }
+        else if (which == M2M_KERNEL_DEC_SELF_ATTN) { if ((rc = decode_launch_attn(s, gr.view, true, layer, self_len, gr.stream, s->sw.headless))) return rc; }
       }
     }
     return M2M_OK;

@@ -15,6 +15,7 @@
 //     buffers the forward wrote — no transposed copies of weights or activations exist;
 //   * every reduction has a fixed order (per-block partials + a second pass, never float atomics), so a
 //     training step is bit-reproducible run to run.
+#include "carver.h"
 #include "mma.h"
 #include "t5.h"
 #include "train.h"
@@ -1370,22 +1371,7 @@ void build_layout(m2m_trainer* t) {
 }
 
 // -------------------------------------------------------------- arena
-// Sizes one device allocation and points the members at their parts of it.  A buffer is declared ONCE, as take(member, bytes): it
-// gets the next 256-byte aligned offset, and the carver notes (member, offset); bind(base), after the allocation, sets every noted
-// member to base + offset.  The order of the declarations is the layout.  The carver keeps REFERENCES to the members: a container of
-// them (the per-layer structs, the residual streams, the rings) is resized before the first declaration into it and never grows after.
-struct Carver {
-  int64_t off = 0;
-  std::vector<std::function<void(unsigned char*)>> binds;
-  int64_t take(int64_t bytes) { const int64_t o = off; off = align_up(off + bytes, 256); return o; }      // unnamed: a reservation
-  template <typename P>
-  void take(P*& member, int64_t bytes) {
-    const int64_t o = take(bytes);
-    binds.push_back([&member, o](unsigned char* base) { member = reinterpret_cast<P*>(base + o); });
-  }
-  void bind(unsigned char* base) const { for (const auto& b : binds) b(base); }
-};
-
+// One device allocation; every buffer is declared once on a Carver (carver.h), and the order of the declarations is the layout.
 int build_optimizer(m2m_trainer* t) {
   std::vector<AfTensor> at;
   std::vector<AfBlock> ab;

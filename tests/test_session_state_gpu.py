@@ -170,3 +170,34 @@ def test_repacking_on_a_larger_session_and_with_the_head_kernel(big, B, S, L, he
     repacks, moved, same, ref = (int(v) for v in line[-1].split()[1:])
     print(f"session {big} >= batch {B}, M2M_HEADLESS={headless}: {repacks} re-packings, {moved} rows moved")
     assert repacks >= 1 and moved >= 1 and same == 1 and ref == 1
+
+
+_RANGED = ("M2M_DA_CLIPS", "M2M_DEC_FF_ROWS", "M2M_DEC_FF_SLICES", "M2M_MC_CIF")
+
+
+@pytest.fixture(scope="module")
+def small_greedy():
+    """inputs [2, 8, d] and their greedy ids (max_length 8) from a model built with none of the ranged switches set"""
+    saved = {k: os.environ.pop(k) for k in _RANGED if k in os.environ}
+    try:
+        m, geom, _ = _model("fp32", eos=False)
+        x = torch.from_numpy(synth.normal(5, "embeds", (2, 8, geom.d_model), 3.0)).cuda()
+        return x, m.generate_from_embeds(x, max_length=8).cpu()
+    finally:
+        os.environ.update(saved)
+
+
+@pytest.mark.parametrize("switch,value", [("M2M_DA_CLIPS", "3"), ("M2M_DEC_FF_ROWS", "4"), ("M2M_DEC_FF_SLICES", "3"), ("M2M_MC_CIF", "5")])
+def test_a_switch_outside_its_range_refuses_the_session(monkeypatch, small_greedy, switch, value):
+    """m2m_session_create latches the decode switches and refuses a value outside a switch's range by name; nothing of the refused
+    session is left behind: with the variable removed the same model creates its session and decodes as one that never saw it."""
+    x, want = small_greedy
+    for k in _RANGED:
+        monkeypatch.delenv(k, raising=False)
+    m, _, _ = _model("fp32", eos=False)
+    monkeypatch.setenv(switch, value)
+    with pytest.raises(native.NativeError) as err:
+        m.generate_from_embeds(x, max_length=8)
+    assert "m2m_session_create" in str(err.value) and f"{switch}={value}" in str(err.value), str(err.value)
+    monkeypatch.delenv(switch)
+    assert torch.equal(m.generate_from_embeds(x, max_length=8).cpu(), want)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """SHA-256 over what the decode kernels produce, per kernel form: greedy ids and out length, the teacher-forced step logits
-(M2M_FORWARD=step, first 24 positions), the scores of a scored decode, beam search.  For device-code changes of decode.hip that
-must not move a bit: run once per build and compare the lines.
+(M2M_FORWARD=step, first 24 positions), the scores of a scored decode, beam search; and the host paths around them: the encoder
+states, the batched teacher-forced logits, a seeded sampled, a processed and a grammar decode, a processed beam search.  For changes
+of decode.hip's device code or of the inference host (t5_api.hip) that must not move a bit: run once per build and compare the lines.
 
     M2M_LIBRARY=<the other build> python tools/decode_digest.py > a.txt;  python tools/decode_digest.py > b.txt;  diff a.txt b.txt
 
@@ -61,6 +62,26 @@ def greedy_case(name, cfg, sd, precision, x, env):
     del m
 
 
+def host_paths_case(cfg, sd, precision, x):
+    """the host paths around the decode step: encoder states, the batched teacher-forced pass, and the calls that reach the kernels
+    through a parameter block (sampled, processed, grammar, processed beam search); default switches"""
+    m = model_for(cfg, sd, precision, {})
+    print(f"encode {precision}: states {sha(m.encode(x))}", flush=True)
+    ids = m.generate_from_embeds(x, max_length=L)
+    print(f"batched logits {precision}: {sha(m.logits_from_embeds(x, ids))}", flush=True)
+    torch.manual_seed(7)
+    ids = m.generate_from_embeds(x, max_length=L, do_sample=True, temperature=0.9, top_k=50, top_p=0.9)
+    print(f"sampled {precision}: out_len {ids.shape[1]} ids {sha(ids)}", flush=True)
+    ids = m.generate_from_embeds(x, max_length=L, repetition_penalty=1.3, no_repeat_ngram_size=3, suppress_tokens=[5, 17, 140])
+    print(f"processed {precision}: out_len {ids.shape[1]} ids {sha(ids)}", flush=True)
+    ids = m.generate_from_embeds(x, max_length=L, midi_grammar=True)
+    print(f"midi_grammar {precision}: out_len {ids.shape[1]} ids {sha(ids)}", flush=True)
+    ids, scores = m.beam_search_processed_from_embeds(x[:5], 2, max_length=L, return_scores=True, midi_grammar=True, min_length=8,
+                                                      suppress_tokens=[5, 17, 140])   # 2 beams on 5 clips
+    print(f"processed beam {precision}: out_len {ids.shape[1]} ids {sha(ids)} sequence scores {sha(scores)}", flush=True)
+    del m
+
+
 def main():
     cfg = DEFAULT_CONFIG
     geom = T5Geometry(load_config(cfg).model.t5)
@@ -78,6 +99,7 @@ def main():
             ids, scores = m.beam_search_from_embeds(x[:5], 2, max_length=L, return_scores=True)
             print(f"beam {precision} M2M_DA_CLIPS={clips}: out_len {ids.shape[1]} ids {sha(ids)} sequence scores {sha(scores)}", flush=True)
             del m
+        host_paths_case(cfg, sd, precision, x)
     # another width: d_model 128 (two waves per feed-forward workgroup, one wave per attention row)
     cfg = copy.deepcopy(DEFAULT_CONFIG)
     cfg["model"]["t5"].update(d_model=128, d_ff=256, num_layers=2, num_decoder_layers=2, num_heads=2)

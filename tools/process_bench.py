@@ -4,8 +4,8 @@
 
     python tools/process_bench.py [--reps 3] [--warmup 1] [--skip-ref]
 
-Legs, timed interleaved rep by rep: greedy (the headless step), greedy with M2M_HEADLESS=0 (latched per process: a child process
-per rep), processed greedy (repetition_penalty 1.2, no_repeat_ngram_size 4, min_length 64) and processed sampling (the same with
+Legs, timed interleaved rep by rep: greedy (the headless step), greedy with M2M_HEADLESS=0 (latched in the session's switches when it
+is created: a child process per rep), processed greedy (repetition_penalty 1.2, no_repeat_ngram_size 4, min_length 64) and processed sampling (the same with
 do_sample, temperature 1.0, top_k 50, top_p 0.9).  Workloads as tools/sample_bench.py: bench.py's default (32 clips x 10 s,
 max_length 1024) and the reference's 128-segment chunk.  A leg's rows may end at other steps, so the like-for-like figure is the
 time per decode step (batch time / decoded columns); the line also gives its ratio to headless greedy.  Prints one JSON line.
