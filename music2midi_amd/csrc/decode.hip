@@ -355,15 +355,20 @@ static int launch_dec_gemm(int precision, const DecGemmArgs& a, hipStream_t st) 
 // block adds the residual rows themselves and zeroes the third buffer of the rotation.  A CU pulls only ~25-30 GB/s
 // from beyond its L2, so the kernel's time is the bytes one workgroup requests (at d_model 384 in bf16: x 24 KB with 8-row tiles,
 // 48 KB with 16-row tiles - real rows only, whole lines, staged through LDS: row_stage_at - + weights 74 KB, 147 KB in fp32);
-// every global load is issued before the first use, the rows first.
+// every global load is issued before the first use, the rows first.  The weights come from the layer's step image (Wimg below, written
+// once in m2m_model_create): a slice's 72 KiB are one block in which every load instruction of a wave reads 1 KiB of consecutive memory -
+// row-major, a wo load used half of each of its 16 lines and the two wf loads of a tile shared theirs (L1 -> L2 read
+// requests per launch 70 368 -> 56 544, L1 accesses 447 k -> 198 k, 6.60 -> 5.76 us).
 struct DecFfArgs {
   const xq_t* x;         // [B, d] residual stream after the attention sub-layers (complete)
   xq_t* x_out;           // [B, d] zero on entry: x + FF(x) is accumulated into it
   xq_t* x_zero;          // [B, d] third buffer of the rotation, left zeroed
   const float* ln_w;
   float eps;
-  const void* Wi;        // [2 * d_ff, d] T, 16-row groups: 8 rows of wi_0 then the same 8 of wi_1
-  const void* Wo;        // [d, d_ff] T
+  const void* Wimg;      // [d_ff / 32][d / 64][12][512] T, the step image of wi and wo_ff (t5.h DecLayerPacked::ff_img): per hidden slice and
+                         // wave the 8 fragment loads wf[j][s] of the interleaved wi (16-row groups: 8 rows of wi_0 then the same 8 of
+                         // wi_1), then the 4 loads wo[j] of wo_ff, each 64 lanes x 16 bytes of consecutive memory (whole 128-byte lines,
+                         // none shared with another slice; in the row-major layouts a wo load used half of each of its 16 lines)
   int d, d_ff, B;
   DecState* state;
   int check_done;        // headless greedy loop, layer 0: the carry workgroup of row block 0 turns "no row unfinished" into done
@@ -420,6 +425,15 @@ __device__ __forceinline__ void dec_ff_carry(const DecFfArgs& a, int b0, int don
 #ifndef M2M_FF_MULTI_SETS
 #define M2M_FF_MULTI_SETS 1
 #endif
+// Fragment load f (0..7: wf[f / 2][f % 2], 8..11: wo[f - 8]) of a wave's block of the step image; p = the block + the lane's chunk.
+// bf16: one 16-byte load.  fp32: two, the lanes' low halves and, 1 KiB on, their high halves.
+__device__ __forceinline__ Frag<bf16_t> ff_img_frag(const bf16_t* p, int f) { return load_frag(p + f * FF_IMG_FRAG); }
+__device__ __forceinline__ Frag<float> ff_img_frag(const float* p, int f) {
+  Frag<float> v;
+  v.lo = *reinterpret_cast<const float4*>(p + f * FF_IMG_FRAG);
+  v.hi = *reinterpret_cast<const float4*>(p + f * FF_IMG_FRAG + FF_IMG_FRAG / 2);
+  return v;
+}
 template <typename T, int KS, int FF_R, int NSL>
 __device__ __forceinline__ void dec_ff_body(const DecFfArgs& a) {
   static_assert(NSL == 1 || FF_R == 8, "several slices per workgroup: the lane pairing of the 8-row form");
@@ -446,9 +460,10 @@ __device__ __forceinline__ void dec_ff_body(const DecFfArgs& a) {
   }
   const int kbeg = ks * 64 + 8 * g;
   const bool row_ok = r < FF_R && (b0 + r) < a.B;
-  const T* Wi = reinterpret_cast<const T*>(a.Wi);
-  const T* Wo = reinterpret_cast<const T*>(a.Wo);
   const int s0 = c * NSL;                                   // first slice of this workgroup
+  // this lane's 16 bytes of the wave's fragment loads, slice 0: slice s is KS blocks further, fragment f of it at ff_img_frag(.., f)
+  const T* const Wimg = reinterpret_cast<const T*>(a.Wimg) + (int64_t)ks * FF_IMG_WAVE + lane * (16 / (int)sizeof(T));
+  constexpr int64_t SLICE = (int64_t)KS * FF_IMG_WAVE;      // elements of a slice's block
 
   // Lane (r, g)'s operand pieces of the rows: xraw[s][q] = elements kbeg + 32 s + 2 q + {0, 1} of row r, raw, converted only below.
   xq2_t xraw[2][4];
@@ -495,9 +510,9 @@ __device__ __forceinline__ void dec_ff_body(const DecFfArgs& a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int s = 0; s < 2; ++s) wf[b][j][s] = load_frag(Wi + (int64_t)(2 * FF_C * (s0 + b) + 16 * j + r) * K + kbeg + 32 * s);
+      for (int s = 0; s < 2; ++s) wf[b][j][s] = ff_img_frag(Wimg + (s0 + b) * SLICE, 2 * j + s);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) wo[b][j] = load_frag(Wo + (int64_t)(16 * (4 * ks + j) + r) * a.d_ff + FF_C * (s0 + b) + 8 * g);
+    for (int j = 0; j < 4; ++j) wo[b][j] = ff_img_frag(Wimg + (s0 + b) * SLICE, 8 + j);
   }
   // every load is in flight; the loop-state flag is forced here (two dependent scalar loads that the
   // compiler would otherwise sink to the first use, in front of the barrier on the critical path)
@@ -570,7 +585,7 @@ __device__ __forceinline__ void dec_ff_body(const DecFfArgs& a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int s = 0; s < 2; ++s) wf[i % NB][j][s] = load_frag(Wi + (int64_t)(2 * FF_C * (s0 + i + NB) + 16 * j + r) * K + kbeg + 32 * s);
+        for (int s = 0; s < 2; ++s) wf[i % NB][j][s] = ff_img_frag(Wimg + (s0 + i + NB) * SLICE, 2 * j + s);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -602,7 +617,7 @@ __device__ __forceinline__ void dec_ff_body(const DecFfArgs& a) {
     }
     if (i + NB < NSL && !(M2M_FF_ABL & 4)) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) wo[i % NB][j] = load_frag(Wo + (int64_t)(16 * (4 * ks + j) + r) * a.d_ff + FF_C * (s0 + i + NB) + 8 * g);
+      for (int j = 0; j < 4; ++j) wo[i % NB][j] = ff_img_frag(Wimg + (s0 + i + NB) * SLICE, 8 + j);
     }
     if (NSL == 1 && (M2M_FF_ABL & 1)) return;
     if constexpr (FF_R <= 8) {
@@ -712,7 +727,8 @@ struct DecAttnArgs {
   int self_len_override; // bench only: pretend t = self_len_override - 1
   const float* bias;     // self: [H][Lmax] by n = q_pos - k_pos
   int bias_stride;
-  const void* Wo;        // [d, inner] T output projection of this sub-layer (this head uses columns [64h, 64h+64))
+  const void* Wo;        // [H][32 / E][2 d][E] T, the step image of this sub-layer's [d, inner] output projection (t5.h DecLayerPacked::wo_img /
+                         // wco_img): per head and load instruction u, thread tid's 16 bytes = row tid / 2, columns 64 h + 32 (tid & 1) + E u
   int H, inner;
   DecState* state;
   // headless greedy loop, layer 0 only (null / 0 elsewhere)
@@ -1170,10 +1186,11 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   // this head's slice of the output projection (2 lanes per output column, 32 inputs each):
   // requested now so it arrives under the K/V stream
   constexpr int OCH = 32 / E;            // 16-byte chunks per lane: 4 (bf16) / 8 (fp32)
-  const T* worow = reinterpret_cast<const T*>(a.Wo) + (int64_t)on_ * a.inner + hh * DK + opart * 32;
+  // (step image: load u of the workgroup's 2 d live threads is 2 d x 16 consecutive bytes; the threads past them re-read the last chunk)
+  const T* woimg = reinterpret_cast<const T*>(a.Wo) + ((int64_t)hh * OCH * 2 * a.d + min(tid, 2 * a.d - 1)) * E;
   Vec16<T> wo[OCH];
 #pragma unroll
-  for (int u = 0; u < OCH; ++u) wo[u].v = *reinterpret_cast<const V16*>(worow + u * E);
+  for (int u = 0; u < OCH; ++u) wo[u].v = *reinterpret_cast<const V16*>(woimg + (int64_t)u * 2 * a.d * E);
   // self: weights of the k,v rows this step appends (128 outputs x 8 lanes), also under the stream
   const int o2 = tid >> 3, part2 = tid & 7;
   const int which2 = 1 + (o2 >> 6), dd2 = o2 & 63;
@@ -1718,10 +1735,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(M2M_MC_WAV
   //         registers that would otherwise be held through every stream).  da_out_row, by hand: called, the bf16 self form read
   //         18.23 us per launch against the parent's 18.15-18.22 ----
   constexpr int OCH = 32 / E;
-  const T* worow = reinterpret_cast<const T*>(a.Wo) + (int64_t)on_ * a.inner + hh * DK + opart * 32;
+  // (step image: load u of the workgroup's 2 d live threads is 2 d x 16 consecutive bytes; the threads past them re-read the last chunk)
+  const T* woimg = reinterpret_cast<const T*>(a.Wo) + ((int64_t)hh * OCH * 2 * a.d + min(tid, 2 * a.d - 1)) * E;
   Vec16<T> wo[OCH];
 #pragma unroll
-  for (int u = 0; u < OCH; ++u) wo[u].v = *reinterpret_cast<const V16*>(worow + u * E);
+  for (int u = 0; u < OCH; ++u) wo[u].v = *reinterpret_cast<const V16*>(woimg + (int64_t)u * 2 * a.d * E);
 #pragma unroll
   for (int c = 0; c < C; ++c) {
     const int bc = min(b0 + c, nb - 1);
@@ -2980,7 +2998,7 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
   }
   if (self) {
     const size_t off = ((size_t)layer * kv_layer_elems(s, s->max_dec) + (size_t)v.b0 * H * s->max_dec * DK) * es;
-    a.ln_w = L.ln0; a.Wp = L.wqkv; a.Wo = L.wo;
+    a.ln_w = L.ln0; a.Wp = L.wqkv; a.Wo = L.wo_img;
     a.Kc = (unsigned char*)s->self_k + off;
     a.Vc = (unsigned char*)s->self_v + off;
     a.kv_stride = s->max_dec; a.n_keys = 0; a.self_len_override = self_len;
@@ -2990,7 +3008,7 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
   // cross K/V: [L][2][B][H][S][64] with B, S = the encoded problem
   const size_t per = (size_t)s->B * H * s->S * DK;
   const size_t voff = (size_t)(beam ? v.b0 / s->beam_nb : v.b0) * H * s->S * DK;
-  a.ln_w = L.ln1; a.Wp = L.wcq; a.Wo = L.wco;
+  a.ln_w = L.ln1; a.Wp = L.wcq; a.Wo = L.wco_img;
   a.Kc = (unsigned char*)s->cross_kv + (((size_t)layer * 2 + 0) * per + voff) * es;
   a.Vc = (unsigned char*)s->cross_kv + (((size_t)layer * 2 + 1) * per + voff) * es;
   a.kv_stride = s->S; a.n_keys = s->S; a.self_len_override = 0; a.bias = nullptr; a.bias_stride = 0;
@@ -3018,7 +3036,7 @@ int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* log
     //    the next layer's self-attention
     DecFfArgs f{};
     f.x = xC; f.x_out = xA; f.x_zero = xB; f.ln_w = L.ln2; f.eps = g.layer_norm_eps;
-    f.Wi = L.wi; f.Wo = L.wo_ff; f.d = g.d_model; f.d_ff = g.d_ff; f.B = v.nb; f.state = v.state;
+    f.Wimg = L.ff_img; f.d = g.d_model; f.d_ff = g.d_ff; f.B = v.nb; f.state = v.state;
     f.check_done = (headless && l == 0) ? 1 : 0;
     if ((rc = launch_dec_ff(P, f, decode_ff_rows(s, v.nb), decode_ff_slices(s, v.nb), st))) return rc;
   }

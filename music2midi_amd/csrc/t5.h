@@ -30,7 +30,21 @@ struct DecLayerPacked {
   const float* ln2;
   const void* wi;     // [2*dff, d]        16-row chunks: 8 rows of wi_0 then the matching 8 rows of wi_1
   const void* wo_ff;  // [d, dff]
+  // Step-weight image of the feed-forward (repack.hip ff_image_kernel): the same elements as wi and wo_ff, in the order the loads of
+  // dec_ff_body read them - hidden slice c (32 columns), wave ks (k-slice of 64), then the wave's 12 fragment loads: wf[j][s]
+  // (j = 0..3, s = 0..1: elements [64 ks + 32 s + 8 g, +8) of row 64 c + 16 j + r of wi), then wo[j] (elements [32 c + 8 g, +8) of
+  // row 16 (4 ks + j) + r of wo_ff).  A fragment load is 512 consecutive elements, lane 16 g + r in lane order (fp32: the lanes'
+  // low halves, then their high halves); a wave's block is 6144 elements, a slice's d / 64 of them.  wi and wo_ff stay for the batched pass.
+  const void* ff_img; // [dff / 32][d / 64][12][512]
+  // Step images of the attention output projections (repack.hip attn_out_image_kernel), self (wo) and cross (wco): head h, then
+  // load instruction u (0 .. 32 / E - 1, E = elements in 16 bytes), then thread tid < 2 d: the 16 bytes the decode attention
+  // kernels' thread tid reads with its load u - row tid / 2, columns 64 h + 32 (tid & 1) + E u.  The same elements as wo / wco.
+  const void* wo_img;   // [H][32 / E][2 d][E]
+  const void* wco_img;  // [H][32 / E][2 d][E]
 };
+
+constexpr int FF_IMG_FRAG = 512;                 // elements of one fragment load of a wave in the feed-forward image
+constexpr int FF_IMG_WAVE = 12 * FF_IMG_FRAG;    // elements of a wave's block: 8 fragments of wi, 4 of wo_ff
 
 }  // namespace m2m
 
@@ -370,6 +384,8 @@ int launch_final_norm_f32(const float* x, const float* w, float* out_f32, void* 
 int launch_convert(int precision, const float* src, void* dst, int64_t n, hipStream_t st);
 int launch_interleave(int precision, const float* wi0, const float* wi1, void* dst, int dff, int d, int half,
                       hipStream_t st);
+int launch_ff_image(int precision, const void* wi, const void* wo_ff, void* img, int dff, int d, hipStream_t st);
+int launch_attn_out_image(int precision, const void* wo, void* img, int H, int d, hipStream_t st);
 int launch_copy_f32(const float* src, float* dst, int64_t n, hipStream_t st);
 int launch_fill_zero(void* dst, int64_t bytes, hipStream_t st);
 int launch_checksum(const void* buf, int64_t bytes, unsigned long long* acc_dev, hipStream_t st);

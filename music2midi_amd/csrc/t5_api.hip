@@ -80,7 +80,8 @@ extern "C" int m2m_model_create(const m2m_t5_geometry* geom, const m2m_t5_weight
   for (DecLayerPacked& L : m->dec) {
     F(L.ln0, d); T(L.wqkv, (int64_t)3 * inner * d); T(L.wo, (int64_t)d * inner);
     F(L.ln1, d); T(L.wcq, (int64_t)inner * d); T(L.wco, (int64_t)d * inner);
-    F(L.ln2, d); T(L.wi, (int64_t)2 * dff * d); T(L.wo_ff, (int64_t)d * dff);
+    F(L.ln2, d); T(L.wi, (int64_t)2 * dff * d); T(L.wo_ff, (int64_t)d * dff); T(L.ff_img, (int64_t)3 * dff * d);
+    T(L.wo_img, (int64_t)d * inner); T(L.wco_img, (int64_t)d * inner);
   }
   F(m->enc_final_ln, d); F(m->dec_final_ln, d);
   F(m->shared, (int64_t)V * d);
@@ -128,8 +129,11 @@ extern "C" int m2m_model_create(const m2m_t5_geometry* geom, const m2m_t5_weight
     conv(s.o, at(L.wo), (int64_t)d * inner);
     conv(s.cq, at(L.wcq), (int64_t)inner * d);
     conv(s.co, at(L.wco), (int64_t)d * inner);
+    if (rc == M2M_OK) rc = launch_attn_out_image(precision, L.wo, at(L.wo_img), g.num_heads, d, st);   // same stream: behind the conversions
+    if (rc == M2M_OK) rc = launch_attn_out_image(precision, L.wco, at(L.wco_img), g.num_heads, d, st);
     interleave(s.wi0, s.wi1, L.wi, 8);
     conv(s.wo, at(L.wo_ff), (int64_t)d * dff);
+    if (rc == M2M_OK) rc = launch_ff_image(precision, L.wi, L.wo_ff, at(L.ff_img), dff, d, st);   // same stream: behind the two conversions
     conv(s.ck, at(m->wckv, l * 2 + 0), (int64_t)inner * d); conv(s.cv, at(m->wckv, l * 2 + 1), (int64_t)inner * d);
   }
   copyf(w->enc_final_ln, m->enc_final_ln, d); copyf(w->dec_final_ln, m->dec_final_ln, d);
