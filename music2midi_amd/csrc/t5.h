@@ -192,7 +192,7 @@ struct CallParams {
 }  // namespace m2m
 
 namespace m2m {
-// Environment switches of the encoder-side kernel families (enc_kernels.hip), read ONCE when a session is created: they choose
+// Environment switches of the encoder-side kernel families (enc_gemm.hip, enc_attn.hip), read ONCE when a session is created: they choose
 // between kernels that are not all bit-identical (the two attention forms differ in the last bits), so a session keeps the forms
 // it started with whatever the environment does later, and no launch reads the environment (not safe against a concurrent setenv;
 // ADVICE r5).  A trainer latches its own the same way.  The public entry points of a session and of a trainer put theirs in scope
@@ -205,6 +205,13 @@ struct EncSwitches {
   int min_blocks = 160;         // M2M_NORM_GEMM_MIN_BLOCKS: row blocks from which the row-panel kernels run
   int norm_gemm_hout = 0;       // M2M_NORM_GEMM_HOUT (diagnostic)
   int norm_gemm_split = 1;      // M2M_NORM_GEMM_SPLIT=0: below min_blocks the two-kernel path instead of the column-group form (round 6)
+  // the form of gemm_kernel a product takes (enc_gemm.hip gemm_small_below, gemm_dma_ns)
+  int gemm_small_below = 512;   // M2M_GEMM_SMALL_BELOW: 64x64 tiles for plain products of fewer 128x128 tiles than this
+  int gemm_dma = 1;             // M2M_GEMM_DMA: 1 the LDS-DMA ring by shape, 0 never ("0"), 2 always ("all")
+  int gemm_dma_ns1 = 4;         // M2M_GEMM_DMA_NS1 / _NS2: ring depth of the small / the large tile
+  int gemm_dma_ns2 = 3;
+  int gemm_dma_mink = 512;      // M2M_GEMM_DMA_MINK: by shape, the ring from this K on ...
+  int gemm_dma_maxt = 1024;     // M2M_GEMM_DMA_MAXT: ... and up to this many small tiles (64 clips: 1 566 tiles per N = 384 product, the ring costs 1 %)
 };
 EncSwitches read_enc_switches();
 const EncSwitches& process_enc_switches();      // read at its first use, once per process
@@ -312,7 +319,7 @@ struct m2m_session {
 namespace m2m {
 
 // -------------------------------------------------------- launch helpers ---
-// encoder-side (enc_kernels.hip)
+// encoder-side (enc_gemm.hip, enc_attn.hip, enc_kernels.hip)
 enum { EPI_STORE = 0, EPI_RESID = 1, EPI_GATED = 2, EPI_HEADS = 3, EPI_STORE_F32 = 4, EPI_GATED16 = 5, EPI_GATED_TRAIN = 6, EPI_GATED_BWD = 7 };
 
 struct GemmArgs {

@@ -1,4 +1,4 @@
-"""GPU: the LDS-DMA main loop of the projection GEMM (csrc/enc_kernels.hip gemm_kernel<..., NS>: operand tiles global -> LDS through
+"""GPU: the LDS-DMA main loop of the projection GEMM (csrc/enc_gemm.hip gemm_kernel<..., NS>: operand tiles global -> LDS through
 global_load_lds_dwordx4 into a ring of 64-deep stages, counted vmcnt + one raw barrier per step, bank swizzle on the source
 address) against the register-staged loop it replaces.  Both accumulate every output element over k in the same order, so every
 result downstream — encoder states, greedy ids, training loss and gradients — must be BIT-identical, at every ring depth.

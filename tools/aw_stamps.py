@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase times of wave 0 of ONE workgroup of attn_wide_kernel (diagnostic build -DM2M_AW_STAMP, loaded through M2M_LIBRARY):
+"""Phase times of wave 0 of ONE workgroup of attn_wide_kernel (csrc/enc_attn.hip; diagnostic build -DM2M_AW_STAMP, loaded through M2M_LIBRARY):
 shader-clock stamps (100 MHz s_memtime ticks are NOT shader cycles: the table prints ticks and the share of the whole wave)."""
 import ctypes as C, sys
 from pathlib import Path

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Compile-time ablation of attn_wide_kernel's 64-key step: builds lib/libmusic2midi_amd_awcut<N>.so for each mask N (only
-# enc_kernels.hip is recompiled, with -DM2M_AW_CUT=N; the other objects come from the product build) — run HERE (no GPU), then
+# enc_attn.hip is recompiled, with -DM2M_AW_CUT=N; the other objects come from the product build) — run HERE (no GPU), then
 # `gpurun -- tools/aw_variants.sh run` times every variant at B = 4 (one workgroup per CU: the lone-wave chain) and B = 32.
 #   bits: 1 exponentials  2 P.V MFMAs + V reads  8 tile barrier  16 staging  64 max exchange
 #   (bits 4 = Q.K MFMAs + K reads and 32 = bias reads existed until the far-tile path restructured that phase; their figures — 17.6 / 19.4
@@ -10,9 +10,9 @@ cd "$(dirname "$0")/.."
 if [ "$1" != run ]; then
   for m in $MASKS; do
     ( mkdir -p music2midi_amd/csrc/build_awcut$m
-      hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DM2M_AW_CUT=$m -c music2midi_amd/csrc/enc_kernels.hip -o music2midi_amd/csrc/build_awcut$m/enc_kernels.o 2>/dev/null
-      objs=$(ls music2midi_amd/csrc/build/*.o | grep -v enc_kernels.o)
-      hipcc -shared -fPIC --offload-arch=gfx950 -o music2midi_amd/lib/libmusic2midi_amd_awcut$m.so $objs music2midi_amd/csrc/build_awcut$m/enc_kernels.o && echo built $m ) &
+      hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DM2M_AW_CUT=$m -c music2midi_amd/csrc/enc_attn.hip -o music2midi_amd/csrc/build_awcut$m/enc_attn.o 2>/dev/null
+      objs=$(ls music2midi_amd/csrc/build/*.o | grep -v enc_attn.o)
+      hipcc -shared -fPIC --offload-arch=gfx950 -o music2midi_amd/lib/libmusic2midi_amd_awcut$m.so $objs music2midi_amd/csrc/build_awcut$m/enc_attn.o && echo built $m ) &
     while [ $(jobs -r | wc -l) -ge 4 ]; do sleep 1; done
   done
   wait

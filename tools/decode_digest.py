@@ -7,7 +7,11 @@ of decode.hip's device code or of the inference host (t5_api.hip) that must not 
     M2M_LIBRARY=<the other build> python tools/decode_digest.py > a.txt;  python tools/decode_digest.py > b.txt;  diff a.txt b.txt
 
 Weights and inputs are fixed; the bits depend on the ROCm build, so the digests are compared, never stored.  The decode switches
-are latched when a session is created, so every leg sets its environment before it creates its model."""
+are latched when a session is created, so every leg sets its environment before it creates its model.
+
+For changes of the encoder-side kernels (enc_gemm.hip, enc_attn.hip) run it a second time with
+M2M_GEMM_SMALL_BELOW=0 M2M_NORM_GEMM=0 M2M_RESID_PANEL=0 M2M_ATTN_WIDE=0 set for the whole process: every product then takes
+gemm_kernel's 128x128 tile and the bf16 attention takes attn_kernel, forms the default run does not launch."""
 import copy
 import hashlib
 import os

@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """Print digests of bf16-mode results whose every projection goes through gemm_kernel: encoder states + greedy ids at two
 geometries, and loss + gradients of training steps at three shapes.  tests/test_gemm_dma_gpu.py runs this once per setting of
-M2M_GEMM_DMA / M2M_GEMM_DMA_NS1 / _NS2 (read once per process) and compares the digests: the LDS-DMA main loop accumulates every
-output element in the same k order as the register-staged one, so the results must be bit-identical."""
+M2M_GEMM_DMA / M2M_GEMM_DMA_NS1 / _NS2 (latched by every session and trainer when it is created) and compares the digests: the LDS-DMA main loop accumulates every
+output element in the same k order as the register-staged one, so the results must be bit-identical.
+
+For changes of the encoder-side kernels (enc_gemm.hip, enc_attn.hip) run it a second time (per M2M_GEMM_DMA setting) with
+M2M_GEMM_SMALL_BELOW=0 M2M_NORM_GEMM=0 M2M_RESID_PANEL=0 M2M_ATTN_WIDE=0 set for the whole process: every product then takes
+gemm_kernel's 128x128 tile and the bf16 attention takes attn_kernel, forms the default run does not launch."""
 import copy, hashlib, sys
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))

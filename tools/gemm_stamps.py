@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase times of one workgroup of gemm_kernel in the 16-clip training step (diagnostic build -DM2M_GEMM_STAMP; last launch per (EPI, tile)):
+"""Phase times of one workgroup of gemm_kernel (csrc/enc_gemm.hip) in the 16-clip training step (diagnostic build -DM2M_GEMM_STAMP; last launch per (EPI, tile)):
    M2M_BUILD_EXTRA=-DM2M_GEMM_STAMP M2M_BUILD_TAG=gstamp python -m music2midi_amd.csrc.build
    M2M_LIBRARY=music2midi_amd/lib/libmusic2midi_amd_gstamp.so M2M_TRAIN_GRAPH=0 python tools/gemm_stamps.py"""
 import ctypes as C, sys

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Phase times of ONE workgroup of resid_panel_kernel (diagnostic build -DM2M_RP_STAMP, loaded through M2M_LIBRARY): shader-clock
+"""Phase times of ONE workgroup of resid_panel_kernel (csrc/enc_gemm.hip; diagnostic build -DM2M_RP_STAMP, loaded through M2M_LIBRARY): shader-clock
 stamps at kernel entry, after the prologue and after every chunk's barrier, then after each half of the epilogue."""
 import ctypes as C, sys
 from pathlib import Path

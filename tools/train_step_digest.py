@@ -6,7 +6,11 @@ the bytes of the trainer's arena.  For host-side changes of the training pass: r
     M2M_LIBRARY=<the other build> python tools/train_step_digest.py > a.txt;  python tools/train_step_digest.py > b.txt;  diff a.txt b.txt
 
 Weights, inputs and the dropout seed are fixed; the bits depend on the ROCm build, so the digests are compared, never stored.
-(tiny model; the trainer's switches are latched when it is created, so every case sets its environment before it creates one)"""
+(tiny model; the trainer's switches are latched when it is created, so every case sets its environment before it creates one)
+
+For changes of the encoder-side kernels (enc_gemm.hip, enc_attn.hip) run it a second time with
+M2M_GEMM_SMALL_BELOW=0 M2M_NORM_GEMM=0 M2M_RESID_PANEL=0 M2M_ATTN_WIDE=0 set for the whole process: every product then takes
+gemm_kernel's 128x128 tile and the bf16 attention takes attn_kernel, forms the default run does not launch."""
 import hashlib
 import os
 import sys

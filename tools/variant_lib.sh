@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build lib/libmusic2midi_amd_<tag>.so from the product objects with ONE source recompiled under extra flags (same-box A/Bs of a
-# compile-time switch without a full tagged build):  tools/variant_lib.sh <tag> <source stem, e.g. enc_kernels> <flags...>
+# compile-time switch without a full tagged build):  tools/variant_lib.sh <tag> <source stem, e.g. enc_attn> <flags...>
 cd "$(dirname "$0")/.."
 tag=$1; stem=$2; shift 2
 mkdir -p music2midi_amd/csrc/build_$tag
