@@ -710,9 +710,15 @@ int m2m_generate_beam_processed(m2m_session* s, int max_length, const m2m_beam_p
  * segments to max_length 1024; a trained checkpoint ends a segment after tens to hundreds of tokens).  Once a quarter of the
  * rows still being decoded have emitted EOS, m2m_generate_greedy (and m2m_generate_sample, m2m_generate_processed) re-packs the live rows into the first slots of the batch at its
  * next host poll and goes on with smaller launches; ids do not depend on it.  The host polls after 16, 32, 64, 96 and 128 steps and
- * then every 64 (without the re-packing: every 64); each poll drains every chain, and a poll at which a re-packing is possible (a
- * chain still running, >= 64 steps left, >= 2 rows) also reads the finished flags back synchronously - so M2M_COMPACT=1 adds four
- * early polls (about a decode step each) even to a batch that never emits EOS.  This returns how often rows were re-packed in the
+ * then every 64 (without the re-packing: every 64).  A poll copies every chain's loop state - and, where a re-packing is possible
+ * (>= 64 steps left, >= 2 rows), its finished flags - to pinned memory on the chain's own stream, launches the first graph of the
+ * next chunk, and only then waits for the copies: the chains do not run dry at a poll, and the host decides from the snapshot alone,
+ * so ids, lengths and these statistics do not depend on it.  Only a poll that does re-pack drains the chains (rows move between
+ * idle chains, one graph later than they were counted).  One case keeps the draining poll because it measured faster with it: two
+ * chains that stream the same cross-K/V layers from HBM (more layers streamed than the two chains' resident windows hold between
+ * them, e.g. 32 clips x 864 positions in fp32).  M2M_POLL_LOOKAHEAD=0 restores the draining poll everywhere (every chain idle from
+ * its last kernel until the host has read the snapshot and launched again, at every poll - M2M_COMPACT=1 adds four early polls
+ * even to a batch that never emits EOS).  This returns how often rows were re-packed in the
  * last call and how many were moved; rows_moved > 0 means that call consumed the session's encode (see m2m_generate_greedy).
  * M2M_COMPACT=0 in the environment disables the re-packing.
  */

@@ -2865,6 +2865,22 @@ int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int 
   return M2M_OK;
 }
 
+// Zero the self K/V positions [t0, t1) of every row of the view, all layers (the decode loop: rows of a chain that ended before the
+// step count at which they are re-packed).  A row's block is [H][max_dec][64]; rows of a view are contiguous: one 2-D fill per plane.
+int decode_clear_self(m2m_session* s, const DecView& v, int t0, int t1, hipStream_t st) {
+  const m2m_model* m = s->m;
+  const m2m_t5_geometry& g = m->g;
+  const size_t es = m->esize;
+  if (t1 > s->max_dec) t1 = s->max_dec;
+  if (t0 < 0 || t0 >= t1 || v.nb <= 0) return M2M_OK;
+  const size_t head = (size_t)s->max_dec * DK * es, row = (size_t)g.num_heads * head, layer = (size_t)s->max_batch * row;
+  for (int l = 0; l < g.num_decoder_layers; ++l)
+    for (unsigned char* base : {(unsigned char*)s->self_k, (unsigned char*)s->self_v})
+      M2M_CHECK_HIP(hipMemset2DAsync(base + (size_t)l * layer + (size_t)v.b0 * row + (size_t)t0 * DK * es, head, 0,
+                                     (size_t)(t1 - t0) * DK * es, (size_t)v.nb * g.num_heads, st));
+  return M2M_OK;
+}
+
 // ============================================================ step driver ====
 static xq_t* xbuf(m2m_session* s, const DecView& v, int which);
 // the headless fold is a greedy-only form: the sampling and processed heads keep their own kernel (the step of M2M_HEADLESS=0)
@@ -2959,6 +2975,33 @@ int decode_ff_slices(const m2m_session* s, int nb) {
   return nb >= 56 ? 4 : (nb >= 32 ? 2 : 1);
 }
 
+// The cache policy of the session's K/V loads: non-temporal once the K/V working set of one decode step (all layers, cross + self
+// at the session's maximum length) is beyond what the 256 MB Infinity Cache can keep between steps, with as many whole layers of
+// cross K/V as fit a 180 MB budget (or M2M_KV_RESIDENT_LAYERS) left on the default policy.  B = 32: 3 of 6 layers, 271.0 -> 266.6 ms
+// per batch.
+KvPolicy decode_kv_policy(const m2m_session* s) {
+  const m2m_model* m = s->m;
+  const m2m_t5_geometry& g = m->g;
+  const double es = (double)m->esize;
+  const double kv_step_bytes = (double)g.num_decoder_layers * 2.0 * s->B * m->inner * ((double)s->S + s->max_dec) * es;
+  const double per_layer = 2.0 * s->B * m->inner * (double)s->S * es;
+  KvPolicy p;
+  p.nt = kv_step_bytes > 200e6;
+  p.resident = s->sw.kv_resident_layers >= 0 ? s->sw.kv_resident_layers : (int)(180e6 / per_layer);
+  return p;
+}
+
+// May `chains` chains run on without the re-alignment that a draining host poll gives them (the decode loop's poll look-ahead)?
+// Not two chains that stream the same cross-K/V layers from HBM: left to drift they measured 2.9 % (bf16) / 3.6 % (fp32) SLOWER than
+// with the draining polls, and only windows that together hold every layer (2 x resident >= layers: the headline's 3 + 3) turned
+// the look-ahead into a gain (profiles/poll_lookahead_ab.txt).
+bool decode_chains_may_drift(const m2m_session* s, int chains) {
+  const KvPolicy p = decode_kv_policy(s);
+  const int L = s->m->g.num_decoder_layers;
+  if (chains != 2 || !p.nt || p.resident >= L) return true;
+  return s->sw.kv_resident_stagger && 2 * p.resident >= L;
+}
+
 int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, int self_len, hipStream_t st, bool headless, bool skip_finished) {
   const m2m_model* m = s->m;
   const m2m_t5_geometry& g = m->g;
@@ -2966,17 +3009,11 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
   const int H = g.num_heads;
   const DecLayerPacked& L = m->dec[layer];
   DecAttnArgs a{};
-  // K/V working set of one decode step (all layers, cross + self at the session's maximum length)
-  const double kv_step_bytes = (double)g.num_decoder_layers * 2.0 * s->B * m->inner * ((double)s->S + s->max_dec) * (double)es;
-  bool nt = kv_step_bytes > 200e6;   // beyond what the 256 MB Infinity Cache can keep between steps
-  if (nt && !self) {
-    // ... but as many whole layers of cross K/V as fit a 180 MB budget keep the default policy and stay
-    // cache-resident from step to step (they are re-read every step; the rest streams past them
-    // non-temporally).  B = 32: 3 of 6 layers, 271.0 -> 266.6 ms per batch.
-    const double per_layer = 2.0 * s->B * m->inner * (double)s->S * (double)es;
-    const int resident = s->sw.kv_resident_layers >= 0 ? s->sw.kv_resident_layers : (int)(180e6 / per_layer);
-    if (layer < resident) nt = false;
-  }
+  const KvPolicy kp = decode_kv_policy(s);
+  bool nt = kp.nt;
+  // ... but `resident` whole layers of cross K/V keep the default policy and stay cache-resident from step to step (they are
+  // re-read every step; the rest streams past them non-temporally): which ones is the chain's window, t5.h kv_layer_resident
+  if (nt && !self && kv_layer_resident(layer, g.num_decoder_layers, kp.resident, v.ord, v.count, s->sw.kv_resident_stagger)) nt = false;
   int clips = decode_attn_clips(s, v.nb);
   if (self && s->sw.attn_clips_self > 0) clips = s->sw.attn_clips_self;      // diagnostic: another width for the self-attention launches
   // self: A -> B (zero C); cross: B -> C (zero A)

@@ -238,6 +238,7 @@ struct SessionSwitches {
   bool headless = env_on("M2M_HEADLESS");                           // 0 keeps dec_head_kernel in the greedy loop (the round-1 step: 20 kernels); default: folded away (19 kernels)
   bool finished_skip = env_on("M2M_FINISHED_SKIP");                 // 0: finished rows keep streaming their K/V (the behaviour before round 4; bench.py's ragged_eos "before" leg)
   int kv_resident_layers = env_int("M2M_KV_RESIDENT_LAYERS", -1);   // layers of cross K/V kept cache-resident when the rest streams non-temporally (-1: by a 180 MB budget)
+  bool kv_resident_stagger = env_on("M2M_KV_RESIDENT_STAGGER");     // two chains: each keeps a window of its own resident (kv_layer_resident); 0: both the first layers
 };
 
 constexpr int MAX_GROUPS = 8;
@@ -246,7 +247,20 @@ constexpr int MAX_GROUPS = 8;
 struct DecView {
   int b0, nb;
   DecState* state;          // device
+  int ord = 0, count = 1;   // the chain's ordinal among the `count` chains of its plan (plan_groups)
 };
+
+// Does cross-K/V layer `layer` of `L` keep the default cache policy (cache-resident from step to step) when `resident` layers may
+// and the rest streams non-temporally?  The first `resident` layers - except with exactly two chains (and `stagger`), where chain
+// i keeps the window [i * resident, i * resident + resident) mod L: the resident bytes are the same, and no layer is streamed
+// from HBM by both chains when the windows hold every layer between them.  Alone this measured equal to one window; it is what
+// lets the decode loop stop draining the chains at its polls (decode.hip decode_chains_may_drift).
+inline bool kv_layer_resident(int layer, int L, int resident, int ord, int count, bool stagger) {
+  if (resident >= L) return true;
+  if (resident <= 0) return false;
+  const int first = (stagger && count == 2) ? (ord * resident) % L : 0;
+  return (layer - first + L) % L < resident;
+}
 
 struct DecGroup {
   DecView view{0, 0, nullptr};
@@ -254,10 +268,10 @@ struct DecGroup {
   hipStream_t stream = nullptr;
   hipEvent_t ev_done = nullptr;
   hipGraphExec_t graph_exec = nullptr;           // the graph of the current view (an entry of `graphs`)
-  // captured graphs by (B, S, b0, nb, steps per graph, finished-row skip on / off, head form, beams) — all baked into the launches.  Re-packing the live
+  // captured graphs by (B, S, b0, nb, steps per graph, finished-row skip on / off, head form, beams, chain ordinal and count) — all baked into the launches.  Re-packing the live
   // rows changes (b0, nb) several times per batch, and the next batch starts from the full views again: a small cache instead of
   // a re-capture (~1 ms per 8-step graph) at every change
-  struct GraphEntry { int key[8]; hipGraph_t graph; hipGraphExec_t exec; unsigned long long used; };
+  struct GraphEntry { int key[10]; hipGraph_t graph; hipGraphExec_t exec; unsigned long long used; };
   std::vector<GraphEntry> graphs;
   unsigned long long graph_clock = 0;
 };
@@ -297,6 +311,7 @@ struct m2m_session {
   int repacks = 0, rows_moved = 0;   // live-row re-packings / rows moved by them in the last m2m_generate_greedy / _sample
   int head_mode = 0;       // head form of the free-running decode step: 0 greedy (arg-max), 1 sampling, 2 beam, | 4 processed, | 8 scored
                            // (set for the length of a call)
+  int* fin_host = nullptr;                    // pinned [max_batch]: the finished flags as of the decode loop's last poll
   m2m::CallParams* call_host = nullptr;       // pinned staging copy of the five parameter blocks; their device blocks, [1] each in the workspace:
   m2m::SampleParams* sample_dev = nullptr;
   m2m::ProcessParams* proc_dev = nullptr;
@@ -403,6 +418,10 @@ int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* log
 int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, int self_len, hipStream_t st, bool headless = false,
                        bool skip_finished = false);
 int decode_move_rows(m2m_session* s, const int* src, const int* dst, int n, int t, hipStream_t st);   // live-row re-packing (decode.hip)
+struct KvPolicy { bool nt; int resident; };   // K/V loads non-temporal; layers of cross K/V that keep the default policy then
+KvPolicy decode_kv_policy(const m2m_session* s);
+bool decode_chains_may_drift(const m2m_session* s, int chains);   // the decode loop's poll look-ahead is taken only then
+int decode_clear_self(m2m_session* s, const DecView& v, int t0, int t1, hipStream_t st);   // zero the self K/V positions [t0, t1) of the view's rows
 int decode_finalize(m2m_session* s, const DecView& v, hipStream_t st);   // headless greedy loop: write the last token, close the chain
 constexpr int HEAD_GREEDY = 0, HEAD_SAMPLE = 1, HEAD_BEAM = 2;
 constexpr int HEAD_PROCESSED = 4;        // bit: logits processors before the greedy (| 0) or sampling (| HEAD_SAMPLE) select, or on the

@@ -314,6 +314,7 @@ extern "C" int m2m_session_create(const m2m_model* m, int max_batch, int max_enc
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming);
   if (e == hipSuccess) e = hipHostMalloc((void**)&s->call_host, sizeof(CallParams), hipHostMallocDefault);
   if (e == hipSuccess) s->call_host->gram = GrammarParams{};
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s->fin_host, (size_t)max_batch * sizeof(int), hipHostMallocDefault);
   for (int i = 0; i < MAX_GROUPS && e == hipSuccess; ++i) {
     DecGroup& gr = s->groups[i];
     gr.view.state = s->states + i;
@@ -344,6 +345,7 @@ extern "C" void m2m_session_destroy(m2m_session* s) {
   }
   if (s->ev_in) (void)hipEventDestroy(s->ev_in);
   if (s->call_host) (void)hipHostFree(s->call_host);
+  if (s->fin_host) (void)hipHostFree(s->fin_host);
   delete s;
 }
 
@@ -468,6 +470,7 @@ struct DecodeSwitches {
   bool graph = env_int("M2M_NO_GRAPH", 0) != 1;                        // 1: every step launched directly
   int graph_steps = std::max(1, env_int("M2M_GRAPH_STEPS", 8));        // decode steps per graph
   bool compact = env_int("M2M_COMPACT", 1) != 0;                       // 0: no live-row re-packing
+  bool lookahead = env_int("M2M_POLL_LOOKAHEAD", 1) != 0;              // 0: every host poll drains the chains before the next launch
 };
 
 // Split the B encoded clips into independent chains: M2M_GROUP_ROWS clips per chain (default 32:
@@ -490,6 +493,7 @@ static int plan_groups(m2m_session* s, int rows_env, int rows = -1) {       // r
   for (int i = 0; i < G; ++i) {
     s->groups[i].view.b0 = b0;
     s->groups[i].view.nb = (base + (i < extra ? 1 : 0)) * unit;
+    s->groups[i].view.ord = i; s->groups[i].view.count = G;
     b0 += s->groups[i].view.nb;
   }
   return G;
@@ -498,7 +502,8 @@ static int plan_groups(m2m_session* s, int rows_env, int rows = -1) {       // r
 // One graph = `steps` consecutive decode steps of one chain (kernels read the step index from
 // device memory, so the same graph replays for every position; steps past the end are no-ops).
 static int ensure_graph(m2m_session* s, DecGroup& gr, int steps) {
-  const int key[8] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, s->sw.finished_skip ? 1 : 0, s->head_mode, s->beam_nb};
+  const int key[10] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, s->sw.finished_skip ? 1 : 0, s->head_mode, s->beam_nb,
+                       gr.view.ord, gr.view.count};       // (ord, count): which cross-K/V layers the chain keeps resident (t5.h)
   ++gr.graph_clock;
   for (auto& ge : gr.graphs)
     if (memcmp(key, ge.key, sizeof(key)) == 0) { ge.used = gr.graph_clock; gr.graph_exec = ge.exec; return M2M_OK; }
@@ -770,64 +775,119 @@ static int decode_loop(m2m_session* s, const DecodeCall& c, int max_length, int*
     if (graph && (rc = ensure_graph(s, gr, U))) return rc;
     gr.state_host->done = (steps == 0);
   }
-  // Launch round-robin over the chains in chunks; after each chunk fetch the loop states so a
-  // batch whose rows have all emitted EOS stops early (the kernels themselves turn into
-  // no-ops once their chain's state.done is set).
+  // Launch round-robin over the chains in chunks; after each chunk (a POLL POINT, P steps launched) fetch the loop states so a
+  // batch whose rows have all emitted EOS stops early (the kernels themselves turn into no-ops once their chain's state.done is
+  // set).  The first polls come sooner (after 16, 32, 64, 96, 128 steps, then every 64): many rows of a real batch end within
+  // their first tens of tokens, and every step before a re-packing costs the full batch.
+  //
+  // Look-ahead (M2M_POLL_LOOKAHEAD, default on): the snapshot of a poll - each chain's DecState and its slice of the finished
+  // flags, copied to pinned memory on the chain's own stream, then an event - is followed AT ONCE by the first launch of the next
+  // chunk, and only then does the host wait for the events.  The chains therefore never run dry at a poll.  What holds:
+  //  (i)   the step counts P at which snapshots are taken are those of the draining poll (=0) for any steps, M2M_GRAPH_STEPS,
+  //        M2M_NO_GRAPH and M2M_COMPACT, after a re-packing too: `launched` advances exactly as without the look-ahead, and the
+  //        look-ahead is the FIRST launch of the chunk that starts at P (never more than that chunk), counted in `ahead`;
+  //  (ii)  every decision - done, re-pack or not, which rows move, the `steps - P >= 64` condition - is a function of P and the
+  //        snapshot at P alone, so ids, out_len, the range flag and repack_stats() do not depend on the switch;
+  //  (iii) outside a re-packing and the end of the call the host waits for events only: no chain is drained;
+  //  (iv)  state_host / fin_host are the targets of a poll's copies only; the next copy into them (the next poll's, or the fresh
+  //        states of a re-packing) is enqueued after the host has read them, and `running` (not state_host) says which chains
+  //        to launch while a copy is in flight;
+  //  (v)   an error return leaves the look-ahead to decode_call's quiesce.
+  // The look-ahead is not taken while two chains stream the same cross-K/V layers (decode_chains_may_drift: measured slower).
+  // Steps that a look-ahead runs past the end of a chain (every row finished, or max_length reached) are no-ops, as the rest of
+  // a graph always was.
   const int CHUNK = 64;
-  int launched = 0;
+  const int unit = graph ? U : 1;      // decode steps per launch
+  auto chunk_at = [&](int p) { return compact ? (p < 32 ? 16 : (p < 128 ? 32 : CHUNK)) : CHUNK; };
+  bool running[MAX_GROUPS];            // chain i was not done in the last snapshot the host has read
+  for (int i = 0; i < MAX_GROUPS; ++i) running[i] = steps > 0;
+  auto launch = [&](int units) -> int {
+    for (int k = 0; k < units; ++k)
+      for (int i = 0; i < G; ++i) {
+        DecGroup& gr = s->groups[i];
+        if (!running[i]) continue;
+        if (graph) M2M_CHECK_HIP(hipGraphLaunch(gr.graph_exec, gr.stream));
+        else if (const int e = decode_launch_step(s, gr.view, false, nullptr, 0, gr.stream)) return e;
+      }
+    return M2M_OK;
+  };
+  int launched = 0;                    // steps launched up to the current poll point (the look-ahead not counted)
+  int ahead = 0;                       // launches of the chunk that starts at `launched` already enqueued (the last poll's look-ahead)
   int cur_rows = rows;                 // packed slots still being decoded
   s->repacks = 0; s->rows_moved = 0;
   int out_len = 1;                     // longest finished chain so far (chains retired by a re-packing included)
   bool range_error = false;
   bool all_done = steps == 0;
-  std::vector<int> fin_host, mv_src, mv_dst;
+  std::vector<int> mv_src, mv_dst;
   while (!all_done && launched < steps) {
-    // the first polls come sooner (after 16, 32, 64, 96, 128 steps, then every 64): many rows of a real batch end within their first
-    // tens of tokens, and a poll costs one drained pipeline (~a step) while every step before a re-packing costs the full batch
-    const int chunk = compact ? (launched < 32 ? 16 : (launched < 128 ? 32 : CHUNK)) : CHUNK;
-    const int n = steps - launched < chunk ? steps - launched : chunk;
-    for (int k = 0; k < n; k += (graph ? U : 1)) {
-      for (int i = 0; i < G; ++i) {
-        DecGroup& gr = s->groups[i];
-        if (gr.state_host->done) continue;
-        if (graph) M2M_CHECK_HIP(hipGraphLaunch(gr.graph_exec, gr.stream));
-        else if ((rc = decode_launch_step(s, gr.view, false, nullptr, 0, gr.stream))) return rc;
-      }
+    const int n = std::min(steps - launched, chunk_at(launched));
+    const int units = ceil_div(n, unit);
+    if ((rc = launch(units - ahead))) return rc;
+    launched += units * unit;
+    ahead = 0;
+    // ---- poll point P = launched: the snapshot ...
+    const bool may_repack = compact && steps - launched >= CHUNK && cur_rows >= 2 && cur_rows < 32000;
+    for (int i = 0; i < G; ++i) {
+      DecGroup& gr = s->groups[i];
+      M2M_CHECK_HIP(hipMemcpyAsync(gr.state_host, gr.view.state, sizeof(DecState), hipMemcpyDeviceToHost, gr.stream));
+      if (may_repack)
+        M2M_CHECK_HIP(hipMemcpyAsync(s->fin_host + gr.view.b0, s->finished + gr.view.b0, (size_t)gr.view.nb * sizeof(int),
+                                     hipMemcpyDeviceToHost, gr.stream));
+      M2M_CHECK_HIP(hipEventRecord(gr.ev_done, gr.stream));
     }
-    launched += ceil_div(n, graph ? U : 1) * (graph ? U : 1);
+    // ... the look-ahead: the first launch of the chunk that starts at P (without graphs: as many direct steps, within that chunk) ...
+    if (sw.lookahead && launched < steps && decode_chains_may_drift(s, G)) {
+      ahead = graph ? 1 : std::min(U, std::min(steps - launched, chunk_at(launched)));
+      if ((rc = launch(ahead))) return rc;
+    }
+    // ... and the wait for the snapshot alone
     all_done = true;
     for (int i = 0; i < G; ++i) {
       DecGroup& gr = s->groups[i];
-      if (gr.state_host->done) continue;
-      M2M_CHECK_HIP(hipMemcpyAsync(gr.state_host, gr.view.state, sizeof(DecState), hipMemcpyDeviceToHost, gr.stream));
+      M2M_CHECK_HIP(hipEventSynchronize(gr.ev_done));
+      running[i] = !gr.state_host->done;
+      if (running[i]) all_done = false;
     }
-    for (int i = 0; i < G; ++i) {
-      DecGroup& gr = s->groups[i];
-      M2M_CHECK_HIP(hipStreamSynchronize(gr.stream));
-      if (!gr.state_host->done) all_done = false;
-    }
-    // ---- re-pack the live rows (every chain is idle here) ----
-    if (compact && !all_done && steps - launched >= CHUNK && cur_rows >= 2 && cur_rows < 32000) {
-      fin_host.resize((size_t)cur_rows);
-      M2M_CHECK_HIP(hipMemcpy(fin_host.data(), s->finished, (size_t)cur_rows * sizeof(int), hipMemcpyDeviceToHost));
+    // ---- re-pack the live rows, decided from the snapshot at P
+    if (may_repack && !all_done) {
+      const int* fin = s->fin_host;
       int live = 0;
-      for (int b = 0; b < cur_rows; ++b) live += fin_host[(size_t)b] ? 0 : 1;
+      for (int b = 0; b < cur_rows; ++b) live += fin[b] ? 0 : 1;
       if (live >= 1 && (cur_rows - live) * 4 >= cur_rows) {
-        int t_cur = -1;
+        if (ahead) {        // drain the look-ahead: rows move between idle chains, at the step count the chains have reached by now
+          for (int i = 0; i < G; ++i) {
+            DecGroup& gr = s->groups[i];
+            M2M_CHECK_HIP(hipMemcpyAsync(gr.state_host, gr.view.state, sizeof(DecState), hipMemcpyDeviceToHost, gr.stream));
+          }
+          for (int i = 0; i < G; ++i) M2M_CHECK_HIP(hipStreamSynchronize(s->groups[i].stream));
+        }
+        int t_cur = -1, t_ended = 0;
         for (int i = 0; i < G; ++i) {                             // retire the current chains: keep what they report
           const DecState& hs = *s->groups[i].state_host;
           range_error |= hs.overflow != 0;
-          if (hs.done) { if (hs.out_len > out_len) out_len = hs.out_len; }
+          if (hs.done) { if (hs.out_len > out_len) out_len = hs.out_len; if (hs.t > t_ended) t_ended = hs.t; }
           else t_cur = hs.t;
         }
-        M2M_REQUIRE(t_cur >= 0, "%s: no running chain at a re-packing point", fn);
+        // a chain still running has done exactly the launched steps (P, and the look-ahead's); every chain may have ENDED inside
+        // the look-ahead: the rows still move (the re-packing was decided at P), and the call ends with the chains as they are
+        const bool ended = t_cur < 0;
+        M2M_REQUIRE(!ended || ahead, "%s: no running chain at a re-packing point", fn);
+        M2M_REQUIRE(ended || t_cur == std::min(launched + ahead * unit, steps), "%s: a chain at step %d, %d launched", fn, t_cur,
+                    launched + ahead * unit);
+        if (ended) t_cur = t_ended;
         mv_src.clear(); mv_dst.clear();
         for (int hole = 0, tail = live; hole < live; ++hole) {    // finished slots in front take the live rows from behind the packed range
-          if (!fin_host[(size_t)hole]) continue;
-          while (tail < cur_rows && fin_host[(size_t)tail]) ++tail;
+          if (!fin[hole]) continue;
+          while (tail < cur_rows && fin[tail]) ++tail;
           mv_src.push_back(tail++); mv_dst.push_back(hole);
         }
         hipStream_t st0 = s->groups[0].stream;
+        // A chain that ended inside the look-ahead (at hs.t < t_cur: all its rows finished) stopped appending self K/V there, and its
+        // rows go on as finished rows of chains at t_cur: with M2M_FINISHED_SKIP=0 they read those positions, so they are cleared.
+        for (int i = 0; i < G && !ended; ++i) {
+          const DecState& hs = *s->groups[i].state_host;
+          if (hs.done && hs.t < t_cur && (rc = decode_clear_self(s, s->groups[i].view, hs.t, t_cur, st0))) return rc;
+        }
         // Moving a row OVERWRITES the finished clip in its destination slot (cross K/V, self K/V, residual row): from here on the
         // session no longer holds the encode of clips 0..B-1 in clip order, so this generate CONSUMES it.  A later
         // m2m_decode_forced / m2m_generate_greedy / m2m_bench_kernel without a new m2m_encode returns M2M_ERR_STATE instead of
@@ -836,6 +896,7 @@ static int decode_loop(m2m_session* s, const DecodeCall& c, int max_length, int*
         if (!mv_src.empty() && (rc = decode_move_rows(s, mv_src.data(), mv_dst.data(), (int)mv_src.size(), t_cur, st0))) return rc;
         M2M_CHECK_HIP(hipStreamSynchronize(st0));
         s->repacks += 1; s->rows_moved += (int)mv_src.size();
+        if (ended) { all_done = true; continue; }
         cur_rows = live;
         G = plan_groups(s, sw.group_rows, cur_rows);
         for (int i = 0; i < G; ++i) {
@@ -845,6 +906,7 @@ static int decode_loop(m2m_session* s, const DecodeCall& c, int max_length, int*
           *gr.state_host = hs;
           M2M_CHECK_HIP(hipMemcpyAsync(gr.view.state, gr.state_host, sizeof(DecState), hipMemcpyHostToDevice, gr.stream));
           if (graph && (rc = ensure_graph(s, gr, U))) return rc;
+          running[i] = true;
         }
       }
     }
