@@ -419,6 +419,77 @@ int m2m_render_notes_f32(const m2m_render_note* notes_dev, int n_notes, const in
                          int n_clips, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Aligning note labels to a recording: integer chroma / onset features of log band energies and batched DTW.  Stands in for the
+ * feature and DTW stages of ref: data/align_audio_midi.py.  This is the project's own aligner, not synctoolbox's; the definition is
+ * music2midi_amd/align.py (features_host, coarse, cost_matrix, dtw_host) and every output below is EQUAL to its: one fp32
+ * subtraction before each comparison of the features, integer arithmetic everywhere else.
+ * No handle, no environment switch; the calls enqueue on `stream` and return nothing to the host.  Every M2M_ERR_INVALID below is
+ * answered on the arguments alone, before the first HIP call.
+ * ------------------------------------------------------------------------- */
+#define M2M_ALIGN_MAX_FRAMES 32768         /* a side of one DTW problem: 10.9 min at 50 frames per second */
+#define M2M_ALIGN_MAX_CLIPS 65535
+#define M2M_ALIGN_MAX_PROBLEMS 65535
+#define M2M_ALIGN_MAX_TOTAL_FRAMES (1 << 26)   /* frames of one features call, all clips together */
+
+/*
+ * L_dev fp32 [total_frames, 88]: the log energies of the 88 bands (MIDI 21..108) of all clips, those of clip b at rows
+ * [frame_offsets_dev[b], frame_offsets_dev[b + 1]) (int32 [n_clips + 1]; offsets outside 0..total_frames are clamped); finite.
+ * max_frames: the longest clip (the launch geometry).  chroma_out_dev, onset_out_dev uint8 [total_frames, 12], per frame t of a clip
+ * with d = (float)(ln 2.5, ln 5, ln 10, ln 20), M = max_p L[t][p], silent when M <= -6.0f (all twelve of both are then 0):
+ *   chroma[c] = sum over the bands p of class c ((21 + p) % 12 == c) of #{k : L[t][p] >= M - d[k]};
+ *   on[t][p] = t >= 2 and L[t][p] - L[t-2][p] >= (float)ln 4 and L[t][p] >= M - d[3] and not silent; first = on[t] and not on[t-1];
+ *   onset[c] = max over tau = 0..3 of (4 - tau) * (sum over the bands of class c of first[t - tau]).
+ * M2M_ERR_INVALID: n_clips outside 1..65535, total_frames outside 1..2^26, max_frames outside 1..total_frames, a null pointer,
+ * L_dev or frame_offsets_dev not 4-byte aligned.
+ */
+int m2m_align_features(const float* L_dev, const int32_t* frame_offsets_dev, int n_clips, int max_frames, int64_t total_frames,
+                       uint8_t* chroma_out_dev, uint8_t* onset_out_dev, void* stream);
+
+/*
+ * out_dev int32 [total_coarse, 12]: row j of clip b (rows [coarse_offsets_dev[b], coarse_offsets_dev[b + 1])) is the sum of the W
+ * chroma frames centred on frame j * D of the clip (W / 2 before it), zeros outside the clip.  max_coarse: the most rows of a clip.
+ * M2M_ERR_INVALID: n_clips outside 1..65535, total_frames outside 1..2^26, total_coarse outside 1..total_frames, max_coarse outside
+ * 1..total_coarse, W or D outside 1..255, a null pointer, a table or out_dev not 4-byte aligned.
+ */
+int m2m_align_coarse(const uint8_t* chroma_dev, const int32_t* frame_offsets_dev, const int32_t* coarse_offsets_dev, int n_clips,
+                     int max_coarse, int64_t total_frames, int64_t total_coarse, int W, int D, int32_t* out_dev, void* stream);
+
+typedef struct {
+  int32_t a_offset;                        /* first frame of side a (the rows) in the a arrays */
+  int32_t n;                               /* frames of side a, 1..32768 */
+  int32_t b_offset;                        /* first frame of side b (the columns) in the b arrays */
+  int32_t m;                               /* frames of side b, 1..32768 */
+  int32_t shift;                           /* 0..11: class c of side b takes class (c - shift) mod 12, np.roll(b, shift, axis=1) */
+  int32_t path_offset;                     /* first point of this problem's path in path_out_dev; n + m - 1 points are reserved */
+} m2m_align_problem;
+
+/* Columns of a strip of the DTW kernel (its workgroup's threads).  Host arithmetic. */
+int m2m_align_dtw_strip(void);
+/* Bytes of workspace m2m_align_dtw needs for problems of rows_host[p] x cols_host[p] frames: the problem table, then per problem
+ * two direction bits per cell and a scratch path.  M2M_ERR_INVALID (negative) for n_problems outside 1..65535 or a side outside
+ * 1..32768.  Host arithmetic. */
+int64_t m2m_align_dtw_workspace_bytes(const int32_t* rows_host, const int32_t* cols_host, int n_problems);
+
+/*
+ * n_problems DTW problems by ONE launch, one workgroup each.  Cell (i, j) of a problem costs, with S = 256 and
+ * cost(u, v) = S - isqrt((S S (u.v)^2) / ((u.u) (v.v))) (S when a vector is zero), u frame a_offset + i of side a and v frame
+ * b_offset + j of side b rolled by `shift`:
+ *   coarse = 1: cost of a0_dev / b0_dev, int32 [frames, 12] with values 0..672 (a1_dev / b1_dev are not read; pass a0_dev / b0_dev);
+ *   coarse = 0: cost of a0_dev / b0_dev (chroma) + cost of a1_dev / b1_dev (onset), uint8 [frames, 12].
+ * D[-1][-1] = 0, the other border cells +inf; D[i][j] = min(D[i-1][j-1] + 4 C, D[i-1][j] + 3 C, D[i][j-1] + 3 C), a tie takes the
+ * diagonal, then (i-1, j), then (i, j-1).  total_out_dev[p] = D[n-1][m-1]; the path from (0, 0) to (n-1, m-1), front to back, has
+ * path_len_out_dev[p] points: its rows at path_out_dev[path_offset + k], its columns at path_out_dev[path_capacity + path_offset + k].
+ * problems_host is copied to the head of workspace_dev on `stream`; it must stay valid until that copy has run.
+ * M2M_ERR_INVALID: n_problems outside 1..65535, coarse other than 0 or 1, a side outside 1..32768, frames outside the arrays
+ * (a_frames, b_frames), a shift outside 0..11, path regions that are not ascending and disjoint or exceed path_capacity
+ * (1..2^31 - 1), a null pointer, feature arrays not 16-byte (coarse) / 4-byte aligned, a workspace not 256-byte aligned.
+ * M2M_ERR_NOMEM: workspace_bytes below m2m_align_dtw_workspace_bytes.
+ */
+int m2m_align_dtw(const void* a0_dev, const void* a1_dev, int a_frames, const void* b0_dev, const void* b1_dev, int b_frames, int coarse,
+                  const m2m_align_problem* problems_host, int n_problems, void* workspace_dev, int64_t workspace_bytes,
+                  int32_t* total_out_dev, int32_t* path_out_dev, int64_t path_capacity, int32_t* path_len_out_dev, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Tokenising of note labels: the note arrays of a batch -> token ids, replaces for the batches it takes
  * ref: music2midi/tokenizer.py:86-141 (MidiTokenizer.__call__, _tokenize).  The definition is music2midi_amd/tokenizer.py
  * (_quantize, _tokenize); the ids are EQUAL to its (integer placement; the quantisation repeats the host's float64 operations).

@@ -66,6 +66,11 @@ class RenderVoice(C.Structure):
                 ("decay_steps", C.c_int32), ("attack", C.c_int32), ("release", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AlignProblem(C.Structure):
+    """m2m_align_problem: one DTW problem of m2m_align_dtw (six 32-bit words)."""
+    _fields_ = [(n, C.c_int32) for n in ("a_offset", "n", "b_offset", "m", "shift", "path_offset")]
+
+
 class T5GeometryC(C.Structure):
     _fields_ = [(n, C.c_int) for n in
                 ("d_model", "d_ff", "num_layers", "num_decoder_layers", "num_heads", "d_kv", "vocab_size",
@@ -155,6 +160,13 @@ _SIGNATURES = {
     "m2m_render_tile": (C.c_int, []),
     "m2m_render_notes_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(RenderVoice), C.c_void_p, C.c_int64,
                                        C.c_int64, C.c_int, C.c_void_p]),
+    "m2m_align_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m2m_align_coarse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p]),
+    "m2m_align_dtw_strip": (C.c_int, []),
+    "m2m_align_dtw_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int]),
+    "m2m_align_dtw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "m2m_tokenize_quantize": (C.c_int, [C.c_double, C.c_double, C.c_int]),
     "m2m_tokenize_row_bound": (C.c_int64, [C.c_int, C.c_int]),
     "m2m_tokenize_notes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
