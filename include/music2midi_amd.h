@@ -273,6 +273,57 @@ int m2m_score_note_counts(const int32_t* notes_dev, const int32_t* counts_dev, c
                           double onset_tolerance, double offset_ratio, double offset_min_tolerance, const float* min_logprobs_dev,
                           int n_thresholds, void* workspace_dev, int64_t workspace_bytes, int32_t* out_dev, void* stream);
 
+#define M2M_SCORE_FRAME_TILE 1024          /* frames of one timeline per workgroup of the frame-roll kernels */
+
+/*
+ * Frame-level scoring (the definition: music2midi_amd/frame_metrics.py, frame_counts - ref music2midi/plot_midi.py:102-126
+ * restated), per timeline and per confidence threshold.  Both note lists become piano rolls at 100 frames per second (a note sounds
+ * in [int(start * 100), int(end * 100)), cut at n_frames - 1; n_frames as m2m_score_frame_count of the later end of both sides) and
+ * every (pitch, frame) cell is a true positive (ref & est), a false negative (ref & ~est) or a false positive (~ref & est); the
+ * melody roll has 12 rows and, in every frame where anything sounds, the row (highest sounding pitch % 12) set.
+ * notes_dev .. frame_cap are m2m_score_chroma_counts', note_lp_dev / min_logprobs_dev / n_thresholds m2m_score_note_counts': output
+ * note e exists under threshold k unless float32(on + off) < min_logprobs_dev[k] is true (a NaN total is kept); n_frames, and with
+ * it the cut, is taken over the labels and the notes kept under k.
+ * out_dev [n_timelines, n_thresholds, 6] int32, zeroed on `stream` first: tp, fn, fp of the full roll, tp, fn, fp of the melody roll.
+ * frames_dev [n_timelines] int32: n_frames with every output note kept - or -1 (and no counts) for a timeline beyond frame_cap.
+ * No workspace; one launch serves all thresholds.
+ * M2M_ERR_INVALID: R, L, sequential, n_timelines, time_step, n_labels, frame_cap as m2m_score_chroma_counts; n_thresholds outside
+ * 1..64; a null notes / counts / offsets / output / frames pointer; null labels with n_labels > 0; a null note_lp_dev with
+ * n_thresholds > 1; a null min_logprobs_dev with note_lp_dev.
+ */
+int m2m_score_frame_counts(const int32_t* notes_dev, const int32_t* counts_dev, const float* note_lp_dev, int R, int L, int sequential,
+                           double time_step, const double* labels_dev, const int32_t* label_offsets_dev, int n_labels, int n_timelines,
+                           int frame_cap, const float* min_logprobs_dev, int n_thresholds, int32_t* out_dev, int32_t* frames_dev,
+                           void* stream);
+
+/* The note slots per timeline and kind m2m_score_error_notes writes for these sizes: max_timeline_labels + L (sequential: + R * L),
+ * twice that for the melody roll - a run of an error roll starts where a run of either side starts or ends, the melody's top pitch
+ * changes only where a note starts or ends.  Host arithmetic; -1 for a size out of range. */
+int m2m_score_error_notes_capacity(int R, int L, int sequential, int max_timeline_labels, int melody_only);
+
+/* The bytes of workspace m2m_score_error_notes needs: per timeline 4, per timeline and tile (of M2M_SCORE_FRAME_TILE frames up to
+ * frame_cap) 12, and the three bit-packed rolls, 128 (melody: 12) rows of 4 * 32 bytes per tile; every array rounded up to 8 bytes.
+ * Host arithmetic; -1 for a size out of range. */
+int64_t m2m_score_error_notes_workspace_bytes(int n_timelines, int frame_cap, int melody_only);
+
+/*
+ * The three error rolls of m2m_score_frame_counts as notes (frame_metrics.error_rolls + roll_to_notes, ref plot_midi.py:19-70),
+ * for ONE threshold (min_logprob, -inf: every note; note_lp_dev may be NULL only then) and the full (melody_only 0) or the melody
+ * roll (1).  Every maximal run of set cells of a row is one note, also across tiles.
+ * notes_out_dev [n_timelines, 3, cap, 3] int32, cap = m2m_score_error_notes_capacity(R, L, sequential, max_timeline_labels,
+ * melody_only): (first frame, end frame = last frame + 1, row) of the runs of tp / fn / fp, in the definition's order: ascending
+ * end frame, then ascending row.  counts_out_dev [n_timelines, 3] int32: their number - or -1 (and nothing written) for a timeline
+ * beyond frame_cap, with more than max_timeline_labels label notes, or (impossible by the bound) more runs than cap.
+ * workspace_dev: at least m2m_score_error_notes_workspace_bytes(n_timelines, frame_cap, melody_only) bytes, 8-byte aligned, the
+ * caller's; its contents are unspecified before and after.  Two launches on `stream`; the library allocates nothing.
+ * M2M_ERR_INVALID: as m2m_score_frame_counts for the shared arguments; melody_only other than 0 / 1; max_timeline_labels outside
+ * 0..2^24; a NaN min_logprob, or one above -inf without note_lp_dev; a null or misaligned workspace, or workspace_bytes below the need.
+ */
+int m2m_score_error_notes(const int32_t* notes_dev, const int32_t* counts_dev, const float* note_lp_dev, int R, int L, int sequential,
+                          double time_step, const double* labels_dev, const int32_t* label_offsets_dev, int n_labels, int n_timelines,
+                          int frame_cap, float min_logprob, int melody_only, int max_timeline_labels, void* workspace_dev,
+                          int64_t workspace_bytes, int32_t* notes_out_dev, int32_t* counts_out_dev, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Audio ingest: the sample bytes of a WAVE file -> mono fp32 -> another sample rate, zero-padded; replaces, for the files it
  * takes, the host step of ref: music2midi/model.py:83-84 (librosa.load).  The definitions are music2midi_amd/audio.py (read_wav,

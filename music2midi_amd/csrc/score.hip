@@ -18,6 +18,7 @@
 //           integer maxima, labels and output side by side; the n_frames - 1 cut and the two counts follow from the tile in LDS, one
 //           integer atomic add per count and workgroup.  The melody never goes to memory.
 #include "common.h"
+#include "score_frames.h"
 
 #include <math.h>
 
@@ -29,24 +30,9 @@ constexpr int SC_MAX_L = M2M_SCORE_MAX_TOKENS;
 constexpr int SC_TILE = 2048;          // frames of one timeline per workgroup of the counts kernel (2 x 8 KiB of LDS)
 constexpr int SC_EOS = 2, SC_ONSET = 3, SC_OFFSET = 4;
 
-// The host's frame arithmetic (music2midi_amd/evaluation.py), float64, one rounded operation per line of the definition:
-//   n_frames = len(np.arange(0, end, 1 / fs)) = ceil(end / (1 / fs)),   a note sounds in [int(start * fs), int(end * fs)),   fs = 100.
-// 1.0 / 100.0 is folded to the double Python's 1 / 100 is; no contraction or reassociation may touch these lines.
+// The frame arithmetic (sc_frame_count, sc_frame_pos, sc_seconds and the saturating conversions) is score_frames.h, shared with
+// frame_roll.hip.  No contraction or reassociation may touch the float sums below either.
 #pragma clang fp contract(off)
-__host__ __device__ inline double sc_frame_count(double end) { return ceil(end / (1.0 / 100.0)); }
-__host__ __device__ inline double sc_frame_pos(double t) { return t * 100.0; }
-// seconds of time index idx, as notes[:, :2] * time_step computes them
-__device__ inline double sc_seconds(int idx, double time_step) { return (double)idx * time_step; }
-
-// saturating conversions: anything at or beyond `cap` becomes cap + 1 / cap (the caller treats it as "too long")
-__device__ inline int sc_count_capped(double end, int cap) {
-  const double f = sc_frame_count(end);
-  return f > (double)cap ? cap + 1 : (int)f;
-}
-__device__ inline int sc_pos_capped(double t, int cap) {
-  const double f = sc_frame_pos(t);
-  return f >= (double)cap ? cap : (int)f;
-}
 
 // SCORED: lp is the log-probability of every id, column-aligned.  Every sum below is one rounded float32 add, in the order of
 // music2midi_amd/confidence.py (note_logprobs): (time + mode) + pitch per emission, on + off per note; contraction is off above.

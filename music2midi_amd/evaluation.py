@@ -143,3 +143,67 @@ def note_scores_host(tokenizer, token_ids, notes_batch, mode: str = "batched", d
             tp, n_ref, n_est = match_counts(want, got, onset_tolerance, offset_ratio, offset_min_tolerance)
             counts[t, k] = (tp, n_est, n_ref)
     return note_scores(counts[:, :, 0], counts[:, :, 1], counts[:, :, 2])
+
+
+_FRAME_KEYS = ("tp", "fn", "fp")
+
+
+def frame_scores(tp, fn, fp, melody_tp=None, melody_fn=None, melody_fp=None) -> dict:
+    """The dict the frame-level scorers return, from [T, K] (or [K]) integers: ``tp``, ``fn``, ``fp`` [K] int64 summed over the
+    timelines and ``precision``, ``recall``, ``f1`` [K] float64 of those sums
+    (``note_metrics.precision_recall_f1(tp, tp + fn, tp + fp)``); with the melody roll's integers the same keys again with a
+    ``melody_`` prefix."""
+    from .note_metrics import precision_recall_f1
+    out = {}
+    for prefix, triple in (("", (tp, fn, fp)), ("melody_", (melody_tp, melody_fn, melody_fp))):
+        if triple[0] is None:
+            continue
+        a, b, c = (np.asarray(x, dtype=np.int64).reshape(-1, np.shape(x)[-1]).sum(axis=0) for x in triple)
+        prf = np.asarray([precision_recall_f1(i, i + j, i + k) for i, j, k in zip(a.tolist(), b.tolist(), c.tolist())],
+                         dtype=np.float64).reshape(-1, 3)
+        out.update({prefix + "precision": prf[:, 0].copy(), prefix + "recall": prf[:, 1].copy(), prefix + "f1": prf[:, 2].copy(),
+                    prefix + "tp": a, prefix + "fn": b, prefix + "fp": c})
+    return out
+
+
+def frame_scores_tokens(tokenizer, token_ids, notes_batch, mode: str = "batched", duration_per_batch=None, token_logprobs=None,
+                        thresholds=None) -> dict:
+    """Frame-level precision, recall and F1 (``music2midi_amd.frame_metrics``: the piano rolls at 100 frames per second of
+    ref plot_midi.py's ``evaluate_midi_result``) of token ids that are on the GPU against their label notes, for every confidence
+    threshold of ``thresholds`` (``None``: ``[0.0]``), computed there (``scoring.frame_counts``, csrc/frame_roll.hip):
+    ``{"precision", "recall", "f1"}`` [K] float64, micro-averaged over the timelines, ``{"tp", "fn", "fp"}`` [K] int64, and the same
+    six with a ``melody_`` prefix for the 12-row melody roll.  Positive thresholds need ``token_logprobs``; ``ValueError`` for labels
+    the device path does not take."""
+    from .scoring import frame_counts
+    c = frame_counts(tokenizer, token_ids, notes_batch, mode, duration_per_batch, token_logprobs=token_logprobs, thresholds=thresholds)
+    return frame_scores(c.tp, c.fn, c.fp, c.melody_tp, c.melody_fn, c.melody_fp)
+
+
+def frame_scores_host(tokenizer, token_ids, notes_batch, mode: str = "batched", duration_per_batch=None, token_logprobs=None,
+                      thresholds=None) -> dict:
+    """``frame_scores_tokens`` by the definition alone, for ids anywhere and any labels: ``confidence.decode_with_confidence`` per
+    threshold (``tokenizer.decode`` without log-probabilities), then ``frame_metrics.frame_counts`` per timeline."""
+    from .frame_metrics import frame_counts
+    from .scoring import threshold_logprobs
+    threshold_logprobs(thresholds, token_logprobs is not None, "frame_scores_host")
+    values = [0.0] if thresholds is None else [float(c) for c in thresholds]
+    labels = [notes_batch] if mode == "sequential" else list(notes_batch)
+    counts = np.zeros((len(labels), len(values), 6), dtype=np.int64)
+    for k, c in enumerate(values):
+        if token_logprobs is None:
+            decoded = tokenizer.decode(token_ids, mode=mode, duration_per_batch=duration_per_batch)
+        else:
+            from .confidence import decode_with_confidence
+            decoded, _ = decode_with_confidence(tokenizer, token_ids, token_logprobs, mode, duration_per_batch, c)
+        decoded = [decoded] if mode == "sequential" else list(decoded)
+        if len(decoded) != len(labels):
+            raise ValueError(f"frame_scores_host: {len(labels)} label arrays for {len(decoded)} timelines")
+        for t, (want, got) in enumerate(zip(labels, decoded)):
+            counts[t, k] = frame_counts(want, got)
+    return frame_scores(*(counts[:, :, i] for i in range(6)))
+
+
+def evaluate_midi_result(target, predict, melody_only: bool = False):
+    """ref plot_midi.py:102-135: the MIDI object with the instruments TP, FN, FP (``frame_metrics.evaluate_midi_result``)."""
+    from .frame_metrics import evaluate_midi_result as definition
+    return definition(target, predict, melody_only)

@@ -23,7 +23,8 @@ from .audio import load_audio as _load_audio
 from .checkpoint import load_t5_state, read_checkpoint
 from .confidence import confidence_velocities, decode_with_confidence, min_logprob
 from .config import inference_beams, load_config
-from .evaluation import evaluate_batch, evaluate_tokens, note_scores_host, note_scores_tokens
+from .evaluation import (evaluate_batch, evaluate_tokens, frame_scores_host, frame_scores_tokens, note_scores_host,
+                         note_scores_tokens)
 from .input import ModelInputs
 from .transformer import T5Transformer
 from .utils import numpy_to_midi
@@ -629,3 +630,65 @@ class Music2MIDI(nn.Module):
         score = note_scores_tokens if _on_device_scorable(token_ids, [label_notes]) else note_scores_host
         return score(self.model.tokenizer, token_ids, label_notes, "sequential", duration, token_logprobs=lps, thresholds=thresholds,
                      offset_ratio=offset_ratio)
+
+    # -- frame-level precision / recall / F1 and the TP / FN / FP error roll (music2midi_amd.frame_metrics) -----------------
+    @torch.no_grad()
+    def frame_scores_batch(self, inputs: ModelInputs, thresholds=None) -> dict:
+        """Frame-level precision, recall and F1 of one labelled batch for every confidence threshold of ``thresholds`` (``None``:
+        ``[0.0]``), on the full piano roll and, with a ``melody_`` prefix, on the 12-row melody roll: ``note_scores_batch``'s decode
+        and routing, then the rolls on the device, one launch for all thresholds (``evaluation.frame_scores_tokens``).  Ids that are
+        not on a GPU, or labels the device path does not take, are scored by the definition from the same ids."""
+        _single_process("frame_scores_batch", "score the decoded notes on the host")
+        scored = _any_positive(thresholds)
+        if scored:
+            budget = 4 * max(len(n) for n in inputs.notes_batch)
+            token_ids, lps = _scored_decode(self.model, self.config, self._grammar_kwargs(), inputs, budget)
+        else:
+            token_ids, lps = _labelled_token_ids(self.model, self.config, self._grammar_kwargs(), inputs), None
+        score = frame_scores_tokens if _on_device_scorable(token_ids, inputs.notes_batch) else frame_scores_host
+        return score(self.model.tokenizer, token_ids, inputs.notes_batch, "batched", None, token_logprobs=lps, thresholds=thresholds)
+
+    def _recording_token_ids(self, audio_path, audio_y, sr, cond_index, scored: bool):
+        """(ids [segments, W], log-probabilities or ``None``) of a whole recording: ``note_scores_recording``'s decode."""
+        padded, seg = self._padded_segments(audio_path, audio_y, sr)
+        if scored:
+            return self.sample_scored_rows(padded, seg, cond_index)
+        rows = self.sample_token_rows(padded, seg, cond_index=cond_index)
+        width = max(int(r.shape[0]) for r in rows)
+        pad = self.model.geometry.pad_token_id
+        return torch.stack([torch.nn.functional.pad(r, (0, width - int(r.shape[0])), value=pad) for r in rows]), None
+
+    @torch.no_grad()
+    def frame_scores_recording(self, label_notes: np.ndarray, audio_path=None, audio_y=None, sr=None, cond_index=None,
+                               thresholds=None) -> dict:
+        """``frame_scores_batch``'s dict for a whole recording against its label notes: ``note_scores_recording``'s segmentation and
+        chunked decode, the sequential detokenising and the rolls on the device.  One GPU, greedy when a threshold is positive."""
+        _single_process("frame_scores_recording", "score generate()'s notes on the host")
+        token_ids, lps = self._recording_token_ids(audio_path, audio_y, sr, cond_index, _any_positive(thresholds))
+        score = frame_scores_tokens if _on_device_scorable(token_ids, [label_notes]) else frame_scores_host
+        return score(self.model.tokenizer, token_ids, label_notes, "sequential", self.config.dataset.segment_duration, token_logprobs=lps,
+                     thresholds=thresholds)
+
+    @torch.no_grad()
+    def error_midi_recording(self, label_notes: np.ndarray, audio_path=None, audio_y=None, sr=None, cond_index=None,
+                             melody_only: bool = False, min_confidence: Optional[float] = None):
+        """Where the transcription of a recording is right, misses and adds: the MIDI object with the instruments TP, FN and FP
+        (programs 0, 1, 2) of ``frame_metrics.evaluate_midi_result(label_notes, generate_notes(...), melody_only)``, with the rolls
+        and the notes extracted on the device (``scoring.error_notes``); it can be ``.write()``n and ``.synthesize()``d.
+        ``min_confidence`` as in ``score_recording``.  Ids that are not on a GPU, or labels the device path does not take, go
+        through the definition from the same ids.  One GPU only."""
+        from .frame_metrics import error_midi, evaluate_midi_result
+        _single_process("error_midi_recording", "compare generate()'s notes on the host")
+        floor = _min_note_confidence(self.config, min_confidence)
+        token_ids, lps = self._recording_token_ids(audio_path, audio_y, sr, cond_index, floor > 0)
+        tok, duration = self.model.tokenizer, self.config.dataset.segment_duration
+        if _on_device_scorable(token_ids, [label_notes]):
+            from .scoring import error_notes
+            found = error_notes(tok, token_ids, label_notes, "sequential", duration, melody_only=melody_only, token_logprobs=lps,
+                                min_confidence=floor if lps is not None else 0.0)
+            return error_midi(*found.to_numpy()[0])
+        if lps is None:
+            decoded = tok.decode(token_ids, mode="sequential", duration_per_batch=duration)
+        else:
+            decoded, _ = decode_with_confidence(tok, token_ids, lps, "sequential", duration, floor)
+        return evaluate_midi_result(np.asarray(label_notes, dtype=np.float64), decoded, melody_only)

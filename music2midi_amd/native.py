@@ -150,6 +150,13 @@ _SIGNATURES = {
     "m2m_score_note_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
                                         C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "m2m_score_frame_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m2m_score_error_notes_capacity": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "m2m_score_error_notes_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "m2m_score_error_notes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                                        C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "m2m_ingest_resampled_length": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "m2m_ingest_phase_taps": (C.c_int, [C.c_int, C.c_int]),
     "m2m_ingest_pcm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

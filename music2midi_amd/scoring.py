@@ -10,9 +10,13 @@ notes, the same counts, the same float.
                                                                                    -> DeviceNotes   (+ .note_lp, .confidence_numpy())
     chroma_counts(tokenizer, token_ids, notes_batch, mode, duration_per_batch)     -> ChromaCounts  (.correct .voiced .frames .score)
     note_counts(tokenizer, token_ids, notes_batch, ..., token_logprobs, thresholds) -> NoteCounts    (.tp .n_est .n_ref [T, K], .f1 ...)
+    frame_counts(tokenizer, token_ids, notes_batch, ..., token_logprobs, thresholds) -> FrameCounts  (.tp .fn .fp .melody_* [T, K], .f1 ...)
+    error_notes(tokenizer, token_ids, notes_batch, ..., melody_only, min_confidence) -> ErrorNotes  (.to_numpy(): TP / FN / FP notes)
     labels_eligible(notes_batch)                                                   -> bool
 
-``note_counts`` is the note-level matching of ``music2midi_amd.note_metrics`` (csrc/note_match.hip): one launch for every confidence
+``frame_counts`` and ``error_notes`` are the frame-level piano-roll comparison of ``music2midi_amd.frame_metrics``
+(csrc/frame_roll.hip): the true-positive, false-negative and false-positive cells of the two rolls, as counts per threshold and as
+notes.  ``note_counts`` is the note-level matching of ``music2midi_amd.note_metrics`` (csrc/note_match.hip): one launch for every confidence
 threshold of a sweep, the integers equal to the definition's.
 
 ``batched``: row i is clip i, scored against ``notes_batch[i]``; ``sequential``: the rows are the segments of one recording, scored
@@ -422,3 +426,188 @@ def note_counts(tokenizer, token_ids: torch.Tensor, notes_batch, mode: str = "ba
     _raise_for_bad_rows(host[3 * T * Kd:])
     res = np.repeat(host[:3 * T * Kd].reshape(T, Kd, 3).astype(np.int64), K // Kd, axis=1)
     return NoteCounts(res[:, :, 0].copy(), res[:, :, 1].copy(), res[:, :, 2].copy())
+
+
+# ----------------------------------------------------------------------------------------------------------------- frame metrics
+FRAME_TILE = 1024                        # M2M_SCORE_FRAME_TILE: frames of one timeline per workgroup of csrc/frame_roll.hip
+
+
+class FrameCounts:
+    """int64 ``tp``, ``fn``, ``fp`` and ``melody_tp``, ``melody_fn``, ``melody_fp`` of shape [T, K]: per timeline and per threshold,
+    the cells of the piano rolls at 100 frames per second that sound on both sides, in the labels only, in the output only
+    (``frame_metrics.frame_counts``), on the full roll and on the 12-row melody roll; ``frames`` [T] is ``n_frames`` with every
+    output note kept.  ``precision``, ``recall``, ``f1`` and their ``melody_`` forms [K] float64 are micro-averaged: the integers
+    are summed over the timelines first; ``per_timeline_f1`` is [T, K]."""
+
+    def __init__(self, tp, fn, fp, melody_tp, melody_fn, melody_fp, frames):
+        self.tp, self.fn, self.fp = tp, fn, fp
+        self.melody_tp, self.melody_fn, self.melody_fp = melody_tp, melody_fn, melody_fp
+        self.frames = frames
+
+    def _micro(self, prefix: str = "") -> np.ndarray:
+        from .note_metrics import precision_recall_f1
+        tp, fn, fp = (getattr(self, prefix + n).sum(axis=0).tolist() for n in ("tp", "fn", "fp"))
+        return np.asarray([precision_recall_f1(a, a + b, a + c) for a, b, c in zip(tp, fn, fp)], dtype=np.float64).reshape(-1, 3)
+
+    precision = property(lambda self: self._micro()[:, 0].copy())
+    recall = property(lambda self: self._micro()[:, 1].copy())
+    f1 = property(lambda self: self._micro()[:, 2].copy())
+    melody_precision = property(lambda self: self._micro("melody_")[:, 0].copy())
+    melody_recall = property(lambda self: self._micro("melody_")[:, 1].copy())
+    melody_f1 = property(lambda self: self._micro("melody_")[:, 2].copy())
+
+    @property
+    def per_timeline_f1(self) -> np.ndarray:
+        from .note_metrics import precision_recall_f1
+        out = np.zeros(self.tp.shape, dtype=np.float64)
+        for i in np.ndindex(*self.tp.shape):
+            out[i] = precision_recall_f1(self.tp[i], self.tp[i] + self.fn[i], self.tp[i] + self.fp[i])[2]
+        return out
+
+
+def _frame_cap(tokenizer, dn: DeviceNotes, vocab_size: Optional[int], label_frames: int, who: str) -> int:
+    """The bound on n_frames of any timeline the grid is sized for: the labels' and the largest time index a row can hold."""
+    R = int(dn.counts.shape[0])
+    top_index = (R - 1) * dn.steps_per_row + max(0, _vocab_size(tokenizer, vocab_size) - 1 - int(tokenizer.time_token_offset))
+    frame_cap = max(1, label_frames, frame_count(top_index * tokenizer.time_step))
+    if frame_cap > MAX_FRAMES:
+        raise ValueError(f"{who}: a timeline of up to {frame_cap} frames exceeds the device limit of {MAX_FRAMES}")
+    return frame_cap
+
+
+def _enqueue_frame_counts(dn: DeviceNotes, labels_dev: torch.Tensor, offsets_dev: torch.Tensor, min_logprobs_dev: Optional[torch.Tensor],
+                          frame_cap: int) -> torch.Tensor:
+    """The counts kernel of csrc/frame_roll.hip on the current stream, for labels and thresholds that are on the device already:
+    [T * K * 6 + T] int32 - (tp, fn, fp, melody tp, fn, fp) per timeline and threshold, then ``frames`` [T]; K = 1 without
+    thresholds."""
+    R, L = int(dn.notes.shape[0]), int(dn.notes.shape[1])
+    T, n_labels = int(offsets_dev.shape[0]) - 1, int(labels_dev.shape[1])
+    scored = dn.note_lp is not None and min_logprobs_dev is not None
+    K = int(min_logprobs_dev.shape[0]) if scored else 1
+    device = dn.notes.device
+    out = torch.empty(T * K * 6 + T, dtype=torch.int32, device=device)
+    native.check(native.load().m2m_score_frame_counts(
+        dn.notes.data_ptr(), dn.counts.data_ptr(), dn.note_lp.data_ptr() if scored else None, R, L, 1 if dn.mode == "sequential" else 0,
+        float(dn.time_step), labels_dev.data_ptr() if n_labels else None, offsets_dev.data_ptr(), n_labels, T, int(frame_cap),
+        min_logprobs_dev.data_ptr() if scored else None, K, out.data_ptr(), out.data_ptr() + 4 * T * K * 6,
+        native.stream_handle(device)), "m2m_score_frame_counts")
+    return out
+
+
+def frame_counts(tokenizer, token_ids: torch.Tensor, notes_batch, mode: str = "batched", duration_per_batch: Optional[float] = None,
+                 vocab_size: Optional[int] = None, token_logprobs: Optional[torch.Tensor] = None, thresholds=None) -> FrameCounts:
+    """``frame_metrics.frame_counts(labels, decoded notes of at least thresholds[k])`` for ids on the device, for every timeline and
+    every threshold: one detokenise, one launch for all thresholds (csrc/frame_roll.hip), one copy of the integers to the host.
+    ``notes_batch`` as in ``chroma_counts``, ``thresholds`` as in ``note_counts``."""
+    labels = [notes_batch] if mode == "sequential" else list(notes_batch)
+    floors = threshold_logprobs(thresholds, token_logprobs is not None, "frame_counts")
+    K = len(floors)
+    if token_logprobs is None:
+        dn = detokenize(tokenizer, token_ids, mode, duration_per_batch, vocab_size)
+    else:
+        dn = detokenize_scored(tokenizer, token_ids, token_logprobs, mode, duration_per_batch, 0.0, vocab_size)
+    R = int(dn.counts.shape[0])
+    T = 1 if mode == "sequential" else R
+    if len(labels) != T:
+        raise ValueError(f"frame_counts: {len(labels)} label arrays for {T} timelines")
+    try:
+        packed, offsets, label_frames = _pack_labels(labels)
+    except ValueError as e:
+        raise ValueError(str(e).replace("chroma_counts", "frame_counts", 1)) from None
+    if R == 0:
+        empty = np.zeros((0, K), dtype=np.int64)
+        return FrameCounts(*(empty.copy() for _ in range(6)), np.zeros(0, dtype=np.int64))
+    frame_cap = _frame_cap(tokenizer, dn, vocab_size, label_frames, "frame_counts")
+    device = dn.notes.device
+    Kd = K if dn.note_lp is not None else 1                  # without log-probabilities every threshold keeps every note: one column
+    with torch.cuda.device(device):
+        lab = torch.from_numpy(packed).to(device)
+        off = torch.from_numpy(offsets).to(device)
+        thr = torch.from_numpy(floors).to(device) if dn.note_lp is not None else None
+        out = _enqueue_frame_counts(dn, lab, off, thr, frame_cap)
+        host = torch.cat([out, dn.counts]).cpu().numpy()
+    n = 6 * T * Kd
+    _raise_for_bad_rows(host[n + T:])
+    frames = host[n:n + T].astype(np.int64)
+    if (frames < 0).any():
+        raise native.NativeError(f"m2m_score_frame_counts: a timeline is longer than its bound of {frame_cap} frames")
+    res = np.repeat(host[:n].reshape(T, Kd, 6).astype(np.int64), K // Kd, axis=1)
+    return FrameCounts(*(res[:, :, i].copy() for i in range(6)), frames)
+
+
+class ErrorNotes:
+    """The TP / FN / FP rolls of every timeline as notes, on the device: ``notes`` [T, 3, cap, 3] int32 (first frame, end frame,
+    row) - the first ``counts[t, kind]`` of kind TP / FN / FP of timeline t, ordered by end frame, then row - and ``counts`` [T, 3]
+    int32.  A row is a pitch, or a pitch class with ``melody_only``."""
+
+    def __init__(self, notes: torch.Tensor, counts: torch.Tensor, row_counts: torch.Tensor, melody_only: bool):
+        self.notes, self.counts, self.melody_only = notes, counts, melody_only
+        self._row_counts = row_counts
+
+    def to_numpy(self) -> list:
+        """Per timeline ``(tp, fn, fp)``: [n, 4] float64 arrays (start, end, row, velocity 1) with ``start = first / 100`` and
+        ``end = end frame / 100`` in float64 - ``frame_metrics.roll_to_notes`` of ``frame_metrics.error_rolls``."""
+        T = int(self.counts.shape[0])
+        host = torch.cat([self.counts.reshape(-1), self._row_counts]).cpu().numpy()
+        _raise_for_bad_rows(host[3 * T:])
+        counts = host[:3 * T].reshape(T, 3)
+        if (counts < 0).any():
+            raise native.NativeError(f"m2m_score_error_notes: timeline {int(np.argmax((counts < 0).any(axis=1)))} is beyond its bounds")
+        notes = self.notes.cpu().numpy()
+        out = []
+        for t in range(T):
+            kinds = []
+            for q in range(3):
+                frames = notes[t, q, :counts[t, q]]
+                a = np.ones((len(frames), 4), dtype=np.float64)
+                a[:, 0], a[:, 1], a[:, 2] = frames[:, 0] / FS, frames[:, 1] / FS, frames[:, 2]
+                kinds.append(a)
+            out.append(tuple(kinds))
+        return out
+
+
+def error_notes(tokenizer, token_ids: torch.Tensor, notes_batch, mode: str = "batched", duration_per_batch: Optional[float] = None,
+                melody_only: bool = False, token_logprobs: Optional[torch.Tensor] = None, min_confidence: float = 0.0,
+                vocab_size: Optional[int] = None) -> ErrorNotes:
+    """``frame_metrics.error_rolls`` + ``roll_to_notes`` for ids on the device: where the decode of at least ``min_confidence``
+    (positive: needs ``token_logprobs``) is right, misses and adds, as three note lists per timeline in the definition's order,
+    extracted on the device (csrc/frame_roll.hip); the tensors stay there until ``to_numpy()``."""
+    from .confidence import min_logprob
+    labels = [notes_batch] if mode == "sequential" else list(notes_batch)
+    floor = float(min_logprob(min_confidence))
+    if token_logprobs is None:
+        if floor != -np.inf:
+            raise ValueError(f"error_notes: min_confidence={min_confidence} needs token_logprobs")
+        dn = detokenize(tokenizer, token_ids, mode, duration_per_batch, vocab_size)
+    else:
+        dn = detokenize_scored(tokenizer, token_ids, token_logprobs, mode, duration_per_batch, 0.0, vocab_size)
+    R, L = int(dn.notes.shape[0]), int(dn.notes.shape[1])
+    T = 1 if mode == "sequential" else R
+    if len(labels) != T:
+        raise ValueError(f"error_notes: {len(labels)} label arrays for {T} timelines")
+    try:
+        packed, offsets, label_frames = _pack_labels(labels)
+    except ValueError as e:
+        raise ValueError(str(e).replace("chroma_counts", "error_notes", 1)) from None
+    device = dn.notes.device
+    if R == 0:
+        return ErrorNotes(torch.zeros((0, 3, 1, 3), dtype=torch.int32, device=device), torch.zeros((0, 3), dtype=torch.int32, device=device),
+                          dn.counts, bool(melody_only))
+    frame_cap = _frame_cap(tokenizer, dn, vocab_size, label_frames, "error_notes")
+    max_labels, n_labels = int(np.diff(offsets).max()), int(packed.shape[1])
+    lib = native.load()
+    sequential, melody = 1 if mode == "sequential" else 0, 1 if melody_only else 0
+    cap = int(lib.m2m_score_error_notes_capacity(R, L, sequential, max_labels, melody))
+    need = int(lib.m2m_score_error_notes_workspace_bytes(T, frame_cap, melody))
+    with torch.cuda.device(device):
+        lab = torch.from_numpy(packed).to(device)
+        off = torch.from_numpy(offsets).to(device)
+        # (sizes the library will refuse are not allocated for: it answers on the arguments alone)
+        workspace = torch.empty(max(need, 8) // 8, dtype=torch.int64, device=device)
+        notes = torch.empty((T, 3, max(cap, 1), 3), dtype=torch.int32, device=device)
+        counts = torch.empty((T, 3), dtype=torch.int32, device=device)
+        native.check(lib.m2m_score_error_notes(
+            dn.notes.data_ptr(), dn.counts.data_ptr(), dn.note_lp.data_ptr() if dn.note_lp is not None else None, R, L, sequential,
+            float(dn.time_step), lab.data_ptr() if n_labels else None, off.data_ptr(), n_labels, T, frame_cap, floor, melody, max_labels,
+            workspace.data_ptr(), need, notes.data_ptr(), counts.data_ptr(), native.stream_handle(device)), "m2m_score_error_notes")
+    return ErrorNotes(notes, counts, dn.counts, bool(melody_only))

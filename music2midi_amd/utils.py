@@ -54,14 +54,9 @@ class SimpleMIDI:
         return np.asarray(rows, dtype=np.float64).reshape(-1, 4)
 
     def write(self, path) -> None:
-        """Standard MIDI file, format 0, one track."""
+        """Standard MIDI file.  One instrument (or none): format 0, one track.  Several: format 1 - a tempo track, then one track
+        per instrument with its name (a track-name meta event), its program change and its notes on channel ``index % 16``."""
         ticks_per_second = self.resolution * self.initial_tempo / 60.0
-        events = []
-        for inst in self.instruments:
-            for n in inst.notes:
-                events.append((int(round(n.start * ticks_per_second)), 1, 0x90, n.pitch, max(1, min(127, n.velocity))))
-                events.append((int(round(n.end * ticks_per_second)), 0, 0x80, n.pitch, 0))
-        events.sort(key=lambda e: (e[0], e[1]))
 
         def vlq(v):
             out = [v & 0x7F]
@@ -71,17 +66,34 @@ class SimpleMIDI:
                 v >>= 7
             return bytes(reversed(out))
 
-        tempo = int(round(60_000_000 / self.initial_tempo))
-        track = b"\x00\xff\x51\x03" + struct.pack(">I", tempo)[1:]
-        track += b"\x00\xc0" + bytes([self.instruments[0].program if self.instruments else 0])
-        last = 0
-        for tick, _, status, pitch, vel in events:
-            track += vlq(tick - last) + bytes([status, pitch & 0x7F, vel & 0x7F])
-            last = tick
-        track += b"\x00\xff\x2f\x00"
+        def note_events(instruments, channel) -> bytes:
+            events = []
+            for inst in instruments:
+                for n in inst.notes:
+                    events.append((int(round(n.start * ticks_per_second)), 1, 0x90 | channel, n.pitch, max(1, min(127, n.velocity))))
+                    events.append((int(round(n.end * ticks_per_second)), 0, 0x80 | channel, n.pitch, 0))
+            events.sort(key=lambda e: (e[0], e[1]))
+            data, last = b"", 0
+            for tick, _, status, pitch, vel in events:
+                data += vlq(tick - last) + bytes([status, pitch & 0x7F, vel & 0x7F])
+                last = tick
+            return data
+
+        tempo = b"\x00\xff\x51\x03" + struct.pack(">I", int(round(60_000_000 / self.initial_tempo)))[1:]
+        end = b"\x00\xff\x2f\x00"
+        if len(self.instruments) <= 1:
+            program = b"\x00\xc0" + bytes([self.instruments[0].program if self.instruments else 0])
+            tracks = [tempo + program + note_events(self.instruments, 0) + end]
+        else:
+            tracks = [tempo + end]
+            for index, inst in enumerate(self.instruments):
+                channel, name = index % 16, str(inst.name or "").encode("utf-8")
+                tracks.append(b"\x00\xff\x03" + vlq(len(name)) + name + b"\x00" + bytes([0xC0 | channel, int(inst.program) & 0x7F])
+                              + note_events([inst], channel) + end)
         with open(path, "wb") as f:
-            f.write(b"MThd" + struct.pack(">IHHH", 6, 0, 1, self.resolution))
-            f.write(b"MTrk" + struct.pack(">I", len(track)) + track)
+            f.write(b"MThd" + struct.pack(">IHHH", 6, 0 if len(tracks) == 1 else 1, len(tracks), self.resolution))
+            for track in tracks:
+                f.write(b"MTrk" + struct.pack(">I", len(track)) + track)
 
     def synthesize(self, fs=44100) -> np.ndarray:
         """The notes as audio at ``fs``, float64 like ``PrettyMIDI.synthesize``: the wavetable voice of ``music2midi_amd.render``,
