@@ -617,7 +617,14 @@ typedef struct {
 typedef struct m2m_model m2m_model;
 
 /* Repacks the weights into kernel layouts (device-side kernels on `stream`,
- * synchronised before returning); the source tensors may be freed afterwards. */
+ * synchronised before returning); the source tensors may be freed afterwards.
+ * Creation also writes the decoder's layer-0 token tables into the same blob: the
+ * layer-0 self-attention's q (fp32) and k, v (storage type) of every (head, token),
+ * [num_heads][vocab_size][64] each, which the greedy decode step reads instead of
+ * projecting (M2M_DEC_TOKEN_TABLES, read when a session is
+ * created: 0 off, 1 this step's q / k / v, 2 the cached K/V rows as well; default 2).  A model whose tables
+ * would exceed 16 MB, or whose vocabulary is above 65 535, has none and decodes as
+ * with 0.  m2m_model_param_bytes and m2m_model_checksum include them. */
 int  m2m_model_create(const m2m_t5_geometry* geom, const m2m_t5_weights* w, int precision,
                       void* stream, m2m_model** out);
 void m2m_model_destroy(m2m_model* m);

@@ -753,6 +753,11 @@ struct DecAttnArgs {
   int64_t anc_par;
   int anc_ld;
   int beam_nb;
+  // Layer-0 token tables (the TAB instantiations of dec_attn_kernel only; null elsewhere): m2m_model::q0_tab / k0_tab / v0_tab,
+  // [H][V][64] each (q fp32; k, v T).  The row's tokens: the current one from keys[b], the cached positions' from tokens[tok_row[b]].
+  const float* q0_tab;
+  const void* k0_tab;
+  const void* v0_tab;
 };
 
 // K/V rows are read once per step.  When the per-step K/V working set is larger than the 256 MB
@@ -901,6 +906,44 @@ __device__ __forceinline__ void da_merge(const DaSoftmax<T>& sm, const DaMergeLd
   __syncthreads();
 }
 
+// RMSNorm of one row into hn (rounded to the GEMM-input type T) by a 1024-thread workgroup, for dec_token_tables_kernel: thread tid
+// holds elements [xc, xc + 4) of the row (`row()`, evaluated by the owning waves only) and of the norm weight gv; redw: 16
+// cross-wave slots; `mid` runs behind the first barrier.  This RESTATES section 1 of dec_attn_kernel, statement for statement (a
+// change there has to be made here): a table entry must have the step's bits, and the sum of squares is a plain expression that
+// the compiler contracts as it sees fit per kernel.  dec_attn_kernel does not call it because called, every instantiation of that
+// kernel got another instruction schedule in its prologue, while with its own text the instantiations without tables stay
+// instruction for instruction the parent's.  In the ISA the two norms are the same sequence (v_mul, three
+// v_fmac, the same wave_sum and 16-slot sum, the same division, v_rsq and v_pk_mul); tests/test_dec_token_tables_gpu.py holds the
+// bits: every table leg is torch.equal with the projecting one.
+template <typename T, typename Row, typename Mid>
+__device__ __forceinline__ void da_norm_row(Row row, const float4& gv, int xc, int d, float eps, float* redw, float* hn, Mid mid) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool own_wave = wave * 256 < d;           // wave-uniform
+  const bool own = tid * 4 < d;
+  float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (own_wave) {
+    xv = row();
+    float ss = own ? (xv.x * xv.x + xv.y * xv.y + xv.z * xv.z + xv.w * xv.w) : 0.f;
+    ss = wave_sum(ss);
+    if (lane == 0) redw[wave] = ss;
+  } else if (lane == 0) {
+    redw[wave] = 0.f;
+  }
+  __syncthreads();
+  mid();
+  if (own) {
+    float tot = 0.f;
+#pragma unroll
+    for (int wv = 0; wv < 16; ++wv) tot += redw[wv];
+    const float rs = rsqrtf(tot / (float)d + eps);
+    put_in<T>(hn, xc + 0, gv.x * (xv.x * rs));
+    put_in<T>(hn, xc + 1, gv.y * (xv.y * rs));
+    put_in<T>(hn, xc + 2, gv.z * (xv.z * rs));
+    put_in<T>(hn, xc + 3, gv.w * (xv.w * rs));
+  }
+  __syncthreads();
+}
+
 // One projection output of this head for C rows: acc[c] = <weight row, hn row c>, the weight row's 16-byte chunks strided over the
 // LPO lanes of the output (`part`: this lane's), the first WREG of them in registers, the rest (d_model / dtype combinations
 // beyond the register budget: fp32) fetched here; every lane of the output gets the sums.  hn: [C][d], normalised, rounded to T.
@@ -979,10 +1022,18 @@ __device__ __forceinline__ void da_book_row(const DecAttnArgs& a, int b, int st_
   if (b == 0) a.state->t_copy = st_t;      // ALWAYS (also in the no-op steps after the end): the lm_head kernel's "live" test reads it
 }
 
-template <typename T, bool SELF, bool NT, bool FETCH = false, bool BEAM = false>
+// TAB (layer-0 self-attention of the headless greedy step, FETCH; M2M_DEC_TOKEN_TABLES): 1 takes this step's q, k, v from the
+// model's token tables (m2m_model::q0_tab ...: no norm, no projection, no q / k / v weights), 2 also reads the cached K/V rows from
+// the tables, addressed by the row's token history, instead of streaming the cache.  Only FETCH: there the input row IS emb[tok].
+// The steps that read the row from x (teacher-forced, M2M_HEADLESS=0, the select and beam heads) see its fixed-point image, which
+// differs from emb[tok] wherever an element is not a multiple of 2^-30 - their q, k, v are not what the tables hold.
+template <typename T, bool SELF, bool NT, bool FETCH = false, bool BEAM = false, int TAB = 0>
 __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   static_assert(!FETCH || SELF, "only the layer-0 self-attention fetches its input row from the embedding table");
   static_assert(!(FETCH && BEAM), "the beam step is not headless");
+  static_assert(TAB == 0 || FETCH, "the token tables serve the headless layer-0 self-attention: its input row is emb[tok] itself");
+  constexpr bool TABLE = TAB > 0;
+  constexpr bool NTS = NT && TAB != 2;   // the stream's cache policy: table rows are re-read by every clip and step, never non-temporal
   constexpr int E = 16 / sizeof(T);      // elements per 16-byte chunk: 8 (bf16) / 4 (fp32)
   constexpr int LPR = DK / E;            // lanes per key row (a "group"): 8 / 16
   constexpr int KPW = 64 / LPR;          // keys per wave-load: 8 / 4
@@ -1058,11 +1109,17 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
     __syncthreads();
   }
   // element offset of key row `key` (clamped) from Kb / Vb, for this lane's part of it
+  // table form of the stream (TAB == 2): key row `key` is row tokl[key] of this head's k / v table
+  unsigned short* const tokl = reinterpret_cast<unsigned short*>(hn + a.d + (SELF ? a.bias_stride : 0));   // [kv_stride] (TAB == 2)
   auto kvoff = [&](int key) -> int64_t {
+    if constexpr (TAB == 2) return (int64_t)tokl[key] * DK + sub * E;
     int64_t o = (int64_t)key * DK + sub * E;
     if constexpr (BEAM && SELF) o += ((int64_t)ancl[key] - beam) * ((int64_t)a.H * a.kv_stride * DK);
     return o;
   };
+  // where the stream reads from: the row's cache block, or (TAB == 2) this head's tables
+  const T* const Ks = TAB == 2 ? reinterpret_cast<const T*>(a.k0_tab) + (int64_t)hh * a.V * DK : Kb;
+  const T* const Vs = TAB == 2 ? reinterpret_cast<const T*>(a.v0_tab) + (int64_t)hh * a.V * DK : Vb;
 
   // ---- 0. requests for the prologue: x row, norm weights, this lane's projection weights.
   //         Every kernel starts with a cold L2 for data other XCDs produced, so these come from
@@ -1077,24 +1134,37 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   xq_t xres = 0;
   unsigned long long kraw = 0;
   int fin0 = 0;
+  const int64_t* hrow = nullptr;  // table form: the row's tokens
   if constexpr (FETCH) {          // headless layer 0: the row is an embedding row, chosen by the previous step's arg-max key
     kraw = a.keys[b];
     fin0 = a.finished[b];
+    if constexpr (TABLE) hrow = a.tokens + (int64_t)a.tok_row[b] * a.max_len;
   } else {
     xr0 = *reinterpret_cast<const longlong2*>(a.x + (int64_t)b * a.d + xc);
     xr1 = *reinterpret_cast<const longlong2*>(a.x + (int64_t)b * a.d + xc + 2);
     // head 0 also carries the residual row into x_out: its raw fixed-point value, requested now
     xres = a.x[(int64_t)b * a.d + on_];   // unconditional: a branch would split the block of loads
   }
-  const float4 gv = *reinterpret_cast<const float4*>(a.ln_w + xc);
+  // table form, cached K/V from the tables: the ids of the cached positions, HPT per thread in registers (2048 positions; more:
+  // the loop below), addresses clamped into the row's written part
+  constexpr int HPT = 2;
+  int64_t hv[TAB == 2 ? HPT : 1];
+  if constexpr (TAB == 2) {
+#pragma unroll
+    for (int u = 0; u < HPT; ++u) hv[u] = hrow[min(tid + 1024 * u, max(st_t - 1, 0))];
+  }
+  float4 gv = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (!TABLE) gv = *reinterpret_cast<const float4*>(a.ln_w + xc);
   __builtin_amdgcn_sched_barrier(0);               // the latency-critical row goes out FIRST (loads retire in order)
   const int po = min(tid / LPO, NOUT - 1), part = tid % LPO;
   const int which = po / DK, dd = po - which * DK;
   const T* wrow = reinterpret_cast<const T*>(a.Wp) + ((int64_t)which * a.inner + hh * DK + dd) * a.d;
   const int cnt = a.d / E / LPO;         // chunks per lane
-  Vec16<T> w[WMAX];
+  Vec16<T> w[TABLE ? 1 : WMAX];
+  if constexpr (!TABLE) {
 #pragma unroll
-  for (int u = 0; u < WMAX; ++u) w[u].v = *reinterpret_cast<const V16*>(wrow + (min(u, cnt - 1) * LPO + part) * E);
+    for (int u = 0; u < WMAX; ++u) w[u].v = *reinterpret_cast<const V16*>(wrow + (min(u, cnt - 1) * LPO + part) * E);
+  }
   // self: this head's relative-position bias row goes to LDS.  Read from global memory inside the key
   // loop it would sit behind the next round's K/V request in the wave's in-order vmcnt queue: the
   // compiler then has to wait vmcnt(0) every round, and the stream runs at one round per memory latency.
@@ -1115,11 +1185,13 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
 
   // ---- 1. RMSNorm of x[b] -> hn (rounded to the GEMM-input type T) ----
   Vec16<T> kv[PF], vv[PF];
+  if constexpr (TAB != 2) {        // (TAB == 2: the stream's addresses are token ids, requested once those are in LDS)
 #pragma unroll
-  for (int u = 0; u < PF; ++u) {   // clamped addresses, never predicated
-    const int64_t off = kvoff(min(kslot + u * KPB, last));
-    kv[u].v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Kb + off));
-    vv[u].v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Vb + off));
+    for (int u = 0; u < PF; ++u) {   // clamped addresses, never predicated
+      const int64_t off = kvoff(min(kslot + u * KPB, last));
+      kv[u].v = kv_load<NTS>(reinterpret_cast<const V16*>(Ks + off));
+      vv[u].v = kv_load<NTS>(reinterpret_cast<const V16*>(Vs + off));
+    }
   }
   // everything above is in flight before anything waits: without the fence the scheduler places the wait for x
   // (and its int64 -> float conversion) ahead of the weight loads and of the K/V prefetch (the ISA showed the
@@ -1132,13 +1204,33 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
   float eres = 0.f;
   float4 e4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  int tok = 0;
   if constexpr (FETCH) {          // second (dependent) round trip of the headless prologue: the embedding row
-    const int tok = amax_key_token(kraw, fin0, a.V, a.pad_id);
+    tok = amax_key_token(kraw, fin0, a.V, a.pad_id);
     const float* er = a.emb + (int64_t)tok * a.d;
-    e4 = *reinterpret_cast<const float4*>(er + xc);
+    if constexpr (!TABLE) e4 = *reinterpret_cast<const float4*>(er + xc);
     eres = er[on_];
   }
-  {
+  if constexpr (TABLE) {
+    // Table form: q, k, v of this row are the entries (head, tok) of the model's tables - what the norm and the two da_project
+    // calls below would produce from emb[tok], bit for bit (dec_token_tables_kernel runs them).  Thread tid < 64 publishes q[tid],
+    // tid < 128 appends k (tid < 64) or v through da_append_kv: the cache stays valid for every other reader of layer 0.
+    const int64_t trow = ((int64_t)hh * a.V + tok) * DK;
+    const int dd2 = tid & 63, which2 = 1 + ((tid >> 6) & 1);
+    const float qe = a.q0_tab[trow + dd2];
+    const T kve = (which2 == 1 ? reinterpret_cast<const T*>(a.k0_tab) : reinterpret_cast<const T*>(a.v0_tab))[trow + dd2];
+    if (tid < DK) qs[dd2] = qe;
+    if (tid < 2 * DK) da_append_kv<T>(to_f32(kve), 0, which2, dd2, t, 0, Kb, Vb, kn, vn, !st_done);   // (T -> fp32 -> T is the identity)
+    if constexpr (TAB == 2) {
+      // ids of the cached positions -> LDS, 16 bits each, clamped into the table: an unwritten position addresses a row of it
+      const int nh = max(t, 1);
+#pragma unroll
+      for (int u = 0; u < HPT; ++u)
+        if (tid + 1024 * u < nh) tokl[tid + 1024 * u] = (unsigned short)min(max(hv[u], (int64_t)0), (int64_t)a.V - 1);
+      for (int n = tid + 1024 * HPT; n < nh; n += 1024) tokl[n] = (unsigned short)min(max(hrow[min(n, last)], (int64_t)0), (int64_t)a.V - 1);
+    }
+  }
+  if constexpr (!TABLE) {
     const bool own = tid * 4 < a.d;
     if (own_wave) {
       if constexpr (FETCH) xv = e4;
@@ -1166,7 +1258,7 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   }
 
   // ---- 2. this head's projection: NOUT outputs, LPO lanes each, 16-byte chunks strided over lanes ----
-  {
+  if constexpr (!TABLE) {
     float q[1];
     da_project<T, 1, LPO>(q, w, wrow, cnt, part, hn, a.d);
 #ifndef M2M_STAMPS_MERGE
@@ -1182,6 +1274,14 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   }
   __syncthreads();
   M2M_STAMP(6 + (SELF ? 1 : 0), 1);
+  if constexpr (TAB == 2) {          // the first PF rounds of the table gather (L2 hits on the head's XCD), in front of the wo loads
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {   // clamped addresses, never predicated
+      const int64_t off = kvoff(min(kslot + u * KPB, last));
+      kv[u].v = kv_load<NTS>(reinterpret_cast<const V16*>(Ks + off));
+      vv[u].v = kv_load<NTS>(reinterpret_cast<const V16*>(Vs + off));
+    }
+  }
 
   // this head's slice of the output projection (2 lanes per output column, 32 inputs each):
   // requested now so it arrives under the K/V stream
@@ -1196,8 +1296,8 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   const int which2 = 1 + (o2 >> 6), dd2 = o2 & 63;
   const T* wrow2 = reinterpret_cast<const T*>(a.Wp) + ((int64_t)which2 * a.inner + hh * DK + dd2) * a.d;
   const int cnt2 = a.d / E / LPO2;
-  Vec16<T> wkv[SELF ? WMAX2 : 1];
-  if (SELF) {
+  Vec16<T> wkv[SELF && !TABLE ? WMAX2 : 1];
+  if (SELF && !TABLE) {
 #pragma unroll
     for (int u = 0; u < WMAX2; ++u) wkv[u].v = *reinterpret_cast<const V16*>(wrow2 + (min(u, cnt2 - 1) * LPO2 + part2) * E);
   }
@@ -1229,8 +1329,8 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
     for (int e = 0; e < E; ++e) vrow[e] = vs.get(e);
     if (reissue == 1 || (reissue == 2 && k0 + (u + PF) * KPB < n_live)) {   // workgroup-uniform, no lane is predicated
       const int64_t off = kvoff(min(key + PF * KPB, last));
-      ks.v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Kb + off));
-      vs.v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Vb + off));
+      ks.v = kv_load<NTS>(reinterpret_cast<const V16*>(Ks + off));
+      vs.v = kv_load<NTS>(reinterpret_cast<const V16*>(Vs + off));
     }
     if (key < n_live) {   // VALU-only predicate
       if (SELF) s += biasl[t - key];
@@ -1250,8 +1350,8 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
     }
     if (reissue == 1 || (reissue == 2 && k0 + (u + PF) * KPB < n_live)) {   // workgroup-uniform, no lane is predicated
       const int64_t off = kvoff(min(key + PF * KPB, last));
-      ks.v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Kb + off));
-      vs.v = M2M_KV_LOAD(reinterpret_cast<const V16*>(Vb + off));
+      ks.v = kv_load<NTS>(reinterpret_cast<const V16*>(Ks + off));
+      vs.v = kv_load<NTS>(reinterpret_cast<const V16*>(Vs + off));
     }
 #endif
   };
@@ -1267,8 +1367,8 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
 #pragma unroll
     for (int u = 0; u < PF; ++u) round(k0, u, kv[u], vv[u], 2);
   }
-  if (SELF) {
-    // project, round to T, append to the cache and publish through LDS the k,v rows of this step
+  if constexpr (SELF && !TABLE) {
+    // project, round to T, append to the cache and publish through LDS the k,v rows of this step (table form: done in the prologue)
     float kvn[1];
     da_project<T, 1, LPO2>(kvn, wkv, wrow2, cnt2, part2, hn, a.d);
     if (part2 == 0) da_append_kv<T>(kvn[0], 0, which2, dd2, t, 0, Kb, Vb, kn, vn, !st_done);
@@ -1288,6 +1388,63 @@ __global__ __launch_bounds__(1024) void dec_attn_kernel(DecAttnArgs a) {
   da_out_row<T>(a, wo, oh, b, !st_done, true, [&] { return FETCH ? xq_fix_guarded(eres, a.state) : xres; });
   if (!SELF && a.book && hh == 0 && tid == 0) da_book_row(a, b, st_t, st_done);
   M2M_STAMP(6 + (SELF ? 1 : 0), 3);
+}
+
+// ---- the layer-0 token tables (t5.h m2m_model::q0_tab / k0_tab / v0_tab; run once in m2m_model_create) ----
+// Workgroup (head, tok) computes what dec_attn_kernel<T, true, NT, FETCH = true> computes from emb[tok] in front of its stream: the
+// same thread -> element maps and the same calls (da_norm_row; da_project<T, 1, LPO> for q, kept fp32; da_project<T, 1, LPO2> +
+// from_f32<T> for k, v), with the same weights in registers - so that an entry has the bits the step would have produced, and the
+// table form of the step changes where bytes come from and nothing else (tests/test_dec_token_tables_gpu.py: torch.equal).
+template <typename T>
+__global__ __launch_bounds__(1024) void dec_token_tables_kernel(const float* __restrict__ emb, const float* __restrict__ ln_w, const T* __restrict__ Wp,
+                                                                int d, int inner, int V, float eps, float* __restrict__ q0, T* __restrict__ k0,
+                                                                T* __restrict__ v0) {
+  constexpr int E = 16 / sizeof(T), NOUT = DK, LPO = 16, LPO2 = 8, WMAX = 3, WMAX2 = 6;   // dec_attn_kernel's
+  using V16 = decltype(Vec16<T>().v);
+  extern __shared__ __align__(16) float hn[];
+  __shared__ float redw[16];
+  const int tid = threadIdx.x, hh = blockIdx.x, tok = blockIdx.y;
+  const int xc = min(tid * 4, d - 4);
+  const float4 gv = *reinterpret_cast<const float4*>(ln_w + xc);
+  const float4 e4 = *reinterpret_cast<const float4*>(emb + (int64_t)tok * d + xc);
+  const int po = min(tid / LPO, NOUT - 1), part = tid % LPO;
+  const int which = po / DK, dd = po - which * DK;
+  const T* wrow = Wp + ((int64_t)which * inner + hh * DK + dd) * d;
+  const int cnt = d / E / LPO;
+  Vec16<T> w[WMAX];
+#pragma unroll
+  for (int u = 0; u < WMAX; ++u) w[u].v = *reinterpret_cast<const V16*>(wrow + (min(u, cnt - 1) * LPO + part) * E);
+  const int o2 = tid >> 3, part2 = tid & 7;
+  const int which2 = 1 + (o2 >> 6), dd2 = o2 & 63;
+  const T* wrow2 = Wp + ((int64_t)which2 * inner + hh * DK + dd2) * d;
+  const int cnt2 = d / E / LPO2;
+  Vec16<T> wkv[WMAX2];
+#pragma unroll
+  for (int u = 0; u < WMAX2; ++u) wkv[u].v = *reinterpret_cast<const V16*>(wrow2 + (min(u, cnt2 - 1) * LPO2 + part2) * E);
+  da_norm_row<T>([&] { return e4; }, gv, xc, d, eps, redw, hn, [] {});
+  const int64_t trow = ((int64_t)hh * V + tok) * DK;
+  float q[1], kvn[1];
+  da_project<T, 1, LPO>(q, w, wrow, cnt, part, hn, d);
+  if (part == 0 && tid < NOUT * LPO) q0[trow + dd] = q[0];
+  da_project<T, 1, LPO2>(kvn, wkv, wrow2, cnt2, part2, hn, d);
+  if (part2 == 0) (which2 == 1 ? k0 : v0)[trow + dd2] = from_f32<T>(kvn[0]);
+}
+
+int launch_token_tables(const m2m_model* m, hipStream_t st) {
+  if (!m->q0_tab) return M2M_OK;
+  const m2m_t5_geometry& g = m->g;
+  const DecLayerPacked& L = m->dec[0];
+  const dim3 grid((unsigned)g.num_heads, (unsigned)g.vocab_size);      // vocab_size <= 65 535 (the gate of m2m_model_create)
+  const size_t smem = (size_t)g.d_model * sizeof(float);
+  float* q0 = const_cast<float*>(m->q0_tab);
+  if (m->precision == M2M_PREC_BF16)
+    hipLaunchKernelGGL(dec_token_tables_kernel<bf16_t>, grid, dim3(1024), smem, st, m->shared, L.ln0, (const bf16_t*)L.wqkv, g.d_model, m->inner,
+                       g.vocab_size, g.layer_norm_eps, q0, (bf16_t*)const_cast<void*>(m->k0_tab), (bf16_t*)const_cast<void*>(m->v0_tab));
+  else
+    hipLaunchKernelGGL(dec_token_tables_kernel<float>, grid, dim3(1024), smem, st, m->shared, L.ln0, (const float*)L.wqkv, g.d_model, m->inner,
+                       g.vocab_size, g.layer_norm_eps, q0, (float*)const_cast<void*>(m->k0_tab), (float*)const_cast<void*>(m->v0_tab));
+  M2M_CHECK_HIP(hipGetLastError());
+  return M2M_OK;
 }
 
 // ---- the same kernel for LARGE chains: C clips of one head per workgroup (round 6) ----
@@ -1795,9 +1952,14 @@ static void launch_dec_attn_form(bool self, bool nt, const DecAttnArgs& a, F lau
   }
 }
 
+// (tab: the token-table form of the layer-0 self-attention, 0 / 1 / 2 - decode_launch_attn decides)
 template <typename T>
-static void launch_dec_attn_t(bool self, bool nt, const DecAttnArgs& a, dim3 grid, size_t smem, hipStream_t st) {
+static void launch_dec_attn_t(bool self, bool nt, int tab, const DecAttnArgs& a, dim3 grid, size_t smem, hipStream_t st) {
   launch_dec_attn_form(self, nt, a, [&](auto s, auto n, auto f, auto bm) {
+    if constexpr (f.value) {
+      if (tab == 1) { hipLaunchKernelGGL((dec_attn_kernel<T, true, n.value, true, false, 1>), grid, dim3(1024), smem, st, a); return; }
+      if (tab == 2) { hipLaunchKernelGGL((dec_attn_kernel<T, true, n.value, true, false, 2>), grid, dim3(1024), smem, st, a); return; }
+    }
     hipLaunchKernelGGL((dec_attn_kernel<T, s.value, n.value, f.value, bm.value>), grid, dim3(1024), smem, st, a);
   });
 }
@@ -1822,17 +1984,20 @@ static void launch_dec_attn_mc_t(bool self, bool nt, const DecAttnArgs& a, int n
   });
 }
 
-static int launch_dec_attn(int precision, bool self, bool nt, DecAttnArgs a, int B, int clips, int cif, hipStream_t st) {
+static int launch_dec_attn(int precision, bool self, bool nt, int tab, DecAttnArgs a, int B, int clips, int cif, hipStream_t st) {
   size_t smem = ((size_t)a.d * (size_t)clips + (self ? (size_t)a.bias_stride : 0)) * sizeof(float);   // hn rows + (self) the bias row
   if (self && a.beam_nb > 0) smem += (size_t)clips * a.kv_stride;         // + the rows' ancestries (a byte per position)
+  M2M_REQUIRE(tab == 0 || (self && clips == 1 && a.beam_nb == 0 && a.emb && a.q0_tab && a.k0_tab && a.v0_tab && a.tokens && a.tok_row),
+              "decode attention: the token-table form %d needs the one-clip headless layer-0 self-attention, the model's tables and the row's tokens", tab);
+  if (tab == 2) smem += ((size_t)a.kv_stride * 2 + 3) / 4 * 4;            // + the row's token history (16 bits per position)
   M2M_REQUIRE(smem <= 24 * 1024, "decode attention: max_dec_len=%d too long for the LDS bias row%s (<= %d)", a.bias_stride,
               self && a.beam_nb > 0 ? " and ancestries" : "",
               (24 * 1024 - a.d * 4 * clips) / (self && a.beam_nb > 0 ? 4 + clips : 4));
   const bool bf = precision == M2M_PREC_BF16;
   if (clips == 1) {
     dim3 grid((unsigned)a.H, (unsigned)B);
-    if (bf) launch_dec_attn_t<bf16_t>(self, nt, a, grid, smem, st);
-    else launch_dec_attn_t<float>(self, nt, a, grid, smem, st);
+    if (bf) launch_dec_attn_t<bf16_t>(self, nt, tab, a, grid, smem, st);
+    else launch_dec_attn_t<float>(self, nt, tab, a, grid, smem, st);
   } else if (clips == 2) {
     if (bf) launch_dec_attn_mc_t<bf16_t, 2>(self, nt, a, B, cif, smem, st);
     else launch_dec_attn_mc_t<float, 2>(self, nt, a, B, cif, smem, st);
@@ -3040,7 +3205,14 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
     a.Vc = (unsigned char*)s->self_v + off;
     a.kv_stride = s->max_dec; a.n_keys = 0; a.self_len_override = self_len;
     a.bias = s->dec_bias_tab; a.bias_stride = s->max_dec;
-    return launch_dec_attn(m->precision, true, nt, a, v.nb, clips, s->sw.mc_cif, st);
+    // Layer 0 from the token tables (M2M_DEC_TOKEN_TABLES, latched per session): the one-clip kernel of the headless greedy step,
+    // on a model that has tables.  Every other form (several clips per workgroup, the teacher-forced, beam, sampled, processed and
+    // scored steps, M2M_HEADLESS=0, the bench's length override) projects and streams the cache, which the table form keeps
+    // appending to.
+    int tab = 0;
+    if (layer == 0 && clips == 1 && !beam && self_len <= 0 && m->q0_tab && a.emb) tab = s->sw.token_tables;
+    if (tab) { a.q0_tab = m->q0_tab; a.k0_tab = m->k0_tab; a.v0_tab = m->v0_tab; }
+    return launch_dec_attn(m->precision, true, nt, tab, a, v.nb, clips, s->sw.mc_cif, st);
   }
   // cross K/V: [L][2][B][H][S][64] with B, S = the encoded problem
   const size_t per = (size_t)s->B * H * s->S * DK;
@@ -3049,7 +3221,7 @@ int decode_launch_attn(m2m_session* s, const DecView& v, bool self, int layer, i
   a.Kc = (unsigned char*)s->cross_kv + (((size_t)layer * 2 + 0) * per + voff) * es;
   a.Vc = (unsigned char*)s->cross_kv + (((size_t)layer * 2 + 1) * per + voff) * es;
   a.kv_stride = s->S; a.n_keys = s->S; a.self_len_override = 0; a.bias = nullptr; a.bias_stride = 0;
-  return launch_dec_attn(m->precision, false, nt, a, v.nb, clips, s->sw.mc_cif, st);
+  return launch_dec_attn(m->precision, false, nt, 0, a, v.nb, clips, s->sw.mc_cif, st);
 }
 
 int decode_launch_step(m2m_session* s, const DecView& v, bool forced, float* logits_out, int Ld, hipStream_t st) {

@@ -45,6 +45,7 @@ struct DecLayerPacked {
 
 constexpr int FF_IMG_FRAG = 512;                 // elements of one fragment load of a wave in the feed-forward image
 constexpr int FF_IMG_WAVE = 12 * FF_IMG_FRAG;    // elements of a wave's block: 8 fragments of wi, 4 of wo_ff
+constexpr int64_t TOKEN_TABLES_MAX_BYTES = 16ll << 20;   // m2m_model::q0_tab / k0_tab / v0_tab: no tables beyond this (T5's own 32 128-token vocabulary: 131 MB)
 
 }  // namespace m2m
 
@@ -63,6 +64,13 @@ struct m2m_model {
   const float* shared = nullptr;     // [V, d] fp32 (feeds the fp32 residual stream)
   const void* lm_head = nullptr;     // [vocab_pad, d]
   const void* wckv = nullptr;        // [L_dec * 2 * inner, d]  per layer: ck rows then cv rows
+  // Layer-0 token tables (decode.hip dec_token_tables_kernel, written once in m2m_model_create): the decoder's layer-0 input row is
+  // emb[tok] and nothing else, so the head's q (fp32) and k, v (rounded to T) of that row are functions of the token id alone -
+  // entry (h, tok) holds the bits the step kernel's own norm + da_project would produce.  Null when the three tables together
+  // would exceed TOKEN_TABLES_MAX_BYTES or the vocabulary does not fit a 16-bit id: every step then projects as before.
+  const float* q0_tab = nullptr;     // [H][V][64] fp32
+  const void* k0_tab = nullptr;      // [H][V][64] T
+  const void* v0_tab = nullptr;      // [H][V][64] T
   std::vector<float> enc_rel_bias_host;  // [num_buckets, H]
   std::vector<float> dec_rel_bias_host;  // [num_buckets, H]
 };
@@ -239,6 +247,7 @@ struct SessionSwitches {
   bool finished_skip = env_on("M2M_FINISHED_SKIP");                 // 0: finished rows keep streaming their K/V (the behaviour before round 4; bench.py's ragged_eos "before" leg)
   int kv_resident_layers = env_int("M2M_KV_RESIDENT_LAYERS", -1);   // layers of cross K/V kept cache-resident when the rest streams non-temporally (-1: by a 180 MB budget)
   bool kv_resident_stagger = env_on("M2M_KV_RESIDENT_STAGGER");     // two chains: each keeps a window of its own resident (kv_layer_resident); 0: both the first layers
+  int token_tables = env_int("M2M_DEC_TOKEN_TABLES", 2);            // layer-0 self-attention of the headless one-clip greedy step: 0 projects q, k, v and streams the cache; 1 takes this step's q, k, v from the model's token tables; 2 reads the cached K/V from them as well
 };
 
 constexpr int MAX_GROUPS = 8;
@@ -268,10 +277,10 @@ struct DecGroup {
   hipStream_t stream = nullptr;
   hipEvent_t ev_done = nullptr;
   hipGraphExec_t graph_exec = nullptr;           // the graph of the current view (an entry of `graphs`)
-  // captured graphs by (B, S, b0, nb, steps per graph, finished-row skip on / off, head form, beams, chain ordinal and count) — all baked into the launches.  Re-packing the live
+  // captured graphs by (B, S, b0, nb, steps per graph, finished-row skip on / off, head form, beams, chain ordinal and count, token-table form) — all baked into the launches.  Re-packing the live
   // rows changes (b0, nb) several times per batch, and the next batch starts from the full views again: a small cache instead of
   // a re-capture (~1 ms per 8-step graph) at every change
-  struct GraphEntry { int key[10]; hipGraph_t graph; hipGraphExec_t exec; unsigned long long used; };
+  struct GraphEntry { int key[11]; hipGraph_t graph; hipGraphExec_t exec; unsigned long long used; };
   std::vector<GraphEntry> graphs;
   unsigned long long graph_clock = 0;
 };
@@ -411,6 +420,7 @@ int launch_attn_out_image(int precision, const void* wo, void* img, int H, int d
 int launch_copy_f32(const float* src, float* dst, int64_t n, hipStream_t st);
 int launch_fill_zero(void* dst, int64_t bytes, hipStream_t st);
 int launch_checksum(const void* buf, int64_t bytes, unsigned long long* acc_dev, hipStream_t st);
+int launch_token_tables(const m2m_model* m, hipStream_t st);   // decode.hip: fills q0_tab / k0_tab / v0_tab from shared, dec[0].ln0 and dec[0].wqkv (behind their conversions)
 
 // decoder-side (decode.hip)
 int decode_init(m2m_session* s, const DecView& v, int max_steps, bool forced, hipStream_t st);

@@ -87,6 +87,10 @@ extern "C" int m2m_model_create(const m2m_t5_geometry* geom, const m2m_t5_weight
   F(m->shared, (int64_t)V * d);
   T(m->lm_head, (int64_t)vocab_pad * d);
   T(m->wckv, (int64_t)Ld * 2 * inner * d);
+  // the layer-0 token tables (t5.h): part of the blob, so m2m_model_checksum covers them like every other byte the kernels read
+  const int64_t tab_elems = (int64_t)g.num_heads * V * DK;
+  const bool tables = V <= 65535 && tab_elems * (int64_t)(4 + 2 * es) <= TOKEN_TABLES_MAX_BYTES;
+  if (tables) { F(m->q0_tab, tab_elems); T(m->k0_tab, tab_elems); T(m->v0_tab, tab_elems); }
   m->blob_bytes = c.off;
   hipError_t e = hipMalloc(&m->blob, (size_t)c.off);
   if (e != hipSuccess) {
@@ -140,6 +144,7 @@ extern "C" int m2m_model_create(const m2m_t5_geometry* geom, const m2m_t5_weight
   copyf(w->shared, m->shared, (int64_t)V * d);
   if (rc == M2M_OK) rc = launch_fill_zero(at(m->lm_head), (int64_t)vocab_pad * d * es, st);
   conv(w->lm_head, at(m->lm_head), (int64_t)V * d);
+  if (rc == M2M_OK && tables) rc = launch_token_tables(m, st);      // same stream: behind shared and the layer-0 conversions
   m->enc_rel_bias_host.resize((size_t)g.num_buckets * g.num_heads);
   m->dec_rel_bias_host.resize((size_t)g.num_buckets * g.num_heads);
   hipError_t he = hipSuccess;
@@ -235,6 +240,8 @@ int check_switches(const SessionSwitches& sw) {
               "M2M_DEC_FF_SLICES=%d: hidden slices per decode feed-forward workgroup must be 0 (by chain size), 1, 2 or 4", sw.ff_slices);
   M2M_REQUIRE(sw.mc_cif == 1 || sw.mc_cif == 2,
               "M2M_MC_CIF=%d: clips in flight in the multi-clip cross-attention must be 0 (default: 1), 1 or 2", sw.mc_cif);
+  M2M_REQUIRE(sw.token_tables >= 0 && sw.token_tables <= 2,
+              "M2M_DEC_TOKEN_TABLES=%d: the layer-0 token-table form must be 0 (off), 1 (this step's q, k, v) or 2 (and the cached K/V)", sw.token_tables);
   return M2M_OK;
 }
 
@@ -502,8 +509,9 @@ static int plan_groups(m2m_session* s, int rows_env, int rows = -1) {       // r
 // One graph = `steps` consecutive decode steps of one chain (kernels read the step index from
 // device memory, so the same graph replays for every position; steps past the end are no-ops).
 static int ensure_graph(m2m_session* s, DecGroup& gr, int steps) {
-  const int key[10] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, s->sw.finished_skip ? 1 : 0, s->head_mode, s->beam_nb,
-                       gr.view.ord, gr.view.count};       // (ord, count): which cross-K/V layers the chain keeps resident (t5.h)
+  const int key[11] = {s->B, s->S, gr.view.b0, gr.view.nb, steps, s->sw.finished_skip ? 1 : 0, s->head_mode, s->beam_nb,
+                       gr.view.ord, gr.view.count,        // (ord, count): which cross-K/V layers the chain keeps resident (t5.h)
+                       s->sw.token_tables};
   ++gr.graph_clock;
   for (auto& ge : gr.graphs)
     if (memcmp(key, ge.key, sizeof(key)) == 0) { ge.used = gr.graph_clock; gr.graph_exec = ge.exec; return M2M_OK; }
