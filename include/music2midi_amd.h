@@ -960,6 +960,25 @@ int64_t m2m_adafactor_state_floats(const m2m_trainer* t);
 int m2m_adafactor_state_export(const m2m_trainer* t, float* state_out_dev, void* stream);
 int m2m_adafactor_state_import(m2m_trainer* t, const float* state_in_dev, int step, void* stream);
 
+/* Gradient clipping as pytorch-lightning's Trainer(gradient_clip_val=, gradient_clip_algorithm=) applies it where the optimizer
+ * steps (the rules: music2midi_amd/clipping.py).  algorithm 0: off (the default after create; `value` is ignored), 1: norm —
+ * torch.nn.utils.clip_grad_norm_(params, value): total = the 2-norm of the per-tensor 2-norms, every gradient times
+ * coef = min(1, value / (total + 1e-6)); 2: value — torch.nn.utils.clip_grad_value_: every element clamped to [-value, value], a NaN
+ * stays a NaN.  M2M_ERR_INVALID for another algorithm, and for a value that is NaN or <= 0 while the algorithm is not 0.
+ * Every m2m_adafactor_step that follows applies the setting: in norm mode it first runs the two norm launches on grads_dev (a full
+ * read of the gradient; no atomics, every sum in a fixed order) and leaves the two words readable; the clip itself costs no
+ * further pass: the step's kernels read g * coef (or the clamped g) on the fly, so the second moments see the clipped gradient.
+ * grads_dev is NOT written: it holds the unclipped gradient after the step (Lightning's .grad is clipped in place).
+ * With algorithm 0 the step is the unclipped one, bit for bit. */
+int m2m_trainer_set_grad_clip(m2m_trainer* t, int algorithm /* 0 off, 1 norm, 2 value */, float value);
+
+/* The global gradient norm of any gradient buffer laid out as the trainer's: out_dev[0] = total norm as above, out_dev[1] = coef
+ * against the trainer's max_norm (clipping off or in value mode: against +inf, i.e. 1).  Two launches and one device-to-device copy
+ * of the two fp32 words on `stream`; never synchronises the host; two calls on the same buffer give bit-identical words.  A
+ * non-finite gradient is not special-cased: one +inf element gives (inf, 0).  grads_dev NULL: nothing is launched, out_dev receives
+ * the two words the last norm-mode m2m_adafactor_step left (zeros before the first). */
+int m2m_trainer_grad_norm(m2m_trainer* t, const float* grads_dev, float* out_dev /* [2] */, void* stream);
+
 /* One MXFP8 product, C[M,N] = A[M,K] . B[N,K]^T (fp32 in and out, device pointers, row-major): both operands are quantised
  * to OCP block-scaled FP8 — 32 elements along K per power-of-two E8M0 scale, e4m3 elements (e5m2 for A when a_is_e5m2, the
  * gradient format) — and multiplied on gfx950's scaled MFMA (v_mfma_scale_f32_32x32x64_f8f6f4).  This is the arithmetic of

@@ -19,11 +19,30 @@ namespace m2m {
 // Three passes over (p, g) with the reductions between them; one launch per pass for ALL tensors (block -> (tensor,
 // row block) through a table), every reduction in a fixed order.  A block takes AF_ROWS rows of a matrix, or a whole vector as one row.
 
+// Gradient clipping (Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm); rules: music2midi_amd/clipping.py) is folded into the
+// three passes that read g, as a template parameter CLIP: 0 off (the code as it was), 1 norm: g * coef with coef the device word
+// gn_finish wrote (grad_clip.hip), 2 value: g clamped to +-v.  The clipped value is taken straight after the load, before anything else
+// touches g, so the second moments see the clipped gradient exactly as Adafactor does after clip_grad_norm_'s g.mul_(coef).  No pass
+// writes G: the gradient buffer keeps the unclipped gradient after the step.
+template <int CLIP>
+__device__ __forceinline__ float af_clip_arg(const float* __restrict__ coef_dev, float clip_v) {      // once per workgroup
+  return CLIP == 1 ? *coef_dev : clip_v;
+}
+template <int CLIP>
+__device__ __forceinline__ float af_clipped(float g, float cv) {
+  if (CLIP == 1) return g * cv;                                  // one rounded fp32 multiply
+  if (CLIP == 2) return g < -cv ? -cv : (g > cv ? cv : g);       // not fminf / fmaxf: they would swallow a NaN
+  return g;
+}
+
 // pass A: per block: sum p^2, per-row sum of (g^2 + eps1) -> rowsum[tensor rows], per-block column partial sums
+template <int CLIP>
 __global__ __launch_bounds__(256) void af_pass_a(const AfBlock* __restrict__ blocks, const AfTensor* __restrict__ tensors,
                                                  const float* __restrict__ P, const float* __restrict__ G, float* __restrict__ rowsum,
-                                                 float* __restrict__ colpart, float* __restrict__ blk_p2) {
+                                                 float* __restrict__ colpart, float* __restrict__ blk_p2,
+                                                 const float* __restrict__ coef_dev, float clip_v) {
   __shared__ float sred[256];
+  const float cv = af_clip_arg<CLIP>(coef_dev, clip_v);
   const AfBlock bk = blocks[blockIdx.x];
   const AfTensor t = tensors[bk.tensor];
   const float* p = P + t.offset;
@@ -43,6 +62,7 @@ __global__ __launch_bounds__(256) void af_pass_a(const AfBlock* __restrict__ blo
     for (int j = 0; j < AF_ROWS; ++j) {
       const int r = min(bk.row0 + j, r1 - 1);          // clamped: every load of the tile is in flight at once
       gv[j] = g[(int64_t)r * t.cols + c];
+      if (CLIP) gv[j] = af_clipped<CLIP>(gv[j], cv);
       pv[j] = p[(int64_t)r * t.cols + c];
     }
     float cs = 0.f;
@@ -134,10 +154,12 @@ __global__ __launch_bounds__(256) void af_pass_a2(const AfTensor* __restrict__ t
 }
 
 // pass B: per block sum of upd^2, upd = g * rfac[row] * cfac[col]
+template <int CLIP>
 __global__ __launch_bounds__(256) void af_pass_b(const AfBlock* __restrict__ blocks, const AfTensor* __restrict__ tensors,
                                                  const float* __restrict__ G, const float* __restrict__ rfac, const float* __restrict__ cfac,
-                                                 float* __restrict__ blk_u2) {
+                                                 float* __restrict__ blk_u2, const float* __restrict__ coef_dev, float clip_v) {
   __shared__ float sred[256];
+  const float cv = af_clip_arg<CLIP>(coef_dev, clip_v);
   const AfBlock bk = blocks[blockIdx.x];
   const AfTensor t = tensors[bk.tensor];
   const float* g = G + t.offset;
@@ -148,6 +170,10 @@ __global__ __launch_bounds__(256) void af_pass_b(const AfBlock* __restrict__ blo
     float gv[AF_ROWS];
 #pragma unroll
     for (int j = 0; j < AF_ROWS; ++j) gv[j] = g[(int64_t)min(bk.row0 + j, r1 - 1) * t.cols + c];
+    if (CLIP) {
+#pragma unroll
+      for (int j = 0; j < AF_ROWS; ++j) gv[j] = af_clipped<CLIP>(gv[j], cv);
+    }
 #pragma unroll
     for (int j = 0; j < AF_ROWS; ++j) {
       if (bk.row0 + j < r1) {
@@ -178,9 +204,12 @@ __global__ __launch_bounds__(256) void af_pass_b2(const AfTensor* __restrict__ t
   }
 }
 // pass C: p -= step * g * rfac[row] * cfac[col]
+template <int CLIP>
 __global__ __launch_bounds__(256) void af_pass_c(const AfBlock* __restrict__ blocks, const AfTensor* __restrict__ tensors,
                                                  float* __restrict__ P, const float* __restrict__ G, const float* __restrict__ rfac,
-                                                 const float* __restrict__ cfac, const float* __restrict__ tstat) {
+                                                 const float* __restrict__ cfac, const float* __restrict__ tstat,
+                                                 const float* __restrict__ coef_dev, float clip_v) {
+  const float cv = af_clip_arg<CLIP>(coef_dev, clip_v);
   const AfBlock bk = blocks[blockIdx.x];
   const AfTensor t = tensors[bk.tensor];
   float* p = P + t.offset;
@@ -196,6 +225,7 @@ __global__ __launch_bounds__(256) void af_pass_c(const AfBlock* __restrict__ blo
       for (int j = 0; j < 8; ++j) {
         const int64_t at = (int64_t)min(r + j, r1 - 1) * t.cols + c;
         gv[j] = g[at];
+        if (CLIP) gv[j] = af_clipped<CLIP>(gv[j], cv);
         pv[j] = p[at];
       }
 #pragma unroll
@@ -205,7 +235,26 @@ __global__ __launch_bounds__(256) void af_pass_c(const AfBlock* __restrict__ blo
   }
 }
 
-int launch_adafactor(const AfPlan& pl, float* P, const float* G, int step, hipStream_t st) {
+namespace {
+
+template <int CLIP>
+void launch_passes(const AfPlan& pl, float* P, const float* G, float beta2t, float omb2t, float rho, const float* coef_dev, float clip_v,
+                   hipStream_t st) {
+  hipLaunchKernelGGL(af_pass_a<CLIP>, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, P, G, pl.rowsum, pl.colpart, pl.blk_a,
+                     coef_dev, clip_v);
+  hipLaunchKernelGGL(af_pass_a2, dim3(pl.n_tensors), dim3(256), 0, st, pl.tensors, pl.rowsum, pl.colpart, pl.blk_a, pl.state, pl.rfac,
+                     pl.cfac, pl.tstat, beta2t, omb2t);
+  hipLaunchKernelGGL(af_pass_b<CLIP>, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, G, pl.rfac, pl.cfac, pl.blk_b, coef_dev,
+                     clip_v);
+  hipLaunchKernelGGL(af_pass_b2, dim3(pl.n_tensors), dim3(256), 0, st, pl.tensors, pl.blk_b, pl.tstat, rho);
+  hipLaunchKernelGGL(af_pass_c<CLIP>, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, P, G, pl.rfac, pl.cfac, pl.tstat,
+                     coef_dev, clip_v);
+}
+
+}  // namespace
+
+int launch_adafactor(const AfPlan& pl, float* P, const float* G, int step, hipStream_t st, int clip, const float* coef_dev,
+                     float clip_value) {
   const double t = (double)step;
   const float beta2t = (float)(1.0 - pow(t, -0.8));
   // 1 - beta2 = t^-0.8 rounded from the double, as the reference's add_(.., alpha=1.0 - beta2t) has it: 1.f - beta2t keeps only the bits
@@ -213,12 +262,9 @@ int launch_adafactor(const AfPlan& pl, float* P, const float* G, int step, hipSt
   const float omb2t = (float)pow(t, -0.8);
   const double rho_d = fmin(1e-6 * t, 1.0 / sqrt(t));
   const float rho = (float)rho_d;
-  hipLaunchKernelGGL(af_pass_a, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, P, G, pl.rowsum, pl.colpart, pl.blk_a);
-  hipLaunchKernelGGL(af_pass_a2, dim3(pl.n_tensors), dim3(256), 0, st, pl.tensors, pl.rowsum, pl.colpart, pl.blk_a, pl.state, pl.rfac,
-                     pl.cfac, pl.tstat, beta2t, omb2t);
-  hipLaunchKernelGGL(af_pass_b, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, G, pl.rfac, pl.cfac, pl.blk_b);
-  hipLaunchKernelGGL(af_pass_b2, dim3(pl.n_tensors), dim3(256), 0, st, pl.tensors, pl.blk_b, pl.tstat, rho);
-  hipLaunchKernelGGL(af_pass_c, dim3(pl.n_blocks), dim3(256), 0, st, pl.blocks, pl.tensors, P, G, pl.rfac, pl.cfac, pl.tstat);
+  if (clip == AF_CLIP_NORM) launch_passes<1>(pl, P, G, beta2t, omb2t, rho, coef_dev, 0.f, st);
+  else if (clip == AF_CLIP_VALUE) launch_passes<2>(pl, P, G, beta2t, omb2t, rho, nullptr, clip_value, st);
+  else launch_passes<0>(pl, P, G, beta2t, omb2t, rho, nullptr, 0.f, st);
   M2M_CHECK_HIP(hipGetLastError());
   return M2M_OK;
 }

@@ -243,7 +243,17 @@ struct AfPlan {
   float *rowsum = nullptr, *colpart = nullptr, *blk_a = nullptr, *blk_b = nullptr, *state = nullptr, *rfac = nullptr,
         *cfac = nullptr, *tstat = nullptr;
   int64_t state_floats = 0;
+  // gradient clipping (grad_clip.hip): per-block sums of g^2, and the norm words — [0] total norm, [1] coef of the last step in
+  // norm mode; [2], [3] the same two of the last m2m_trainer_grad_norm call
+  float *blk_g = nullptr, *gn_words = nullptr;
 };
-int launch_adafactor(const AfPlan& pl, float* P, const float* G, int step, hipStream_t st);
+// Gradient clipping folded into the step (Lightning's Trainer(gradient_clip_val, gradient_clip_algorithm); music2midi_amd/clipping.py)
+enum { AF_CLIP_OFF = 0, AF_CLIP_NORM = 1, AF_CLIP_VALUE = 2 };
+// clip AF_CLIP_NORM: passes A, B and C read g * *coef_dev (the word launch_grad_norm wrote);  AF_CLIP_VALUE: g clamped to +-clip_value
+int launch_adafactor(const AfPlan& pl, float* P, const float* G, int step, hipStream_t st, int clip = AF_CLIP_OFF,
+                     const float* coef_dev = nullptr, float clip_value = 0.f);
+// global 2-norm of G as torch.nn.utils.clip_grad_norm_ takes it (the norm of the per-tensor norms) -> words[0], and
+// coef = min(1, max_norm / (norm + 1e-6)) -> words[1].  Two launches, no atomics, every sum in a fixed order.
+int launch_grad_norm(const AfPlan& pl, const float* G, float max_norm, float* words, hipStream_t st);
 
 }  // namespace m2m

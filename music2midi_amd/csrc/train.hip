@@ -1301,6 +1301,8 @@ struct m2m_trainer {
   AfPlan af;
   unsigned char* af_mem = nullptr;
   int step = 0;
+  int clip_mode = AF_CLIP_OFF;           // m2m_trainer_set_grad_clip: applied by every m2m_adafactor_step
+  float clip_value = 0.f;                // norm: max_norm;  value: the clamp
 };
 
 namespace {
@@ -1403,6 +1405,8 @@ int build_optimizer(m2m_trainer* t) {
   c.take(p.rfac, (int64_t)row_off * 4);
   c.take(p.cfac, (int64_t)cfac_off * 4);
   c.take(p.tstat, (int64_t)at.size() * 2 * 4);
+  c.take(p.blk_g, (int64_t)ab.size() * 4);
+  c.take(p.gn_words, 4 * 4);
   M2M_CHECK_HIP(hipMalloc((void**)&t->af_mem, (size_t)c.off));
   M2M_CHECK_HIP(hipMemset(t->af_mem, 0, (size_t)c.off));
   c.bind(t->af_mem);
@@ -2748,7 +2752,34 @@ extern "C" int m2m_trainer_graph_nodes(const m2m_trainer* t) {
 extern "C" int m2m_adafactor_step(m2m_trainer* t, float* params_dev, const float* grads_dev, void* stream) {
   M2M_REQUIRE(t && params_dev && grads_dev, "m2m_adafactor_step: null argument");
   t->step += 1;
-  return launch_adafactor(t->af, params_dev, grads_dev, t->step, (hipStream_t)stream);
+  if (t->clip_mode == AF_CLIP_NORM) {      // the norm of this step's gradient first; its two words stay readable (m2m_trainer_grad_norm, grads_dev = NULL)
+    const int rc = launch_grad_norm(t->af, grads_dev, t->clip_value, t->af.gn_words, (hipStream_t)stream);
+    if (rc != M2M_OK) return rc;
+  }
+  return launch_adafactor(t->af, params_dev, grads_dev, t->step, (hipStream_t)stream, t->clip_mode, t->af.gn_words + 1, t->clip_value);
+}
+
+extern "C" int m2m_trainer_set_grad_clip(m2m_trainer* t, int algorithm, float value) {
+  M2M_REQUIRE(t, "m2m_trainer_set_grad_clip: null trainer");
+  M2M_REQUIRE(algorithm == AF_CLIP_OFF || algorithm == AF_CLIP_NORM || algorithm == AF_CLIP_VALUE,
+              "m2m_trainer_set_grad_clip: algorithm must be 0 (off), 1 (norm) or 2 (value), got %d", algorithm);
+  M2M_REQUIRE(algorithm == AF_CLIP_OFF || value > 0.f, "m2m_trainer_set_grad_clip: the clip value must be > 0 (got %g)", (double)value);
+  t->clip_mode = algorithm;
+  t->clip_value = algorithm == AF_CLIP_OFF ? 0.f : value;
+  return M2M_OK;
+}
+
+extern "C" int m2m_trainer_grad_norm(m2m_trainer* t, const float* grads_dev, float* out_dev, void* stream) {
+  M2M_REQUIRE(t && out_dev, "m2m_trainer_grad_norm: null argument");
+  const float* words = t->af.gn_words;                 // grads_dev NULL: the words the last norm-mode step left
+  if (grads_dev) {
+    const float max_norm = t->clip_mode == AF_CLIP_NORM ? t->clip_value : INFINITY;      // off / value: coef against +inf, i.e. 1
+    const int rc = launch_grad_norm(t->af, grads_dev, max_norm, t->af.gn_words + 2, (hipStream_t)stream);
+    if (rc != M2M_OK) return rc;
+    words = t->af.gn_words + 2;
+  }
+  M2M_CHECK_HIP(hipMemcpyAsync(out_dev, words, 2 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return M2M_OK;
 }
 
 extern "C" int m2m_adafactor_get_step(const m2m_trainer* t) { return t ? t->step : M2M_ERR_INVALID; }

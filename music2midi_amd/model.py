@@ -21,6 +21,7 @@ from . import distributed as D
 from .accumulation import check_accumulate_grad_batches, micro_step, windows
 from .audio import load_audio as _load_audio
 from .checkpoint import load_t5_state, read_checkpoint
+from .clipping import NORM, OFF, check_gradient_clip
 from .confidence import confidence_velocities, decode_with_confidence, min_logprob
 from .config import inference_beams, load_config
 from .evaluation import (evaluate_batch, evaluate_tokens, frame_scores_host, frame_scores_tokens, note_scores_host,
@@ -212,6 +213,41 @@ class Music2MIDI(nn.Module):
             return check_accumulate_grad_batches(self._accumulate_override)
         return check_accumulate_grad_batches(self.config.trainer.get("accumulate_grad_batches", 1))
 
+    # Gradient clipping (music2midi_amd.clipping): Lightning's automatic optimisation clips where the optimizer steps, with the
+    # Trainer's gradient_clip_val / gradient_clip_algorithm — here fit_batches, from config.trainer or its own keywords.  A
+    # hand-written loop clips only what clip_gradients() armed, as a LightningModule under manual optimisation does.
+    _clip_override = None              # (val, algorithm) of fit_batches' keywords, for the duration of that call
+    _clip_fit = None                   # (mode, value) every step of the running fit_batches applies
+    _clip_armed = None                 # (mode, value) clip_gradients() set for the next optimizer.step()
+
+    def _gradient_clip(self):
+        """(mode, value) of ``trainer.gradient_clip_val`` / ``trainer.gradient_clip_algorithm`` (absent keys: off, "norm"), each
+        replaced by ``fit_batches``' keyword when that is given; TypeError / ValueError as ``check_gradient_clip`` raises them."""
+        val = self.config.trainer.get("gradient_clip_val", None)
+        algorithm = self.config.trainer.get("gradient_clip_algorithm", None)
+        if self._clip_override is not None:
+            o_val, o_alg = self._clip_override
+            val = o_val if o_val is not None else val
+            algorithm = o_alg if o_alg is not None else algorithm
+        return check_gradient_clip(val, algorithm)
+
+    def clip_gradients(self, optimizer=None, gradient_clip_val=None, gradient_clip_algorithm=None):
+        """``LightningModule.clip_gradients`` for hand-written loops: call it between the backward pass and ``optimizer.step()``.
+        Arguments left ``None`` take ``config.trainer``'s values.  Unlike Lightning's it does not touch ``.grad``: it ARMS the next
+        ``optimizer.step()``, whose kernels read the clipped gradient on the fly (second moments and update see exactly what
+        ``clip_grad_norm_`` / ``clip_grad_value_`` would have left), and ``.grad`` keeps the unclipped gradient afterwards."""
+        val = gradient_clip_val if gradient_clip_val is not None else self.config.trainer.get("gradient_clip_val", None)
+        algorithm = gradient_clip_algorithm if gradient_clip_algorithm is not None else self.config.trainer.get("gradient_clip_algorithm", None)
+        self._clip_armed = check_gradient_clip(val, algorithm)
+
+    def _sync_grad_clip(self, tr):
+        """Set the clipping the next optimizer step applies on the trainer (a rebuilt trainer starts with clipping off): what
+        clip_gradients() armed, else the running fit_batches' setting, else off.  Returns it."""
+        want = self._clip_armed or self._clip_fit or (OFF, 0.0)
+        if getattr(tr, "grad_clip", (OFF, 0.0)) != want:
+            tr.set_grad_clip(*want)
+        return want
+
     def training_step(self, inputs: ModelInputs, batch_idx):
         """ref model.py:32-43.  Lightning calls backward() on the returned loss; here forward AND backward have
         already been ENQUEUED when this returns: every parameter's ``.grad`` will hold d loss / d parameter (views of one flat
@@ -315,7 +351,7 @@ class Music2MIDI(nn.Module):
             tr.dropout = -1.0                                # the mask sequence restarts from the restored step (see _native_trainer)
 
     def fit_batches(self, batches, optimizer=None, world_size: int = 1, ckpt_path=None, save_path=None, save_every_n_steps: int = 0,
-                    accumulate_grad_batches=None, augment=None):
+                    accumulate_grad_batches=None, augment=None, gradient_clip_val=None, gradient_clip_algorithm=None):
         """Minimal stand-in for ``pl.Trainer.fit`` (ref train.py:40-41): step over an iterable of ModelInputs.  ``ckpt_path``
         resumes a run (weights + Adafactor state + step counter) as ``trainer.fit(..., ckpt_path=)`` does; ``save_path`` is
         (re)written every ``save_every_n_steps`` steps and at the end.  The host never waits for a step: losses stay on the device
@@ -325,6 +361,11 @@ class Music2MIDI(nn.Module):
         ``music2midi_amd.accumulation``): the optimizer steps — and the gradients are all-reduced — once per window of N batches
         and after the last batch; ``global_step``, ``save_every_n_steps`` and ``log_every_n_steps`` count optimizer steps, so
         checkpoints fall on window boundaries.  The returned losses are per batch, unscaled.  The override holds for this call only.
+        Gradient clipping (``gradient_clip_val`` / ``gradient_clip_algorithm``, default ``config.trainer``'s, absent: off / "norm";
+        see ``music2midi_amd.clipping``): every optimizer step clips — once per window, on the summed gradient, after the
+        all-reduce.  A bad value is refused before the first step; the override holds for this call only.  ``.grad`` keeps the
+        unclipped gradient (the step clips on the fly).  In norm mode every ``log_history`` entry carries ``train/grad_norm``, the
+        total norm before clipping of that step, read at the log step only.
         ``augment`` (a ``np.random.Generator``, or ``True`` for ``default_rng(0)``): every batch goes through
         ``music2midi_amd.augment.augment`` first — the reference dataset's normalise / transpose draws (ref dataset.py:130-133), the
         audio shifted on the device; ``None`` leaves the batches as they are."""
@@ -334,13 +375,17 @@ class Music2MIDI(nn.Module):
             batches = (augment_batch(batch, rng) for batch in batches)
         if accumulate_grad_batches is not None:
             check_accumulate_grad_batches(accumulate_grad_batches)
-        previous = self._accumulate_override
+        if gradient_clip_val is not None or gradient_clip_algorithm is not None:
+            check_gradient_clip(gradient_clip_val, gradient_clip_algorithm)
+        previous = self._accumulate_override, self._clip_override, self._clip_fit
         self._accumulate_override = accumulate_grad_batches
+        self._clip_override = (gradient_clip_val, gradient_clip_algorithm)
         try:
             n = self._accumulation()                     # ValueError before the first step
+            self._clip_fit = self._gradient_clip()       # TypeError / ValueError before the first step
             return self._fit_windows(batches, n, optimizer, ckpt_path, save_path, save_every_n_steps)
         finally:
-            self._accumulate_override = previous
+            self._accumulate_override, self._clip_override, self._clip_fit = previous
 
     def _fit_windows(self, batches, n, optimizer, ckpt_path, save_path, save_every_n_steps):
         if ckpt_path is not None:
@@ -364,9 +409,12 @@ class Music2MIDI(nn.Module):
                 D.all_reduce_gradients_overlapped(tr.grads, tr.early_ranges, tr.sync_stream)
             else:
                 D.all_reduce_gradients(tr.grads)
+            clip_mode, _ = self._sync_grad_clip(tr)      # clipping runs where the optimizer steps: after the all-reduce, on the window's sum
             optimizer.step()
             self.global_step += 1
             if self.global_step % log_every == 0:
+                if clip_mode == NORM:                    # the step's own norm word, still on the device: read with the other metrics
+                    self.logged["train/grad_norm"] = self._trainer.grad_stats()[0]
                 self.log_history.append(dict(self.logged_metrics(), step=self.global_step))
                 # logged_metrics() has just waited for this step: move the window's losses to the host here, so that a long run
                 # (119 200 steps in the reference's) holds at most log_every device scalars, not one per step

@@ -225,6 +225,8 @@ _SIGNATURES = {
     "m2m_adafactor_state_floats": (C.c_int64, [C.c_void_p]),
     "m2m_adafactor_state_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "m2m_adafactor_state_import": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "m2m_trainer_set_grad_clip": (C.c_int, [C.c_void_p, C.c_int, C.c_float]),
+    "m2m_trainer_grad_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m2m_mx8_matmul_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "m2m_mx8_matmul_bf16a": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "m2m_mx8_quantize_cols": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

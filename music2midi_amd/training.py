@@ -63,6 +63,7 @@ class NativeTrainer:
         self._adopt_parameters()
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self.dropout = 0.0
+        self.grad_clip = ("off", 0.0)
         self.sync_stream = None
         self.early_ranges = []
 
@@ -159,6 +160,38 @@ class NativeTrainer:
                                                           native.stream_handle(self.device)), "m2m_adafactor_step")
         self.module._weights_epoch += 1            # the inference path repacks its weights on next use
 
+    # -- gradient clipping (music2midi_amd.clipping) ---------------------------------
+    def set_grad_clip(self, mode: str, value: float = 0.0):
+        """Clipping every ``optimizer_step`` from now on applies: ``mode`` "off", "norm" (``clip_grad_norm_(params, value)``) or
+        "value" (``clip_grad_value_(params, value)``), as ``clipping.check_gradient_clip`` returns them.  The step reads the clipped
+        gradient on the fly: ``grads`` (every parameter's ``.grad``) keeps the UNCLIPPED gradient, unlike Lightning's."""
+        from .clipping import MODE_CODES
+        if mode not in MODE_CODES:
+            raise ValueError(f"clipping mode must be one of {sorted(MODE_CODES)}, got {mode!r}")
+        native.check(native.load().m2m_trainer_set_grad_clip(self.handle, MODE_CODES[mode], float(value)), "m2m_trainer_set_grad_clip")
+        self.grad_clip = (mode, float(value) if mode != "off" else 0.0)
+
+    def grad_stats(self) -> torch.Tensor:
+        """[total gradient norm before clipping, coef] of the last ``optimizer_step`` in norm mode (zeros before the first), a
+        2-element fp32 tensor on the device.  Enqueued on the current stream; nothing is synchronised."""
+        out = torch.empty(2, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            native.check(native.load().m2m_trainer_grad_norm(self.handle, None, out.data_ptr(), native.stream_handle(self.device)),
+                         "m2m_trainer_grad_norm")
+        return out
+
+    def grad_norm(self, grads: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[total norm, coef against the trainer's max_norm (1 unless in norm mode)] of a flat gradient buffer laid out as
+        ``self.grads`` (default: ``self.grads``), on the device; two launches, nothing is synchronised."""
+        g = self.grads if grads is None else grads
+        if g.dtype != torch.float32 or g.device != self.device or g.numel() != self.n_floats or not g.is_contiguous():
+            raise ValueError("grad_norm takes a contiguous fp32 buffer of the trainer's layout on its device")
+        out = torch.empty(2, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            native.check(native.load().m2m_trainer_grad_norm(self.handle, g.data_ptr(), out.data_ptr(), native.stream_handle(self.device)),
+                         "m2m_trainer_grad_norm")
+        return out
+
     @property
     def step_count(self) -> int:
         return int(native.load().m2m_adafactor_get_step(self.handle))
@@ -253,7 +286,12 @@ class Adafactor:
 
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        self._owner._native_trainer().optimizer_step()
+        tr = self._owner._native_trainer()
+        self._owner._sync_grad_clip(tr)            # fit_batches' clipping, or what clip_gradients() armed for this step
+        try:
+            tr.optimizer_step()
+        finally:
+            self._owner._clip_armed = None
         return loss
 
     def zero_grad(self, set_to_none: bool = False):
