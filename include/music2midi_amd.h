@@ -324,6 +324,43 @@ int m2m_score_error_notes(const int32_t* notes_dev, const int32_t* counts_dev, c
                           int frame_cap, float min_logprob, int melody_only, int max_timeline_labels, void* workspace_dev,
                           int64_t workspace_bytes, int32_t* notes_out_dev, int32_t* counts_out_dev, void* stream);
 
+#define M2M_CONSENSUS_MAX_CANDIDATES 16    /* candidate rows per clip of the consensus calls */
+
+/* The bytes of workspace m2m_consensus_pairwise_counts needs: 28 per note slot (R * L: three float64 and one int32 array) +
+ * 16 per pair slot (R * (K - 1) * L: match, stamp, stack and interval, int32), every array rounded up to 8 bytes - 28 * R * L +
+ * 16 * R * (K - 1) * L, 31 MB of pair slots at R = 128, L = 1024, K = 16.  Host arithmetic; -1 for a size out of range or an R
+ * that is no multiple of K. */
+int64_t m2m_consensus_workspace_bytes(int R, int L, int K);
+
+/*
+ * Pairwise note-level agreement of the K candidate rows of every clip (the definition: music2midi_amd/consensus.py,
+ * pairwise_counts).  notes_dev [R, L, 3] / counts_dev [R] are m2m_score_detokenize's, batched (steps_per_row 0); the candidates of
+ * clip b are rows b * K .. b * K + K - 1, B = R / K clips.  time_step and the three tolerances are m2m_score_note_counts'
+ * (offset_ratio < 0: onsets only), and so are the hit test and the exact maximum matching: tp_out_dev [B, K, K] int32, zeroed on
+ * `stream` first, holds at [b, i, j], i != j, the size of a maximum matching of the hit graph with candidate j as the reference
+ * (its duration gives the offset tolerance) and candidate i as the estimate, and at [b, i, i] the kept notes (end > start) of
+ * candidate i; n_out_dev [B, K] int32 holds those counts too.  A clip that contains a row whose count is -1 gets
+ * tp_out_dev[b, 0, 0] = -1 and nothing else.
+ * workspace_dev: at least m2m_consensus_workspace_bytes bytes for (R, L, K), 8-byte aligned, the caller's; its contents are
+ * unspecified before and after, and nothing read from it was written by an earlier call.  One launch; the library allocates nothing.
+ * M2M_ERR_INVALID: R, L, time_step and the tolerances as m2m_score_note_counts; K outside 2..16; R % K != 0; a null notes / counts
+ * / output pointer; a null or misaligned workspace, or workspace_bytes below the need.
+ */
+int m2m_consensus_pairwise_counts(const int32_t* notes_dev, const int32_t* counts_dev, int R, int L, int K, double time_step,
+                                  double onset_tolerance, double offset_ratio, double offset_min_tolerance, void* workspace_dev,
+                                  int64_t workspace_bytes, int32_t* tp_out_dev, int32_t* n_out_dev, void* stream);
+
+/*
+ * The candidate the others agree with most (consensus.py, expected_agreement and select).  tp_dev [B, K, K] and n_dev [B, K] are
+ * m2m_consensus_pairwise_counts'.  utility_out_dev [B, K] float64: u[i] = (sum over j != i, in increasing j, of a(i, j)) / (K - 1)
+ * with a(i, j) = 1.0 when n[i] + n[j] == 0 and double(2 * tp[i, j]) / double(n[i] + n[j]) otherwise - float64, one rounded
+ * operation each, the sum started at 0.0.  chosen_out_dev [B] int32: the first maximum of u.  A clip with tp[b, 0, 0] < 0 gets
+ * chosen -1 and utilities 0.  One launch of one wave per clip.
+ * M2M_ERR_INVALID: B outside 1..65535, K outside 2..16, a null pointer, a utility pointer that is not 8-byte aligned.
+ */
+int m2m_consensus_select(const int32_t* tp_dev, const int32_t* n_dev, int B, int K, int32_t* chosen_out_dev, double* utility_out_dev,
+                         void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Audio ingest: the sample bytes of a WAVE file -> mono fp32 -> another sample rate, zero-padded; replaces, for the files it
  * takes, the host step of ref: music2midi/model.py:83-84 (librosa.load).  The definitions are music2midi_amd/audio.py (read_wav,

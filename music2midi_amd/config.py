@@ -146,6 +146,33 @@ def inference_beams(config) -> dict:
     return {"num_beams": n, "length_penalty": float(inf.get("length_penalty", 1.0)), "early_stopping": inf.get("early_stopping", False)}
 
 
+def inference_consensus(config, samples=None) -> dict:
+    """The consensus settings of ``config.inference``: ``{}`` when ``consensus_samples`` is absent, 0 or 1 (every call decodes as
+    before), otherwise ``{"num_samples": K}`` with ``temperature`` / ``top_k`` / ``top_p`` for the optional keys
+    ``consensus_temperature`` / ``consensus_top_k`` / ``consensus_top_p`` - the keywords ``Music2MIDI`` passes to
+    ``T5Transformer.generate_consensus``.  ``samples`` (a call's ``consensus=`` keyword) overrides ``consensus_samples``.  K outside
+    2..16 and consensus together with ``inference.num_beams`` > 1 raise ``ValueError``."""
+    inf = config.inference
+    n = inf.get("consensus_samples", 0) if samples is None else samples
+    if n is None:
+        n = 0
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        raise ValueError(f"inference.consensus_samples has to be a non-negative integer, but is {n!r}")
+    if n <= 1:
+        return {}
+    if n > 16:
+        raise ValueError(f"inference.consensus_samples = {n}: at most 16 candidates per clip")
+    if inference_beams(config):
+        raise ValueError("consensus decoding chooses among one greedy and K - 1 sampled rows; it does not combine with "
+                         "inference.num_beams > 1")
+    out = {"num_samples": n}
+    for key, name, kind in (("consensus_temperature", "temperature", float), ("consensus_top_k", "top_k", int),
+                            ("consensus_top_p", "top_p", float)):
+        if inf.get(key, None) is not None:
+            out[name] = kind(inf.get(key))
+    return out
+
+
 # T5 hyper-parameters that the reference leaves to the HF defaults
 # (hf: models/t5/configuration_t5.py:44-62): they are not in config.yaml.
 T5_DEFAULTS = {

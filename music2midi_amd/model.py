@@ -23,7 +23,7 @@ from .audio import load_audio as _load_audio
 from .checkpoint import load_t5_state, read_checkpoint
 from .clipping import NORM, OFF, check_gradient_clip
 from .confidence import confidence_velocities, decode_with_confidence, min_logprob
-from .config import inference_beams, load_config
+from .config import inference_beams, inference_consensus, load_config
 from .evaluation import (evaluate_batch, evaluate_tokens, frame_scores_host, frame_scores_tokens, note_scores_host,
                          note_scores_tokens)
 from .input import ModelInputs
@@ -31,21 +31,40 @@ from .transformer import T5Transformer
 from .utils import numpy_to_midi
 
 
-def _decode_entry(model, config, grammar_kwargs: dict):
+def _decode_entry(model, config, grammar_kwargs: dict, consensus: Optional[int] = None):
     """(decode function, its keywords): ``model.generate`` with the grammar keyword, or - with ``config.inference.num_beams`` > 1 -
-    ``model.beam_search_processed`` with the config's beam settings, one returned sequence per clip and the same grammar switch."""
+    ``model.beam_search_processed`` with the config's beam settings, one returned sequence per clip and the same grammar switch, or
+    - with ``config.inference.consensus_samples`` > 1, or a call's ``consensus`` - ``model.generate_consensus`` with the config's
+    sampling settings.  Consensus together with beams raises ``ValueError``."""
+    chosen = inference_consensus(config, consensus)
+    if chosen:
+        return model.generate_consensus, dict(chosen, **grammar_kwargs)
     beams = inference_beams(config)
     if not beams:
         return model.generate, grammar_kwargs
     return model.beam_search_processed, dict(beams, num_return_sequences=1, **grammar_kwargs)
 
 
+def _rows_per_clip(decode_kwargs: dict) -> int:
+    """The rows one clip takes in a decode call: its beams, or its consensus candidates."""
+    return int(decode_kwargs.get("num_beams", decode_kwargs.get("num_samples", 1)))
+
+
+def _no_consensus(config, consensus: Optional[int], what: str) -> None:
+    """``ValueError`` when consensus decoding is on and the call also asks for per-note confidence: a sampled row's log-probabilities
+    are those of the warped distribution and a greedy row's are raw, so they are not mixed."""
+    if inference_consensus(config, consensus):
+        raise ValueError(f"consensus decoding does not combine with {what}: the log-probabilities of sampled rows (warped) and of "
+                         "the greedy row (raw) are not comparable")
+
+
 def _labelled_token_ids(model, config, grammar_kwargs: dict, inputs) -> torch.Tensor:
     """The decode of one labelled batch that ``evaluate_batch`` and ``score_batch`` share: four tokens per label note of the busiest
-    clip; with beams, chunks of batch_size // num_beams clips, as sample_tokens, so a call's rows stay within inference.batch_size."""
+    clip; with beams, chunks of batch_size // num_beams clips, as sample_tokens, so a call's rows stay within inference.batch_size;
+    with consensus decoding, chunks of batch_size // consensus_samples clips by the same rule."""
     budget = 4 * max(len(n) for n in inputs.notes_batch)
     decode, decode_kwargs = _decode_entry(model, config, grammar_kwargs)
-    nb = int(decode_kwargs.get("num_beams", 1))
+    nb = _rows_per_clip(decode_kwargs)
     if nb == 1:
         return decode(inputs, max_length=budget, **decode_kwargs)
     per_call = max(1, int(config.inference.get("batch_size", 128)) // nb)
@@ -73,6 +92,7 @@ def _scored_decode(model, config, grammar_kwargs: dict, inputs, max_length: int)
     if inference_beams(config):
         raise ValueError("per-note confidence needs the log-probability of every token; with inference.num_beams > 1 the beam search "
                          "returns sequences_scores only")
+    _no_consensus(config, None, "per-note confidence (min_note_confidence, a positive threshold)")
     out = model.generate(inputs, max_length=max_length, return_dict_in_generate=True, output_logprobs=True, **grammar_kwargs)
     return out.sequences, torch.nn.functional.pad(out.logprobs, (1, 0), value=0.0)
 
@@ -471,11 +491,15 @@ class Music2MIDI(nn.Module):
         return float(_score_on_host(self.model.tokenizer, token_ids, inputs.notes_batch)[0])
 
     def generate(self, audio_path: Optional[Union[str, Path]] = None, audio_y: Optional[np.ndarray] = None,
-                 sr: Optional[int] = None, cond_index: Optional[list] = None, confidence_velocity: bool = False):
+                 sr: Optional[int] = None, cond_index: Optional[list] = None, confidence_velocity: bool = False,
+                 consensus: Optional[int] = None):
         """Specify either audio_path or audio_y as input; returns a MIDI object.  ``confidence_velocity=True`` writes every note's
-        confidence into its velocity: ``max(1, min(127, int(round(127 * confidence))))``."""
+        confidence into its velocity: ``max(1, min(127, int(round(127 * confidence))))``.  ``consensus=K`` as in
+        :meth:`generate_notes`."""
         if not confidence_velocity:
-            return numpy_to_midi(self.generate_notes(audio_path, audio_y, sr, cond_index))
+            override = {} if consensus is None else {"consensus": consensus}
+            return numpy_to_midi(self.generate_notes(audio_path, audio_y, sr, cond_index, **override))
+        _no_consensus(self.config, consensus, "confidence_velocity=True")
         notes, confidence = self.generate_notes(audio_path, audio_y, sr, cond_index, return_confidence=True)
         notes[:, 3] = confidence_velocities(confidence)
         return numpy_to_midi(notes)
@@ -496,15 +520,29 @@ class Music2MIDI(nn.Module):
         return int(self.config.model.sample_rate * self.config.dataset.segment_duration)
 
     def generate_notes(self, audio_path=None, audio_y=None, sr=None, cond_index=None, return_confidence: bool = False,
-                       min_confidence: Optional[float] = None):
+                       min_confidence: Optional[float] = None, consensus: Optional[int] = None):
         """Note array [n, 4] (onset_s, offset_s, pitch, velocity) for a whole recording.  ``return_confidence=True`` returns
         ``(notes, confidence [n] float64)``: the probability the model gave the six tokens that made each note
         (``music2midi_amd.confidence``).  ``min_confidence`` (``None``: ``config.inference.min_note_confidence``, absent 0.0) drops
-        the notes below it.  Either one decodes with ``output_logprobs=True`` and detokenises on the device; greedy, one GPU."""
+        the notes below it.  Either one decodes with ``output_logprobs=True`` and detokenises on the device; greedy, one GPU.
+
+        ``consensus=K`` (``None``: ``config.inference.consensus_samples``, off when absent, 0 or 1) decodes every segment K times -
+        the greedy row and K - 1 sampled rows (``inference.consensus_temperature`` / ``consensus_top_k`` / ``consensus_top_p``) -
+        and keeps the row the others agree with most by note-level F1 (``T5Transformer.generate_consensus``,
+        ``music2midi_amd.consensus``); a chunk is then ``batch_size // K`` segments.  The selection is per segment: each row is
+        detokenised on its own in batched mode, where a note left open at the row's end is dropped; the chosen rows then go
+        through the sequential decode as always.  Consensus with ``inference.num_beams`` > 1, with ``return_confidence=True`` or
+        with a positive ``min_confidence`` raises ``ValueError``.  Whether the chosen rows transcribe better than the greedy ones
+        on a trained model has not been measured."""
         floor = _min_note_confidence(self.config, min_confidence)
+        if return_confidence or floor > 0:
+            _no_consensus(self.config, consensus, "return_confidence=True or a positive min_confidence")
+        else:
+            inference_consensus(self.config, consensus)          # a bad K, or consensus with beams, is refused before the audio is read
         padded, seg = self._padded_segments(audio_path, audio_y, sr)
         if not return_confidence and not floor > 0:
-            return self.sample_tokens(padded, seg, split_duration=self.config.dataset.segment_duration, cond_index=cond_index)
+            override = {} if consensus is None else {"consensus": consensus}
+            return self.sample_tokens(padded, seg, split_duration=self.config.dataset.segment_duration, cond_index=cond_index, **override)
         token_ids, lps = self.sample_scored_rows(padded, seg, cond_index)
         duration = self.config.dataset.segment_duration
         if token_ids.is_cuda:
@@ -565,17 +603,19 @@ class Music2MIDI(nn.Module):
 
     @torch.no_grad()
     def sample_tokens(self, waveform: torch.Tensor, split_size: int, split_duration: float,
-                      cond_index: Optional[list] = None) -> np.ndarray:
+                      cond_index: Optional[list] = None, consensus: Optional[int] = None) -> np.ndarray:
         """Segments -> chunks of inference.batch_size -> generate(max_length=1024) -> notes.  With inference.num_beams > 1 a chunk is
-        batch_size // num_beams clips, decoded by beam_search_processed: the rows of a call stay what the config sized the session for."""
-        token_rows = self.sample_token_rows(waveform, split_size, cond_index)
+        batch_size // num_beams clips, decoded by beam_search_processed: the rows of a call stay what the config sized the session for.
+        With consensus decoding (``consensus``, else inference.consensus_samples) a chunk is batch_size // K clips by the same rule."""
+        token_rows = self.sample_token_rows(waveform, split_size, cond_index, **({} if consensus is None else {"consensus": consensus}))
         return self.model.tokenizer.decode(token_rows, mode="sequential", duration_per_batch=split_duration)
 
     @torch.no_grad()
-    def sample_token_rows(self, waveform: torch.Tensor, split_size: int, cond_index: Optional[list] = None) -> list:
+    def sample_token_rows(self, waveform: torch.Tensor, split_size: int, cond_index: Optional[list] = None,
+                          consensus: Optional[int] = None) -> list:
         """The token row of every segment, in segment order, not detokenised (rows of different chunks may differ in width)."""
-        decode, decode_kwargs = _decode_entry(self.model, self.config, self._grammar_kwargs())
-        per_call = max(1, int(self.config.inference.batch_size) // int(decode_kwargs.get("num_beams", 1)))
+        decode, decode_kwargs = _decode_entry(self.model, self.config, self._grammar_kwargs(), consensus)
+        per_call = max(1, int(self.config.inference.batch_size) // _rows_per_clip(decode_kwargs))
         token_rows = []
         for inputs in self._segment_chunks(waveform, split_size, cond_index, per_call):
             # with a process group (one process per GPU) the chunk's segments are sharded over the ranks and the ids

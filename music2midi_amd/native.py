@@ -157,6 +157,10 @@ _SIGNATURES = {
     "m2m_score_error_notes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p,
                                         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m2m_consensus_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "m2m_consensus_pairwise_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "m2m_consensus_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "m2m_ingest_resampled_length": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "m2m_ingest_phase_taps": (C.c_int, [C.c_int, C.c_int]),
     "m2m_ingest_pcm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -611,3 +611,123 @@ def error_notes(tokenizer, token_ids: torch.Tensor, notes_batch, mode: str = "ba
             float(dn.time_step), lab.data_ptr() if n_labels else None, off.data_ptr(), n_labels, T, frame_cap, floor, melody, max_labels,
             workspace.data_ptr(), need, notes.data_ptr(), counts.data_ptr(), native.stream_handle(device)), "m2m_score_error_notes")
     return ErrorNotes(notes, counts, dn.counts, bool(melody_only))
+
+
+# ----------------------------------------------------------------------------------------------------------------- consensus
+MAX_CANDIDATES = 16                      # M2M_CONSENSUS_MAX_CANDIDATES
+
+
+class PairwiseCounts:
+    """int64 numpy ``tp`` [B, K, K] and ``n`` [B, K] of ``consensus.pairwise_counts`` for every clip: ``tp[b, i, j]`` is the size of
+    the maximum matching with candidate j as the reference and candidate i as the estimate, ``tp[b, i, i] = n[b, i]`` the kept
+    notes of candidate i."""
+
+    def __init__(self, tp: np.ndarray, n: np.ndarray):
+        self.tp, self.n = tp, n
+
+
+def _consensus_tolerances(who: str, onset_tolerance, offset_ratio, offset_min_tolerance) -> tuple:
+    for name, value in (("onset_tolerance", onset_tolerance), ("offset_min_tolerance", offset_min_tolerance)):
+        if not 0.0 <= float(value) <= 3600.0:
+            raise ValueError(f"{who}: {name}={value} out of range [0, 3600] seconds")
+    ratio = -1.0 if offset_ratio is None else float(offset_ratio)
+    if offset_ratio is not None and not 0.0 <= ratio <= 1e6:
+        raise ValueError(f"{who}: offset_ratio={offset_ratio} out of range [0, 1e6] (None: onsets only)")
+    return float(onset_tolerance), ratio, float(offset_min_tolerance)
+
+
+def _consensus_rows(who: str, token_ids, K) -> tuple:
+    """(K, clips) for ids [B * K, L]; ``ValueError`` for a K outside 2..16, ids that are no 2-D int64 tensor or rows that are not
+    whole clips."""
+    from .consensus import check_candidates
+    K = check_candidates(K, who)
+    if not (isinstance(token_ids, torch.Tensor) and token_ids.dim() == 2 and token_ids.dtype == torch.int64):
+        raise ValueError(f"{who}: token_ids must be an int64 tensor [clips * candidates, length]")
+    R = int(token_ids.shape[0])
+    if R % K != 0:
+        raise ValueError(f"{who}: {R} rows are not whole clips of {K} candidates")
+    return K, R // K
+
+
+def _enqueue_pairwise(dn: DeviceNotes, K: int, onset_tolerance: float, offset_ratio: float, offset_min_tolerance: float) -> tuple:
+    """The pairwise kernel of csrc/consensus.hip on the current stream: (tp [B, K, K], n [B, K]) int32 on the device.
+    ``offset_ratio`` < 0: onsets only.  The workspace is torch's."""
+    R, L = int(dn.notes.shape[0]), int(dn.notes.shape[1])
+    device = dn.notes.device
+    lib = native.load()
+    need = int(lib.m2m_consensus_workspace_bytes(R, L, K))
+    # (sizes the library will refuse are not allocated for: it answers on the arguments alone)
+    workspace = torch.empty(max(need, 8) // 8, dtype=torch.int64, device=device)
+    B = R // K
+    tp = torch.empty((B, K, K), dtype=torch.int32, device=device)
+    n = torch.empty((B, K), dtype=torch.int32, device=device)
+    native.check(lib.m2m_consensus_pairwise_counts(
+        dn.notes.data_ptr(), dn.counts.data_ptr(), R, L, K, float(dn.time_step), onset_tolerance, offset_ratio, offset_min_tolerance,
+        workspace.data_ptr(), need, tp.data_ptr(), n.data_ptr(), native.stream_handle(device)), "m2m_consensus_pairwise_counts")
+    return tp, n
+
+
+def _enqueue_select(tp: torch.Tensor, n: torch.Tensor) -> tuple:
+    """The select kernel on the current stream: (chosen [B] int32, utility [B, K] float64) on the device."""
+    B, K = int(n.shape[0]), int(n.shape[1])
+    device = tp.device
+    chosen = torch.empty(B, dtype=torch.int32, device=device)
+    utility = torch.empty((B, K), dtype=torch.float64, device=device)
+    native.check(native.load().m2m_consensus_select(tp.data_ptr(), n.data_ptr(), B, K, chosen.data_ptr(), utility.data_ptr(),
+                                                    native.stream_handle(device)), "m2m_consensus_select")
+    return chosen, utility
+
+
+def _consensus_tensors(who: str, tokenizer, token_ids, K, vocab_size, onset_tolerance, offset_ratio, offset_min_tolerance,
+                       choose: bool) -> tuple:
+    """The one path both public calls and ``generate_consensus`` take: (tp [B, K, K] int32, n [B, K] int32, counts [B * K] int32,
+    chosen [B] int32, utility [B, K] float64) on the device of the ids, the last two ``None`` unless ``choose``.  Ids on a GPU go
+    through the detokenise and the kernels on the current stream and nothing is copied to the host; ids on the host take the
+    definition."""
+    K, B = _consensus_rows(who, token_ids, K)
+    onset, ratio, floor = _consensus_tolerances(who, onset_tolerance, offset_ratio, offset_min_tolerance)
+    device = token_ids.device
+    if B == 0:
+        tp, n = torch.zeros((0, K, K), dtype=torch.int32, device=device), torch.zeros((0, K), dtype=torch.int32, device=device)
+        counts, chosen = torch.zeros(0, dtype=torch.int32, device=device), torch.zeros(0, dtype=torch.int32, device=device)
+        return tp, n, counts, chosen if choose else None, torch.zeros((0, K), dtype=torch.float64, device=device) if choose else None
+    if not token_ids.is_cuda:
+        from .consensus import pairwise_counts, select
+        decoded = tokenizer.decode(token_ids, mode="batched")
+        pairs = [pairwise_counts(decoded[b * K:(b + 1) * K], onset_tolerance, offset_ratio, offset_min_tolerance) for b in range(B)]
+        tp = torch.from_numpy(np.stack([p[0] for p in pairs]).astype(np.int32))
+        n = torch.from_numpy(np.stack([p[1] for p in pairs]).astype(np.int32))
+        counts = torch.zeros(B * K, dtype=torch.int32)
+        if not choose:
+            return tp, n, counts, None, None
+        picks = [select(*p) for p in pairs]
+        return tp, n, counts, torch.tensor([p[0] for p in picks], dtype=torch.int32), torch.from_numpy(np.stack([p[1] for p in picks]))
+    dn = detokenize(tokenizer, token_ids, "batched", None, vocab_size)
+    with torch.cuda.device(device):
+        tp, n = _enqueue_pairwise(dn, K, onset, ratio, floor)
+        chosen, utility = _enqueue_select(tp, n) if choose else (None, None)
+    return tp, n, dn.counts, chosen, utility
+
+
+def pairwise_note_counts(tokenizer, token_ids: torch.Tensor, K: int, vocab_size: Optional[int] = None, onset_tolerance: float = 0.05,
+                         offset_ratio: Optional[float] = 0.2, offset_min_tolerance: float = 0.05) -> PairwiseCounts:
+    """``consensus.pairwise_counts`` of the K candidate rows of every clip for ids [B * K, L] on the device (rows b * K .. b * K + K - 1
+    are clip b's, HF's ``repeat_interleave`` order): one detokenise in batched mode, one launch (csrc/consensus.hip), one copy of the
+    integers to the host.  A row with an id outside the vocabulary raises ``ValueError`` as ``note_counts`` does.  Ids on the host
+    take the definition."""
+    tp, n, counts, _, _ = _consensus_tensors("pairwise_note_counts", tokenizer, token_ids, K, vocab_size, onset_tolerance, offset_ratio,
+                                             offset_min_tolerance, choose=False)
+    B, K = int(n.shape[0]), int(n.shape[1])
+    host = torch.cat([tp.reshape(-1), n.reshape(-1), counts]).cpu().numpy()
+    _raise_for_bad_rows(host[B * K * K + B * K:])
+    return PairwiseCounts(host[:B * K * K].reshape(B, K, K).astype(np.int64), host[B * K * K:B * K * K + B * K].reshape(B, K).astype(np.int64))
+
+
+def consensus_choice(tokenizer, token_ids: torch.Tensor, K: int, vocab_size: Optional[int] = None, onset_tolerance: float = 0.05,
+                     offset_ratio: Optional[float] = 0.2, offset_min_tolerance: float = 0.05) -> tuple:
+    """(chosen [B] int32 tensor, utility [B, K] float64 tensor) on the device of the ids: ``consensus.select`` of every clip's K
+    candidate rows - the detokenise and both kernels of csrc/consensus.hip on the current stream, nothing copied to the host.  A clip
+    that holds a row with an id outside the vocabulary gets ``chosen = -1`` and utilities 0.  Ids on the host take the definition."""
+    return _consensus_tensors("consensus_choice", tokenizer, token_ids, K, vocab_size, onset_tolerance, offset_ratio,
+                              offset_min_tolerance, choose=True)[3:]
+

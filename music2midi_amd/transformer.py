@@ -140,6 +140,27 @@ class GenerateOutput(Seq2SeqOutput):
     unbound views of one buffer), or ``None``; ``logprobs`` [B * n, L - 1] float32, or ``None``."""
 
 
+class ConsensusOutput(Seq2SeqOutput):
+    """``generate_consensus(return_candidates=True)``: ``sequences`` [B, W] the chosen rows; ``candidates`` [B, K, W] with the greedy
+    row first; ``chosen`` [B] int32; ``utility`` [B, K] float64; ``tp`` [B, K, K] and ``n`` [B, K] int32 - all on the device."""
+
+
+def _consensus_arguments(num_samples, keywords: dict) -> int:
+    """K of a consensus decode; ``ValueError`` for a K outside 2..16 or beams, ``NotImplementedError`` with a process group of more
+    than one rank (the candidates of a clip are not gathered across ranks)."""
+    from .consensus import check_candidates
+    K = check_candidates(num_samples, "generate_consensus: num_samples")
+    if "num_beams" in keywords:
+        raise ValueError("generate_consensus: num_beams is not supported - the candidates are one greedy and num_samples - 1 sampled rows")
+    for name in ("do_sample", "num_return_sequences", "return_dict_in_generate", "output_scores", "output_logprobs"):
+        if name in keywords:
+            raise ValueError(f"generate_consensus: {name} is set by the consensus decode itself")
+    dist = torch.distributed
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError("generate_consensus runs on one GPU: with a process group, decode on one rank")
+    return K
+
+
 # --------------------------------------------------------------------------
 class T5Transformer(nn.Module):
     def __init__(self, config_path, precision: Optional[str] = None):
@@ -627,3 +648,44 @@ class T5Transformer(nn.Module):
                                       vocab_size=self.geometry.vocab_size,
                                       grammar=self.tokenizer.grammar if kwargs.get("midi_grammar") is True else None)
         return self._decode(self.encoder_inputs(inputs), cfg)
+
+    @torch.no_grad()
+    def generate_consensus_from_embeds(self, inputs_embeds: torch.Tensor, num_samples: int, max_length: int = 20, temperature: float = 1.0,
+                                       top_k: int = 50, top_p: float = 1.0, midi_grammar: bool = False, return_candidates: bool = False,
+                                       **processor_keywords):
+        """:meth:`generate_consensus` from encoder inputs [B, S, d]."""
+        K = _consensus_arguments(num_samples, processor_keywords)
+        from .scoring import _consensus_tensors
+        common = dict(processor_keywords, midi_grammar=True) if midi_grammar else dict(processor_keywords)
+        greedy = self.generate_from_embeds(inputs_embeds, max_length=max_length, **common)
+        sampled = self.generate_from_embeds(inputs_embeds, max_length=max_length, do_sample=True, num_return_sequences=K - 1,
+                                            temperature=temperature, top_k=top_k, top_p=top_p, **common)
+        B, pad = int(greedy.shape[0]), self.geometry.pad_token_id
+        W = max(int(greedy.shape[1]), int(sampled.shape[1]))
+        greedy = torch.nn.functional.pad(greedy, (0, W - int(greedy.shape[1])), value=pad)
+        sampled = torch.nn.functional.pad(sampled, (0, W - int(sampled.shape[1])), value=pad)
+        candidates = torch.cat([greedy.unsqueeze(1), sampled.reshape(B, K - 1, W)], dim=1).contiguous()      # [B, K, W], greedy first
+        tp, n, _, chosen, utility = _consensus_tensors("generate_consensus", self.tokenizer, candidates.reshape(B * K, W), K,
+                                                       self.geometry.vocab_size, 0.05, 0.2, 0.05, choose=True)
+        # (a generated id is inside the vocabulary, so no clip is marked; the clamp keeps the gather in bounds regardless)
+        pick = chosen.clamp_min(0).long().reshape(B, 1, 1).expand(B, 1, W)
+        sequences = candidates.gather(1, pick).squeeze(1)
+        if not return_candidates:
+            return sequences
+        return ConsensusOutput(sequences=sequences, candidates=candidates, chosen=chosen, utility=utility, tp=tp, n=n)
+
+    def generate_consensus(self, inputs: ModelInputs, num_samples: int, max_length: int = 20, temperature: float = 1.0, top_k: int = 50,
+                           top_p: float = 1.0, midi_grammar: bool = False, return_candidates: bool = False, **processor_keywords):
+        """Consensus (minimum-Bayes-risk) decode: per clip, the greedy row and ``num_samples - 1`` sampled rows (``temperature``,
+        ``top_k``, ``top_p`` as in :meth:`generate`; ``midi_grammar`` and the logits-processor keywords go to both decodes) are
+        detokenised on their own in batched mode and scored against each other with the note-level metric of
+        ``music2midi_amd.note_metrics``; the row the others agree with most (``music2midi_amd.consensus``; ties go to the greedy row)
+        is returned, [B, W] with W the wider of the two decodes, PAD-filled.  The scoring and the selection run on the GPU
+        (csrc/consensus.hip) and nothing is copied to the host.  ``return_candidates=True`` returns a :class:`ConsensusOutput` that
+        also carries ``candidates`` [B, K, W], ``chosen``, ``utility``, ``tp`` and ``n``.  ``torch.manual_seed`` makes a call
+        reproducible, as for sampling.  ``num_samples`` outside 2..16 and ``num_beams`` raise ``ValueError``; a process group of
+        more than one rank raises ``NotImplementedError``.  Whether the chosen row is a better transcription than the greedy one
+        on a trained model has not been measured."""
+        _consensus_arguments(num_samples, processor_keywords)
+        return self.generate_consensus_from_embeds(self.encoder_inputs(inputs), num_samples, max_length, temperature, top_k, top_p,
+                                                   midi_grammar, return_candidates, **processor_keywords)
