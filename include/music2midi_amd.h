@@ -578,6 +578,66 @@ int m2m_align_dtw(const void* a0_dev, const void* a1_dev, int a_frames, const vo
                   int32_t* total_out_dev, int32_t* path_out_dev, int64_t path_capacity, int32_t* path_len_out_dev, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Beat tracking: an onset envelope of log band energies, a tempo from its autocorrelation, the beats by a dynamic program.  This is
+ * the project's own tracker in the family of Ellis (2007), not librosa's or madmom's; the definition is music2midi_amd/beats.py
+ * (onset_envelope_host, track_envelope_host) and every output below is EQUAL to its: one fp32 subtraction, one scaling by 16 and one
+ * truncation per band of the envelope, integer arithmetic everywhere else.  Every transcendental number is a table the caller passes.
+ * No handle, no environment switch; the calls enqueue on `stream` and return nothing to the host.  Every M2M_ERR_INVALID below is
+ * answered on the arguments alone, before the first HIP call.
+ * ------------------------------------------------------------------------- */
+#define M2M_BEAT_MAX_FRAMES 32768          /* frames of one clip: 10.9 min at 50 frames per second */
+#define M2M_BEAT_MAX_CLIPS 65535
+#define M2M_BEAT_MAX_TOTAL_FRAMES (1 << 26) /* frames of one call, all clips together */
+#define M2M_BEAT_LAG_MIN 15                /* periods in frames: 200 BPM .. */
+#define M2M_BEAT_LAG_MAX 100               /* .. 30 BPM */
+#define M2M_BEAT_HALF 12                   /* the novelty's local sum reaches this many frames to either side */
+#define M2M_BEAT_ENV_MAX 22440             /* the largest envelope value: 88 bands of 255 */
+
+/*
+ * L_dev fp32 [total_frames, 88] and frame_offsets_dev as in m2m_align_features.  env_out_dev int32 [total_frames]; frame t of a clip,
+ * with M = max_p L[t][p]: 0 when t = 0 or M <= -6.0f, otherwise the sum over the bands with L[t][p] >= M - (float)ln 20 of
+ * (int)min(max(L[t][p] - L[t-1][p], 0.0f) * 16.0f, 255.0f).
+ * M2M_ERR_INVALID: n_clips outside 1..65535, total_frames outside 1..2^26, max_frames outside 1..total_frames, a null pointer, a
+ * pointer that is not 4-byte aligned.
+ */
+int m2m_beat_envelope(const float* L_dev, const int32_t* frame_offsets_dev, int n_clips, int max_frames, int64_t total_frames,
+                      int32_t* env_out_dev, void* stream);
+
+typedef struct {
+  int32_t env_offset;                      /* first frame of the clip in env_dev */
+  int32_t frames;                          /* 1..32768 */
+  int32_t period;                          /* 0: estimate the period; 15..100: use this one */
+  int32_t beat_offset;                     /* first beat of the clip in beats_out_dev; frames / 8 + 2 entries are reserved */
+} m2m_beat_clip;
+
+/* Bytes of workspace m2m_beat_track needs for clips of frames_host[b] frames: the clip table, then the novelty of every frame.
+ * M2M_ERR_INVALID (negative) for n_clips outside 1..65535 or a clip outside 1..32768 frames.  Host arithmetic. */
+int64_t m2m_beat_track_workspace_bytes(const int32_t* frames_host, int n_clips);
+
+/*
+ * n_clips envelopes (env_dev int32 [env_frames], values 0..22440) by ONE launch, one workgroup each.  With e zero outside the clip
+ * and F its frames:
+ *   o[t] = max(0, 25 e[t] - sum_{|k| <= 12} e[t + k]);
+ *   a[k] = (sum_{t >= k} o[t] o[t - k]) / (F - k) for k = 15..min(200, F - 1), 0 for every other lag; 64-bit integers;
+ *   score[l] = (a[l] + a[2 l] / 2) * prior_dev[l] for l = 15..100 (prior_dev int32 [101]), 0 below 15;
+ *   P = the clip's period when that is not 0; otherwise the first maximum of score, default_period when that maximum is 0;
+ *   s = (sum of o) / max(1, #{o > 0});  pen[tau] = (penalty_dev[P * 201 + tau] * s) >> 8 (penalty_dev int32 [101, 201], not negative);
+ *   lo = (P + 1) / 2, hi = 2 P;  C[t] = o[t] for t < lo, else o[t] + max over tau = lo..min(hi, t) of (C[t - tau] - pen[tau]), the
+ *   smallest tau on a tie, back[t] = t - tau;  the last beat is the first maximum of C over [max(0, F - P), F), the beats the chain
+ *   of back from there in ascending order; no beats when every o is 0.
+ * period_out_dev int32 [n_clips]: P.  score_out_dev int64 [n_clips, 101], may be null.  beats_out_dev int32 [beat_capacity]: the
+ * beats of clip b from beat_offset on, n_beats_out_dev[b] of them (at most frames / 8 + 1).
+ * clips_host is copied to the head of workspace_dev on `stream`; it must stay valid until that copy has run.
+ * M2M_ERR_INVALID: n_clips outside 1..65535, a clip outside 1..32768 frames or outside env_frames (1..2^26), a period that is neither
+ * 0 nor in 15..100, default_period outside 15..100, beat regions that are not ascending and disjoint or exceed beat_capacity
+ * (1..2^31 - 1), a null pointer other than score_out_dev, a table or output not 4-byte (score_out_dev: 8-byte) aligned, a workspace
+ * not 256-byte aligned.  M2M_ERR_NOMEM: workspace_bytes below m2m_beat_track_workspace_bytes.
+ */
+int m2m_beat_track(const int32_t* env_dev, int64_t env_frames, const m2m_beat_clip* clips_host, int n_clips, const int32_t* prior_dev,
+                   const int32_t* penalty_dev, int default_period, void* workspace_dev, int64_t workspace_bytes, int32_t* period_out_dev,
+                   int64_t* score_out_dev, int32_t* beats_out_dev, int64_t beat_capacity, int32_t* n_beats_out_dev, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Tokenising of note labels: the note arrays of a batch -> token ids, replaces for the batches it takes
  * ref: music2midi/tokenizer.py:86-141 (MidiTokenizer.__call__, _tokenize).  The definition is music2midi_amd/tokenizer.py
  * (_quantize, _tokenize); the ids are EQUAL to its (integer placement; the quantisation repeats the host's float64 operations).

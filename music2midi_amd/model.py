@@ -492,17 +492,48 @@ class Music2MIDI(nn.Module):
 
     def generate(self, audio_path: Optional[Union[str, Path]] = None, audio_y: Optional[np.ndarray] = None,
                  sr: Optional[int] = None, cond_index: Optional[list] = None, confidence_velocity: bool = False,
-                 consensus: Optional[int] = None):
+                 consensus: Optional[int] = None, beat_grid: Optional[bool] = None, quantize: Optional[int] = None):
         """Specify either audio_path or audio_y as input; returns a MIDI object.  ``confidence_velocity=True`` writes every note's
         confidence into its velocity: ``max(1, min(127, int(round(127 * confidence))))``.  ``consensus=K`` as in
-        :meth:`generate_notes`."""
+        :meth:`generate_notes`.
+
+        ``beat_grid=True`` (``None``: ``config.inference.beat_grid``, absent off) tracks the recording's beats
+        (:meth:`generate_beats`) and returns the stand-in ``SimpleMIDI`` - always, also with pretty_midi installed - with its
+        ``beat_times`` set, so that ``write`` lays a tempo map along the beats and an editor shows bars and beats that follow the
+        music; note times in seconds are unchanged.  ``quantize=n`` (with the beat grid only) snaps onsets and offsets to ``n`` grid
+        points per beat first (``music2midi_amd.beats.quantize``).  Without the keyword and the config key a call is what it was."""
+        if beat_grid is None:
+            beat_grid = bool(self.config.inference.get("beat_grid", False))
+        if quantize is not None and not beat_grid:
+            raise ValueError("generate: quantize needs beat_grid=True")
         if not confidence_velocity:
             override = {} if consensus is None else {"consensus": consensus}
-            return numpy_to_midi(self.generate_notes(audio_path, audio_y, sr, cond_index, **override))
-        _no_consensus(self.config, consensus, "confidence_velocity=True")
-        notes, confidence = self.generate_notes(audio_path, audio_y, sr, cond_index, return_confidence=True)
-        notes[:, 3] = confidence_velocities(confidence)
-        return numpy_to_midi(notes)
+            notes = self.generate_notes(audio_path, audio_y, sr, cond_index, **override)
+        else:
+            _no_consensus(self.config, consensus, "confidence_velocity=True")
+            notes, confidence = self.generate_notes(audio_path, audio_y, sr, cond_index, return_confidence=True)
+            notes[:, 3] = confidence_velocities(confidence)
+        if not beat_grid:
+            return numpy_to_midi(notes)
+        from . import beats as beats_mod
+        from .utils import simple_midi
+        result = self.generate_beats(audio_path, audio_y, sr)
+        if quantize is not None and len(result.beat_times) >= 2:
+            notes = beats_mod.quantize(notes, result.beat_times, quantize)
+        midi = simple_midi(notes)
+        midi.beat_times = result.beat_times if len(result.beat_times) >= 2 else None
+        return midi
+
+    def generate_beats(self, audio_path=None, audio_y=None, sr=None):
+        """``music2midi_amd.beats.BeatResult`` of a recording: its beat times in seconds, their frames, the period and the tempo.
+        The audio is read as :meth:`generate` reads it (at the model's sample rate) and tracked on the model's device
+        (``beats.track``), by the definition in numpy when the model is on the CPU."""
+        from . import beats as beats_mod
+        samples = self._resolve_audio(audio_path, audio_y, sr)
+        rate = self.config.model.sample_rate
+        if self.device.type != "cuda":
+            return beats_mod.track_host(samples, sr=rate)
+        return beats_mod.track(samples, sr=rate, device=self.device)
 
     # The three steps below are what ref model.py:67-140 does inline: validate/load, cut the song into
     # whole segments (zero-padded tail), decode the segments in chunks and stitch the notes together.

@@ -71,6 +71,11 @@ class AlignProblem(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("a_offset", "n", "b_offset", "m", "shift", "path_offset")]
 
 
+class BeatClip(C.Structure):
+    """m2m_beat_clip: one clip of m2m_beat_track (four 32-bit words)."""
+    _fields_ = [(n, C.c_int32) for n in ("env_offset", "frames", "period", "beat_offset")]
+
+
 class T5GeometryC(C.Structure):
     _fields_ = [(n, C.c_int) for n in
                 ("d_model", "d_ff", "num_layers", "num_decoder_layers", "num_heads", "d_kv", "vocab_size",
@@ -178,6 +183,10 @@ _SIGNATURES = {
     "m2m_align_dtw_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int]),
     "m2m_align_dtw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "m2m_beat_envelope": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "m2m_beat_track_workspace_bytes": (C.c_int64, [C.c_void_p, C.c_int]),
+    "m2m_beat_track": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "m2m_tokenize_quantize": (C.c_int, [C.c_double, C.c_double, C.c_int]),
     "m2m_tokenize_row_bound": (C.c_int64, [C.c_int, C.c_int]),
     "m2m_tokenize_notes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
